@@ -25,7 +25,13 @@ drain untimed.  barrier + torch.cuda.synchronize() bracket the whole run; `drain
 from the first issue to the last completion (fill and drain included).  MAX over ranks; ranks shard by proof (no
 data-path collective): scaling = weak.
 
+A plain run sets up, warms up, times the K steps and prints the line of record.  --full adds everything else the line can
+carry, each from runs of its own: the 65 536-lane kernel leg and the PCIe-inclusive drop-in leg, the side arrangements and the
+native caller loop (child processes), config 5's batch-of-1 latency and the single-thread CPU baseline.  --dump-outputs DIR
+writes what the callers received from their last call (dump_outputs) after the run.
+
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 """
@@ -93,6 +99,45 @@ def cgroup_cpu():
 
 def tapes_for(first, count, nbytes):
     return [hashlib.shake_256(("kosk-tape-v1:%d" % (first + b)).encode()).digest(nbytes) for b in range(count)]
+
+
+DUMP_MAX_ROWS = 16384            # (slot, proof) rows kept by dump_outputs; a seeded sample beyond that
+DUMP_BYTES_PER_ARRAY = 16 << 20  # float32 bytes per pk / sk / proof array: three of them plus the small ones stay under 64 MB
+
+
+def dump_outputs(out_dir, slots, prefix=""):
+    """--dump-outputs: what the callers of the timed path received from their last call, as float32 .npy files, one row per
+    (slot, proof) in slot order: verify_ok (the verify bit), proof_sha3_256 (SHA3-256 of the whole proof image, 32 byte values),
+    pk / sk / proof (byte values 0..255).  Under 64 MB in all: where a whole array would not fit, a fixed seeded sample of its
+    byte positions (and, past DUMP_MAX_ROWS rows, of its rows) is kept, the same on every run with the same arguments."""
+    import numpy as np
+    c0, B = slots[0].c, slots[0].B
+    nrows = len(slots) * B
+    rows = np.arange(nrows) if nrows <= DUMP_MAX_ROWS else np.sort(np.random.default_rng(1).choice(nrows, DUMP_MAX_ROWS, replace=False))
+
+    def cols(n):
+        c = max(1, min(n, DUMP_BYTES_PER_ARRAY // (4 * len(rows))))
+        return np.arange(n) if c == n else np.sort(np.random.default_rng(n).choice(n, c, replace=False))
+    pk_c, sk_c, pi_c = cols(c0.pk_bytes), cols(c0.sk_bytes), cols(c0.proof_bytes)
+    out = {"verify_ok": [], "proof_sha3_256": [], "pk": [], "sk": [], "proof": []}
+    for si, sl in enumerate(slots):
+        sel = rows[(rows >= si * B) & (rows < (si + 1) * B)] - si * B
+        if not len(sel):
+            continue
+        ok = np.frombuffer(sl._ok.raw, np.uint8)
+        pk = np.frombuffer(sl.c._pk.raw, np.uint8).reshape(B, sl.c.pk_bytes)
+        sk = np.frombuffer(sl.c._sk.raw, np.uint8).reshape(B, sl.c.sk_bytes)
+        pis = sl.c.fetch_proofs(B)
+        for b in sel:
+            out["verify_ok"].append(ok[b])
+            out["proof_sha3_256"].append(np.frombuffer(hashlib.sha3_256(pis[b]).digest(), np.uint8))
+            out["pk"].append(pk[b, pk_c])
+            out["sk"].append(sk[b, sk_c])
+            out["proof"].append(np.frombuffer(pis[b], np.uint8)[pi_c])
+        del pis
+    os.makedirs(out_dir, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.asarray(v, dtype=np.float32))
 
 
 def cpu_baseline(k, tapes, nproofs):
@@ -437,7 +482,8 @@ def threads_per_caller(budget_threads, blocking, combine, cores_per_rank):
 class Slot:
     """One pipeline slot: a library context with its tape bank in HBM (and, for config 4, its own process group)."""
 
-    def __init__(self, api, torch, k, B, device, first_tape, nsets, combine=1, prewake_us=None, fs="host", threads=0, blocking=False):
+    def __init__(self, api, torch, k, B, device, first_tape, nsets, combine=1, prewake_us=None, fs="host", threads=0, blocking=False,
+                 host_staged=False):
         # combine = C > 1: the handle joins a cohort of C handles whose resident calls the library merges (kosk_options::combine).  The
         # slots are closed loops that pause between the bench's runs (conditioning, barrier, timed run): members stay "expected" by
         # their cohort for 20 ms instead of the library's default 1 ms, so that a run's first calls merge like all the others
@@ -450,6 +496,12 @@ class Slot:
             # (c) where the configuration says so (config 4's 273-proof runs of three callers: the same rate with 1.3 cores fewer)
             if blocking or combine >= 5 or prewake_us is not None:
                 opts["combine_prewake_us"] = int(os.environ.get("KOSK_BENCH_PREWAKE_US", prewake_us or 0))
+            # (d) the one-GPU rehearsal of config 4 (enable_gather(host_staged=True)): every member copies its digest tables to the host
+            # and all-gathers them over gloo before its verify call, so the members of a cohort come back from their gathers several
+            # milliseconds apart -- a skew of the rehearsal's own staging that the library's 5 ms window does not cover and the RCCL
+            # path does not have.  The rehearsal's window covers it (members stay expected for 100 ms), so its calls merge as config 4's do.
+            if host_staged:
+                opts["combine_wait_us"], opts["combine_idle_us"] = 50000, 100000
         self.c = api.Kosk(kyber_k=k, max_batch=B, device=device, **opts)
         self.B, self.nsets = B, nsets
         self.stride = (self.c.tape_bytes + 63) // 64 * 64
@@ -552,9 +604,14 @@ def main():
     ap.add_argument("--threads", type=int, default=int(os.environ.get("KOSK_BENCH_THREADS", "0")), help="Fiat-Shamir workers per caller (0: the host budget's)")
     ap.add_argument("--phase-stats", action="store_true", help="mean of the library's phase clocks over every step (diagnostic; one extra ABI call per step)")
     ap.add_argument("--tape-sets", type=int, default=4, help="distinct resident tape sets per slot, rotated step by step")
-    ap.add_argument("--cpu-proofs", type=int, default=12, help="bounded CPU baseline sample (about 13 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernels", action="store_true", help="skip the 65 536-lane kernel leg and the PCIe-inclusive drop-in leg")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the auxiliary legs (kernel and drop-in legs, side arrangements, native callers, config 5's batch-of-1 "
+                         "latency, CPU baseline); a plain run measures the line of record only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the run, write what the callers received from their last call as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--cpu-proofs", type=int, default=12, help="bounded CPU baseline sample (about 13 s; with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-kernels", action="store_true", help="with --full: skip the 65 536-lane kernel leg, the PCIe-inclusive drop-in leg and the side runs")
     ap.add_argument("--leg", default="", choices=["", "drop_in"], help="(internal) run ONE auxiliary leg in this process and print its JSON object")
     args = ap.parse_args()
     cfg = dict(CONFIGS[args.config])
@@ -634,7 +691,7 @@ def main():
 
     from mpcith_kyber_kosk_amd import api, sharding
     slots = [Slot(api, torch, k, B, local_rank, ((rank * S + si) * args.tape_sets) * B, args.tape_sets, combine=CMB, prewake_us=cfg.get("prewake_us"), fs=FS,
-                  threads=threads, blocking=blocking) for si in range(S)]
+                  threads=threads, blocking=blocking, host_staged=want_gather and rehearse) for si in range(S)]
     ctx = slots[0].c
     tapes = slots[0].first_tapes
     if want_gather:
@@ -655,7 +712,9 @@ def main():
     lock = threading.Lock()
     done_t = []
     lat = []
-    static = want_gather or CMB > 1  # collectives: every rank must run the same steps on the same slot; cohorts: see `total`
+    # collectives: every rank must run the same steps on the same slot; cohorts: see `total`; --dump-outputs: every slot's last
+    # step reads the same tape set on every run
+    static = want_gather or CMB > 1 or bool(args.dump_outputs)
 
     def take(si, nth):
         """index of slot si's nth step of this run, or None when the run is over"""
@@ -837,6 +896,8 @@ def main():
             mine = torch.frombuffer(bytearray(hashlib.sha3_256(b"".join(pr)).digest()), dtype=torch.uint8).reshape(1, 32).to(cdev)
             table = sharding.allgather_digest_table(mine, world, dist)
             assert table.shape == (world, 32) and bytes(table[rank].tolist()) == bytes(mine[0].tolist())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, slots, prefix="rank%d_" % rank if world > 1 else "")
 
     if rank == 0:
         kern = {}
@@ -943,7 +1004,7 @@ def main():
         if dist is not None:
             line["rccl"] = rccl_info
             line["host_per_rank"] = host_per_rank
-        if args.config == 5 and not custom:
+        if args.full and args.config == 5 and not custom:
             # batch-of-1 latency: one verifiable keygen + verify alone on an idle GPU
             c1 = api.Kosk(kyber_k=k, max_batch=1, device=local_rank)
             t1s = []
@@ -957,7 +1018,7 @@ def main():
             c1.close()
             line["latency"] = {"batch_of_512_ms_median": lats[len(lats) // 2] * 1e3, "batch_of_1_ms_median": t1s[len(t1s) // 2] * 1e3,
                                "per_proof_us_at_throughput": dt / K / B * 1e6}
-        aux = world == 1 and not args.no_kernels and args.config in (2, 3) and not custom
+        aux = args.full and world == 1 and not args.no_kernels and args.config in (2, 3) and not custom
         if aux:
             try:
                 line["kernels_65536_lanes"] = kernel_microbench(ctx, torch, k)
@@ -1054,7 +1115,7 @@ def main():
                                                       "record (147.6 k proofs/s at 2.8 ms there), on this box for a like-for-like comparison; not the line of record")
             line["cohorts_of_four"] = side_run(12, 4, "python bench.py --combine 4 --slots 12: twelve callers, four per merged run (184 proofs per launch; less latency "
                                                       "per call, fewer proofs per launch than the default's six); not the line of record")
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline(k, tapes, min(args.cpu_proofs, B))
             except Exception as e:  # noqa: BLE001

@@ -3,10 +3,15 @@
   libkosk_ref_k*.so  : + ss.cpp + mlwe_prover.cpp + our sizeof/offsetof probe (oracle/ref_layout.cpp); the generated
                        utils/precomputed_kyber.c is not mounted, so get_precomputed_* are unresolved and the library is
                        loaded with RTLD_LAZY: only functions that never reach them are called here.
-Skipped when that build is absent (it cannot be rebuilt without /root/reference; oracle/_ref is git-ignored) -- but a FAILURE
-where the pins are required: KOSK_REQUIRE_REF=1, which tests/conftest.py sets by itself wherever /root/reference exists (the
-build container); the skip count is printed in the suite summary either way."""
+Where that build is absent (it cannot be rebuilt without the reference tree; oracle/_ref is git-ignored) the same checks run
+against tests/golden/ref_pins_v1.json: SHA3-256 digests of what the compiled reference returned on the same seeded inputs, the
+struct layouts it reported and the seeds and digests of keys it generated.  With oracle/_ref present every check compares the
+reference with the oracle directly AND with the stored digests.  KOSK_REQUIRE_REF=1 (tests/conftest.py sets it wherever the
+reference tree exists) makes a missing oracle/_ref a FAILURE; KOSK_RECORD_REF_PINS=1 rewrites the pins file from oracle/_ref
+(run the whole module)."""
 import ctypes as C
+import hashlib
+import json
 import os
 
 import numpy as np
@@ -14,103 +19,172 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = {2: "pqcrystals_kyber512_ref_", 3: "pqcrystals_kyber768_ref_", 4: "pqcrystals_kyber1024_ref_"}
+PINS_PATH = os.path.join(ROOT, "tests", "golden", "ref_pins_v1.json")
+RECORD = os.environ.get("KOSK_RECORD_REF_PINS") == "1"
+if RECORD:
+    PINS = {"note": "recorded from oracle/_ref by KOSK_RECORD_REF_PINS=1 python -m pytest tests/test_oracle_vs_ref.py",
+            "digests": {}, "layouts": {}, "keygen": {}}
+else:
+    with open(PINS_PATH) as f_:
+        PINS = json.load(f_)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _record_pins():
+    yield
+    if RECORD:
+        with open(PINS_PATH, "w") as f:
+            json.dump(PINS, f, indent=1, sort_keys=True)
+            f.write("\n")
 
 
 def _no_ref(path):
-    if os.environ.get("KOSK_REQUIRE_REF") == "1":
-        pytest.fail("KOSK_REQUIRE_REF=1 but %s is missing: run `make -C oracle` where /root/reference is mounted" % path)
-    pytest.skip("oracle/_ref not built (reference tree absent)")
+    if os.environ.get("KOSK_REQUIRE_REF") == "1" or RECORD:
+        pytest.fail("KOSK_REQUIRE_REF=1 or KOSK_RECORD_REF_PINS=1 but %s is missing: run `make -C oracle` where the reference tree is mounted" % path)
+    return None  # the checks run against the stored pins
 
 
 def _ref(k):
     path = os.path.join(ROOT, "oracle", "_ref", "libkyber_ref_k%d.so" % k)
     if not os.path.exists(path):
-        _no_ref(path)
+        return _no_ref(path)
     return C.CDLL(path)
+
+
+def _bytes(x):
+    if isinstance(x, int):
+        return x.to_bytes(4, "little", signed=True)
+    if isinstance(x, np.ndarray):
+        return x.tobytes()
+    return bytes(getattr(x, "raw", x))
+
+
+def _sha(x):
+    return hashlib.sha3_256(_bytes(x)).hexdigest()
+
+
+class Pins:
+    """One digest per check `key` over everything the oracle produced for it in a test; add() also compares the reference's
+    output with the oracle's where oracle/_ref exists (ref_out None: it does not)."""
+
+    def __init__(self, name):
+        self.name, self.h = name, {}
+
+    def add(self, key, ref_out, oracle_out):
+        if ref_out is not None:
+            assert _bytes(ref_out) == _bytes(oracle_out), (self.name, key)
+        self.h.setdefault(key, hashlib.sha3_256()).update(_bytes(oracle_out))
+
+    def check(self):
+        got = {self.name + "/" + key: h.hexdigest() for key, h in self.h.items()}
+        if RECORD:
+            PINS["digests"].update(got)
+            return
+        want = {key: v for key, v in PINS["digests"].items() if key.startswith(self.name + "/")}
+        assert want and set(got) == set(want), (self.name, sorted(set(got) ^ set(want)))
+        for key in sorted(got):
+            assert got[key] == want[key], "%s: the oracle no longer gives what the compiled reference gave" % key
 
 
 @pytest.mark.parametrize("k", [2, 3, 4])
 def test_ring_arithmetic_and_sampling(k, oracle):
     ref, pre = _ref(k), NAMES[k]
+    live = ref is not None
+    pins = Pins("ring_k%d" % k)
     rng = np.random.default_rng(k)
     vp = C.c_void_p
     for trial in range(20):
         a = rng.integers(-3328, 3329, size=256).astype(np.int16)
         r1, r2 = a.copy(), a.copy()
-        getattr(ref, pre + "poly_ntt")(r1.ctypes.data_as(vp))
+        if live:
+            getattr(ref, pre + "poly_ntt")(r1.ctypes.data_as(vp))
         oracle.lib.ko_poly_ntt(r2.ctypes.data_as(vp))
-        assert np.array_equal(r1, r2)
+        pins.add("poly_ntt", r1 if live else None, r2)
         r1, r2 = a.copy(), a.copy()
-        getattr(ref, pre + "ntt")(r1.ctypes.data_as(vp))
+        if live:
+            getattr(ref, pre + "ntt")(r1.ctypes.data_as(vp))
         oracle.lib.ko_ntt(r2.ctypes.data_as(vp))
-        assert np.array_equal(r1, r2)
+        pins.add("ntt", r1 if live else None, r2)
         r1, r2 = a.copy(), a.copy()
-        getattr(ref, pre + "poly_tomont")(r1.ctypes.data_as(vp))
+        if live:
+            getattr(ref, pre + "poly_tomont")(r1.ctypes.data_as(vp))
         oracle.lib.ko_poly_tomont(r2.ctypes.data_as(vp))
-        assert np.array_equal(r1, r2)
+        pins.add("poly_tomont", r1 if live else None, r2)
         A = rng.integers(0, 3329, size=k * 256).astype(np.int16)
         B = rng.integers(-1664, 1665, size=k * 256).astype(np.int16)
         o1, o2 = np.zeros(256, np.int16), np.zeros(256, np.int16)
-        getattr(ref, pre + "polyvec_basemul_acc_montgomery")(o1.ctypes.data_as(vp), A.ctypes.data_as(vp), B.ctypes.data_as(vp))
+        if live:
+            getattr(ref, pre + "polyvec_basemul_acc_montgomery")(o1.ctypes.data_as(vp), A.ctypes.data_as(vp), B.ctypes.data_as(vp))
         oracle.lib.ko_polyvec_basemul_acc(o2.ctypes.data_as(vp), A.ctypes.data_as(vp), B.ctypes.data_as(vp), k)
-        assert np.array_equal(o1, o2)
+        pins.add("polyvec_basemul_acc", o1 if live else None, o2)
         t = rng.integers(-3328, 3329, size=256).astype(np.int16)
         b1, b2 = C.create_string_buffer(384), C.create_string_buffer(384)
-        getattr(ref, pre + "poly_tobytes")(b1, t.ctypes.data_as(vp))
+        if live:
+            getattr(ref, pre + "poly_tobytes")(b1, t.ctypes.data_as(vp))
         oracle.lib.ko_poly_tobytes(b2, t.ctypes.data_as(vp))
-        assert b1.raw == b2.raw
+        pins.add("poly_tobytes", b1 if live else None, b2)
         p1, p2 = np.zeros(256, np.int16), np.zeros(256, np.int16)
-        getattr(ref, pre + "poly_frombytes")(p1.ctypes.data_as(vp), b1)
-        oracle.lib.ko_poly_frombytes(p2.ctypes.data_as(vp), b1)
-        assert np.array_equal(p1, p2)
+        if live:
+            getattr(ref, pre + "poly_frombytes")(p1.ctypes.data_as(vp), b2)
+        oracle.lib.ko_poly_frombytes(p2.ctypes.data_as(vp), b2)
+        pins.add("poly_frombytes", p1 if live else None, p2)
         seed = bytes(rng.integers(0, 256, size=32, dtype=np.uint8))
         eta1 = 3 if k == 2 else 2
         n1 = np.zeros(256, np.int16)
-        getattr(ref, pre + "poly_getnoise_eta1")(n1.ctypes.data_as(vp), C.c_char_p(seed), C.c_uint8(trial))
+        if live:
+            getattr(ref, pre + "poly_getnoise_eta1")(n1.ctypes.data_as(vp), C.c_char_p(seed), C.c_uint8(trial))
         prf = oracle.shake256(seed + bytes([trial]), eta1 * 64)
         n2 = np.zeros(256, np.int16)
         oracle.lib.ko_cbd(n2.ctypes.data_as(vp), C.c_char_p(prf), eta1)
-        assert np.array_equal(n1, n2)
+        pins.add("poly_getnoise_eta1", n1 if live else None, n2)
         for transposed in (0, 1):
             m1, m2 = np.zeros(k * k * 256, np.int16), np.zeros(k * k * 256, np.int16)
-            getattr(ref, pre + "gen_matrix")(m1.ctypes.data_as(vp), C.c_char_p(seed), transposed)
+            if live:
+                getattr(ref, pre + "gen_matrix")(m1.ctypes.data_as(vp), C.c_char_p(seed), transposed)
             oracle.lib.ko_gen_matrix(m2.ctypes.data_as(vp), C.c_char_p(seed), transposed, k)
-            assert np.array_equal(m1, m2)
+            pins.add("gen_matrix_%d" % transposed, m1 if live else None, m2)
+    pins.check()
 
 
 def test_fips202_and_gf3329(oracle):
     ref = _ref(2)
+    live = ref is not None
+    pins = Pins("fips202_gf3329")
     rng = np.random.default_rng(9)
     for n in (0, 1, 33, 135, 136, 137, 500, 46528):
         d = bytes(rng.integers(0, 256, size=n, dtype=np.uint8))
         o1 = C.create_string_buffer(32)
-        ref.pqcrystals_kyber_fips202_ref_sha3_256(o1, C.c_char_p(d), C.c_size_t(n))
-        assert o1.raw == oracle.sha3_256(d)
+        if live:
+            ref.pqcrystals_kyber_fips202_ref_sha3_256(o1, C.c_char_p(d), C.c_size_t(n))
+        pins.add("sha3_256", o1 if live else None, oracle.sha3_256(d))
         o1 = C.create_string_buffer(333)
-        ref.pqcrystals_kyber_fips202_ref_shake256(o1, C.c_size_t(333), C.c_char_p(d), C.c_size_t(n))
-        assert o1.raw == oracle.shake256(d, 333)
-    for f in ("gf3329_add", "gf3329_sub", "gf3329_mul"):
-        getattr(ref, f).restype = C.c_uint16
-        getattr(ref, f).argtypes = [C.c_uint16, C.c_uint16]
-    ref.gf3329_inv.restype = C.c_uint16
-    ref.gf3329_inv.argtypes = [C.c_uint16]
-    ref.encode_to_gf3329.restype = C.c_uint16
-    ref.encode_to_gf3329.argtypes = [C.c_int16]
-    ref.decode_from_gf3329.restype = C.c_int16
-    ref.decode_from_gf3329.argtypes = [C.c_uint16]
+        if live:
+            ref.pqcrystals_kyber_fips202_ref_shake256(o1, C.c_size_t(333), C.c_char_p(d), C.c_size_t(n))
+        pins.add("shake256", o1 if live else None, oracle.shake256(d, 333))
+    if live:
+        for f in ("gf3329_add", "gf3329_sub", "gf3329_mul"):
+            getattr(ref, f).restype = C.c_uint16
+            getattr(ref, f).argtypes = [C.c_uint16, C.c_uint16]
+        ref.gf3329_inv.restype = C.c_uint16
+        ref.gf3329_inv.argtypes = [C.c_uint16]
+        ref.encode_to_gf3329.restype = C.c_uint16
+        ref.encode_to_gf3329.argtypes = [C.c_int16]
+        ref.decode_from_gf3329.restype = C.c_int16
+        ref.decode_from_gf3329.argtypes = [C.c_uint16]
     oracle.lib.ko_gf_encode.restype = C.c_uint16
     oracle.lib.ko_gf_encode.argtypes = [C.c_int16]
     oracle.lib.ko_gf_decode.restype = C.c_int16
     oracle.lib.ko_gf_decode.argtypes = [C.c_uint16]
     for a in list(range(0, 3329, 13)) + [3328]:
-        assert ref.gf3329_inv(a) == oracle.lib.ko_gf_inv(a)
-        assert ref.decode_from_gf3329(a) == oracle.lib.ko_gf_decode(a)
+        pins.add("gf3329_inv", ref.gf3329_inv(a) if live else None, oracle.lib.ko_gf_inv(a))
+        pins.add("decode_from_gf3329", ref.decode_from_gf3329(a) if live else None, oracle.lib.ko_gf_decode(a))
         for b in (0, 1, 1664, 1665, 3328, (a * 5 + 1) % 3329):
-            assert ref.gf3329_add(a, b) == oracle.lib.ko_gf_add(a, b)
-            assert ref.gf3329_sub(a, b) == oracle.lib.ko_gf_sub(a, b)
-            assert ref.gf3329_mul(a, b) == oracle.lib.ko_gf_mul(a, b)
+            pins.add("gf3329_add", ref.gf3329_add(a, b) if live else None, oracle.lib.ko_gf_add(a, b))
+            pins.add("gf3329_sub", ref.gf3329_sub(a, b) if live else None, oracle.lib.ko_gf_sub(a, b))
+            pins.add("gf3329_mul", ref.gf3329_mul(a, b) if live else None, oracle.lib.ko_gf_mul(a, b))
     for a in range(-1664, 1665, 7):
-        assert ref.encode_to_gf3329(a) == oracle.lib.ko_gf_encode(a)
+        pins.add("encode_to_gf3329", ref.encode_to_gf3329(a) if live else None, oracle.lib.ko_gf_encode(a))
+    pins.check()
 
 
 @pytest.mark.parametrize("k", [2, 3, 4])
@@ -118,45 +192,61 @@ def test_kyber_keygen_of_the_reference_on_its_own_randomness(k, oracle):
     """kosk.cpp:4-70 compiled in place, called as the reference's main.cpp:21-47 would (its own randombytes = OS entropy, so a
     different key every trial).  It hands both halves of hash_g back -- the public seed is pk[-32:] (kosk.cpp:58) and, the
     reference's quirk, the noise seed is sk's z (kosk.cpp:67-69) -- so everything after the sha3_512 is checked against the
-    oracle without touching randombytes: pk, sk (incl. H(pk) and the z quirk) and the raw A / s / e / t of mlwe_inst."""
+    oracle without touching randombytes: pk, sk (incl. H(pk) and the z quirk) and the raw A / s / e / t of mlwe_inst.
+    The keys of the recorded run (their two seeds and the digests of pk, sk and mlwe_inst) are checked the same way."""
     ref = _kosk_ref(k)
     p = oracle.params(k)
-    fn = ref._Z12kyber_keygenP13kyber_keypairP9mlwe_inst
-    fn.restype = None
-    fn.argtypes = [C.c_void_p, C.c_void_p]
     oracle.lib.ko_keygen_from_seeds.restype = None
     oracle.lib.ko_keygen_from_seeds.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
     inst_bytes = 512 * (k * k + 3 * k)  # mlwe_inst { polyvec A[K]; polyvec t, s, e; }  mlwe_prover.hpp:34-37 (layout test above)
-    seen = set()
-    for trial in range(20):
-        pair = C.create_string_buffer(p.pk_bytes + p.sk_bytes)  # kyber_keypair { pk[]; sk[]; }  kosk.hpp:13-16
-        inst = C.create_string_buffer(inst_bytes)
-        fn(pair, inst)
-        pk, sk = pair.raw[:p.pk_bytes], pair.raw[p.pk_bytes:]
-        assert pk not in seen  # the reference really drew fresh randomness
-        seen.add(pk)
-        pub, noise = pk[-32:], sk[-32:]
+
+    def from_seeds(pub, noise):
+        """the oracle's pk, sk and mlwe_inst image from the two halves of hash_g"""
         opk, osk = C.create_string_buffer(p.pk_bytes), C.create_string_buffer(p.sk_bytes)
         raw = oracle.Mlwe()
         oracle.lib.ko_keygen_from_seeds(k, pub, noise, opk, osk, C.byref(raw))
-        assert opk.raw == pk and osk.raw == sk
-        assert sk[384 * k:384 * k + p.pk_bytes] == pk and sk[-64:-32] == oracle.sha3_256(pk)
-        got = np.frombuffer(inst.raw, np.int16)
         A = np.ctypeslib.as_array(raw.A).reshape(4, 4, 256)[:k, :k].reshape(-1)
         t, s_, e = (np.ctypeslib.as_array(getattr(raw, n_)).reshape(4, 256)[:k].reshape(-1) for n_ in "tse")
-        assert np.array_equal(got[:k * k * 256], A)
-        assert np.array_equal(got[k * k * 256:(k * k + k) * 256], t)
-        assert np.array_equal(got[(k * k + k) * 256:(k * k + 2 * k) * 256], s_)
-        assert np.array_equal(got[(k * k + 2 * k) * 256:], e)
         assert int(np.abs(s_).max()) <= p.eta1 and int(np.abs(e).max()) <= p.eta1
+        return opk.raw, osk.raw, np.concatenate([A, t, s_, e]).astype(np.int16)
+    recorded = []
+    if ref is not None:
+        fn = ref._Z12kyber_keygenP13kyber_keypairP9mlwe_inst
+        fn.restype = None
+        fn.argtypes = [C.c_void_p, C.c_void_p]
+        seen = set()
+        for trial in range(20):
+            pair = C.create_string_buffer(p.pk_bytes + p.sk_bytes)  # kyber_keypair { pk[]; sk[]; }  kosk.hpp:13-16
+            inst = C.create_string_buffer(inst_bytes)
+            fn(pair, inst)
+            pk, sk = pair.raw[:p.pk_bytes], pair.raw[p.pk_bytes:]
+            assert pk not in seen  # the reference really drew fresh randomness
+            seen.add(pk)
+            pub, noise = pk[-32:], sk[-32:]
+            opk, osk, oinst = from_seeds(pub, noise)
+            assert opk == pk and osk == sk
+            assert sk[384 * k:384 * k + p.pk_bytes] == pk and sk[-64:-32] == oracle.sha3_256(pk)
+            got = np.frombuffer(inst.raw, np.int16)
+            assert np.array_equal(got[:k * k * 256], oinst[:k * k * 256])
+            assert np.array_equal(got[k * k * 256:(k * k + k) * 256], oinst[k * k * 256:(k * k + k) * 256])
+            assert np.array_equal(got[(k * k + k) * 256:(k * k + 2 * k) * 256], oinst[(k * k + k) * 256:(k * k + 2 * k) * 256])
+            assert np.array_equal(got[(k * k + 2 * k) * 256:], oinst[(k * k + 2 * k) * 256:])
+            recorded.append({"pub": pub.hex(), "noise": noise.hex(), "pk": _sha(pk), "sk": _sha(sk), "inst": _sha(inst)})
+    if RECORD:
+        PINS["keygen"][str(k)] = recorded
+    else:
+        stored = PINS["keygen"][str(k)]
+        assert len(stored) == 20
+        for t_ in stored:
+            opk, osk, oinst = from_seeds(bytes.fromhex(t_["pub"]), bytes.fromhex(t_["noise"]))
+            assert (_sha(opk), _sha(osk), _sha(oinst)) == (t_["pk"], t_["sk"], t_["inst"])
+            assert osk[384 * k:384 * k + p.pk_bytes] == opk and osk[-64:-32] == oracle.sha3_256(opk) and osk[-32:] == bytes.fromhex(t_["noise"])
     # the oracle's tape-driven keygen is the same function behind kosk.cpp:12-14's hash_g
     tape = oracle.tape_bytes_for(k, 7)
     g = oracle.sha3_512(tape[:32] + bytes([k]))
-    opk, osk = C.create_string_buffer(p.pk_bytes), C.create_string_buffer(p.sk_bytes)
-    raw = oracle.Mlwe()
-    oracle.lib.ko_keygen_from_seeds(k, g[:32], g[32:], opk, osk, C.byref(raw))
+    opk, osk, _ = from_seeds(g[:32], g[32:])
     pk2, sk2, _, _, _ = oracle.verifiable_keygen(k, tape)
-    assert (opk.raw, osk.raw) == (pk2, sk2)
+    assert (opk, osk) == (pk2, sk2)
 
 
 # ---- L2/L3 pieces of the reference that compile without the unmounted Lagrange tables -----------------------------
@@ -164,15 +254,22 @@ def test_kyber_keygen_of_the_reference_on_its_own_randomness(k, oracle):
 def _kosk_ref(k):
     path = os.path.join(ROOT, "oracle", "_ref", "libkosk_ref_k%d.so" % k)
     if not os.path.exists(path):
-        _no_ref(path)
+        return _no_ref(path)
     return C.CDLL(path, mode=os.RTLD_LAZY)  # get_precomputed_* stay unresolved (see the module docstring)
 
 
 def _layout(k):
     ref = _kosk_ref(k)
+    if ref is None:
+        return PINS["layouts"][str(k)]
     ref.ref_layout_name.restype = C.c_char_p
     ref.ref_layout_value.restype = C.c_size_t
-    return {ref.ref_layout_name(i).decode(): ref.ref_layout_value(i) for i in range(ref.ref_layout_count())}
+    L = {ref.ref_layout_name(i).decode(): ref.ref_layout_value(i) for i in range(ref.ref_layout_count())}
+    if RECORD:
+        PINS["layouts"][str(k)] = L
+    else:
+        assert L == PINS["layouts"][str(k)]
+    return L
 
 
 FIELD_NAMES = ["f_shares", "NTT_f_shares", "beta_shares", "gamma_shares", "Tcomm", "I", "s_shares", "e_shares", "t_shares",
@@ -232,6 +329,8 @@ class ShareVec(C.Structure):  # ss.hpp:33-37
 def test_shares_add_sub_mul(oracle):
     """ss.cpp:101-136 (compiled reference) against the oracle's lane ops, including the x-mismatch error return."""
     ref = _kosk_ref(3)
+    live = ref is not None
+    pins = Pins("shares_k3")
     rng = np.random.default_rng(5)
     oracle.lib.ko_gf_add.restype = oracle.lib.ko_gf_sub.restype = oracle.lib.ko_gf_mul.restype = C.c_uint16
     for trial in range(4):
@@ -244,11 +343,15 @@ def test_shares_add_sub_mul(oracle):
         # C++ linkage in the reference (ss.hpp declares them outside extern "C")
         for name, fn in (("_Z10shares_addP9share_vecPKS_S2_", oracle.lib.ko_gf_add), ("_Z10shares_subP9share_vecPKS_S2_", oracle.lib.ko_gf_sub),
                          ("_Z10shares_mulP9share_vecPKS_S2_", oracle.lib.ko_gf_mul)):
-            assert getattr(ref, name)(C.byref(r), C.byref(a), C.byref(b)) == 0
-            exp = [fn(int(x), int(y)) for x, y in zip(ya, yb)]
-            assert list(r.share_y) == exp and list(r.share_x) == list(a.share_x)
-    b.share_x[700] += 1
-    assert ref._Z10shares_addP9share_vecPKS_S2_(C.byref(r), C.byref(a), C.byref(b)) == -1  # error convention: -1 on mismatching x
+            exp = np.array([fn(int(x), int(y)) for x, y in zip(ya, yb)], np.uint16)
+            if live:
+                assert getattr(ref, name)(C.byref(r), C.byref(a), C.byref(b)) == 0
+                assert list(r.share_x) == list(a.share_x)
+            pins.add(name, np.array(r.share_y, np.uint16) if live else None, exp)
+    if live:
+        b.share_x[700] += 1
+        assert ref._Z10shares_addP9share_vecPKS_S2_(C.byref(r), C.byref(a), C.byref(b)) == -1  # error convention: -1 on mismatching x
+    pins.check()
 
 
 @pytest.mark.parametrize("k", [2, 3, 4])
@@ -256,19 +359,24 @@ def test_decode_and_encode_mpcith_proof(k, oracle):
     """mlwe_prover.cpp:540-630: decode copies field by field at the struct's offsets, encode is the struct image.  An
     oracle proof must survive decode -> encode unchanged, i.e. the oracle's wire layout is the reference's."""
     ref = _kosk_ref(k)
+    live = ref is not None
+    pins = Pins("proof_codec_k%d" % k)
     _, _, pi, _, _ = oracle.verifiable_keygen(k, oracle.tape_bytes_for(k, 1))
     st = C.create_string_buffer(len(pi))
-    ref._Z19decode_mpcith_proofP12mpcith_proofPKh(st, C.c_char_p(pi))
-    assert st.raw == pi
     out = C.create_string_buffer(len(pi))
-    ref._Z19encode_mpcith_proofPhPK12mpcith_proof(out, st)
-    assert out.raw == pi
+    if live:
+        ref._Z19decode_mpcith_proofP12mpcith_proofPKh(st, C.c_char_p(pi))
+        ref._Z19encode_mpcith_proofPhPK12mpcith_proof(out, st)
+    pins.add("decode", st if live else None, pi)
+    pins.add("encode", out if live else None, pi)
     # every field on its own: a buffer that holds 0x00.. except one field decodes to the same
     p = oracle.params(k)
     for i in (0, 4, 5, 8, 15, 21, 23):
         buf = bytearray(len(pi)); buf[p.off[i]:p.off[i] + p.size[i]] = pi[p.off[i]:p.off[i] + p.size[i]]
-        ref._Z19decode_mpcith_proofP12mpcith_proofPKh(st, C.c_char_p(bytes(buf)))
-        assert st.raw == bytes(buf)
+        if live:
+            ref._Z19decode_mpcith_proofP12mpcith_proofPKh(st, C.c_char_p(bytes(buf)))
+        pins.add("decode_field_%d" % i, st if live else None, bytes(buf))
+    pins.check()
 
 
 def test_lagrange_tables_against_the_reference_interpolation(oracle):
@@ -276,8 +384,11 @@ def test_lagrange_tables_against_the_reference_interpolation(oracle):
     poly_eval_from_points): table . y must equal the reference's interpolation of y evaluated at the table's points,
     for the three node sets (ss.cpp:26-27, :47, :66)."""
     ref = _kosk_ref(2)
-    fn = ref._Z21poly_eval_from_pointsPtPKtS1_tS1_t
-    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint16, C.c_void_p, C.c_uint16]
+    live = ref is not None
+    pins = Pins("lagrange")
+    if live:
+        fn = ref._Z21poly_eval_from_pointsPtPKtS1_tS1_t
+        fn.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint16, C.c_void_p, C.c_uint16]
     rng = np.random.default_rng(11)
     vp = C.c_void_p
     cases = [(0, np.arange(407), 407 + np.arange(1303)), (1, 256 + np.arange(407), np.arange(256)), (2, 256 + np.arange(813), np.arange(256))]
@@ -288,16 +399,19 @@ def test_lagrange_tables_against_the_reference_interpolation(oracle):
         e = np.zeros(len(nodes), np.uint16); e[len(nodes) // 3] = 1   # one unit vector = one full table column
         for y in ys + [e]:
             res = np.zeros(len(evalx), np.uint16)
-            fn(res.ctypes.data_as(vp), nodes.ctypes.data_as(vp), y.ctypes.data_as(vp), len(nodes) - 1, evalx.ctypes.data_as(vp), len(evalx))
-            assert np.array_equal(res.astype(np.int64), (T @ y.astype(np.int64)) % 3329)
+            if live:
+                fn(res.ctypes.data_as(vp), nodes.ctypes.data_as(vp), y.ctypes.data_as(vp), len(nodes) - 1, evalx.ctypes.data_as(vp), len(evalx))
+            pins.add("table_%d" % which, res if live else None, ((T @ y.astype(np.int64)) % 3329).astype(np.uint16))
     # and the oracle's replacement for NTL interpolate + eval agrees with the reference's interpolation on an I-like node set
     nodes = np.sort(rng.choice(np.arange(256, 1710), 407, replace=False)).astype(np.uint16)
     y = rng.integers(0, 3329, 407).astype(np.uint16)
     evalx = np.arange(407, dtype=np.uint16)
     r1, r2 = np.zeros(407, np.uint16), np.zeros(407, np.uint16)
-    fn(r1.ctypes.data_as(vp), nodes.ctypes.data_as(vp), y.ctypes.data_as(vp), 406, evalx.ctypes.data_as(vp), 407)
+    if live:
+        fn(r1.ctypes.data_as(vp), nodes.ctypes.data_as(vp), y.ctypes.data_as(vp), 406, evalx.ctypes.data_as(vp), 407)
     oracle.lib.ko_interp_eval(r2.ctypes.data_as(vp), 407, nodes.ctypes.data_as(vp), y.ctypes.data_as(vp), 407)
-    assert np.array_equal(r1, r2)
+    pins.add("interp_eval", r1 if live else None, r2)
+    pins.check()
 
 
 @pytest.mark.parametrize("k", [2, 3])
@@ -305,15 +419,20 @@ def test_preprocessed_randomness_codec(k, oracle):
     """mlwe_prover.cpp:61-79: encode is two memcpys; decode restores `rand` but forgets `eta_shares` (the quirk the
     product's decoder fixes)."""
     ref = _kosk_ref(k)
+    live = ref is not None
+    pins = Pins("randomness_codec_k%d" % k)
     img = oracle.main_order(k, oracle.tape_bytes_for(k, 2))
     buf = C.create_string_buffer(len(img["rand"]) + len(img["range"]))
-    ref._Z30encode_preprocessed_randomnessPhPK17mpcith_randomnessPK18mpcith_range_proof(buf, C.c_char_p(img["rand"]), C.c_char_p(img["range"]))
-    assert buf.raw == img["rand"] + img["range"]
+    if live:
+        ref._Z30encode_preprocessed_randomnessPhPK17mpcith_randomnessPK18mpcith_range_proof(buf, C.c_char_p(img["rand"]), C.c_char_p(img["range"]))
+    pins.add("encode", buf if live else None, img["rand"] + img["range"])
     r2 = C.create_string_buffer(len(img["rand"])); e2 = C.create_string_buffer(b"\xAA" * len(img["range"]), len(img["range"]))
-    ref._Z30decode_preprocessed_randomnessP17mpcith_randomnessP18mpcith_range_proofPKh(r2, e2, buf)
+    if live:
+        ref._Z30decode_preprocessed_randomnessP17mpcith_randomnessP18mpcith_range_proofPKh(r2, e2, buf)
     exp = bytearray(img["rand"])  # the decoder copies f, NTT_f, share_x, share_y -- not the (unused) share_vec.len words
     M = oracle.params(k).M
     for i in range(2 * M):
         exp[2 * M * 512 + i * 5824: 2 * M * 512 + i * 5824 + 8] = bytes(8)
-    assert r2.raw == bytes(exp)
-    assert e2.raw == b"\xAA" * len(img["range"])  # untouched: the reference's decoder never writes eta_shares
+    pins.add("decode_rand", r2 if live else None, bytes(exp))
+    pins.add("decode_range", e2 if live else None, b"\xAA" * len(img["range"]))  # untouched: the reference's decoder never writes eta_shares
+    pins.check()

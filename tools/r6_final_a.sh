@@ -3,12 +3,12 @@
 set -o pipefail
 O=gpurun_out/r6f
 mkdir -p $O
-python bench.py > $O/r06_bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
+python bench.py --full > $O/r06_bench_default.json 2> $O/bench_default.err || { tail -20 $O/bench_default.err; exit 1; }
 echo "default done"
-python bench.py --steps 20 --warmup 5 > $O/r06_bench_driver_flags.json 2> $O/bench_driver.err || { tail -20 $O/bench_driver.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_driver_flags.json 2> $O/bench_driver.err || { tail -20 $O/bench_driver.err; exit 1; }
 echo "driver flags done"
 for c in 2 4 5; do
-  python bench.py --config $c --no-kernels --no-cpu-baseline > $O/r06_bench_config$c.json 2> $O/bench_c$c.err || { tail -20 $O/bench_c$c.err; exit 1; }
+  python bench.py --full --config $c --no-kernels --no-cpu-baseline > $O/r06_bench_config$c.json 2> $O/bench_c$c.err || { tail -20 $O/bench_c$c.err; exit 1; }
   echo "config $c done"
 done
 python tools/latency_one.py > $O/r06_latency_one.txt 2>&1 || exit 1

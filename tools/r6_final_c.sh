@@ -6,10 +6,10 @@ mkdir -p $O
 timeout -k 10 1000 python -m pytest tests -x -q -m gpu > $O/r06_gputest.log 2>&1 || { tail -40 $O/r06_gputest.log; exit 1; }
 tail -2 $O/r06_gputest.log
 SECONDS=0
-python bench.py --steps 20 --warmup 5 > $O/r06_bench_driver_flags_2.json 2> $O/bench_driver2.err || { tail -20 $O/bench_driver2.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $O/r06_bench_driver_flags_2.json 2> $O/bench_driver2.err || { tail -20 $O/bench_driver2.err; exit 1; }
 echo "driver-flags bench wall time: $SECONDS s"
 SECONDS=0
-python bench.py > $O/r06_bench_default_2.json 2> $O/bench_default2.err || { tail -20 $O/bench_default2.err; exit 1; }
+python bench.py --full > $O/r06_bench_default_2.json 2> $O/bench_default2.err || { tail -20 $O/bench_default2.err; exit 1; }
 echo "default bench wall time: $SECONDS s"
 python - <<'PY'
 import json, glob

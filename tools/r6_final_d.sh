@@ -5,8 +5,8 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 O=gpurun_out/r6f; mkdir -p $O
 python -m pytest tests/test_sharding.py tests/test_gpu_11_fs_device.py -m gpu -x -q 2>&1 | tail -3 || exit 1
-python bench.py --steps 20 --warmup 5 > $O/r06c_bench_driver_flags.json 2> $O/d.err || { tail -10 $O/d.err; exit 1; }
-python bench.py --fs device --no-cpu-baseline > $O/r06c_bench_fs_device.json 2> $O/d.err || { tail -10 $O/d.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $O/r06c_bench_driver_flags.json 2> $O/d.err || { tail -10 $O/d.err; exit 1; }
+python bench.py --full --fs device --no-cpu-baseline > $O/r06c_bench_fs_device.json 2> $O/d.err || { tail -10 $O/d.err; exit 1; }
 python - <<'PY'
 import json
 for f in ("gpurun_out/r6f/r06c_bench_driver_flags.json", "gpurun_out/r6f/r06c_bench_fs_device.json"):

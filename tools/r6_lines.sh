@@ -4,8 +4,8 @@ set -o pipefail
 cd "$(dirname "$0")/.."
 O=gpurun_out/r6f; mkdir -p $O
 tag=${1:-x}
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/line_driver_$tag.json 2> $O/line.err || { tail -5 $O/line.err; exit 1; }
-python bench.py --no-cpu-baseline > $O/line_default_$tag.json 2> $O/line.err || { tail -5 $O/line.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/line_driver_$tag.json 2> $O/line.err || { tail -5 $O/line.err; exit 1; }
+python bench.py --full --no-cpu-baseline > $O/line_default_$tag.json 2> $O/line.err || { tail -5 $O/line.err; exit 1; }
 python - $O/line_driver_$tag.json $O/line_default_$tag.json <<'PY'
 import json, sys
 for f in sys.argv[1:]:

@@ -5,7 +5,7 @@ O=gpurun_out/r6
 mkdir -p $O
 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/gputest2.log 2>&1 || { tail -40 $O/gputest2.log; exit 1; }
 tail -3 $O/gputest2.log
-python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err || { tail -20 $O/bench_driver_flags.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2> $O/bench_driver_flags.err || { tail -20 $O/bench_driver_flags.err; exit 1; }
 python - <<'PY'
 import json
 j = json.loads([l for l in open("gpurun_out/r6/bench_driver_flags.json") if l.startswith("{")][-1])
