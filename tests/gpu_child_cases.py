@@ -7,6 +7,7 @@ with its stderr in the report, not the end of the pytest process and of every te
 import os
 
 from tests import oracle_lib as oracle
+from tests import oracle_pins
 
 
 def _kosk(k, max_batch, **kw):
@@ -164,6 +165,12 @@ def pinned_buffers(k):
     print("pinned_buffers ok", k)
 
 
+def _tables(blob, n):
+    """a digest table fetched as bytes -> [n][1454][32]"""
+    import numpy as np
+    return np.frombuffer(blob, np.uint8).reshape(n, 1454, 32)
+
+
 def big_batches():
     """The batch shapes of BASELINE configs[2..4] through the host-buffer calls (chunked: n above the context's capacity), the
     resident split, the compact staging and the second-level entry points, in one fresh process."""
@@ -174,10 +181,13 @@ def big_batches():
         pks, sks, pis = ctx.verifiable_keygen(tapes)
         opk, osk, opi, _, _ = oracle.verifiable_keygen(k, tapes[n - 1])
         assert (pks[-1], sks[-1], pis[-1]) == (opk, osk, opi)
+        oracle_pins.assert_batch(k, range(1000, 1000 + n), pks, sks, pis, what="host-buffer call K=%d n=%d" % (k, n))
         assert ctx.verify(pis, pks) == [True] * n
         m = min(n, 91)
         ctx.verifiable_keygen_resident(tapes[:m])
         assert ctx.verify_resident_pk(m) == [True] * m
+        rpk, rsk = ctx.keys(m)
+        oracle_pins.assert_batch(k, range(1000, 1000 + m), rpk, rsk, ctx.fetch_proofs(m), what="resident call K=%d n=%d" % (k, m))
         blobs = ctx.fetch_proofs_compact(m)
         ctx.stage_verifier_inputs_compact(blobs, pks[:m])
         assert ctx.verify_resident(m) == [True] * m
@@ -196,7 +206,8 @@ def combined_calls(k, threads=6, rounds=4, min_merge=0.5):
     """combine=3: six caller threads, each with its own handle and its own small resident calls.  The calls of a cohort's
     members are served by merged pipeline runs; every caller must get exactly what an uncombined handle gives it -- pk, sk, proof
     images, resident digest tables, verify bits and fail masks byte for byte -- with host tapes, device tapes read by a merged
-    run, a short (ragged) batch on one member, and given / resident public keys.  The oracle pins three of the proofs."""
+    run, a short (ragged) batch on one member, and given / resident public keys.  The oracle checks three of the proofs, its pinned
+    digests (tests/oracle_pins.py) every key, proof and digest table."""
     import ctypes as C
     import threading
     import torch
@@ -222,6 +233,11 @@ def combined_calls(k, threads=6, rounds=4, min_merge=0.5):
     for (t, r) in ((0, 0), (threads - 1, 1), (2, rounds - 1)):
         opk, osk, opi, _, _ = oracle.verifiable_keygen(k, tapes[t, r][-1])
         assert (want[t, r][0][-1], want[t, r][1][-1], want[t, r][2][-1]) == (opk, osk, opi)
+    # every position of every (caller, round) against the oracle's pins: what each caller is compared with below
+    for (t, r), w in want.items():
+        idx = [5000 + (t * rounds + r) * per + b for b in range(len(tapes[t, r]))]
+        oracle_pins.assert_batch(k, idx, w[0], w[1], w[2], what="caller %d round %d" % (t, r))
+        oracle_pins.assert_tables(k, idx, _tables(w[3][0], len(idx)), _tables(w[3][1], len(idx)), what="tables of caller %d round %d" % (t, r))
     errs = []
     barrier = threading.Barrier(threads)
 
@@ -307,7 +323,8 @@ def line_of_record_shape(k=3, per=46, callers=3, rounds=3, fs_device=0):
     resident for the verifier (pk == NULL) -- so every launch covers 138 proofs: the single-buffer instantiation of the commitment
     hash (3 174 waves), three rounds of row blocks in the expansion product.  Every caller's pk / sk / proof images / both digest
     tables equal an uncombined handle's, the first and last proof of every caller equal the oracle's, and the digest tables of
-    those proofs equal the oracle's Tcomm / view commitments."""
+    those proofs equal the oracle's Tcomm / view commitments; every position of every caller and round (keys, images, both digest tables)
+    equals the oracle's pinned digests (tests/oracle_pins.py)."""
     import ctypes as C
     import threading
     import numpy as np
@@ -337,6 +354,11 @@ def line_of_record_shape(k=3, per=46, callers=3, rounds=3, fs_device=0):
         assert plain.verify_resident_pk(per) == [True] * per
         want[key] = (pk, sk, plain.fetch_proofs(per),
                      [torch.as_tensor(plain.resident_digests(i, per), device="cuda").cpu().numpy().tobytes() for i in (0, 1)])
+    # every position of every (caller, round) against the oracle's pins: what each caller is compared with below
+    for (t, r), w in want.items():
+        idx = [20000 + ((t * nsets) + r) * per + b for b in range(per)]
+        oracle_pins.assert_batch(k, idx, w[0], w[1], w[2], what="caller %d round %d" % (t, r))
+        oracle_pins.assert_tables(k, idx, _tables(w[3][0], per), _tables(w[3][1], per), what="tables of caller %d round %d" % (t, r))
     # the oracle on the first and the last proof of every caller (last round): images, keys and both digest tables
     for t in range(callers):
         for b in (0, per - 1):
@@ -410,11 +432,13 @@ def member_big_batch_stays_in_its_block(k=3, per=3):
     n_big = 2 * per + 1
     big_tapes = [oracle.tape_bytes_for(k, 7000 + b) for b in range(n_big)]
     want_big = plain.verifiable_keygen(big_tapes)
+    oracle_pins.assert_batch(k, range(7000, 7000 + n_big), *want_big, what="member 0")
     nb_tapes = {t: [oracle.tape_bytes_for(k, 7100 + t * per + b) for b in range(per)] for t in (1, 2)}
     want_nb = {}
     for t in (1, 2):
         plain.verifiable_keygen_resident(nb_tapes[t])
         want_nb[t] = (plain.keys(per), plain.fetch_proofs(per))
+        oracle_pins.assert_batch(k, range(7100 + t * per, 7100 + (t + 1) * per), *want_nb[t][0], want_nb[t][1], what="neighbour %d" % t)
     errs, stop = [], threading.Event()
 
     def neighbour(t):
@@ -474,6 +498,7 @@ def cohort_round_hooks(k=2, per=3, rounds=4):
         plain.verifiable_keygen_resident(tapes[t])
         want.append((plain.keys(ns[t]), plain.fetch_proofs(ns[t]),
                      [hashlib.sha3_256(torch.as_tensor(plain.resident_digests(r, ns[t]), device="cuda").cpu().numpy().tobytes()).hexdigest() for r in (0, 1)]))
+        oracle_pins.assert_batch(k, range(9500 + t * per, 9500 + t * per + ns[t]), *want[t][0], want[t][1], what="caller %d" % t)
     hs = [_kosk(k, per, combine=3, combine_wait_us=2000000, combine_idle_us=1000000),
           _kosk(k, per, combine=3, combine_wait_us=2000000, combine_idle_us=1000000),
           _kosk(k, per, combine=3, combine_wait_us=2000000, combine_idle_us=1000000, hooks_unmerged=1)]
@@ -537,9 +562,10 @@ def combined_members_come_and_go(k):
     mk = lambda: _kosk(k, per, combine=3, combine_wait_us=100000, combine_idle_us=50000)
     tapes = [[oracle.tape_bytes_for(k, 9000 + t * per + b) for b in range(per)] for t in range(5)]
     want = []
-    for tp in tapes:
+    for t, tp in enumerate(tapes):
         plain.verifiable_keygen_resident(tp)
         want.append((plain.keys(per), plain.fetch_proofs(per)))
+        oracle_pins.assert_batch(k, range(9000 + t * per, 9000 + (t + 1) * per), *want[t][0], want[t][1], what="tape set %d" % t)
 
     def round_of(handles, idx):
         """every handle of `handles` (list of (handle, tape set)) does keygen + verify concurrently; returns nothing, asserts bytes"""

@@ -88,6 +88,10 @@ def test_commit_hash_column_layout(k, with_prefix, torch, oracle):
     for l in list(range(0, n, 97)) + [n - 1]:
         msg = (prefix[l].tobytes() if with_prefix else b"") + rows[:, l].astype("<u2").tobytes()
         assert out[l].tobytes() == hashlib.sha3_256(msg).digest(), l
+    # every lane
+    cols = np.ascontiguousarray(rows[:, :n].T).astype("<u2")
+    bad = [l for l in range(n) if out[l].tobytes() != hashlib.sha3_256((prefix[l].tobytes() if with_prefix else b"") + cols[l].tobytes()).digest()]
+    assert not bad, ("lanes whose digest differs from hashlib", len(bad), bad[:32])
     c.close()
 
 
@@ -105,8 +109,17 @@ def test_ntt256_matches_oracle(torch, ctx, oracle):
     out = d_out.cpu().numpy()
     for i in list(range(0, n, 37)) + [0, 1, 2, 3, n - 1]:
         assert np.array_equal(out[i], oracle.poly_ntt(a[i])), i
+    bad = [i for i in range(n) if not np.array_equal(out[i], oracle.poly_ntt(a[i]))]   # every polynomial
+    assert not bad, ("polynomials that differ from the oracle", len(bad), bad[:32])
     assert out.min() >= -1664 and out.max() <= 1664
 
+
+def expand_exact(oracle, y):
+    """oracle.recompute_shares on every row of y ([n][407] values in [0, q)): shares 0..150 are y[:, 256:407], shares 151..1453 the
+    product with the oracle's share table mod q"""
+    tab = oracle.table(0).astype(np.float64)                       # [1303][407]
+    rest = np.mod(y.astype(np.float64) @ tab.T, 3329).astype(np.uint16)
+    return np.concatenate([y[:, 256:407], rest], axis=1)
 
 
 @pytest.mark.parametrize("n", [300, 9982])  # 9 982 rows = 46 proofs: every wave walks 10-11 table chunks (the pipelined epilogue's steady state)
@@ -128,6 +141,13 @@ def test_lagrange_expand_and_recon_match_oracle(n, torch, ctx, oracle):
     sec = d_sec.cpu().numpy().view(np.uint16)
     for i in list(range(0, n, 29 if n < 1000 else 499)) + [0, 1, 2, 3, 4, n - 1]:
         assert np.array_equal(sh[i], oracle.recompute_shares(y[i])), i
+    # every row: the oracle's expansion as one exact float64 product (407 * 3328^2 < 2^53: every partial sum is an exact integer),
+    # itself pinned against oracle.recompute_shares on the sampled rows first
+    want = expand_exact(oracle, y)
+    for i in (0, 1, 2, 3, 4, n // 2, n - 1):
+        assert np.array_equal(want[i], oracle.recompute_shares(y[i])), i
+    bad = np.flatnonzero((sh != want).any(axis=1))
+    assert not bad.size, ("rows that differ from the oracle's expansion", bad.size, bad[:32].tolist())
     # encode -> erase -> decode round trip on every row: the packed secrets come back
     assert np.array_equal(sec, y[:, :256])
     # degree-2d reconstruction of share-wise products = product of the packed secrets

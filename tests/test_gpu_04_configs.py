@@ -1,11 +1,14 @@
 """BASELINE.json configs[3] and configs[4] at their per-GPU sizes, and the resident one-call entry points bench.py times
 (kosk_verifiable_keygen_resident / kosk_verify_resident_pk), against the CPU oracle: every verify bit, spot proofs byte
-for byte, the digest tables a multi-GPU job all-gathers (kosk_resident_digests, kosk_set_round_hook)."""
+for byte, every key and proof against the oracle's pinned digests (tests/oracle_pins.py), the digest tables a multi-GPU job
+all-gathers (kosk_resident_digests, kosk_set_round_hook)."""
 import ctypes as C
 import hashlib
 
 import numpy as np
 import pytest
+
+from tests import oracle_pins
 
 pytestmark = pytest.mark.gpu
 
@@ -86,20 +89,26 @@ def test_config4_kyber1024_91_proofs_and_digest_tables(fs, oracle, torch_cuda):
 
     def hook(role, rnd, ptr, nbytes):
         t = torch.as_tensor(api.DeviceView(ptr, (n, 1454, 32)), device="cuda")
-        seen.append((role, rnd, nbytes, t[[0, 45, 90]].cpu().numpy().copy()))
+        seen.append((role, rnd, nbytes, t.cpu().numpy().copy()))
     ctx.set_round_hook(hook)
     ctx.verifiable_keygen_resident(tapes)
     assert [(s[0], s[1], s[2]) for s in seen] == [(0, 0, n * 1454 * 32), (0, 1, n * 1454 * 32)]
     tables = [torch.as_tensor(ctx.resident_digests(r, n), device="cuda").cpu().numpy().copy() for r in (0, 1)]
     assert tables[0].shape == (n, 1454, 32)
-    for j, (b, pi, tr, p) in enumerate(_spot_check(ctx, oracle, k, tapes, n, (0, 45, 90))):
+    for b, pi, tr, p in _spot_check(ctx, oracle, k, tapes, n, (0, 45, 90)):
         tc = np.frombuffer(bytes(tr.tcomm), np.uint8).reshape(1454, 32)
         vw = np.frombuffer(bytes(tr.view_digest), np.uint8).reshape(1454, 32)
         assert np.array_equal(tables[0][b], tc) and np.array_equal(tables[1][b], vw)
-        assert np.array_equal(seen[0][3][j], tc) and np.array_equal(seen[1][3][j], vw)   # complete when the hook fires
+        assert np.array_equal(seen[0][3][b], tc) and np.array_equal(seen[1][3][b], vw)   # complete when the hook fires
         # sha3_256(Tcomm[0..N)) / sha3_256(ch_seeds) of mlwe_prover.cpp:130-135, :445-449 from the gathered bytes
         assert hashlib.sha3_256(tables[0][b].tobytes()).digest() == bytes(tr.h1)
         assert hashlib.sha3_256(tables[1][b].tobytes()).digest() == bytes(tr.ch)
+    # every position: keys, proofs and both digest tables (resident, and as the hooks saw them) against the oracle's pins
+    idx = [2000 + b for b in range(n)]
+    pks, sks = ctx.keys(n)
+    oracle_pins.assert_batch(k, idx, pks, sks, ctx.fetch_proofs(n))
+    oracle_pins.assert_tables(k, idx, tables[0], tables[1])
+    oracle_pins.assert_tables(k, idx, seen[0][3], seen[1][3], what="digest tables at the round hooks")
     assert ctx.verify_resident_pk(n) == [True] * n
     assert [(s[0], s[1]) for s in seen[2:]] == [(1, 0), (1, 1)]
     # the verifier rebuilds the same tables (opened digests recomputed, the others taken from the proofs)
@@ -121,9 +130,10 @@ def test_config5_kyber768_512_keygens(fs, oracle, torch_cuda):
         pass
     assert hashlib.sha3_256(ctx.fetch_proofs(1)[0]).hexdigest() == "3c8192372ced98f0eb195db9dd2e68afcddddd9762a565baa6fea85504decec1"
     assert ctx.verify_resident_pk(n) == [True] * n
-    # a tampered proof inside the big batch is the only one rejected
     pis = ctx.fetch_proofs(n)
-    pks, _ = ctx.keys(n)
+    pks, sks = ctx.keys(n)
+    oracle_pins.assert_batch(k, range(n), pks, sks, pis)   # every position
+    # a tampered proof inside the big batch is the only one rejected
     bad = bytearray(pis[300]); bad[api.proof_field(k, 13)[0] + 7] ^= 2
     pis[300] = bytes(bad)
     ok = ctx.verify(pis, pks)

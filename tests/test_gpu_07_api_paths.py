@@ -1,6 +1,8 @@
 """GPU tests of the API paths around the kernels: randomness sources, context reuse, no stale state."""
 import pytest
 
+from tests import oracle_pins
+
 pytestmark = pytest.mark.gpu
 
 
@@ -73,7 +75,7 @@ def test_fresh_context_verifies_foreign_proofs_without_stale_state(oracle, torch
 
 
 def test_larger_batch_and_bench_shape(oracle, torch_cuda):
-    """64 proofs in one call (> 46 of the bench, ragged against every tile size), spot-checked against the oracle."""
+    """64 proofs in one call (> 46 of the bench, ragged against every tile size), three proofs against the oracle, every one against its pinned digests."""
     from mpcith_kyber_kosk_amd import api
     k = 3
     n = 64
@@ -84,6 +86,7 @@ def test_larger_batch_and_bench_shape(oracle, torch_cuda):
     for b in (0, 31, 63):
         opk, osk, opi, _, _ = oracle.verifiable_keygen(k, tapes[b])
         assert (pks[b], sks[b], pis[b]) == (opk, osk, opi)
+    oracle_pins.assert_batch(k, range(100, 100 + n), pks, sks, pis)   # every position
     assert len(set(pis)) == n
     ctx.close()
 

@@ -1,10 +1,13 @@
 """Parity at BASELINE.json's sizes: configs[1] (Kyber-512, 46 proofs = 66 884 party lanes) end to end, and the graded kernel
 entry points at exactly 65 536 lanes / 65 536 polynomials for K = 2 and K = 3, checked on
-sampled lanes against hashlib / the oracle -- the same helpers bench.py's 65 536-lane leg asserts with."""
+every lane against hashlib / the oracle (sampled lanes first: the same helpers bench.py's 65 536-lane leg asserts with), every proof
+against the oracle's pinned digests (tests/oracle_pins.py)."""
 import hashlib
 
 import numpy as np
 import pytest
+
+from tests import oracle_pins
 
 pytestmark = pytest.mark.gpu
 
@@ -55,13 +58,23 @@ def test_commit_hash_at_65536_lanes(k, torch_cuda, oracle):
         t = hashlib.sha3_256(rows[:tc_words, l].astype("<u2").tobytes()).digest()
         assert tc[l].tobytes() == t, l
         assert vw[l].tobytes() == hashlib.sha3_256(t + rows[:, l].astype("<u2").tobytes()).digest(), l
+    # every lane
+    cols = np.ascontiguousarray(rows.T).astype("<u2")
+    bad_tc, bad_vw = [], []
+    for l in range(LANES):
+        t = hashlib.sha3_256(cols[l, :tc_words].tobytes()).digest()
+        if tc[l].tobytes() != t:
+            bad_tc.append(l)
+        if vw[l].tobytes() != hashlib.sha3_256(t + cols[l].tobytes()).digest():
+            bad_vw.append(l)
+    assert not bad_tc and not bad_vw, ("lanes that differ from hashlib", len(bad_tc), bad_tc[:32], len(bad_vw), bad_vw[:32])
     # size-independent property: every digest differs from its neighbours' (no lane wrote another lane's slot)
     assert len({bytes(x) for x in vw[::257]}) == len(vw[::257])
     c.close()
 
 
 def test_ntt256_at_65536_polynomials(torch_cuda, oracle):
-    """kosk_ntt256_batch on 65 536 polynomials (ntt.c:80-95 + poly.c:261-265), sampled against the oracle's poly_ntt, plus
+    """kosk_ntt256_batch on 65 536 polynomials (ntt.c:80-95 + poly.c:261-265), every one against the oracle's poly_ntt, plus
     linearity over the whole batch: NTT(a) + NTT(b) == NTT(a + b) mod q."""
     torch = torch_cuda
     from mpcith_kyber_kosk_amd import api
@@ -79,6 +92,8 @@ def test_ntt256_at_65536_polynomials(torch_cuda, oracle):
         outs.append(d_out.cpu().numpy())
     for i in sample_lanes(LANES):
         assert np.array_equal(outs[0][i], oracle.poly_ntt(a[i])), i
+    bad = [i for i in range(LANES) if not np.array_equal(outs[0][i], oracle.poly_ntt(a[i]))]   # every polynomial
+    assert not bad, ("polynomials that differ from the oracle", len(bad), bad[:32])
     assert outs[0].min() >= -1664 and outs[0].max() <= 1664
     lin = (outs[0].astype(np.int32) + outs[1] - outs[2]) % 3329
     assert not lin.any()
@@ -87,7 +102,7 @@ def test_ntt256_at_65536_polynomials(torch_cuda, oracle):
 
 def test_config2_kyber512_46_proofs(oracle, torch_cuda):
     """BASELINE.json configs[1]: K = 2, 46 proofs = 66 884 party lanes in one batch.  Every verify bit, three proofs byte for
-    byte against the oracle, the reference-recorded digest of proof 0 (tape "kosk-tape-v1:0")."""
+    byte against the oracle and every pk / sk / proof against its pinned digests, the reference-recorded digest of proof 0 (tape "kosk-tape-v1:0")."""
     from mpcith_kyber_kosk_amd import api
     k, n = 2, 46
     ctx = api.Kosk(kyber_k=k, max_batch=n)
@@ -101,6 +116,7 @@ def test_config2_kyber512_46_proofs(oracle, torch_cuda):
     for b in (0, 22, 45):
         opk, osk, opi, _, _ = oracle.verifiable_keygen(k, tapes[b])
         assert pks[b] == opk and sks[b] == osk and pis[b] == opi, b
+    oracle_pins.assert_batch(k, range(n), pks, sks, pis)   # every position
     assert ctx.verify_resident_pk(n) == [True] * n
     # the drop-in calls on host buffers give the same bytes and bits; one tampered proof in the middle is the only reject
     pks2, sks2, pis2 = ctx.verifiable_keygen(tapes)
