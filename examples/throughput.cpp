@@ -8,8 +8,12 @@
 // `native_callers` next to `value`, never instead of it.
 //   hipcc -std=c++17 -O2 -Iinclude examples/throughput.cpp -Lmpcith_kyber_kosk_amd -lkosk_mi355x -Wl,-rpath,'$ORIGIN/../mpcith_kyber_kosk_amd' -lpthread -o examples/throughput
 //   examples/throughput [--k 3] [--batch 46] [--callers 18] [--combine 6] [--fs host|device] [--threads 3] [--steps 3600] [--warmup 180]
-//                       [--tape-sets 4] [--device 0] [--blocking 0|1]
+//                       [--tape-sets 4] [--device 0] [--blocking 0|1] [--entropy bank|seed|os|os-seed]
 // Prints ONE JSON line.  Tapes: SHAKE256("kosk-tape-v1:<index>") as in bench.py (tapes_for), resident in HBM before the timed run.
+// --entropy: where a proof's randomness comes from.  bank (default): the resident tape banks, as above.  seed: seeded proving --
+// kosk_verifiable_keygen_seeded_resident with fresh 32-byte host seeds per call from a cheap counter (a throughput harness: NOT how a
+// real caller makes seeds).  os: tapes = NULL, the library draws whole tapes from OS entropy in the reference's call sequence.
+// os-seed: tapes = NULL after kosk_set_entropy(KOSK_ENTROPY_SEED): one 32-byte draw per proof.
 #include <hip/hip_runtime.h>
 #include <sys/resource.h>
 
@@ -43,7 +47,8 @@ static double cpu_s()
 struct Caller {
     kosk_ctx *h = nullptr;
     uint8_t *bank = nullptr; // device: [nsets][B][stride]
-    std::vector<uint8_t> pk, sk, ok;
+    std::vector<uint8_t> pk, sk, ok, seeds;
+    uint64_t seed_ctr = 0;
     long steps = 0;
     double t_prove = 0, t_verify = 0;
 };
@@ -51,7 +56,7 @@ struct Caller {
 int main(int argc, char **argv)
 {
     int k = 3, B = 46, S = 18, CMB = 6, threads = 3, steps = 3600, warmup = 180, nsets = 4, device = 0, blocking = -1;
-    std::string fs = "host";
+    std::string fs = "host", entropy = "bank";
     for (int i = 1; i + 1 < argc; i += 2) {
         const std::string a = argv[i];
         const char *v = argv[i + 1];
@@ -66,9 +71,12 @@ int main(int argc, char **argv)
         else if (a == "--device") device = atoi(v);
         else if (a == "--blocking") blocking = atoi(v);
         else if (a == "--fs") fs = v;
+        else if (a == "--entropy") entropy = v;
         else DIE("unknown argument %s", a.c_str());
     }
     if (k < 2 || k > 4 || B < 1 || S < 1 || CMB < 1 || nsets < 1 || steps < 1) DIE("bad arguments");
+    if (entropy != "bank" && entropy != "seed" && entropy != "os" && entropy != "os-seed") DIE("--entropy bank|seed|os|os-seed");
+    const bool bank = entropy == "bank";
     HIPOK(hipSetDevice(device));
     const size_t tape_bytes = kosk_tape_bytes(k), stride = (tape_bytes + 63) / 64 * 64;
     const size_t pkb = kosk_pk_bytes(k), skb = kosk_sk_bytes(k);
@@ -84,6 +92,13 @@ int main(int argc, char **argv)
         o.host_threads = threads;
         o.blocking_sync = blocking;
         if (kosk_create_ex(&cs[s].h, device, k, B, &o)) DIE("kosk_create_ex: %s", kosk_last_error(nullptr));
+        cs[s].pk.resize(pkb * B); cs[s].sk.resize(skb * B); cs[s].ok.assign((size_t)B, 0);
+        if (!bank) {
+            if (entropy == "os-seed" && kosk_set_entropy(cs[s].h, KOSK_ENTROPY_SEED)) DIE("kosk_set_entropy: %s", kosk_last_error(cs[s].h));
+            cs[s].seeds.assign((size_t)B * KOSK_SEED_BYTES, 0);
+            cs[s].seed_ctr = (uint64_t)s << 40;
+            continue;
+        }
         std::vector<uint8_t> host((size_t)nsets * B * stride, 0);
         for (int t = 0; t < nsets; t++)
             for (int b = 0; b < B; b++) {
@@ -93,13 +108,20 @@ int main(int argc, char **argv)
             }
         HIPOK(hipMalloc(reinterpret_cast<void **>(&cs[s].bank), host.size()));
         HIPOK(hipMemcpy(cs[s].bank, host.data(), host.size(), hipMemcpyHostToDevice));
-        cs[s].pk.resize(pkb * B); cs[s].sk.resize(skb * B); cs[s].ok.assign((size_t)B, 0);
     }
     HIPOK(hipDeviceSynchronize());
 
     auto step = [&](Caller &c, long index) {
         const double t0 = now_s();
-        if (kosk_verifiable_keygen_resident(c.h, B, c.bank + (size_t)(index % nsets) * B * stride, stride, c.pk.data(), c.sk.data()))
+        if (entropy == "seed") { // fresh seeds per call: a counter in the first eight bytes of each
+            for (int b = 0; b < B; b++) {
+                const uint64_t v = ++c.seed_ctr;
+                memcpy(&c.seeds[(size_t)b * KOSK_SEED_BYTES], &v, sizeof v);
+            }
+            if (kosk_verifiable_keygen_seeded_resident(c.h, B, c.seeds.data(), KOSK_SEED_BYTES, c.pk.data(), c.sk.data()))
+                DIE("kosk_verifiable_keygen_seeded_resident: %s", kosk_last_error(c.h));
+        } else if (kosk_verifiable_keygen_resident(c.h, B, bank ? c.bank + (size_t)(index % nsets) * B * stride : nullptr, bank ? stride : 0,
+                                                   c.pk.data(), c.sk.data()))
             DIE("kosk_verifiable_keygen_resident: %s", kosk_last_error(c.h));
         const double t1 = now_s();
         if (kosk_verify_resident_pk(c.h, B, nullptr, c.ok.data())) DIE("kosk_verify_resident_pk: %s", kosk_last_error(c.h));
@@ -174,11 +196,12 @@ int main(int argc, char **argv)
            "\"callers\": %d, \"handles_per_cohort\": %d, \"fiat_shamir\": \"%s\", \"host_threads_per_caller\": %d, \"steps\": %ld, \"warmup\": %ld, "
            "\"proofs_per_s\": %.1f, \"ms_per_step\": %.5f, \"drained_proofs_per_s\": %.1f, \"step_latency_ms\": {\"median\": %.3f, \"p99\": %.3f, \"max\": %.3f, "
            "\"mean_in_keygen_call\": %.3f, \"mean_in_verify_call\": %.3f}, \"host_cpu_cores_busy\": %.2f, \"mean_callers_per_run\": %.2f, "
-           "\"fs_rounds_on_device\": %ld, \"fs_rounds_on_host\": %ld, \"every_verify_bit_asserted\": true}\n",
+           "\"fs_rounds_on_device\": %ld, \"fs_rounds_on_host\": %ld, \"every_verify_bit_asserted\": true%s}\n",
            S, k, B, S, CMB, fs.c_str(), threads, K, W, (double)K * B / dt, dt / (double)K * 1e3, (double)total * B / (t_e - t_s),
            lat[lat.size() / 2] * 1e3, lat[(size_t)((double)lat.size() * 0.99)] * 1e3, lat.back() * 1e3, tp / (double)std::max(1L, st) * 1e3,
-           tv / (double)std::max(1L, st) * 1e3, (cpu1 - cpu0) / std::max(t_e - t_s, 1e-9), calls ? (double)members / (double)calls : 0.0, fs_dev, fs_host);
+           tv / (double)std::max(1L, st) * 1e3, (cpu1 - cpu0) / std::max(t_e - t_s, 1e-9), calls ? (double)members / (double)calls : 0.0, fs_dev, fs_host,
+           bank ? "" : (std::string(", \"entropy\": \"") + entropy + "\"").c_str());
     fflush(stdout);
-    for (auto &c : cs) { kosk_destroy(c.h); (void)hipFree(c.bank); }
+    for (auto &c : cs) { kosk_destroy(c.h); if (c.bank) (void)hipFree(c.bank); }
     return 0;
 }

@@ -96,6 +96,11 @@ inline kosk_ctx *ctx()
             abort(); /* the reference has no error channel either (randombytes.c:49-52 aborts) */
         }
         kosk_set_randombytes(h, rb_tramp, nullptr);
+#ifdef KOSK_COMPAT_SEEDED
+        /* seeded proving: ONE 32-byte randombytes call per proof, the tape expanded on the GPU (kosk_mi355x.h).  Off by default: the
+         * call sequence -- and with a deterministic randombytes the proofs -- then differ from the reference's */
+        kosk_set_entropy(h, KOSK_ENTROPY_SEED);
+#endif
         return h;
     }();
     return c;

@@ -38,6 +38,17 @@ size_t kosk_tape_bytes(int kyber_k);
  * mlwe_prover.hpp:57-75) inside the proof image; returns 0 on success */
 int kosk_proof_field(int kyber_k, int idx, size_t *offset, size_t *size);
 
+/* ---- Seeded proving (no reference counterpart: the reference draws every tape byte with randombytes, kosk.cpp:12,
+ * mlwe_prover.cpp:9, ss.cpp:5).  Format kosk-seedtape-v1: with T = kosk_tape_bytes(kyber_k),
+ *   block_j = SHAKE256(seed[32] || "kosk-seedtape-v1" || LE32(kyber_k) || LE32(j))[0 : 136],  j = 0 .. ceil(T / 136) - 1
+ *   tape    = (block_0 || block_1 || ...)[0 : T]
+ * (counter mode: every block is one independent Keccak-f[1600]).  A seeded call returns byte for byte what the explicit-tape call
+ * returns on that tape.  A seed determines the key seed and all masking randomness of its proof: it is as secret as the secret key
+ * and must be used once. */
+#define KOSK_SEED_BYTES 32
+/* host, no handle: the tape of one seed (kosk_tape_bytes(kyber_k) bytes); -1 for kyber_k outside 2..4 or a null pointer */
+int kosk_tape_from_seed(int kyber_k, const uint8_t seed[KOSK_SEED_BYTES], uint8_t *tape);
+
 int kosk_create(kosk_ctx **ctx, int device, int kyber_k, int max_batch);
 
 /* ---- Per-handle options (round 6).  The reference has no run-time configuration at all (kosk.hpp:18-24 takes pointers, nothing
@@ -70,6 +81,12 @@ int kosk_create_ex(kosk_ctx **ctx, int device, int kyber_k, int max_batch, const
 void kosk_destroy(kosk_ctx *ctx);
 const char *kosk_last_error(const kosk_ctx *ctx); /* ctx may be NULL: error of the last failed kosk_create */
 int kosk_set_randombytes(kosk_ctx *ctx, kosk_randombytes_fn fn, void *user); /* NULL: OS entropy */
+/* What a call with `tapes` == NULL draws through the randombytes callback / OS entropy (a setter like kosk_set_randombytes, applied to
+ * every sub-context of the handle; not a field of kosk_options).  KOSK_ENTROPY_TAPE (the default of every handle): the reference's
+ * sequence of 64, M x 32 and 302-byte calls per proof, a whole tape.  KOSK_ENTROPY_SEED: ONE call of KOSK_SEED_BYTES per proof, in
+ * proof order; the call then behaves as its *_seeded form below with seeds == NULL.  Any other mode: -1, nothing changed. */
+enum { KOSK_ENTROPY_TAPE = 0, KOSK_ENTROPY_SEED = 1 };
+int kosk_set_entropy(kosk_ctx *ctx, int mode);
 
 /* void kyber_verifiable_keygen(kyber_keypair *keypair, uint8_t *pi)   kosk.hpp:20-21, kosk.cpp:72-86
  * n independent instances; pk/sk/pi are n consecutive records of kosk_*_bytes().
@@ -89,6 +106,17 @@ int kosk_set_randombytes(kosk_ctx *ctx, kosk_randombytes_fn fn, void *user); /* 
  * decoding of a public key alike. */
 int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
                                  uint8_t *pk, uint8_t *sk, uint8_t *pi);
+
+/* The seeded forms of the four calls that take tapes at the reference's first level: proof b uses the tape of the seed at
+ * seeds + b * seed_stride (seed_stride >= KOSK_SEED_BYTES; host or DEVICE memory).  seeds == NULL: the library draws one
+ * KOSK_SEED_BYTES call per proof, in proof order, through the randombytes callback / OS entropy.  The seeds (32 bytes per proof) are
+ * the only randomness that crosses PCIe; the tapes are expanded in HBM (k_tape_expand) on the handle's stream.  Chunking, streams and
+ * call combining as for the tape forms: a merged run of a cohort may mix seeded callers with callers that bring device or host tapes. */
+int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi);
+int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
+                                                uint8_t *out);
+int kosk_verifiable_keygen_seeded_resident(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk);
+int kosk_stage_prover_inputs_seeded(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk);
 
 /* Page-locked host memory for the proof buffers of the two host-buffer calls (no reference counterpart: the reference's
  * caller owns plain arrays, main.cpp:71).  Proof images in such a buffer (or in any memory the caller page-locked itself with
@@ -168,7 +196,8 @@ int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, 
  * kernel-level entry points), 4 proof images copied straight between HBM and page-locked caller memory (kosk_host_alloc or locked by the
  * caller), 5 through the pinned staging buffer (pageable caller memory), 6 hipGraph segment replays (KOSK_GRAPHS=1), 7 commitment rounds
  * whose digest table was copied to the host (host Fiat-Shamir mode), 8 small copies between HBM and the library's own page-locked buffers
- * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host. */
+ * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded
+ * proving: tapes expanded from seeds in HBM). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);
@@ -203,8 +232,9 @@ int kosk_profile_read_units(const kosk_ctx *ctx, int id, double *total_ms, long 
  * one less than combine_idle_us (default 1000) ago: a lone caller is never delayed, callers that loop fall into step after
  * one or two calls (a request whose kind is in the minority of its window is held back once, so that callers alternating
  * keygen / verify in opposite phase meet).  The callers of a merged run sleep while it executes and are woken shortly before its
- * end (they then spin at most combine_prewake_us, default 400, for the return).  Calls that draw randomness through
- * the callback (tapes == NULL) and every other entry point run unmerged on the member's own block.  A member's round hook
+ * end (they then spin at most combine_prewake_us, default 400, for the return).  Calls that draw whole tapes through
+ * the callback (tapes == NULL in the default entropy mode) and every other entry point run unmerged on the member's own block; seeded
+ * calls merge like calls with tapes (their seeds, given or drawn on the caller's own thread, are expanded by the run).  A member's round hook
  * (kosk_set_round_hook) fires from a merged run as well, with that member's block of the table, ON THE THREAD OF THE RUN'S LEADER while
  * the member's own caller sleeps inside its call: a hook that relies on thread-local state (a current device, a stream context, a
  * thread-affine communicator) or that blocks must opt out with kosk_options::hooks_unmerged = 1, which keeps the calls of a handle
@@ -246,6 +276,10 @@ int kosk_fs_opened_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_s
 /* shake256(out, outlen, in, inlen)                           kyber/fips202.c:723-734 */
 int kosk_shake256_batch(kosk_ctx *ctx, const uint8_t *d_in, size_t in_stride, size_t inlen,
                         uint8_t *d_out, size_t outlen, int n);
+/* kosk-seedtape-v1 (above) for n seeds at once: seeds host or device memory (seed_stride >= KOSK_SEED_BYTES), tapes DEVICE memory,
+ * tape b at d_tapes + b * tape_stride (base and tape_stride multiples of 8, tape_stride >= kosk_tape_bytes); nothing outside the
+ * kosk_tape_bytes() bytes of each tape is written.  n <= max_batch.  Synchronised on return. */
+int kosk_tape_expand_device(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride);
 /* The view-commitment kernel on its native column layout: lane l hashes
  * [prefix32(l)] || rows[r][l], r < words, rows being u16 arrays `row_stride`
  * elements apart (mlwe_prover.cpp:116-127 when with_prefix == 0, :397-444 when 1).

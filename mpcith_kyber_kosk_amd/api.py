@@ -91,6 +91,20 @@ def _load():
         "kosk_host_sha3_256_multi": (C.c_int, [vp, vp, sz, sz, C.c_int, C.c_int]),
         "kosk_lagrange_table": (C.c_int, [C.c_int, vp]),
     }
+    # seeded proving (kosk-seedtape-v1)
+    seeded = {
+        "kosk_tape_from_seed": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_set_entropy": (C.c_int, [vp, C.c_int]),
+        "kosk_tape_expand_device": (C.c_int, [vp, C.c_int, vp, sz, vp, sz]),
+        "kosk_verifiable_keygen_seeded_batch": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verifiable_keygen_seeded_batch_compact": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verifiable_keygen_seeded_resident": (C.c_int, [vp, C.c_int, vp, sz, vp, vp]),
+        "kosk_stage_prover_inputs_seeded": (C.c_int, [vp, C.c_int, vp, sz, vp, vp]),
+    }
+    # an older build named by KOSK_LIB_PATH (the "before" leg of an A/B measurement) has no seeded entry points: its explicit-tape
+    # calls must stay usable from this binding.  The tree's own library has to export everything
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_tape_from_seed")):
+        sig.update(seeded)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -109,7 +123,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_shake256_batch", "kosk_commit_hash_lanes", "kosk_ntt256_batch", "kosk_lagrange_expand",
            "kosk_recon_secrets", "kosk_profile_enable", "kosk_profile_read", "kosk_profile_read_units", "kosk_combine_stats", "kosk_stream_timer_start", "kosk_stream_timer_stop", "kosk_device_synchronize", "kosk_streams", "kosk_resident_proofs", "kosk_keygen", "kosk_fs_alpha",
            "kosk_fs_opened", "kosk_host_sha3_256", "kosk_host_shake256", "kosk_host_sha3_256_multi", "kosk_lagrange_table",
-           "kosk_options_init", "kosk_create_ex", "kosk_sha3_256_batch_wave", "kosk_fs_alpha_device", "kosk_fs_opened_device"]
+           "kosk_options_init", "kosk_create_ex", "kosk_sha3_256_batch_wave", "kosk_fs_alpha_device", "kosk_fs_opened_device",
+           "kosk_tape_from_seed", "kosk_set_entropy", "kosk_tape_expand_device", "kosk_verifiable_keygen_seeded_batch",
+           "kosk_verifiable_keygen_seeded_batch_compact", "kosk_verifiable_keygen_seeded_resident", "kosk_stage_prover_inputs_seeded"]
 
 
 class KoskOptions(C.Structure):
@@ -120,6 +136,8 @@ class KoskOptions(C.Structure):
 
 
 FS_HOST, FS_DEVICE = 0, 1
+ENTROPY_TAPE, ENTROPY_SEED = 0, 1  # kosk_set_entropy
+SEED_BYTES = 32
 
 
 def options(**fields):
@@ -136,6 +154,17 @@ def pk_bytes(k): return lib.kosk_pk_bytes(k)
 def sk_bytes(k): return lib.kosk_sk_bytes(k)
 def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
+
+
+def tape_from_seed(k, seed):
+    """the randomness tape of one 32-byte seed (format kosk-seedtape-v1, kosk_tape_from_seed)"""
+    seed = bytes(seed)
+    if len(seed) != SEED_BYTES:
+        raise KoskError("a seed has %d bytes" % SEED_BYTES)
+    out = C.create_string_buffer(tape_bytes(k) or 1)
+    if lib.kosk_tape_from_seed(k, C.c_char_p(seed), out):
+        raise KoskError("kosk_tape_from_seed: kyber_k outside 2..4")
+    return out.raw
 
 
 def proof_field(k, idx):
@@ -191,9 +220,10 @@ class Kosk:
       verify(pi, pk) -> list[bool]                         kyber_kosk_verify
     """
 
-    def __init__(self, kyber_k=2, max_batch=1, device=0, **opts):
+    def __init__(self, kyber_k=2, max_batch=1, device=0, entropy=None, **opts):
         """opts: fields of kosk_options (streams, combine, strict_encoding, fs_mode, host_threads, blocking_sync, ...): the handle is
-        then created with kosk_create_ex; without any, with kosk_create (library defaults and the KOSK_* environment)"""
+        then created with kosk_create_ex; without any, with kosk_create (library defaults and the KOSK_* environment).
+        entropy: ENTROPY_TAPE / ENTROPY_SEED, handed to set_entropy() once the handle exists (a setter, not an options field)"""
         self.k = kyber_k
         self.max_batch = max_batch
         self._h = C.c_void_p()
@@ -209,6 +239,12 @@ class Kosk:
         self._cb = None
         self._hook = None
         self._pk = self._sk = None
+        if entropy is not None:
+            try:
+                self.set_entropy(entropy)
+            except KoskError:
+                self.close()
+                raise
 
     def close(self):
         if self._h:
@@ -243,8 +279,61 @@ class Kosk:
         self._cb = CB(tramp)
         self._chk(lib.kosk_set_randombytes(self._h, C.cast(self._cb, C.c_void_p), None), "set_randombytes")
 
-    def verifiable_keygen(self, tapes=None, n=None):
-        """tapes: list of bytes (one randomness tape per instance) or None (callback / OS entropy)."""
+    def set_entropy(self, mode):
+        """what a call without tapes draws: ENTROPY_TAPE (default) the reference's sequence, a whole tape per proof; ENTROPY_SEED one
+        32-byte seed per proof, expanded on the device (kosk_set_entropy)"""
+        self._chk(lib.kosk_set_entropy(self._h, int(mode)), "set_entropy")
+
+    def _seed_arg(self, seeds, n, seed_stride):
+        """seeds: list of 32-byte bytes, an int DEVICE pointer (with n and seed_stride), or True (the library draws one 32-byte seed
+        per proof through the callback / OS entropy; with n) -> (pointer, stride, n, keepalive)"""
+        if seeds is True:
+            if n is None:
+                raise KoskError("seeds=True needs n")
+            return None, SEED_BYTES, n, None
+        if isinstance(seeds, int):
+            if n is None:
+                raise KoskError("a device seed pointer needs n")
+            return C.c_void_p(seeds), SEED_BYTES if seed_stride is None else seed_stride, n, None
+        for s_ in seeds:
+            if len(s_) != SEED_BYTES:
+                raise KoskError("a seed has %d bytes" % SEED_BYTES)
+        blob = b"".join(bytes(s_) for s_ in seeds)
+        return C.c_char_p(blob), SEED_BYTES, len(seeds), blob
+
+    def tape_expand_device(self, seeds, d_tapes, tape_stride, n=None, seed_stride=None):
+        """n tapes into DEVICE memory at d_tapes (int pointer), tape_stride apart, from seeds (list of bytes or int device pointer)"""
+        sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+        self._chk(lib.kosk_tape_expand_device(self._h, n, sp, ss, d_tapes, tape_stride), "tape_expand_device")
+
+    def verifiable_keygen_compact(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """verifiable_keygen with the proofs in the compact wire format (kosk_verifiable_keygen_[seeded_]batch_compact)"""
+        cb = lib.kosk_compact_proof_bytes(self.k)
+        if seeds is not None:
+            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+            fn, tp, stride = lib.kosk_verifiable_keygen_seeded_batch_compact, sp, ss
+        elif tapes is not None:
+            n = len(tapes)
+            fn, tp, stride = lib.kosk_verifiable_keygen_batch_compact, C.c_char_p(b"".join(t[:self.tape_bytes] for t in tapes)), self.tape_bytes
+        else:
+            n = 1 if n is None else n
+            fn, tp, stride = lib.kosk_verifiable_keygen_batch_compact, None, 0
+        pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
+        out = C.create_string_buffer(cb * n)
+        self._chk(fn(self._h, n, tp, stride, pk, sk, out), "verifiable_keygen_compact")
+        cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
+        return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(out, cb)
+
+    def verifiable_keygen(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """tapes: list of bytes (one randomness tape per instance) or None (callback / OS entropy).
+        seeds (instead of tapes): seeded proving, see _seed_arg."""
+        if seeds is not None:
+            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+            pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
+            pi = C.create_string_buffer(self.proof_bytes * n)
+            self._chk(lib.kosk_verifiable_keygen_seeded_batch(self._h, n, sp, ss, pk, sk, pi), "verifiable_keygen")
+            cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
+            return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(pi, self.proof_bytes)
         if tapes is not None:
             n = len(tapes)
             stride = self.tape_bytes
@@ -320,11 +409,17 @@ class Kosk:
         return [bool(x) for x in ok]
 
     # resident split (bench)
-    def stage_prover_inputs(self, tapes):
-        n = len(tapes)
-        blob = b"".join(t[:self.tape_bytes] for t in tapes)
+    def stage_prover_inputs(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        if seeds is not None:
+            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+            self._pk = C.create_string_buffer(self.pk_bytes * n); self._sk = C.create_string_buffer(self.sk_bytes * n)
+            self._chk(lib.kosk_stage_prover_inputs_seeded(self._h, n, sp, ss, self._pk, self._sk), "stage_prover_inputs")
+            return n
+        if tapes is not None:
+            n = len(tapes)
+        blob = b"".join(t[:self.tape_bytes] for t in tapes) if tapes is not None else None  # None: callback / OS entropy, with n
         self._pk = C.create_string_buffer(self.pk_bytes * n); self._sk = C.create_string_buffer(self.sk_bytes * n)
-        self._chk(lib.kosk_stage_prover_inputs(self._h, n, C.c_char_p(blob), self.tape_bytes, self._pk, self._sk), "stage_prover_inputs")
+        self._chk(lib.kosk_stage_prover_inputs(self._h, n, C.c_char_p(blob) if blob is not None else None, self.tape_bytes, self._pk, self._sk), "stage_prover_inputs")
         return n
 
     def prove_resident(self, n):
@@ -340,9 +435,16 @@ class Kosk:
         self._chk(lib.kosk_fetch_proofs(self._h, n, pi), "fetch_proofs")
         return [pi.raw[i * self.proof_bytes:(i + 1) * self.proof_bytes] for i in range(n)]
 
-    def verifiable_keygen_resident(self, tapes, n=None, tape_stride=None):
+    def verifiable_keygen_resident(self, tapes=None, n=None, tape_stride=None, seeds=None, seed_stride=None):
         """kyber_verifiable_keygen as one resident call: key generation + prove, pk/sk returned, proofs stay in HBM.
-        tapes: list of bytes, or an int DEVICE pointer (with n and tape_stride), or None (callback / OS entropy, with n)."""
+        tapes: list of bytes, or an int DEVICE pointer (with n and tape_stride), or None (callback / OS entropy, with n).
+        seeds (instead of tapes): seeded proving, see _seed_arg."""
+        if seeds is not None:
+            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+            if getattr(self, "_pk", None) is None or len(self._pk) != self.pk_bytes * n:
+                self._pk = C.create_string_buffer(self.pk_bytes * n); self._sk = C.create_string_buffer(self.sk_bytes * n)
+            self._chk(lib.kosk_verifiable_keygen_seeded_resident(self._h, n, sp, ss, self._pk, self._sk), "verifiable_keygen_resident")
+            return n
         if isinstance(tapes, int):
             tp, stride = C.c_void_p(tapes), tape_stride
         elif tapes is None:
@@ -423,7 +525,7 @@ class Kosk:
         return a.value, b.value
 
     PATH_IDS = ["hash_dma", "hash_plain", "table_gemm", "limb_gemm", "copy_direct", "copy_staged", "graph_replay", "digest_copy", "small_copy_kernel",
-                "fs_device", "fs_host"]
+                "fs_device", "fs_host", "tape_expand"]
 
     def path_counts(self):
         """{name: launches / copies} of the alternative kernel and copy paths on this handle since it was created"""

@@ -210,6 +210,65 @@ static void draw_tapes(const kosk_ctx *ctx, int n, std::vector<uint8_t> &drawn)
     }
 }
 
+// Where the randomness of a tape-taking call comes from.  Explicit tapes; seeds (seeded proving: kosk-seedtape-v1, expanded on the
+// device); or neither -- then the handle's entropy mode (kosk_set_entropy) decides between the reference's draw sequence for whole
+// tapes and one 32-byte draw per proof.  resolve() makes the draws (sequentially, in proof order: the callback is stateful) and
+// leaves either `tapes` or `seeds` set.
+struct RandSrc {
+    const uint8_t *tapes = nullptr;
+    size_t tape_stride = 0;
+    const uint8_t *seeds = nullptr;
+    size_t seed_stride = 0;
+    bool seeded = false; // a *_seeded entry point, or tapes == NULL on a handle in KOSK_ENTROPY_SEED mode
+    std::vector<uint8_t> drawn;
+
+    static RandSrc from_tapes(const kosk_ctx *ctx, const uint8_t *tapes, size_t tape_stride)
+    {
+        RandSrc r;
+        r.tapes = tapes;
+        r.tape_stride = tape_stride;
+        r.seeded = !tapes && ctx->c->entropy_seed;
+        return r;
+    }
+    static RandSrc from_seeds(const uint8_t *seeds, size_t seed_stride)
+    {
+        RandSrc r;
+        r.seeds = seeds;
+        r.seed_stride = seed_stride;
+        r.seeded = true;
+        return r;
+    }
+    // draw_tapes_too: false leaves a NULL tape pointer alone (the callee draws inside a single sub-context's call)
+    void resolve(const kosk_ctx *ctx, int n, bool draw_tapes_too = true)
+    {
+        if (seeded && !seeds) {
+            drawn.resize((size_t)n * SEED_BYTES);
+            draw_seeds(*ctx->c, n, drawn.data());
+            seeds = drawn.data();
+            seed_stride = SEED_BYTES;
+        } else if (!seeded && !tapes && draw_tapes_too) {
+            draw_tapes(ctx, n, drawn);
+            tapes = drawn.data();
+            tape_stride = ctx->c->P.tape_bytes;
+        }
+    }
+    // the part of this source that serves proofs [first, ...) of the call
+    KeygenIn part(const Params &P, int first, uint8_t *pk, uint8_t *sk) const
+    {
+        KeygenIn kg{tapes ? tapes + (size_t)first * tape_stride : nullptr, tape_stride, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes};
+        if (seeded) { kg.seeds = seeds + (size_t)first * seed_stride; kg.seed_stride = seed_stride; }
+        return kg;
+    }
+};
+// seeded entry points: seed_stride below one seed fails the call before anything is started
+static int bad_seed_stride(kosk_ctx *ctx, const char *fn)
+{
+    ctx->clear_err();
+    ctx->err = std::string(fn) + ": seed_stride is smaller than one seed (KOSK_SEED_BYTES)";
+    ctx->c->err = ctx->err;
+    return -1;
+}
+
 static thread_local std::string g_create_err; // error text of the last failed kosk_create on this thread
 
 #define HIPCHK_C(x) KOSK_HIPCHK(x)
@@ -220,6 +279,13 @@ size_t kosk_pk_bytes(int k) { Params p; return make_params(k, p) ? p.pk_bytes : 
 size_t kosk_sk_bytes(int k) { Params p; return make_params(k, p) ? p.sk_bytes : 0; }
 size_t kosk_proof_bytes(int k) { Params p; return make_params(k, p) ? p.proof_bytes : 0; }
 size_t kosk_tape_bytes(int k) { Params p; return make_params(k, p) ? p.tape_bytes : 0; }
+int kosk_tape_from_seed(int k, const uint8_t seed[KOSK_SEED_BYTES], uint8_t *tape)
+{
+    Params p;
+    if (!make_params(k, p) || !seed || !tape) return -1;
+    tape_from_seed(p, seed, tape);
+    return 0;
+}
 int kosk_proof_field(int k, int idx, size_t *offset, size_t *size)
 {
     Params p;
@@ -364,21 +430,38 @@ int kosk_set_randombytes(kosk_ctx *ctx, kosk_randombytes_fn fn, void *user)
     return 0;
 }
 
+int kosk_set_entropy(kosk_ctx *ctx, int mode)
+{
+    if (!ctx) return -1;
+    if (mode != KOSK_ENTROPY_TAPE && mode != KOSK_ENTROPY_SEED) return bad_args(ctx, __func__);
+    for (Ctx *c : ctx->sub) c->entropy_seed = mode == KOSK_ENTROPY_SEED;
+    return 0;
+}
+
+static int stage_prover_inputs_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk)
+{
+    const Params &P = ctx->c->P;
+    src.resolve(ctx, n); // the randombytes callback is stateful: draw everything sequentially, then stage in parallel
+    return ctx->run(n, [&](Ctx &c, int first, int count) {
+        const KeygenIn kg = src.part(P, first, pk, sk);
+        return stage_prover_inputs(c, count, kg.tapes, kg.tape_stride, kg.pk, kg.sk, kg.seeds, kg.seed_stride);
+    });
+}
 int kosk_stage_prover_inputs(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
     GUARD(ctx)
-    const Params &P = ctx->c->P;
-    std::vector<uint8_t> drawn;
-    if (!tapes) { // the randombytes callback is stateful: draw every tape sequentially, then stage in parallel
-        draw_tapes(ctx, n, drawn);
-        tapes = drawn.data();
-        tape_stride = P.tape_bytes;
-    }
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        return stage_prover_inputs(c, count, tapes + (size_t)first * tape_stride, tape_stride,
-                                   pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes);
-    });
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return stage_prover_inputs_from(ctx, n, src, pk, sk);
+    GUARD_END
+}
+int kosk_stage_prover_inputs_seeded(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return stage_prover_inputs_from(ctx, n, src, pk, sk);
     GUARD_END
 }
 int kosk_prove_resident(kosk_ctx *ctx, int n)
@@ -433,7 +516,7 @@ int kosk_verify_resident(kosk_ctx *ctx, int n, uint8_t *ok)
 }
 
 // ---- merged resident calls of a cohort (KOSK_COMBINE) ----
-struct KeygenCall { const uint8_t *tapes; size_t tape_stride; uint8_t *pk, *sk; };
+struct KeygenCall { const uint8_t *tapes; size_t tape_stride; uint8_t *pk, *sk; const uint8_t *seeds; size_t seed_stride; };
 struct VerifyCall { const uint8_t *pk; uint8_t *ok; };
 
 // what every member of a finished run takes over from the run's leader
@@ -489,7 +572,9 @@ static int combined_keygen(kosk_ctx *h, int n, const KeygenCall &call)
         return -1;
     }
     CombineReq r;
-    r.kind = call.tapes ? CK_KEYGEN : CK_ALONE; // the stateful randombytes callback is per handle
+    // the stateful randombytes callback is per handle: a call that draws whole tapes through it runs alone (a seeded call's seeds were
+    // drawn by its own caller before it got here, and the entropy source is not part of what makes calls mergeable)
+    r.kind = (call.tapes || call.seeds) ? CK_KEYGEN : CK_ALONE;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE; // the hook must fire on this caller's own thread (kosk_options::hooks_unmerged)
     r.n = n;
     r.full = n == co.per;
@@ -502,7 +587,8 @@ static int combined_keygen(kosk_ctx *h, int n, const KeygenCall &call)
         for (int k = 0; k < count; k++) {
             const KeygenCall *a = static_cast<const KeygenCall *>(reqs[k]->args);
             const Ctx &mv = *co.member[first + k]->c; // round hooks are per handle: every member's fires with its own block of the tables
-            segs[k] = KeygenIn{a->tapes, a->tape_stride, a->pk, a->sk, reqs[k]->n, k + 1 < count ? &segs[k + 1] : nullptr, mv.round_hook, mv.round_user};
+            segs[k] = KeygenIn{a->tapes, a->tape_stride, a->pk, a->sk, reqs[k]->n, k + 1 < count ? &segs[k + 1] : nullptr, mv.round_hook, mv.round_user,
+                               a->seeds, a->seed_stride};
             total += reqs[k]->n;
         }
         NearEnd ne(c, co, first, count);
@@ -581,23 +667,42 @@ static int combined_verify(kosk_ctx *h, int n, const VerifyCall &call)
     return rc;
 }
 
+static int keygen_resident_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk)
+{
+    // stateful callback: seeds are drawn here, on the caller's own thread and in proof order, whatever serves the call afterwards; whole
+    // tapes only where the sub-batches of the call run in parallel (one sub-context draws its own inside its call)
+    src.resolve(ctx, n, !ctx->cohort && ctx->sub.size() > 1);
+    if (ctx->cohort) return combined_keygen(ctx, n, KeygenCall{src.tapes, src.tape_stride, pk, sk, src.seeds, src.seed_stride});
+    const Params &P = ctx->c->P;
+    return ctx->run(n, [&](Ctx &c, int first, int count) {
+        const KeygenIn kg = src.part(P, first, pk, sk);
+        return prove_resident(c, count, false, &kg);
+    });
+}
 int kosk_verifiable_keygen_resident(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
     GUARD(ctx)
-    if (ctx->cohort) return combined_keygen(ctx, n, KeygenCall{tapes, tape_stride, pk, sk});
-    const Params &P = ctx->c->P;
-    std::vector<uint8_t> drawn;
-    if (!tapes && ctx->sub.size() > 1) { // stateful callback: draw sequentially in proof order, then prove the sub-batches in parallel
-        draw_tapes(ctx, n, drawn);
-        tapes = drawn.data();
-        tape_stride = P.tape_bytes;
-    }
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg{tapes ? tapes + (size_t)first * tape_stride : nullptr, tape_stride, pk + (size_t)first * P.pk_bytes,
-                          sk + (size_t)first * P.sk_bytes};
-        return prove_resident(c, count, false, &kg);
-    });
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return keygen_resident_from(ctx, n, src, pk, sk);
+    GUARD_END
+}
+int kosk_verifiable_keygen_seeded_resident(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return keygen_resident_from(ctx, n, src, pk, sk);
+    GUARD_END
+}
+int kosk_tape_expand_device(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !seeds || !d_tapes) return bad_args(ctx, __func__);
+    if (seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return tape_expand_device(*ctx->c, n, seeds, seed_stride, d_tapes, tape_stride);
     GUARD_END
 }
 int kosk_verify_resident_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *ok)
@@ -634,26 +739,36 @@ int kosk_resident_digests(kosk_ctx *ctx, int round, void **d_digests, size_t *st
     GUARD_END
 }
 
+static int keygen_batch_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *pi)
+{
+    const Params &P = ctx->c->P;
+    src.resolve(ctx, n); // stateful callback: everything sequentially, in proof order, then the chunks in parallel
+    // images go straight into a buffer the CALLER page-locked (KOSK_REGISTER=0: never), else through the pinned staging buffer
+    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
+    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        const KeygenIn kg = src.part(P, first, pk, sk);
+        if (prove_resident(c, count, false, &kg)) return -1;
+        return fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned);
+    });
+}
 int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
                                  uint8_t *pk, uint8_t *sk, uint8_t *pi)
 {
     if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
     if (n == 0) return 0;
     GUARD(ctx)
-    const Params &P = ctx->c->P;
-    std::vector<uint8_t> drawn;
-    if (!tapes) { // stateful callback: every tape sequentially, in proof order, then the chunks in parallel
-        draw_tapes(ctx, n, drawn);
-        tapes = drawn.data();
-        tape_stride = P.tape_bytes;
-    }
-    // images go straight into a buffer the CALLER page-locked (KOSK_REGISTER=0: never), else through the pinned staging buffer
-    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
-    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg{tapes + (size_t)first * tape_stride, tape_stride, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes};
-        if (prove_resident(c, count, false, &kg)) return -1;
-        return fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned);
-    });
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return keygen_batch_from(ctx, n, src, pk, sk, pi);
+    GUARD_END
+}
+int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi)
+{
+    if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    if (n == 0) return 0;
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return keygen_batch_from(ctx, n, src, pk, sk, pi);
     GUARD_END
 }
 
@@ -682,26 +797,37 @@ int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk
 
 // The two host-buffer calls with the proofs in the compact wire format: packed / unpacked on the GPU, so PCIe
 // carries 78 % of the image bytes in each direction.  Same chunking and lanes as the calls above.
+static int keygen_batch_compact_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *out)
+{
+    const Params &P = ctx->c->P;
+    const size_t cb = make_compact_plan(P).bytes;
+    src.resolve(ctx, n);
+    const bool pinned = ctx->c->host_register && span_is_pinned(out, (size_t)n * cb);
+    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        const KeygenIn kg = src.part(P, first, pk, sk);
+        if (prove_resident(c, count, false, &kg)) return -1;
+        return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned);
+    });
+}
 int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
                                          uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
     if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
     if (n == 0) return 0;
     GUARD(ctx)
-    const Params &P = ctx->c->P;
-    const size_t cb = make_compact_plan(P).bytes;
-    std::vector<uint8_t> drawn;
-    if (!tapes) {
-        draw_tapes(ctx, n, drawn);
-        tapes = drawn.data();
-        tape_stride = P.tape_bytes;
-    }
-    const bool pinned = ctx->c->host_register && span_is_pinned(out, (size_t)n * cb);
-    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg{tapes + (size_t)first * tape_stride, tape_stride, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes};
-        if (prove_resident(c, count, false, &kg)) return -1;
-        return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned);
-    });
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
+    GUARD_END
+}
+int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
+                                                uint8_t *out)
+{
+    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    if (n == 0) return 0;
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
     GUARD_END
 }
 int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)

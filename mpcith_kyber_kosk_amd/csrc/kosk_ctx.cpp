@@ -75,12 +75,12 @@ Ctx::~Ctx()
         return; // the stream is the arena's
     }
     void *dev[] = {t_expand.d, t_recon_d.d, t_recon_2d.d, t_expand.dfrag, t_recon_d.dfrag, t_recon_2d.dfrag, d_fresh_rows, d_gemm1_rows, d_gemm2_rows, d_off, d_fields, d_asm_groups, d_asm_elems,
-                   d_rowtab, d_P, d_tape, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_limbs, d_coef, d_lin_rows,
+                   d_rowtab, d_P, d_tape, d_seedbuf, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_limbs, d_coef, d_lin_rows,
                    d_gather, d_gather2, d_O, d_w, d_ell, d_sec, d_sec_u1, d_sec_u2, d_fail, d_inv, d_invlimb, d_vfields,
                    d_vrowtab, d_rows_bg, d_rows_isrc, d_rows_idst, d_rows_u, d_fact, d_invfact, d_node_of, d_isort, d_hrange, d_odig};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {h_err, h_tape, h_dig, h_dig2, h_proof, h_alpha, h_I, h_fail, h_Iimg, h_kg, h_odig};
+    void *host[] = {h_err, h_tape, h_seedbuf, h_dig, h_dig2, h_proof, h_alpha, h_I, h_fail, h_Iimg, h_kg, h_odig};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     if (d_compact) (void)hipFree(d_compact);
@@ -481,6 +481,7 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         HIPCHK(dev(&c.d_P, c.proof_stride));
         HIPCHK(hipMemsetAsync(c.d_P, 0, B * c.proof_stride * 2, c.stream));
         HIPCHK(dev(&c.d_tape, c.tape_stride));
+        HIPCHK(dev(&c.d_seedbuf, SEED_BYTES));
         HIPCHK(dev(&c.d_dig1, (size_t)NPARTY * 32));
         HIPCHK(dev(&c.d_dig2, (size_t)NPARTY * 32));
         HIPCHK(dev(&c.d_proof, c.image_stride));
@@ -509,6 +510,7 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         HIPCHK(dev(&c.d_coef, 2 * (size_t)8 * 2 * 2048));
         HIPCHK(dev(&c.d_fail, 1));
         HIPCHK(host(&c.h_tape, c.tape_stride));
+        HIPCHK(host(&c.h_seedbuf, SEED_BYTES));
         HIPCHK(host(&c.h_dig, (size_t)NPARTY * 32));
         HIPCHK(host(&c.h_dig2, (size_t)NPARTY * 32));
         HIPCHK(host(&c.h_proof, c.image_stride));
@@ -638,6 +640,90 @@ static int upload_tapes_part(Ctx &c, int first, int n, const uint8_t *tapes, siz
     return 0;
 }
 
+// ---- seeded proving: tapes of the context's own tape buffer from 32-byte seeds (kosk-seedtape-v1, k_tape_expand) ----
+void draw_seeds(const Ctx &c, int n, uint8_t *out)
+{
+    for (int b = 0; b < n; b++) {
+        if (c.rb) c.rb(c.rb_user, out + (size_t)b * SEED_BYTES, SEED_BYTES);
+        else os_randombytes(out + (size_t)b * SEED_BYTES, SEED_BYTES);
+    }
+}
+
+// host seeds wait in the page-locked staging buffer for proofs [first, first + n) until the run is flushed: neighbouring seeded
+// callers of a merged run then share one staging copy and one expansion launch
+struct SeedRun { int first = 0, n = 0; };
+
+static int expand_into_own(Ctx &c, int first, int n, const uint8_t *d_seeds, size_t seed_stride)
+{
+    HIPCHK(launch_tape_expand(d_seeds, seed_stride, c.d_tape + (size_t)first * c.tape_stride, c.tape_stride, c.P.K, (int)c.P.tape_bytes, n, c.stream));
+    if (!c.capturing) c.path_n[PATH_TAPE_EXPAND]++;
+    return 0;
+}
+
+static int flush_seed_run(Ctx &c, SeedRun &r)
+{
+    if (!r.n) return 0;
+    uint8_t *d = c.d_seedbuf + (size_t)r.first * SEED_BYTES;
+    HIPCHK(copy_small(c, d, 0, c.h_seedbuf + (size_t)r.first * SEED_BYTES, 0, (size_t)r.n * SEED_BYTES, 1, hipMemcpyHostToDevice, c.stream));
+    const int rc = expand_into_own(c, r.first, r.n, d, SEED_BYTES);
+    r.n = 0;
+    return rc;
+}
+
+static int seed_tapes_part(Ctx &c, int first, int n, const uint8_t *seeds, size_t seed_stride, SeedRun &run)
+{
+    if (seed_stride < SEED_BYTES) { c.err = "seed_stride smaller than KOSK_SEED_BYTES"; return -1; }
+    if (is_device_pointer(seeds)) {
+        if (flush_seed_run(c, run)) return -1;
+        // the caller keeps its seeds in HBM: read in place when the kernel's 8-byte loads are aligned, else one D2D copy
+        if (seed_stride % 8 == 0 && (reinterpret_cast<uintptr_t>(seeds) & 7) == 0) return expand_into_own(c, first, n, seeds, seed_stride);
+        uint8_t *d = c.d_seedbuf + (size_t)first * SEED_BYTES;
+        HIPCHK(hipMemcpy2DAsync(d, SEED_BYTES, seeds, seed_stride, SEED_BYTES, n, hipMemcpyDeviceToDevice, c.stream));
+        return expand_into_own(c, first, n, d, SEED_BYTES);
+    }
+    for (int b = 0; b < n; b++) memcpy(c.h_seedbuf + (size_t)(first + b) * SEED_BYTES, seeds + (size_t)b * seed_stride, SEED_BYTES);
+    if (run.n && run.first + run.n == first) { run.n += n; return 0; }
+    if (flush_seed_run(c, run)) return -1;
+    run.first = first;
+    run.n = n;
+    return 0;
+}
+
+static int seed_tapes(Ctx &c, int n, const uint8_t *seeds, size_t seed_stride)
+{
+    SeedRun run;
+    c.tape_segs.count = 0;
+    if (seed_tapes_part(c, 0, n, seeds, seed_stride, run) || flush_seed_run(c, run)) return -1;
+    c.tape_cur = c.d_tape;
+    c.tape_cur_stride = c.tape_stride;
+    return 0;
+}
+
+int tape_expand_device(Ctx &c, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride)
+{
+    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    if (!seeds || seed_stride < SEED_BYTES) { c.err = "seeds missing or seed_stride smaller than KOSK_SEED_BYTES"; return -1; }
+    if (!d_tapes || (reinterpret_cast<uintptr_t>(d_tapes) & 7) || tape_stride % 8 || tape_stride < c.P.tape_bytes || !is_device_pointer(d_tapes)) {
+        c.err = "d_tapes must be device memory, base and tape_stride multiples of 8, tape_stride >= kosk_tape_bytes";
+        return -1;
+    }
+    HIPCHK(hipSetDevice(c.device));
+    const uint8_t *d = seeds;
+    size_t ds = seed_stride;
+    if (!is_device_pointer(seeds)) {
+        for (int b = 0; b < n; b++) memcpy(c.h_seedbuf + (size_t)b * SEED_BYTES, seeds + (size_t)b * seed_stride, SEED_BYTES);
+        HIPCHK(copy_small(c, c.d_seedbuf, 0, c.h_seedbuf, 0, (size_t)n * SEED_BYTES, 1, hipMemcpyHostToDevice, c.stream));
+        d = c.d_seedbuf; ds = SEED_BYTES;
+    } else if (seed_stride % 8 || (reinterpret_cast<uintptr_t>(seeds) & 7)) {
+        HIPCHK(hipMemcpy2DAsync(c.d_seedbuf, SEED_BYTES, seeds, seed_stride, SEED_BYTES, n, hipMemcpyDeviceToDevice, c.stream));
+        d = c.d_seedbuf; ds = SEED_BYTES;
+    }
+    HIPCHK(launch_tape_expand(d, ds, d_tapes, tape_stride, c.P.K, (int)c.P.tape_bytes, n, c.stream));
+    c.path_n[PATH_TAPE_EXPAND]++;
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
 int upload_tapes(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride)
 {
     c.tape_segs.count = 0;
@@ -648,14 +734,15 @@ int upload_tapes(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride)
 static int upload_tapes_segs(Ctx &c, int n, const KeygenIn &kg)
 {
     c.tape_segs.count = 0;
-    if (!kg.next && (kg.count == 0 || kg.count == n)) return upload_tapes(c, n, kg.tapes, kg.tape_stride);
+    if (!kg.next && (kg.count == 0 || kg.count == n))
+        return kg.seeds ? seed_tapes(c, n, kg.seeds, kg.seed_stride) : upload_tapes(c, n, kg.tapes, kg.tape_stride);
     { // every caller keeps aligned tapes in HBM, equal strides, full blocks except the last: read them where they are
         const int per = kg.count;
         int j = 0, total = 0;
         bool ok = per > 0;
         for (const KeygenIn *s = &kg; s && ok; s = s->next, j++) {
             const int cnt = s->count ? s->count : n - total;
-            ok = j < 16 && s->tapes && s->tape_stride == kg.tape_stride && s->tape_stride >= c.P.tape_bytes && s->tape_stride % 8 == 0 &&
+            ok = j < 16 && !s->seeds && s->tapes && s->tape_stride == kg.tape_stride && s->tape_stride >= c.P.tape_bytes && s->tape_stride % 8 == 0 &&
                  (reinterpret_cast<uintptr_t>(s->tapes) & 7) == 0 && cnt >= 1 && (cnt == per || (!s->next && cnt < per)) && is_device_pointer(s->tapes);
             if (ok) c.tape_segs.ptr[j] = s->tapes;
             total += cnt;
@@ -668,13 +755,19 @@ static int upload_tapes_segs(Ctx &c, int n, const KeygenIn &kg)
             return 0;
         }
     }
+    // the members' blocks of the context's own tape buffer, each from its caller's source: seeds (neighbouring seeded callers share one
+    // staging copy and one expansion launch), device tapes, host tapes
     int first = 0;
+    SeedRun run;
     for (const KeygenIn *s = &kg; s; s = s->next) {
         const int cnt = s->count ? s->count : n - first;
         if (cnt < 1 || first + cnt > n) { c.err = "internal: merged call segments do not add up"; return -1; }
-        if (upload_tapes_part(c, first, cnt, s->tapes, s->tape_stride, false)) return -1;
+        if (s->seeds ? seed_tapes_part(c, first, cnt, s->seeds, s->seed_stride, run) : upload_tapes_part(c, first, cnt, s->tapes, s->tape_stride, false)) return -1;
         first += cnt;
     }
+    if (flush_seed_run(c, run)) return -1;
+    c.tape_cur = c.d_tape;
+    c.tape_cur_stride = c.tape_stride;
     if (first != n) { c.err = "internal: merged call segments do not add up"; return -1; }
     return 0;
 }
@@ -755,13 +848,13 @@ static void finish_keygen_segs(Ctx &c, int n, const KeygenIn &kg)
     });
 }
 
-int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
+int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, const uint8_t *seeds, size_t seed_stride)
 {
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     if (!pk || !sk) { c.err = "pk / sk output buffers are required"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     const double t0 = now_sec();
-    if (upload_tapes(c, n, tapes, tape_stride)) return -1;
+    if (seeds ? seed_tapes(c, n, seeds, seed_stride) : upload_tapes(c, n, tapes, tape_stride)) return -1;
     if (issue_keygen(c, n)) return -1;
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;

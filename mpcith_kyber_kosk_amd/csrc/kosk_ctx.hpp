@@ -46,6 +46,10 @@ struct KeygenIn {
     // unmerged call leaves these null and the context's round_hook fires for the whole batch)
     round_fn hook = nullptr;
     void *hook_user = nullptr;
+    // seeded proving: `seeds` != nullptr (host or device memory, seed_stride >= 32 apart) replaces `tapes` -- this caller's tapes are
+    // expanded from its 32-byte seeds into the context's own tape buffer (kosk-seedtape-v1, k_tape_expand)
+    const uint8_t *seeds = nullptr;
+    size_t seed_stride = 0;
 };
 // the verifier's per-caller parts of a merged call: `count` proofs each, own key source and own result bytes
 struct VerifySeg {
@@ -68,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *d = nullptr; // limb matrix (kosk_device.hpp)
@@ -138,6 +142,9 @@ struct Ctx {
     std::string err;
     randombytes_fn rb = nullptr;
     void *rb_user = nullptr;
+    // kosk_set_entropy: what a call with tapes == NULL draws through `rb` -- false (default) the reference's 64 / M x 32 / 302-byte
+    // sequence, a whole tape per proof; true ONE 32-byte seed per proof, expanded on the device
+    bool entropy_seed = false;
     round_fn round_hook = nullptr;
     void *round_user = nullptr;
 
@@ -166,6 +173,8 @@ struct Ctx {
     // the tapes the kernels read: d_tape after an upload, or the caller's own device buffer used in place
     const uint8_t *tape_cur = nullptr;
     size_t tape_cur_stride = 0;
+    // seeded proving: the seeds of a call, 32 bytes per proof (page-locked staging and its device copy, which k_tape_expand reads)
+    uint8_t *d_seedbuf = nullptr, *h_seedbuf = nullptr;
     TapeSegs tape_segs{}; // a merged call whose callers' device tapes are read in place (count > 0; valid for that call only)
     int16_t *d_A = nullptr, *d_se = nullptr;
     // key generation on the device (kosk_keygen_kernels.hip)
@@ -389,7 +398,13 @@ inline int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst
 }
 
 // tapes (host or device memory, nullptr = callback) -> pk/sk on host, tape + key material resident in HBM
-int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk);
+// seeds != nullptr: seeded proving, the tapes are expanded on the device from 32-byte seeds (host or device memory) and `tapes` is not read
+int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, const uint8_t *seeds = nullptr,
+                        size_t seed_stride = 0);
+// n seeds (host or device memory) -> n tapes in DEVICE memory (base and stride multiples of 8), on the context's stream, synchronised
+int tape_expand_device(Ctx &c, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride);
+// draw n 32-byte seeds through the context's randombytes callback / OS entropy, one call per proof, in proof order
+void draw_seeds(const Ctx &c, int n, uint8_t *out);
 // its three parts: make the tapes resident (async), kyber_keygen on the device + D2H of pk / NTT(s) / seeds (async),
 // and, once the stream has been synchronised, the host half (sk = NTT(s) || pk || H(pk) || z, kosk.cpp:62-69)
 int upload_tapes(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride);

@@ -282,6 +282,11 @@ hipError_t launch_interp_apply(const InterpArgs &a, uint16_t *P, size_t proof_st
                                int n1, const uint8_t *y1, int n2, const uint8_t *y2, uint16_t *out2, int nproofs, hipStream_t st);
 hipError_t launch_check_opened(const VerifyArgs &v, int nproofs, hipStream_t st);
 
+// ---- seeded proving (kosk_tape_kernels.hip): tape b = kosk-seedtape-v1 of the 32-byte seed at seeds + b * seed_stride, written to
+// tapes + b * tape_stride (tape_bytes each, nothing behind them); seeds, tapes and both strides multiples of 8
+hipError_t launch_tape_expand(const uint8_t *seeds, size_t seed_stride, uint8_t *tapes, size_t tape_stride, int K, int tape_bytes, int n,
+                              hipStream_t st);
+
 // ---- key generation (kosk_keygen_kernels.hip) ----
 hipError_t launch_keygen(const uint8_t *tape, size_t tape_stride, uint8_t *seeds, size_t seed_stride, int16_t *A, size_t A_stride,
                          int16_t *se, size_t se_stride, int K, int eta1, int n, hipStream_t st, XofGuard xof = XofGuard());

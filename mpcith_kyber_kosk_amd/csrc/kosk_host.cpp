@@ -782,4 +782,19 @@ void os_randombytes(uint8_t *out, size_t len)
     }
 }
 
+void tape_from_seed(const Params &P, const uint8_t seed[SEED_BYTES], uint8_t *tape)
+{
+    uint8_t in[56], block[136];
+    memcpy(in, seed, 32);
+    memcpy(in + 32, "kosk-seedtape-v1", 16);
+    const uint32_t k = (uint32_t)P.K;
+    for (int i = 0; i < 4; i++) in[48 + i] = (uint8_t)(k >> (8 * i));
+    for (size_t off = 0, j = 0; off < P.tape_bytes; off += sizeof(block), j++) {
+        for (int i = 0; i < 4; i++) in[52 + i] = (uint8_t)(j >> (8 * i));
+        const size_t take = P.tape_bytes - off < sizeof(block) ? P.tape_bytes - off : sizeof(block);
+        shake256(block, sizeof(block), in, sizeof(in));
+        memcpy(tape + off, block, take);
+    }
+}
+
 } // namespace kosk

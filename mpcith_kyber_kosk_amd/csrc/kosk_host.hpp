@@ -82,4 +82,10 @@ void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I,
 // OS entropy (kyber/randombytes.c:44-57, Linux branch)
 void os_randombytes(uint8_t *out, size_t len);
 
+// Seeded proving, format kosk-seedtape-v1 (no reference counterpart): the randomness tape of one 32-byte seed,
+//   block_j = SHAKE256(seed || "kosk-seedtape-v1" || LE32(K) || LE32(j))[0:136],  tape = (block_0 || block_1 || ...)[0:tape_bytes]
+// (the host definition of what k_tape_expand, kosk_tape_kernels.hip, computes on the device)
+constexpr int SEED_BYTES = 32;
+void tape_from_seed(const Params &P, const uint8_t seed[SEED_BYTES], uint8_t *tape);
+
 } // namespace kosk
