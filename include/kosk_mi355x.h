@@ -191,9 +191,9 @@ int kosk_fetch_proofs_compact(kosk_ctx *ctx, int n, uint8_t *out);        /* lik
 int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk); /* like kosk_stage_verifier_inputs */
 
 /* Which kernel / copy paths ran on this handle since it was created (the tests of the fallbacks and of the Fiat-Shamir mode assert on
- * these).  ids: 0 commitment hash with LDS-DMA staging, 1 without (a layout the staged kernel cannot take: unaligned rows, a lane map),
- * 2 shared-table products on k_table_gemm / k_table_gemm_p, 3 products on the generic limb GEMM (grouped products, unaligned callers of the
- * kernel-level entry points), 4 proof images copied straight between HBM and page-locked caller memory (kosk_host_alloc or locked by the
+ * these).  ids: 0 commitment hash with LDS-DMA staging, 1 without (a layout the staged kernel cannot take: unaligned rows),
+ * 2 shared-table products on k_table_gemm / k_table_gemm_p (every mod-q product), 3 retired, always 0 (the generic limb GEMM, which no call
+ * could reach; the id keeps its number), 4 proof images copied straight between HBM and page-locked caller memory (kosk_host_alloc or locked by the
  * caller), 5 through the pinned staging buffer (pageable caller memory), 6 hipGraph segment replays (KOSK_GRAPHS=1), 7 commitment rounds
  * whose digest table was copied to the host (host Fiat-Shamir mode), 8 small copies between HBM and the library's own page-locked buffers
  * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded

@@ -1188,7 +1188,6 @@ int kosk_commit_hash_lanes(kosk_ctx *ctx, const uint16_t *d_rows, size_t row_str
     ha.row_stride = (int)row_stride;
     ha.col_off = 0;
     ha.lanes_per_group = n_lanes;
-    ha.lane_map = nullptr;
     ha.prefix = d_prefix;
     ha.out = d_out;
     ha.out_lanes_per_group = n_lanes;
@@ -1224,12 +1223,11 @@ int kosk_lagrange_expand(kosk_ctx *ctx, const uint16_t *d_y407, uint16_t *d_shar
     Ctx &c = *ctx->c;
     ctx->clear_err();
     HIPCHK_C(hipSetDevice(c.device));
-    const int cap_rows = c.own_batch * c.rm.nrows; // the row matrix doubles as scratch (this handle's own block of it)
-    const int cap = std::min<long>(cap_rows, (long)(c.limb_cap / (7 * 128)) - 64);
+    const int cap = c.own_batch * c.rm.nrows; // the row matrix doubles as scratch (this handle's own block of it)
     for (int done = 0; done < n;) {
         const int m = (n - done) < cap ? (n - done) : cap;
         HIPCHK_C(launch_rows_copy(d_y407 + (size_t)done * XLEN, XLEN, c.d_P, RS, XLEN, m, c.stream));
-        const GemmSrc gs{c.d_P, 0, nullptr, RS, 0, XLEN, 0}; // caller data: folded while converted
+        const GemmSrc gs{c.d_P, 0, nullptr, RS, 0, 0}; // caller data: folded while converted
         const GemmDst gd{c.d_P, 0, nullptr, RS, EXP_OFF};
         if (gemm_modq(c, c.t_expand, gs, gd, m, 1)) return -1;
         HIPCHK_C(launch_rows_copy(c.d_P + NSEC, RS, d_shares + (size_t)done * NPARTY, NPARTY, NPARTY, m, c.stream));
@@ -1247,12 +1245,11 @@ int kosk_recon_secrets(kosk_ctx *ctx, const uint16_t *d_shares, uint16_t *d_secr
     ctx->clear_err();
     HIPCHK_C(hipSetDevice(c.device));
     const GemmTable &t = two_d ? c.t_recon_2d : c.t_recon_d;
-    const int cap_rows = c.own_batch * c.rm.nrows;
-    const int cap = std::min<long>(cap_rows, (long)(c.limb_cap / ((size_t)t.KS * 128)) - 64);
+    const int cap = c.own_batch * c.rm.nrows;
     for (int done = 0; done < n;) {
         const int m = (n - done) < cap ? (n - done) : cap;
         HIPCHK_C(launch_rows_copy(d_shares + (size_t)done * NPARTY, NPARTY, c.d_P + NSEC, RS, NPARTY, m, c.stream));
-        const GemmSrc gs{c.d_P, 0, nullptr, RS, NSEC, t.Kdim, 0};
+        const GemmSrc gs{c.d_P, 0, nullptr, RS, NSEC, 0};
         const GemmDst gd{c.d_P, 0, nullptr, RS, 0};
         if (gemm_modq(c, t, gs, gd, m, 1)) return -1;
         HIPCHK_C(launch_rows_copy(c.d_P, RS, d_secrets + (size_t)done * NSEC, NSEC, NSEC, m, c.stream));

@@ -74,8 +74,8 @@ Ctx::~Ctx()
             if (e) (void)hipEventDestroy(e);
         return; // the stream is the arena's
     }
-    void *dev[] = {t_expand.d, t_recon_d.d, t_recon_2d.d, t_expand.dfrag, t_recon_d.dfrag, t_recon_2d.dfrag, d_fresh_rows, d_gemm1_rows, d_gemm2_rows, d_off, d_fields, d_asm_groups, d_asm_elems,
-                   d_rowtab, d_P, d_tape, d_seedbuf, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_limbs, d_coef, d_lin_rows,
+    void *dev[] = {t_expand.dfrag, t_recon_d.dfrag, t_recon_2d.dfrag, d_fresh_rows, d_gemm1_rows, d_gemm2_rows, d_off, d_fields, d_asm_groups, d_asm_elems,
+                   d_rowtab, d_P, d_tape, d_seedbuf, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_coef, d_lin_rows,
                    d_gather, d_gather2, d_O, d_w, d_ell, d_sec, d_sec_u1, d_sec_u2, d_fail, d_inv, d_invlimb, d_vfields,
                    d_vrowtab, d_rows_bg, d_rows_isrc, d_rows_idst, d_rows_u, d_fact, d_invfact, d_node_of, d_isort, d_hrange, d_odig};
     for (void *p : dev)
@@ -98,20 +98,13 @@ Ctx::~Ctx()
 static int upload_table(Ctx &c, GemmTable &t, const std::vector<uint16_t> &A, int M, int Kdim)
 {
     t.M = M;
-    t.Kdim = Kdim;
     t.Mpad = (M + 127) / 128 * 128;
     t.KS = (Kdim + 63) / 64;
     std::vector<uint8_t> pk;
-    pack_limb_table(A, M, Kdim, t.Mpad, t.KS, pk);
-    HIPCHK(dalloc(&t.d, pk.size()));
-    HIPCHK(hipMemcpyAsync(t.d, pk.data(), pk.size(), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
+    pack_frag_table(A, M, Kdim, t.Mpad, t.KS, pk);
+    HIPCHK(dalloc(&t.dfrag, pk.size()));
+    HIPCHK(hipMemcpyAsync(t.dfrag, pk.data(), pk.size(), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
     HIPCHK(hipStreamSynchronize(c.stream));
-    if (t.KS == 7 || t.KS == 13) {
-        pack_frag_table(A, M, Kdim, t.Mpad, t.KS, pk);
-        HIPCHK(dalloc(&t.dfrag, pk.size()));
-        HIPCHK(hipMemcpyAsync(t.dfrag, pk.data(), pk.size(), hipMemcpyHostToDevice, c.stream));
-        HIPCHK(hipStreamSynchronize(c.stream));
-    }
     return 0;
 }
 
@@ -216,43 +209,19 @@ hipError_t stream_sync_site(Ctx &c, int site, int n)
     return e != hipSuccess ? e : wait_event(c, c.ev_sync, site, n);
 }
 
-int gemm_modq(Ctx &c, const uint8_t *A, size_t a_gstride, int Mpad, int M, int KS, const GemmSrc &s, const GemmDst &d,
-              int npg, int ngroups, bool grouped, const uint8_t *Afrag)
+int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, int npg, int ngroups)
 {
     if (npg <= 0 || ngroups <= 0) return 0;
     GemmArgs ga{};
-    ga.Afrag = Afrag;
-    ga.A = A; ga.a_gstride = a_gstride; ga.Mpad = Mpad; ga.M = M; ga.KS = KS;
+    ga.Afrag = t.dfrag; ga.Mpad = t.Mpad; ga.M = t.M; ga.KS = t.KS;
+    ga.src = s.src; ga.src_gstride = s.gstride; ga.src_rows = s.rows; ga.src_rstride = s.rstride; ga.src_koff = s.koff;
+    ga.src_canonical = s.canonical;
     ga.C = d.C; ga.c_gstride = d.gstride; ga.c_rows = d.rows; ga.c_rstride = d.rstride; ga.c_off = d.off;
-    ga.npg = npg; ga.npg_pad = grouped ? (npg + 63) / 64 * 64 : npg; ga.ngroups = ngroups; ga.grouped = grouped ? 1 : 0;
-    if (!grouped && Afrag) {
-        // shared table, 407-wide inputs: data rows resident in LDS, no limb matrix in HBM (k_table_gemm)
-        GemmArgs ta = ga;
-        ta.B = nullptr; ta.BRT = 0;
-        ta.src = s.src; ta.src_gstride = s.gstride; ta.src_rows = s.rows; ta.src_rstride = s.rstride; ta.src_koff = s.koff;
-        ta.src_canonical = s.canonical;
-        if (table_gemm_usable(ta)) {
-            HIPCHK(launch_table_gemm(ta, reinterpret_cast<uint16_t *>(c.d_limbs), c.stream));
-            if (!c.capturing) c.path_n[PATH_TABLE_GEMM]++;
-            return 0;
-        }
-    }
-    const int rows = ((grouped ? ga.npg_pad * ngroups : npg * ngroups) + 63) / 64 * 64;
-    const int mtiles = Mpad / 128;
-    if (mtiles >= 4 && rows >= 2048 && (size_t)(rows / 16) * KS * 2048 <= c.limb_cap) {
-        // large product: every data row is used by many table tiles -> convert it to limbs once, in its own pass
-        LimbArgs la{};
-        la.src = s.src; la.src_gstride = s.gstride; la.rows = s.rows; la.src_rstride = s.rstride; la.src_koff = s.koff;
-        la.ncols = s.ncols; la.KS = KS; la.dst = c.d_limbs; la.RT = rows / 16; la.npg = npg; la.npg_pad = ga.npg_pad; la.ngroups = ngroups;
-        HIPCHK(launch_rows_to_limbs(la, c.stream));
-        ga.B = c.d_limbs; ga.BRT = rows / 16;
-    } else {
-        // small product (latency-bound): convert inside the GEMM's own staging and save a launch
-        ga.B = nullptr; ga.BRT = 0;
-        ga.src = s.src; ga.src_gstride = s.gstride; ga.src_rows = s.rows; ga.src_rstride = s.rstride; ga.src_koff = s.koff;
-    }
-    HIPCHK(launch_gemm(ga, c.stream));
-    if (!c.capturing) c.path_n[PATH_LIMB_GEMM]++;
+    ga.npg = npg; ga.ngroups = ngroups;
+    // the kernels load 16 bytes at a time from the source rows and store 8: checked, not assumed
+    if (!table_gemm_ok(ga)) { c.err = "internal: table_gemm_ok() refuses the operands of a mod-q product"; return -1; }
+    HIPCHK(launch_table_gemm(ga, c.stream));
+    if (!c.capturing) c.path_n[PATH_TABLE_GEMM]++;
     return 0;
 }
 
@@ -504,9 +473,6 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         c.d_rest = c.d_I + B * c.sel_stride;
         c.reg_pp(&c.d_I, (size_t)c.sel_stride * 2); c.reg_pp(&c.d_rest, (size_t)c.sel_stride * 2);
         HIPCHK(dev(&c.d_pwT, (size_t)MAXM * 80));
-        // data operand of the largest GEMM: every fresh sharing of every proof (<= 256 per proof), 13 k-steps
-        c.limb_cap = ((B * 256 + 63) / 64 * 64 / 16) * (size_t)13 * 2048;
-        HIPCHK(dev(&c.d_limbs, (size_t)(256 / 16) * 13 * 2048));
         HIPCHK(dev(&c.d_coef, 2 * (size_t)8 * 2 * 2048));
         HIPCHK(dev(&c.d_fail, 1));
         HIPCHK(host(&c.h_tape, c.tape_stride));
@@ -564,7 +530,6 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
         char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
         *reinterpret_cast<char **>(reinterpret_cast<char *>(&c) + pp.field_off) = base ? base + (size_t)first * pp.stride_bytes : nullptr;
     }
-    c.limb_cap = (size_t)c.max_batch * (256 / 16) * 13 * 2048;
     auto fail = [&]() { err = c.err; delete vp; return -1; };
     auto body = [&]() -> int {
         HIPCHK(hipSetDevice(c.device));
@@ -897,7 +862,7 @@ int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen)
         c.prof_end(PR_NTT_F);
     }
     if (matvec) HIPCHK(launch_matvec_ntt(c.d_A, c.key_stride, c.d_P, c.proof_stride, rm.shat, rm.nttas, K, n, st)); // :284-285
-    const GemmSrc xsrc{c.d_P, c.proof_stride, c.d_gemm1_rows + s0, RS, 0, XLEN};
+    const GemmSrc xsrc{c.d_P, c.proof_stride, c.d_gemm1_rows + s0, RS, 0};
     const GemmDst xdst{c.d_P, c.proof_stride, c.d_gemm1_rows + s0, RS, EXP_OFF};
     c.prof_begin(PR_GEMM_EXPAND1, n);
     if (gemm_modq(c, c.t_expand, xsrc, xdst, s1 - s0, n)) return -1;
@@ -925,7 +890,6 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     ha.row_stride = RS;
     ha.col_off = NSEC;
     ha.lanes_per_group = NPARTY;
-    ha.lane_map = nullptr;
     ha.out_lanes_per_group = NPARTY;
 
     // ---- key generation rides in the first launch of P1 (tape pointers may change from call to call: never part of a captured graph)
@@ -1055,7 +1019,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         na.dst_off = c.d_off + c.off_nttsr_er;
         na.out_canonical = 1;
         HIPCHK(launch_relation_ntt(na, c.d_A, c.key_stride, c.d_P, c.proof_stride, rm, n, st)); // NTT, A o NTT(s+r) (:287-288), tails
-        const GemmSrc x2src{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, 0, XLEN};
+        const GemmSrc x2src{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, 0};
         const GemmDst x2dst{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, EXP_OFF};
         c.prof_begin(PR_GEMM_EXPAND2, n);
         if (gemm_modq(c, c.t_expand, x2src, x2dst, c.n_gemm2, n)) return -1; // recompute_share_secrets_ddeg x 3K   :298-299,:315

@@ -75,9 +75,8 @@ enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEM
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_COUNT };
 
 struct GemmTable {
-    uint8_t *d = nullptr; // limb matrix (kosk_device.hpp)
-    uint8_t *dfrag = nullptr; // the same in fragment-linear tile order (k_table_gemm), tables with Kdim <= 448 only
-    int M = 0, Mpad = 0, KS = 0, Kdim = 0;
+    uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
+    int M = 0, Mpad = 0, KS = 0; // KS = k-steps of 64: 7 (407-wide) or 13 (813-wide)
 };
 
 // source rows / destination rows of one mod-q GEMM
@@ -85,7 +84,7 @@ struct GemmSrc {
     const uint16_t *src;
     size_t gstride;
     const int16_t *rows;
-    int rstride, koff, ncols;
+    int rstride, koff;
     // every u16 of the rows is a canonical field element (< q): true for everything the pipelines produce (the verifier folds what it
     // takes from a proof image before it reaches the row matrix); 0 for caller data of the kernel-level entry points, which is
     // folded while it is converted (the slower conversion)
@@ -190,10 +189,8 @@ struct Ctx {
     uint16_t *d_t = nullptr; // pk's t, canonical (verifier)
     uint16_t *d_alpha = nullptr, *d_I = nullptr, *d_rest = nullptr;
     int32_t *d_pwT = nullptr;
-    uint8_t *d_limbs = nullptr; // limb-matrix staging of the GEMM data operand
     uint8_t *d_coef = nullptr; // K3 operand: alpha-power coefficients as a limb matrix
     int16_t *d_lin_rows = nullptr; // [2][128] output rows of the lincomb GEMM (beta/r, gamma/NTT_r)
-    size_t limb_cap = 0;
     // verifier workspace (allocated on first use, kosk_verify.cpp)
     bool verify_ready = false;
     uint16_t *d_O = nullptr;         // opened matrix [proof][nrows][OS] (kosk_params.hpp)
@@ -377,7 +374,6 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
 // workers created now (a merged run led by this view uses base_threads x members of them)
 int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx **out, std::string &err);
 
-// C[g][rows_d[i]][off + m] = sum_k A[m][k] * src[g][rows_s[i]][koff + k] mod q  (conversion to limbs + MFMA GEMM)
 // host wait for everything queued on the context's stream (spinning, or sleeping with KOSK_BLOCKING_SYNC=1)
 hipError_t stream_sync(Ctx &c);
 // wait for `ev` (recorded on the context's stream); site = which of the pipeline's long waits this is (0..WAIT_SITES-1: napped with
@@ -390,12 +386,9 @@ hipError_t copy_round_table(Ctx &c, uint8_t *h_dst, const uint8_t *d_src, int n)
 hipError_t copy_small(Ctx &c, void *dst, size_t dst_stride, const void *src, size_t src_stride, size_t row_bytes, size_t nrows, hipMemcpyKind kind, hipStream_t st);
 // after the stream has been synchronised: -1 (with c.err set, the word cleared) if a kernel of this context raised an error
 int device_error_check(Ctx &c);
-int gemm_modq(Ctx &c, const uint8_t *A, size_t a_gstride, int Mpad, int M, int KS, const GemmSrc &s, const GemmDst &d,
-              int npg, int ngroups, bool grouped, const uint8_t *Afrag = nullptr);
-inline int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, int npg, int ngroups)
-{
-    return gemm_modq(c, t.d, 0, t.Mpad, t.M, t.KS, s, d, npg, ngroups, false, t.dfrag);
-}
+// C[g][rows_d[i]][off + m] = sum_k T[m][k] * src[g][rows_s[i]][koff + k] mod q on the table kernels; -1 (c.err set) if the operands
+// fail table_gemm_ok() (kosk_device.hpp), which nothing the library itself issues does
+int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, int npg, int ngroups);
 
 // tapes (host or device memory, nullptr = callback) -> pk/sk on host, tape + key material resident in HBM
 // seeds != nullptr: seeded proving, the tapes are expanded on the device from 32-byte seeds (host or device memory) and `tapes` is not read

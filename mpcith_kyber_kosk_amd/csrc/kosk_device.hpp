@@ -24,8 +24,6 @@ struct HashArgs {
     int row_stride;            // u16 between rows
     int col_off;               // column of lane 0 (NSEC for party lanes)
     int lanes_per_group;
-    const uint16_t *lane_map;  // optional: lane -> party (opened list), else identity
-    int lane_map_stride;
     const uint8_t *prefix;     // [group][out_lanes_per_group][32], read at the output index
     uint8_t *out;              // [group][out_lanes_per_group][32]
     int out_lanes_per_group;
@@ -67,43 +65,23 @@ KOSK_HD inline void limb_split(int32_t centred, int &c0, int &c1)
     c1 = (centred - c0) >> 6;
 }
 
-// rows of canonical u16 -> limb matrix (k_rows_to_limbs)
-struct LimbArgs {
-    const uint16_t *src;
-    size_t src_gstride;    // u16 between groups
-    const int16_t *rows;   // row index per i (null: i)
-    int src_rstride;       // u16 between rows
-    int src_koff;
-    int ncols;             // valid k (rest zero), padded to KS*64
-    int KS;
-    uint8_t *dst;
-    int RT;                // row tiles of the destination (= total rows / 16)
-    int npg, npg_pad, ngroups; // destination row = g*npg_pad + i
-};
-
-// C[n][c_off + m] = sum_k A[m][k] * B[n][k] mod q, both operands limb matrices
+// C[n][c_off + m] = sum_k T[m][k] * X[n][k] mod q (k_table_gemm, k_table_gemm_p)
 struct GemmArgs {
-    const uint8_t *A;  // table limb matrix, RT = Mpad/16
-    const uint8_t *Afrag; // the same table with fragment-linear tiles (k_table_gemm), or null
-    size_t a_gstride;  // bytes between per-group operands (grouped mode)
+    const uint8_t *Afrag; // table limb matrix with fragment-linear tiles (pack_frag_table), RT = Mpad/16
     int Mpad, M, KS;   // Mpad multiple of 128; m < M is stored
-    const uint8_t *B;  // data operand as a limb matrix, rows n = g*npg_pad + i (null: convert from `src` on the fly)
-    int BRT;           // row tiles of B
     // data operand as canonical u16 rows, k contiguous: row (g, i) at src + g*src_gstride + src_rows[i]*src_rstride + src_koff
     const uint16_t *src;
     size_t src_gstride;
     const int16_t *src_rows; // null: i
     int src_rstride, src_koff;
-    int src_canonical; // 1: every source value is < q (no folding while converting to limbs)
     uint16_t *C;
     size_t c_gstride;
     const int16_t *c_rows; // output row per i (null: i)
     int c_rstride;
     int c_off;
-    int npg, npg_pad, ngroups;
-    int grouped; // 1: A + g*a_gstride (npg_pad must be a multiple of 64)
-    int c_gdiv;  // groups per output block: C + (g / c_gdiv) * c_gstride, rows from c_rows + (g % c_gdiv) * c_rows_gstride
-    int c_rows_gstride;
+    int npg;           // rows per group: row n = g * npg + i
+    int src_canonical; // 1: every source value is < q (no folding while converting to limbs); picks the kernel, no kernel reads it
+    int ngroups;
 };
 
 struct LincombArgs {
@@ -296,7 +274,7 @@ hipError_t launch_keygen_pack(const int16_t *A, size_t A_stride, const int16_t *
 hipError_t launch_decode_pk(const uint8_t *pk, size_t pk_stride, uint16_t *t_out, int16_t *A, size_t A_stride, int K, int n, hipStream_t st,
                             XofGuard xof = XofGuard());
 
-// the LDS-DMA staged kernel runs where the layout allows it (aligned rows, no lane map), else the plain kernel; *variant: bit 0 the DMA kernel ran
+// the LDS-DMA staged kernel runs where the layout allows it (aligned rows), else the plain kernel; *variant: bit 0 the DMA kernel ran
 hipError_t launch_commit_hash(const HashArgs &a, int ngroups, int K, bool view, hipStream_t st, int *variant = nullptr);
 hipError_t launch_sha3_msgs(const uint8_t *in, size_t in_stride, int len, uint8_t *out, size_t out_stride,
                             int outlen, int n, int domain, hipStream_t st);
@@ -355,11 +333,10 @@ hipError_t launch_relation_ntt(const NttArgs &na, const int16_t *A, size_t A_str
                                int nproofs, hipStream_t st);
 hipError_t launch_matvec_ntt(const int16_t *A, size_t A_stride, uint16_t *P, size_t proof_stride, int v_row0, int row0, int K,
                              int nproofs, hipStream_t st);
-hipError_t launch_rows_to_limbs(const LimbArgs &a, hipStream_t st);
-hipError_t launch_gemm(const GemmArgs &a, hipStream_t st);
-// table products (shared table, 407-wide u16 input rows) with the data rows resident in LDS; `sink` = 4 KiB of scratch
-bool table_gemm_usable(const GemmArgs &a);
-hipError_t launch_table_gemm(const GemmArgs &a, uint16_t *sink, hipStream_t st);
+// table products (shared table, 407- or 813-wide u16 input rows) with the data rows resident in LDS.  table_gemm_ok: the operands
+// take the kernels' 16-byte loads and 8-byte stores; launch_table_gemm must not be called with operands that fail it
+bool table_gemm_ok(const GemmArgs &a);
+hipError_t launch_table_gemm(const GemmArgs &a, hipStream_t st);
 // K3 on the matrix cores (prover): beta / gamma / r / NTT_r rows of every proof from its f / NTT f rows and the alpha-power coefficient
 // matrix (k_coef_limbs), plus s + r and e + r in the epilogue (k_lincomb_stream: persistent workgroups, prefetched inputs)
 hipError_t launch_lincomb_stream(const uint16_t *P, size_t proof_stride, const RowMap &rm, const uint8_t *coef, uint16_t *C,

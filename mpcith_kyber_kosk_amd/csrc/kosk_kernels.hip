@@ -8,7 +8,7 @@
 //   k_prover_pre         mlwe_prover.cpp:8-14 (SHAKE256 PRF, BE16 % q), ss.cpp:5-11 (tape randoms), witness secrets
 //   k_ntt256        K5   kyber/ntt.c:80-95 + poly.c:261-265
 //   k_matvec_ntt    K6   polyvec.c:202-214 + poly.c:307-313
-//   k_rows_to_limbs, k_gemm_modq  K1/K2 ss.cpp:23-32, :44-51, :63-70, :88-97 (+ verifier interpolation apply)
+//   k_table_gemm_p, k_table_gemm  K1/K2 ss.cpp:23-32, :44-51, :63-70, :88-97 (+ verifier interpolation apply)
 //   k_lincomb       K3   mlwe_prover.cpp:159-203 ; mlwe_verifier.cpp:68-89, :149-170
 //   k_post_*        K7   ss.cpp:101-136 call sites in prove()
 //   k_assemble_*    K8   mlwe_prover.cpp:480-537
@@ -39,9 +39,8 @@ __global__ __launch_bounds__(64) void k_commit_hash(HashArgs a)
     const int lane = blockIdx.x * 64 + threadIdx.x;
     const int g = blockIdx.y;
     if (lane >= a.lanes_per_group) return;
-    const int col = a.lane_map ? (int)a.lane_map[(size_t)g * a.lane_map_stride + lane] : lane;
-    const uint16_t *__restrict__ base = a.rows + (size_t)g * a.group_stride + a.col_off + col;
-    const size_t dig = ((size_t)g * a.out_lanes_per_group + col) * 32;
+    const uint16_t *__restrict__ base = a.rows + (size_t)g * a.group_stride + a.col_off + lane;
+    const size_t dig = ((size_t)g * a.out_lanes_per_group + lane) * 32;
 
     constexpr int W = PREFIX_WORDS + NROWS; // u16 words in the message
     constexpr int RATE_W = 68;              // 136-byte rate
@@ -836,219 +835,35 @@ __global__ __launch_bounds__(256) void k_relation_ntt(NttArgs na, const int16_t 
 }
 
 // =========================================================================
-// K1/K2  C[n][c_off + m] = sum_k A[m][k] * B[n][k]  mod q   on the matrix cores.
+// K1/K2  C[n][c_off + m] = sum_k T[m][k] * X[n][k]  mod q   on the matrix cores, T one of the context's three tables.
 // GF(3329) values are exact in two int8 limbs of the centred representative (c = c0 + 64 c1), so
-//   A*B = sum a0 b0 + 64 sum (a0 b1 + a1 b0) + 4096 sum a1 b1
+//   T*X = sum t0 x0 + 64 sum (t0 x1 + t1 x0) + 4096 sum t1 x1
 // is four v_mfma_i32_16x16x64_i8 per 16x16x64 block into three exact i32 accumulators
 // (|S0| <= 2^20, |S1| <= 2^21, |S2| <= 2^20 for k <= 832), recombined mod q (4096 = 767 mod q).
-// Both operands arrive pre-tiled as limb matrices (kosk_device.hpp); a workgroup computes 128 m x 64 n,
-// a wave 64 x 32 (4 x 2 MFMA blocks), double-buffered through LDS with plain 16-byte copies.
+// The table arrives pre-tiled as a limb matrix in fragment order (pack_frag_table); the data rows are canonical u16 in HBM and
+// become limb tiles (kosk_device.hpp) in LDS.
 // =========================================================================
-
-// canonical u16 rows -> limb matrix; one thread per (row, 16-k chunk)
-__global__ __launch_bounds__(256) void k_rows_to_limbs(LimbArgs a)
-{
-    const int t = threadIdx.x;
-    const int ks = blockIdx.x * 4 + (t >> 6);
-    const int rt = blockIdx.y; // destination row tile
-    if (ks >= a.KS) return;
-    const int rr = t & 15, kc = (t >> 4) & 3;
-    const int r = rt * 16 + rr;
-    const int g = r / a.npg_pad, i = r - g * a.npg_pad;
-    uint32_t lo[4] = {0, 0, 0, 0}, hi[4] = {0, 0, 0, 0};
-    if (g < a.ngroups && i < a.npg) {
-        const int k0 = ks * 64 + kc * 16;
-        const uint16_t *src = a.src + (size_t)g * a.src_gstride + (size_t)(a.rows ? (int)a.rows[i] : i) * a.src_rstride + a.src_koff + k0;
-        uint16_t v[16];
-        if (k0 + 16 <= a.ncols && ((a.src_koff | a.src_rstride) & 7) == 0 && (a.src_gstride & 7) == 0) {
-            const uint4 x0 = *reinterpret_cast<const uint4 *>(src), x1 = *reinterpret_cast<const uint4 *>(src + 8);
-            const uint32_t w[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-#pragma unroll
-            for (int q = 0; q < 8; q++) { v[2 * q] = (uint16_t)w[q]; v[2 * q + 1] = (uint16_t)(w[q] >> 16); }
-        } else {
-#pragma unroll
-            for (int q = 0; q < 16; q++) v[q] = (k0 + q < a.ncols) ? src[q] : (uint16_t)0;
-        }
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            int c0, c1;
-            limb_split(gf_center(v[q] >= Q ? v[q] % Q : v[q]), c0, c1);
-            lo[q >> 2] |= ((uint32_t)c0 & 0xFFu) << (8 * (q & 3));
-            hi[q >> 2] |= ((uint32_t)c1 & 0xFFu) << (8 * (q & 3));
-        }
-    }
-    uint8_t *d = a.dst + ((size_t)(ks * a.RT + rt) * 2) * 1024 + rr * 64 + ((kc ^ limb_swz(rr)) << 4);
-    *reinterpret_cast<uint4 *>(d) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
-    *reinterpret_cast<uint4 *>(d + 1024) = make_uint4(hi[0], hi[1], hi[2], hi[3]);
-}
-
-constexpr int GM_TM = 128, GM_TN = 64;            // workgroup tile
-constexpr int GM_A_BYTES = (GM_TM / 16) * 2048;    // 16 KiB per k-step
-constexpr int GM_B_BYTES = (GM_TN / 16) * 2048;    //  8 KiB per k-step
-
-// BLIMB: the data operand is already a limb matrix (lincomb coefficients); otherwise it is converted from
-// canonical u16 rows while it is staged (16 values per thread and k-step), which saves a conversion launch.
-template <bool BLIMB>
-__device__ __forceinline__ void gemm_modq_block(const GemmArgs &a, const int bx, const int by, const int bz,
-                                                uint8_t (&lds)[2][GM_A_BYTES + GM_B_BYTES])
-{
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    const int grp = a.grouped ? bz : 0;
-    const int mt0 = bx * (GM_TM / 16);     // first A row tile of this workgroup
-    const int ART = a.Mpad / 16;
-    // staging: A 16 KiB = 4 x 16 B per thread and k-step, contiguous in the limb matrix.
-    // (named registers on purpose: arrays captured by a lambda end up in scratch memory)
-    const uint4 *__restrict__ ap = reinterpret_cast<const uint4 *>(a.A + (size_t)grp * a.a_gstride + (size_t)mt0 * 2048) + tid;
-    const size_t a_step = (size_t)ART * 128; // uint4 per k-step
-    // B: either 8 KiB of limb tiles (2 x 16 B per thread), or 64 rows x 64 u16 (32 B per thread: row tid>>2, chunk tid&3)
-    const uint4 *__restrict__ bp;
-    size_t b_step;
-    int b_lds; // byte offset of this thread's converted 16 bytes inside the B region (limb 0)
-    bool b_ok = true;
-    if (BLIMB) {
-        const int nt0 = by * (GM_TN / 16) + (a.grouped ? grp * (a.npg_pad / 16) : 0);
-        bp = reinterpret_cast<const uint4 *>(a.B + (size_t)nt0 * 2048) + tid;
-        b_step = (size_t)a.BRT * 128;
-        b_lds = 0;
-    } else {
-        const int row_l = tid >> 2, kc = tid & 3;
-        const int n_loc = by * GM_TN + row_l;
-        int g, i;
-        if (a.grouped) { g = grp; i = n_loc; b_ok = i < a.npg; }
-        else { g = n_loc / a.npg; i = n_loc - g * a.npg; b_ok = n_loc < a.npg * a.ngroups; }
-        const size_t off = b_ok ? (size_t)g * a.src_gstride + (size_t)(a.src_rows ? (int)a.src_rows[i] : i) * a.src_rstride + a.src_koff + kc * 16 : 0;
-        bp = reinterpret_cast<const uint4 *>(a.src + off);
-        b_step = 8; // 64 u16 per k-step
-        b_lds = (row_l >> 4) * 2048 + (row_l & 15) * 64 + ((kc ^ limb_swz(row_l & 15)) << 4);
-    }
-    uint4 ra0, ra1, ra2, ra3, rb0, rb1;
-#define GM_GLOAD()                                                           \
-    ra0 = ap[0]; ra1 = ap[256]; ra2 = ap[512]; ra3 = ap[768];                \
-    if (BLIMB) { rb0 = bp[0]; rb1 = bp[256]; }                               \
-    else if (b_ok) { rb0 = bp[0]; rb1 = bp[1]; }                             \
-    else { rb0 = make_uint4(0, 0, 0, 0); rb1 = rb0; }                        \
-    ap += a_step; bp += b_step;
-#define GM_LSTORE(buf)                                                       \
-    {                                                                        \
-        uint4 *la_ = reinterpret_cast<uint4 *>(lds[buf]) + tid;              \
-        la_[0] = ra0; la_[256] = ra1; la_[512] = ra2; la_[768] = ra3;        \
-        if (BLIMB) {                                                         \
-            uint4 *lb_ = reinterpret_cast<uint4 *>(lds[buf] + GM_A_BYTES) + tid; \
-            lb_[0] = rb0; lb_[256] = rb1;                                    \
-        } else {                                                             \
-            uint4 lo_, hi_;                                                  \
-            gm_split16(rb0, rb1, lo_, hi_);                                  \
-            uint8_t *lb_ = lds[buf] + GM_A_BYTES + b_lds;                    \
-            *reinterpret_cast<uint4 *>(lb_) = lo_;                           \
-            *reinterpret_cast<uint4 *>(lb_ + 1024) = hi_;                    \
-        }                                                                    \
-    }
-
-    v4i s0[4][2], s1[4][2], s2[4][2];
-#pragma unroll
-    for (int i = 0; i < 4; i++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) { s0[i][j] = (v4i){0, 0, 0, 0}; s1[i][j] = s0[i][j]; s2[i][j] = s0[i][j]; }
-
-    // fragment address inside a 1 KiB tile: row l&15, k-chunk l>>4 (swizzled)
-    const int frag = (lane & 15) * 64 + (((lane >> 4) ^ limb_swz(lane & 15)) << 4);
-
-    GM_GLOAD();
-    GM_LSTORE(0);
-    __syncthreads();
-    for (int ks = 0; ks < a.KS; ks++) {
-        const int buf = ks & 1;
-        if (ks + 1 < a.KS) { GM_GLOAD(); }
-        const uint8_t *la = lds[buf] + (wm * 4) * 2048 + frag;
-        const uint8_t *lb = lds[buf] + GM_A_BYTES + (wn * 2) * 2048 + frag;
-        v4i a0[4], a1[4], b0[2], b1[2];
-#pragma unroll
-        for (int i = 0; i < 4; i++) {
-            a0[i] = *reinterpret_cast<const v4i *>(la + i * 2048);
-            a1[i] = *reinterpret_cast<const v4i *>(la + i * 2048 + 1024);
-        }
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            b0[j] = *reinterpret_cast<const v4i *>(lb + j * 2048);
-            b1[j] = *reinterpret_cast<const v4i *>(lb + j * 2048 + 1024);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) {
-                s0[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0[i], b0[j], s0[i][j], 0, 0, 0);
-                s1[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0[i], b1[j], s1[i][j], 0, 0, 0);
-                s1[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1[i], b0[j], s1[i][j], 0, 0, 0);
-                s2[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1[i], b1[j], s2[i][j], 0, 0, 0);
-            }
-        if (ks + 1 < a.KS) {
-            if (buf) { GM_LSTORE(0); } else { GM_LSTORE(1); }
-        }
-        __syncthreads();
-    }
-#undef GM_GLOAD
-#undef GM_LSTORE
-
-    // D[row = m: 4(l>>4)+r][col = n: l&15] -> four consecutive m per lane: one 8-byte store per block
-#pragma unroll
-    for (int j = 0; j < 2; j++) {
-        const int n_loc = by * GM_TN + wn * 32 + j * 16 + (lane & 15); // row inside the group (grouped) or flat
-        int g, i;
-        bool valid;
-        if (a.grouped) { g = grp; i = n_loc; valid = i < a.npg; }
-        else { g = n_loc / a.npg; i = n_loc - g * a.npg; valid = n_loc < a.npg * a.ngroups; }
-        if (!valid) continue;
-        const int gd = a.c_gdiv > 1 ? a.c_gdiv : 1;
-        uint16_t *crow = a.C + (size_t)(g / gd) * a.c_gstride +
-                         (size_t)(a.c_rows ? (int)a.c_rows[(g % gd) * a.c_rows_gstride + i] : i) * a.c_rstride + a.c_off;
-#pragma unroll
-        for (int ib = 0; ib < 4; ib++) {
-            const int m0 = bx * GM_TM + wm * 64 + ib * 16 + (lane >> 4) * 4;
-            if (m0 >= a.M) continue;
-            uint32_t v[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = gf_reduce_limbs(s0[ib][j][r], s1[ib][j][r], s2[ib][j][r]); // k <= 832
-            if (m0 + 4 <= a.M) {
-                *reinterpret_cast<uint2 *>(crow + m0) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-            } else { // M % 4 != 0 (the 407-point interpolation operator): never write past the logical output
-#pragma unroll
-                for (int r = 0; r < 4; r++)
-                    if (m0 + r < a.M) crow[m0 + r] = (uint16_t)v[r];
-            }
-        }
-    }
-}
-
-template <bool BLIMB>
-__global__ __launch_bounds__(256) void k_gemm_modq(GemmArgs a)
-{
-    __shared__ __attribute__((aligned(16))) uint8_t lds[2][GM_A_BYTES + GM_B_BYTES];
-    gemm_modq_block<BLIMB>(a, blockIdx.x, blockIdx.y, blockIdx.z, lds);
-}
 
 // ---- table products with the DATA ROWS resident in LDS (k_table_gemm) ------------------------------------------
 // C[n][c_off + m] = sum_k T[m][k] * X[n][k] mod q for a table T shared by every row: the Lagrange expansion
-// (ss.cpp:23-32, :88-97; T = 1344 x 407) and recon_secrets_ddeg (ss.cpp:44-51; T = 256 x 407).
-// The generic kernel above re-streams a 128 x 64 table tile AND a 64-row data tile for every k-step of every output
-// tile (87 MAC per byte staged) and needs the data operand as a limb matrix in HBM, written by one launch and re-read
-// by each of the 11 table tiles.  Here a workgroup owns 48 data rows: they are converted to limbs ONCE, straight from
-// the canonical u16 rows into LDS (42 KiB), and stay there while the workgroup's 8 waves walk the table.  Each wave
+// (ss.cpp:23-32, :88-97; T = 1344 x 407), recon_secrets_ddeg (ss.cpp:44-51; T = 256 x 407) and recon_secrets_2ddeg
+// (ss.cpp:63-70; T = 256 x 813).
+// A workgroup owns 48 data rows: they are converted to limbs ONCE, straight from the canonical u16 rows into LDS
+// (6 KiB per k-step), and stay there while the workgroup's 8 waves walk the table: no limb matrix of the data in HBM,
+// no tile staged again for every k-step of every output tile.  Each wave
 // takes 16-row chunks of the table on its own (no workgroup barrier after the prologue): the chunk's MFMA fragments
-// (7 k-steps x 2 limbs x 16 bytes per lane) are loaded from the L2-resident table limb matrix straight into registers -- a
+// (KS k-steps x 2 limbs x 16 bytes per lane) are loaded from the L2-resident table limb matrix straight into registers -- a
 // fragment is 16 contiguous bytes of a 1 KiB tile, the wave reads each tile exactly once -- and every register set is
-// re-loaded for the NEXT chunk right after its MFMAs have been issued, so a whole chunk (7 k-steps, ~1350 MFMA cycles)
-// of loads is in flight behind the arithmetic.  After the last k-step the wave reduces mod q and stores 16 x 48 outputs;
-// with two waves per SIMD that epilogue runs under the partner's MFMAs.
+// re-loaded for the NEXT chunk right after its MFMAs have been issued, so a whole chunk of loads is in flight behind
+// the arithmetic.  After the last k-step the wave reduces mod q and stores 16 x 48 outputs.
 // HBM traffic = the data rows once + the output once + the table once (L2-resident afterwards).
 // In-place use (the expansion writes points >= 384 of the rows it reads points < 448 of): the rows are read in the
 // prologue only; with the table split over several workgroups per row block (msplit) another workgroup may already be
 // writing points 384..447 of the same rows -- points < 407 are rewritten with their own values (identity rows of the
 // table) and points >= 407 meet zero table columns, so any value read there is harmless.
 constexpr int TG_WAVES = 8;
-// NBT = data row tiles (of 16) per workgroup: 3 (48 rows, 42 KiB of LDS at 7 k-steps) or 4 (64 rows, 56 KiB).  One workgroup is
-// resident per CU (172+ VGPRs x 8 waves), so a launch takes ceil(row blocks / CUs) rounds of NBT units each: the launcher picks
-// the NBT with the smaller product -- 29 946 rows (138 proofs): 624 blocks of 48 = 3 rounds x 3, 468 blocks of 64 = 2 rounds x 4.
+// NBT = data row tiles (of 16) per workgroup.  Both instantiations use 3 (48 rows): k_table_gemm_p<7, 3, .> keeps two row blocks
+// of 42 KiB in LDS, k_table_gemm<13, 1, 3> one of 78 KiB; one workgroup is resident per CU either way.
 
 // TG_RT = table row tiles (of 16) per chunk
 template <int KS, int TG_RT, int NBT>
@@ -2012,7 +1827,7 @@ static int launch_hash_t(const HashArgs &a, int ngroups, hipStream_t st)
     const long waves = (long)grid.x * grid.y;
     // LDS-DMA staging needs 16-byte aligned 128-byte row segments per wave and readable row padding up to the last
     // wave's 64th lane (true for the row matrix: RS = 1728 = 256 + 23 * 64)
-    const bool dma_ok = !a.lane_map && a.row_stride % 8 == 0 && a.group_stride % 8 == 0 && a.col_off % 8 == 0 &&
+    const bool dma_ok = a.row_stride % 8 == 0 && a.group_stride % 8 == 0 && a.col_off % 8 == 0 &&
                         (reinterpret_cast<uintptr_t>(a.rows) & 15) == 0 && a.col_off + (int)grid.x * 64 <= a.row_stride &&
                         (!PW || (reinterpret_cast<uintptr_t>(a.prefix) & 15) == 0);
     if (dma_ok) {
@@ -2169,24 +1984,20 @@ hipError_t launch_matvec_ntt(const int16_t *A, size_t A_stride, uint16_t *P, siz
     return hipGetLastError();
 }
 
-hipError_t launch_rows_to_limbs(const LimbArgs &a, hipStream_t st)
+// what the table kernels ask of a product: a fragment-order table of 7 k-steps (407-wide inputs) or 13 (813-wide:
+// recon_secrets_2ddeg), whole pairs of 16-row table chunks, source rows that take 16-byte loads, output rows that take 8-byte stores.
+// Every product the library issues meets it by construction: its strides and offsets are the constants checked here, its pointers
+// rows of the context's own buffers (a view's are offset by whole proofs of nrows * RS u16).
+static_assert(RS % 8 == 0 && NSEC % 8 == 0 && EXP_OFF % 4 == 0 && EXP_M % 32 == 0 && NSEC % 32 == 0,
+              "row stride, source offsets, output offsets and table heights of the library's own products");
+bool table_gemm_ok(const GemmArgs &a)
 {
-    if (a.RT <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_rows_to_limbs, dim3((a.KS + 3) / 4, a.RT), dim3(256), 0, st, a);
-    return hipGetLastError();
-}
-
-// the table-product kernel: shared table, KS == 7 (407-wide inputs) or 13 (813-wide: recon_secrets_2ddeg), aligned u16 rows
-static bool table_gemm_ok(const GemmArgs &a)
-{
-    return a.Afrag && !a.grouped && !a.B && (a.KS == 7 || a.KS == 13) && a.M % 32 == 0 && a.c_gdiv <= 1 && a.src_koff % 8 == 0 && a.src_rstride % 8 == 0 &&
+    return a.Afrag && (a.KS == 7 || a.KS == 13) && a.M % 32 == 0 && a.src_koff % 8 == 0 && a.src_rstride % 8 == 0 &&
            a.src_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 && a.c_off % 4 == 0 && a.c_rstride % 4 == 0 &&
            a.c_gstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
 }
 
-bool table_gemm_usable(const GemmArgs &a) { return table_gemm_ok(a); }
-
-hipError_t launch_table_gemm(const GemmArgs &a, uint16_t *sink, hipStream_t st)
+hipError_t launch_table_gemm(const GemmArgs &a, hipStream_t st)
 {
     const int ntot = a.npg * a.ngroups;
     if (ntot <= 0) return hipSuccess;
@@ -2196,7 +2007,6 @@ hipError_t launch_table_gemm(const GemmArgs &a, uint16_t *sink, hipStream_t st)
         return cus;
     }();
     const int nblk = (ntot + 47) / 48, nchunks = a.M / 16; // 48 rows per block
-    (void)sink;
     // eight consecutive outputs per lane and 16-byte stores where the output rows allow it
     const int ws = a.c_off % 8 == 0 && a.c_rstride % 8 == 0 && a.c_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0;
     if (a.KS == 7) {
@@ -2218,16 +2028,6 @@ hipError_t launch_table_gemm(const GemmArgs &a, uint16_t *sink, hipStream_t st)
     msplit = (nchunks + cpb - 1) / cpb;
     const dim3 grid((unsigned)((nblk * msplit + 7) / 8 * 8));
     hipLaunchKernelGGL((k_table_gemm<13, 1, 3>), grid, dim3(512), 0, st, a, nchunks, cpb, nblk, msplit, ws);
-    return hipGetLastError();
-}
-
-hipError_t launch_gemm(const GemmArgs &a, hipStream_t st)
-{
-    const int ntot = a.grouped ? a.npg : a.npg * a.ngroups;
-    if (ntot <= 0) return hipSuccess;
-    dim3 grid(a.Mpad / GM_TM, (ntot + GM_TN - 1) / GM_TN, a.grouped ? a.ngroups : 1);
-    if (a.B) hipLaunchKernelGGL(k_gemm_modq<true>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(k_gemm_modq<false>, grid, dim3(256), 0, st, a);
     return hipGetLastError();
 }
 

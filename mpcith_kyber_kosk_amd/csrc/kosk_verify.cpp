@@ -2,9 +2,9 @@
 // from kyber_kosk_verify, kosk.cpp:88-117).
 //
 //   V0  I / rest from the proof image (host, 300 bytes per proof)        :8-19
-//   V1  scatter the proof into rows; Tcomm of the opened parties          :22-38   k_commit_hash (lane map)
+//   V1  scatter the proof into rows; Tcomm of the opened parties          :22-38   k_commit_hash[_dma]
 //       -> host: alpha                                                    :40-65
-//   V2  beta/gamma/r/NTT_r on the opened columns; recon x140; NTT check   :67-170  k_lincomb, k_gemm_modq, k_ntt256
+//   V2  beta/gamma/r/NTT_r on the opened columns; recon x140; NTT check   :67-170  k_lincomb, k_table_gemm_p, k_ntt256
 //   V4  interpolate the unopened s+r, e+r, t, eta shares: per-proof
 //       operator W (407x407) built on the GPU, applied as a GEMM, then
 //       the Lagrange expansion and the share comparisons                  :173-247, :316-352, :382-444
@@ -352,10 +352,10 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
         HIPCHK(launch_interp_apply(ia, c.d_P, c.proof_stride, c.d_rows_isrc, c.d_rows_idst, c.n_interp_d, c.d_gather, c.n_interp_2d,
                                    c.d_gather2, c.d_sec_u1, n, st));
         c.prof_end(PR_V_GEMM_INTERP);
-        const GemmSrc gs3{c.d_P, c.proof_stride, c.d_rows_u, RS, NSEC, DEG2 + 1};
+        const GemmSrc gs3{c.d_P, c.proof_stride, c.d_rows_u, RS, NSEC};
         const GemmDst gd3{c.d_sec_u2, (size_t)c.n_interp_2d * 256, nullptr, 256, 0};
         if (gemm_modq(c, c.t_recon_2d, gs3, gd3, c.n_interp_2d, n)) return -1;
-        const GemmSrc xs{c.d_P, c.proof_stride, c.d_rows_idst, RS, 0, XLEN};
+        const GemmSrc xs{c.d_P, c.proof_stride, c.d_rows_idst, RS, 0};
         const GemmDst xd{c.d_P, c.proof_stride, c.d_rows_idst, RS, EXP_OFF};
         c.prof_begin(PR_V_GEMM_EXPAND, n);
         if (gemm_modq(c, c.t_expand, xs, xd, c.n_interp_d, n)) return -1; // recompute_share_secrets_ddeg   :224-225, :351, :441-442
@@ -375,7 +375,7 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
     na.out_canonical = 1;
     HIPCHK(launch_relation_ntt(na, c.d_A, c.key_stride, c.d_P, c.proof_stride, rm, n, st));
     {
-        const GemmSrc xs{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, 0, XLEN};
+        const GemmSrc xs{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, 0};
         const GemmDst xd{c.d_P, c.proof_stride, c.d_gemm2_rows, RS, EXP_OFF};
         if (gemm_modq(c, c.t_expand, xs, xd, c.n_gemm2, n)) return -1;
     }
@@ -463,7 +463,7 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
     if (run_segment(c, Ctx::SEG_V2B, n, [&]() -> int {
     NttArgs na{};
     {
-        const GemmSrc gs{c.d_P, c.proof_stride, c.d_rows_bg, RS, NSEC, XLEN};
+        const GemmSrc gs{c.d_P, c.proof_stride, c.d_rows_bg, RS, NSEC};
         const GemmDst gd{c.d_sec, (size_t)2 * NCHK * 256, nullptr, 256, 0};
         c.prof_begin(PR_V_GEMM_RECON, n);
         if (gemm_modq(c, c.t_recon_d, gs, gd, 2 * NCHK, n)) return -1; // recon_secrets_ddeg x 140   :106-107

@@ -1,6 +1,6 @@
 // gfx950 kernels that exist only on the verifier side (mlwe_verifier.cpp:4-686).
-// The heavy steps reuse kosk_kernels.hip: k_commit_hash (opened lanes through a
-// lane map), k_lincomb (opened columns), k_ntt256, k_matvec_ntt and k_gemm_modq
+// The heavy steps reuse kosk_kernels.hip: k_commit_hash[_dma], k_lincomb (opened
+// columns), k_ntt256, k_matvec_ntt and the table products k_table_gemm[_p]
 // (recon_secrets_*, recompute_share_secrets_ddeg, and -- with a per-proof
 // operand -- the application of the interpolation operator that replaces NTL
 // interpolate()/eval(), mlwe_verifier.cpp:201-219 etc.).

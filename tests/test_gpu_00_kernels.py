@@ -70,12 +70,19 @@ def test_sha3_256_lane_pair_sponge(length, torch, ctx):
 @pytest.mark.parametrize("k", [2, 3, 4])
 @pytest.mark.parametrize("with_prefix", [0, 1])
 def test_commit_hash_column_layout(k, with_prefix, torch, oracle):
+    """Both row layouts in every case (one pytest parameter more would rename the cases).  Stride 1600: 16-byte aligned rows that
+    cover the last wave's 64 lanes, the LDS-DMA kernel.  Stride 1531 = the lane count, odd: rows that take neither 16-byte loads nor
+    a read past lane n - 1, the plain kernel (24 waves: its pipelined variant, all six (PREFIX_WORDS, NROWS) instantiations)."""
+    for stride in (1600, 1531):
+        _commit_hash_column_layout(k, with_prefix, stride, torch, oracle)
+
+
+def _commit_hash_column_layout(k, with_prefix, stride, torch, oracle):
     from mpcith_kyber_kosk_amd import api
     p = oracle.params(k)
     words = (p.view_msg_bytes - 32) // 2 if with_prefix else p.tcomm_msg_bytes // 2
     n = 1454 + 77  # ragged lane count
     rng = np.random.default_rng(100 * k + with_prefix)
-    stride = 1600
     rows = rng.integers(0, 3329, size=(words, stride), dtype=np.uint16)
     prefix = rng.integers(0, 256, size=(n, 32), dtype=np.uint8)
     c = api.Kosk(kyber_k=k, max_batch=1)
@@ -87,11 +94,16 @@ def test_commit_hash_column_layout(k, with_prefix, torch, oracle):
     out = d_out.cpu().numpy()
     for l in list(range(0, n, 97)) + [n - 1]:
         msg = (prefix[l].tobytes() if with_prefix else b"") + rows[:, l].astype("<u2").tobytes()
-        assert out[l].tobytes() == hashlib.sha3_256(msg).digest(), l
+        assert out[l].tobytes() == hashlib.sha3_256(msg).digest(), (stride, l)
     # every lane
     cols = np.ascontiguousarray(rows[:, :n].T).astype("<u2")
     bad = [l for l in range(n) if out[l].tobytes() != hashlib.sha3_256((prefix[l].tobytes() if with_prefix else b"") + cols[l].tobytes()).digest()]
-    assert not bad, ("lanes whose digest differs from hashlib", len(bad), bad[:32])
+    assert not bad, ("lanes whose digest differs from hashlib", stride, len(bad), bad[:32])
+    paths = c.path_counts()
+    if stride % 8:
+        assert paths["hash_plain"] == 1 and paths["hash_dma"] == 0, (stride, paths)
+    else:
+        assert paths["hash_plain"] == 0 and paths["hash_dma"] == 1, (stride, paths)
     c.close()
 
 
@@ -161,3 +173,6 @@ def test_lagrange_expand_and_recon_match_oracle(n, torch, ctx, oracle):
     exp = (y[0::2, :256].astype(np.uint32) * y[1::2, :256].astype(np.uint32) % 3329).astype(np.uint16)
     assert np.array_equal(s2, exp)
     assert np.array_equal(s2[3], oracle.recon(prod[3], True))
+    # all three tables (7 and 13 k-steps), caller data: every product ran on the table kernels
+    paths = ctx.path_counts()
+    assert paths["table_gemm"] > 0 and paths["limb_gemm"] == 0, paths

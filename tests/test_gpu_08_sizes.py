@@ -37,31 +37,47 @@ def sample_lanes(lanes, count=64):
 def test_commit_hash_at_65536_lanes(k, torch_cuda, oracle):
     """kosk_commit_hash_lanes at exactly 65 536 lanes: Tcomm messages (308 / 320 B), then view messages (452 / 472 B) whose
     first 32 bytes are the Tcomm digest of the same lane (mlwe_prover.cpp:116-127, :397-444; fips202.c:745-754)."""
+    commit_hash_tcomm_then_view(k, LANES, "hash_dma", torch_cuda, oracle)   # the kernel the bench times (LDS-DMA staged), not a fallback
+
+
+PLAIN_LANES = 3 * 1024 * 64 + 1
+
+
+@pytest.mark.parametrize("k", [2, 3])
+def test_commit_hash_plain_at_196609_lanes(k, torch_cuda, oracle):
+    """The same two rounds on rows the LDS-DMA kernel cannot take (row stride = lane count, odd) and 3 073 waves: at 3 * 1024 waves
+    and above the launcher takes the plain kernel WITHOUT the software pipeline, which no smaller test reaches."""
+    commit_hash_tcomm_then_view(k, PLAIN_LANES, "hash_plain", torch_cuda, oracle)
+
+
+def commit_hash_tcomm_then_view(k, lanes, path, torch_cuda, oracle):
+    """Tcomm then view digests of `lanes` lanes (row stride = lanes), every lane against hashlib; both launches counted under `path`"""
     torch = torch_cuda
     from mpcith_kyber_kosk_amd import api
     p = oracle.params(k)
     tc_words, vw_words = p.tcomm_msg_bytes // 2, (p.view_msg_bytes - 32) // 2
     assert (p.tcomm_msg_bytes, p.view_msg_bytes) == {2: (308, 452), 3: (320, 472)}[k]
-    rows = bench_rows(k, vw_words)
+    rows = bench_rows(k, vw_words, lanes)
     d_rows = torch.from_numpy(rows.view(np.int16)).cuda()
-    d_tc = torch.zeros((LANES, 32), dtype=torch.uint8, device="cuda")
-    d_vw = torch.zeros((LANES, 32), dtype=torch.uint8, device="cuda")
+    d_tc = torch.zeros((lanes, 32), dtype=torch.uint8, device="cuda")
+    d_vw = torch.zeros((lanes, 32), dtype=torch.uint8, device="cuda")
     c = api.Kosk(kyber_k=k, max_batch=1)
     torch_cuda.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
-    c.commit_hash_lanes(d_rows.data_ptr(), LANES, LANES, 0, 0, d_tc.data_ptr())          # rows 0..tc_words-1
+    c.commit_hash_lanes(d_rows.data_ptr(), lanes, lanes, 0, 0, d_tc.data_ptr())          # rows 0..tc_words-1
     torch_cuda.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
-    c.commit_hash_lanes(d_rows.data_ptr(), LANES, LANES, d_tc.data_ptr(), 1, d_vw.data_ptr())
+    c.commit_hash_lanes(d_rows.data_ptr(), lanes, lanes, d_tc.data_ptr(), 1, d_vw.data_ptr())
     c.synchronize()
-    assert c.path_counts()["hash_dma"] == 2          # the kernel the bench times (LDS-DMA staged), not a fallback
+    paths = c.path_counts()
+    assert paths[path] == 2 and paths["hash_dma"] + paths["hash_plain"] == 2, paths
     tc, vw = d_tc.cpu().numpy(), d_vw.cpu().numpy()
-    for l in sample_lanes(LANES):
+    for l in sample_lanes(lanes):
         t = hashlib.sha3_256(rows[:tc_words, l].astype("<u2").tobytes()).digest()
         assert tc[l].tobytes() == t, l
         assert vw[l].tobytes() == hashlib.sha3_256(t + rows[:, l].astype("<u2").tobytes()).digest(), l
     # every lane
     cols = np.ascontiguousarray(rows.T).astype("<u2")
     bad_tc, bad_vw = [], []
-    for l in range(LANES):
+    for l in range(lanes):
         t = hashlib.sha3_256(cols[l, :tc_words].tobytes()).digest()
         if tc[l].tobytes() != t:
             bad_tc.append(l)

@@ -128,7 +128,7 @@ def test_handle_settings_do_not_change_results(knob, oracle, torch_cuda, monkeyp
         base = api.Kosk(kyber_k=k, max_batch=n)
         ref = base.verifiable_keygen(tapes)
         pc0 = base.path_counts()
-        assert pc0["table_gemm"] > 0 and pc0["hash_dma"] > 0 and pc0["graph_replay"] == 0 and pc0["hash_plain"] == 0
+        assert pc0["table_gemm"] > 0 and pc0["limb_gemm"] == 0 and pc0["hash_dma"] > 0 and pc0["graph_replay"] == 0 and pc0["hash_plain"] == 0
         assert pc0["fs_host"] > 0 and pc0["fs_device"] == 0 and pc0["digest_copy"] > 0  # the default: the host hashes the digest tables
         assert pc0["small_copy_kernel"] > 0  # challenge vectors, opened lists, key records and fail masks move by kernel
         if name.islower():

@@ -10,7 +10,7 @@ for n in "${@:-9982}"; do
   python3 - $f $n <<PY
 import csv,sys
 for r in csv.DictReader(open(sys.argv[1])):
-    if "gemm" in r["Name"] or "limbs" in r["Name"]:
+    if "gemm" in r["Name"]:
         print("rows %6s  %-44s calls %3s avg %7.1f us" % (sys.argv[2], r["Name"].split("(")[0].replace("void ","").replace("kosk::","")[:44], r["Calls"], float(r["AverageNs"])/1e3))
 PY
 done

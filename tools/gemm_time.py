@@ -14,4 +14,4 @@ ctx.synchronize()
 ctx.timer_start()
 for _ in range(10):
     ctx.lagrange_expand(y.data_ptr(), sh.data_ptr(), n)
-print("dbg=%s n=%d: %.1f us per expand (incl. 2 row copies + limb conversion)" % (os.environ.get("KOSK_GEMM_DBG", "0"), n, ctx.timer_stop_ms() * 100))
+print("dbg=%s n=%d: %.1f us per expand (incl. 2 row copies)" % (os.environ.get("KOSK_GEMM_DBG", "0"), n, ctx.timer_stop_ms() * 100))
