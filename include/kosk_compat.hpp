@@ -22,6 +22,12 @@
 #define KYBER_POLYVECBYTES (KYBER_K * KYBER_POLYBYTES)
 #define KYBER_PUBLICKEYBYTES (KYBER_POLYVECBYTES + KYBER_SYMBYTES)                              /* kyber/params.h:49 */
 #define KYBER_SECRETKEYBYTES (KYBER_POLYVECBYTES + KYBER_PUBLICKEYBYTES + 2 * KYBER_SYMBYTES)   /* kyber/params.h:51 */
+#define KYBER_SSBYTES 32
+#if KYBER_K == 4
+#define KYBER_CIPHERTEXTBYTES (KYBER_K * 352 + 160) /* kyber/params.h:41-53: d_u = 11, d_v = 5 */
+#else
+#define KYBER_CIPHERTEXTBYTES (KYBER_K * 320 + 128) /* d_u = 10, d_v = 4 */
+#endif
 #if KYBER_K == 2
 #define KYBER_ETA1 3
 #else
@@ -140,8 +146,6 @@ inline bool kyber_kosk_verify(const uint8_t *pi, const uint8_t *pk)
     return ok == 1;
 }
 
-
-/* ---- second-level entry points, used directly by main.cpp:21-47 ---- */
 namespace kosk_compat {
 inline void must(int rc, const char *what)
 {
@@ -151,6 +155,27 @@ inline void must(int rc, const char *what)
     }
 }
 } // namespace kosk_compat
+
+/* ---- the KEM on those keys (kyber/kem.h: crypto_kem_enc_derand, crypto_kem_enc, crypto_kem_dec), one item per call on the
+ * process-wide handle; all return 0 like the reference's (kem.c:95, :120, :168) ---- */
+inline int crypto_kem_enc_derand(uint8_t *ct, uint8_t *ss, const uint8_t *pk, const uint8_t *coins)
+{
+    kosk_compat::must(kosk_kem_enc_batch(kosk_compat::ctx(), 1, pk, coins, ct, ss), "crypto_kem_enc_derand");
+    return 0;
+}
+/* kem.c:113-121: the 32 coins come from randombytes (one call), through the handle's callback */
+inline int crypto_kem_enc(uint8_t *ct, uint8_t *ss, const uint8_t *pk)
+{
+    kosk_compat::must(kosk_kem_enc_batch(kosk_compat::ctx(), 1, pk, nullptr, ct, ss), "crypto_kem_enc");
+    return 0;
+}
+inline int crypto_kem_dec(uint8_t *ss, const uint8_t *ct, const uint8_t *sk)
+{
+    kosk_compat::must(kosk_kem_dec_batch(kosk_compat::ctx(), 1, ct, sk, ss), "crypto_kem_dec");
+    return 0;
+}
+
+/* ---- second-level entry points, used directly by main.cpp:21-47 ---- */
 /* mlwe_prover.hpp:77 */
 inline void prepare_randomness(mpcith_randomness *rand)
 {

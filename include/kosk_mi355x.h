@@ -190,6 +190,34 @@ int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uin
 int kosk_fetch_proofs_compact(kosk_ctx *ctx, int n, uint8_t *out);        /* like kosk_fetch_proofs */
 int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk); /* like kosk_stage_verifier_inputs */
 
+/* ---- Kyber KEM on the keys this library makes and vouches for: crypto_kem_enc_derand / crypto_kem_enc / crypto_kem_dec
+ * (kyber/kem.c:76-96, :113-121, :140-169; indcpa_enc / indcpa_dec, kyber/indcpa.c:264-336), bit-exact, for kyber_k 2 / 3 / 4, n items
+ * per call.  Records are consecutive: kosk_pk_bytes, kosk_sk_bytes (s || pk || H(pk) || z, what kosk_verifiable_keygen_* returns),
+ * kosk_ct_bytes, KOSK_SS_BYTES.  Every buffer may be host or device memory (told apart like the seeds of the seeded calls).  n is any
+ * positive number: the calls work through launch groups of 16384 items.  The KEM workspace (about 13 KB per item of the largest launch group
+ * the handle has seen, for kyber_k = 4) is allocated at a handle's first KEM call; a handle that never makes one takes no HBM for it.
+ * coins: n x 32 bytes, the m of crypto_kem_enc_derand; NULL: one 32-byte draw per item, in item order, on the caller's thread, through
+ * the randombytes callback / OS entropy (kem.c:117-118).
+ * Encoding: like the reference's polyvec_frombytes these calls take any 12-bit coefficient in a pk or sk and compute with it mod q
+ * (the ciphertext then differs from the canonical key's because H(pk) does); kosk_options::strict_encoding concerns proofs and is
+ * not consulted.  Decapsulation has no branch and no address that depends on s, m', the comparison or z; its secret-derived scratch
+ * (m', K-bar || coins, r, e1, e2, the rejection key) stays in the handle's HBM workspace until the next KEM call overwrites it or
+ * the handle is destroyed.
+ * All three calls run unmerged on the handle's own stream, reset and check the HIP error state like every entry point, and return -1
+ * ("block limit", no results) if gen_matrix reached its block limit. */
+#define KOSK_SS_BYTES 32
+size_t kosk_ct_bytes(int kyber_k); /* KYBER_CIPHERTEXTBYTES 768 / 1088 / 1568; 0 outside 2..4 */
+int kosk_kem_enc_batch(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
+int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss);
+/* The registrar's step: encapsulate to the public keys that the LAST COMPLETED verify call of at least n proofs left in HBM on this
+ * handle (the rule of kosk_verify_resident_pk(pk == NULL)), and only where that call's verify bit is 1.  done[b] is that bit; ct and
+ * ss of a rejected position are zero-filled; coins are consumed for every position, so the draw order does not depend on the outcome.
+ * The public keys are decoded again from their resident bytes (the same result as reusing the verifier's t and A).  Needs
+ * streams = 1.  -1 with a text when no verify call has completed, when the last one covered fewer than n proofs, was a
+ * chunked kosk_verify_batch call (n > max_batch), verified with A and t from instances (kosk_verify_inst, or kosk_verify_resident after it: no pk bytes were decoded) or was followed
+ * by a call that replaced the resident keys (a key generation, a verifier staging call in either wire format); and for a member of a cohort (combine >= 2): "not available with call combining". */
+int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
+
 /* Which kernel / copy paths ran on this handle since it was created (the tests of the fallbacks and of the Fiat-Shamir mode assert on
  * these).  ids: 0 commitment hash with LDS-DMA staging, 1 without (a layout the staged kernel cannot take: unaligned rows),
  * 2 shared-table products on k_table_gemm / k_table_gemm_p (every mod-q product), 3 retired, always 0 (the generic limb GEMM, which no call
@@ -197,7 +225,7 @@ int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, 
  * caller), 5 through the pinned staging buffer (pageable caller memory), 6 hipGraph segment replays (KOSK_GRAPHS=1), 7 commitment rounds
  * whose digest table was copied to the host (host Fiat-Shamir mode), 8 small copies between HBM and the library's own page-locked buffers
  * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded
- * proving: tapes expanded from seeds in HBM). */
+ * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

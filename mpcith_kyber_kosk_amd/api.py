@@ -105,6 +105,15 @@ def _load():
     # calls must stay usable from this binding.  The tree's own library has to export everything
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_tape_from_seed")):
         sig.update(seeded)
+    # Kyber KEM; optional under the same rule (and only then)
+    kem = {
+        "kosk_ct_bytes": (sz, [C.c_int]),
+        "kosk_kem_enc_batch": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "kosk_kem_dec_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_kem_enc_verified": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_enc_batch")):
+        sig.update(kem)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -125,7 +134,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_fs_opened", "kosk_host_sha3_256", "kosk_host_shake256", "kosk_host_sha3_256_multi", "kosk_lagrange_table",
            "kosk_options_init", "kosk_create_ex", "kosk_sha3_256_batch_wave", "kosk_fs_alpha_device", "kosk_fs_opened_device",
            "kosk_tape_from_seed", "kosk_set_entropy", "kosk_tape_expand_device", "kosk_verifiable_keygen_seeded_batch",
-           "kosk_verifiable_keygen_seeded_batch_compact", "kosk_verifiable_keygen_seeded_resident", "kosk_stage_prover_inputs_seeded"]
+           "kosk_verifiable_keygen_seeded_batch_compact", "kosk_verifiable_keygen_seeded_resident", "kosk_stage_prover_inputs_seeded",
+           "kosk_ct_bytes", "kosk_kem_enc_batch", "kosk_kem_dec_batch", "kosk_kem_enc_verified"]
+HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
 class KoskOptions(C.Structure):
@@ -138,6 +149,7 @@ class KoskOptions(C.Structure):
 FS_HOST, FS_DEVICE = 0, 1
 ENTROPY_TAPE, ENTROPY_SEED = 0, 1  # kosk_set_entropy
 SEED_BYTES = 32
+SS_BYTES = 32  # KOSK_SS_BYTES
 
 
 def options(**fields):
@@ -154,6 +166,7 @@ def pk_bytes(k): return lib.kosk_pk_bytes(k)
 def sk_bytes(k): return lib.kosk_sk_bytes(k)
 def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
+def ct_bytes(k): return lib.kosk_ct_bytes(k)
 
 
 def tape_from_seed(k, seed):
@@ -180,6 +193,12 @@ def _buf(b):
         arr = (C.c_uint8 * len(b)).from_buffer_copy(b) if isinstance(b, bytes) else (C.c_uint8 * len(b)).from_buffer(b)
         return C.cast(arr, C.c_void_p), arr
     raise TypeError(type(b))
+
+
+def _cut(buf, size, n):
+    """n records of `size` bytes out of a ctypes buffer (ONE copy of the buffer: .raw copies all of it every time it is read)"""
+    raw = buf.raw
+    return [raw[i * size:(i + 1) * size] for i in range(n)]
 
 
 def host_keygen(k, seed64):
@@ -524,13 +543,78 @@ class Kosk:
         self._chk(lib.kosk_combine_stats(self._h, C.byref(a), C.byref(b)), "combine_stats")
         return a.value, b.value
 
+    def _records(self, what, x, n, size):
+        """list of `size`-byte records or an int DEVICE pointer (with n) -> (pointer, n, keepalive)"""
+        if isinstance(x, int):
+            if n is None:
+                raise KoskError("a device pointer for %s needs n" % what)
+            return C.c_void_p(x), n, None
+        for r_ in x:
+            if len(r_) != size:
+                raise KoskError("a %s record has %d bytes" % (what, size))
+        blob = b"".join(bytes(r_) for r_ in x)
+        return C.c_char_p(blob), len(x), blob
+
+    def _kem_out(self, out, n, sizes):
+        """out: None (host buffers, returned as lists of bytes) or a tuple of int DEVICE pointers, one per output"""
+        if out is not None:
+            if len(out) != len(sizes):
+                raise KoskError("out needs %d device pointers" % len(sizes))
+            return [C.c_void_p(int(p_)) for p_ in out], None
+        bufs = [C.create_string_buffer(s_ * n) for s_ in sizes]
+        return bufs, bufs
+
+    def kem_enc(self, pks, coins=None, n=None, out=None):
+        """crypto_kem_enc_derand for n public keys (kosk_kem_enc_batch).  pks / coins: lists of bytes or int DEVICE pointers (with n);
+        coins=None: one 32-byte draw per item through the randombytes callback / OS entropy.  Returns (cts, sss) as lists of bytes, or,
+        with out=(d_ct, d_ss) int device pointers, writes there and returns out."""
+        pp, n, _k1 = self._records("pk", pks, n, self.pk_bytes)
+        cp, _k2 = None, None
+        if coins is not None:
+            cp, nc, _k2 = self._records("coins", coins, n, 32)
+            if nc != n:
+                raise KoskError("coins for %d items, public keys for %d" % (nc, n))
+        ctb = ct_bytes(self.k)
+        bufs, host = self._kem_out(out, n, (ctb, SS_BYTES))
+        self._chk(lib.kosk_kem_enc_batch(self._h, n, pp, cp, bufs[0], bufs[1]), "kem_enc")
+        if host is None:
+            return out
+        return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n)
+
+    def kem_dec(self, cts, sks, n=None, out=None):
+        """crypto_kem_dec for n (ciphertext, secret key) pairs (kosk_kem_dec_batch); inputs as in kem_enc.  Returns the list of shared
+        secrets, or, with out = an int device pointer, writes there and returns it."""
+        ctb = ct_bytes(self.k)
+        cp, n, _k1 = self._records("ct", cts, n, ctb)
+        sp, ns, _k2 = self._records("sk", sks, n, self.sk_bytes)
+        if ns != n:
+            raise KoskError("secret keys for %d items, ciphertexts for %d" % (ns, n))
+        bufs, host = self._kem_out(None if out is None else (out,), n, (SS_BYTES,))
+        self._chk(lib.kosk_kem_dec_batch(self._h, n, cp, sp, bufs[0]), "kem_dec")
+        if host is None:
+            return out
+        return _cut(bufs[0], SS_BYTES, n)
+
+    def kem_enc_verified(self, n, coins=None):
+        """kosk_kem_enc_verified: encapsulate to the public keys the last completed verify call left in HBM, where its verify bit is 1.
+        Returns (cts, sss, done); ct and ss of a rejected position are zero-filled."""
+        cp, _k = None, None
+        if coins is not None:
+            cp, nc, _k = self._records("coins", coins, n, 32)
+            if nc != n:
+                raise KoskError("coins for %d items, n = %d" % (nc, n))
+        ctb = ct_bytes(self.k)
+        ct = C.create_string_buffer(ctb * n); ss = C.create_string_buffer(SS_BYTES * n); done = C.create_string_buffer(n)
+        self._chk(lib.kosk_kem_enc_verified(self._h, n, cp, ct, ss, done), "kem_enc_verified")
+        return _cut(ct, ctb, n), _cut(ss, SS_BYTES, n), [bool(x) for x in done.raw[:n]]
+
     PATH_IDS = ["hash_dma", "hash_plain", "table_gemm", "limb_gemm", "copy_direct", "copy_staged", "graph_replay", "digest_copy", "small_copy_kernel",
-                "fs_device", "fs_host", "tape_expand"]
+                "fs_device", "fs_host", "tape_expand", "kem_enc", "kem_dec"]
 
     def path_counts(self):
         """{name: launches / copies} of the alternative kernel and copy paths on this handle since it was created"""
         out = {}
-        for i, name in enumerate(self.PATH_IDS):
+        for i, name in enumerate(self.PATH_IDS if HAS_KEM else self.PATH_IDS[:12]):
             v = C.c_long()
             self._chk(lib.kosk_path_count(self._h, i, C.byref(v)), "path_count")
             out[name] = v.value

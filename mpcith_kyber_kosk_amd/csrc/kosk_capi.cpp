@@ -60,6 +60,10 @@ struct kosk_ctx {
     Cohort *cohort = nullptr;    // KOSK_COMBINE: this handle is member `member_i` of a cohort, sub[0] a view of its arena
     int member_i = -1;
     long merged_calls = 0, merged_members = 0; // resident calls of this handle served by a run, and the members those runs served
+    // kosk_kem_enc_verified: the last completed verify call left its public keys in HBM (pk_epoch of sub[0] at that moment), whole
+    // (one pipeline run, not chunks that overwrote each other) -- verify_keys 0: no such call, 1: yes, 2: chunked, 3: no pk bytes (instances)
+    unsigned long verify_epoch = 0;
+    int verify_keys = 0;
     bool hooks_unmerged = false; // kosk_options::hooks_unmerged: with a round hook set, this handle's resident calls run on their own
 
     ~kosk_ctx()
@@ -502,6 +506,13 @@ static void reset_masks(kosk_ctx *ctx, int n)
 {
     ctx->masks_n = 0;
     ctx->masks.assign((size_t)n, 0);
+    ctx->verify_keys = 0;
+}
+// a verify call completed: what kosk_kem_enc_verified may rely on
+static void note_verified_keys(kosk_ctx *ctx, int kind)
+{
+    ctx->verify_keys = kind;
+    ctx->verify_epoch = ctx->c->pk_epoch;
 }
 
 int kosk_verify_resident(kosk_ctx *ctx, int n, uint8_t *ok)
@@ -511,6 +522,7 @@ int kosk_verify_resident(kosk_ctx *ctx, int n, uint8_t *ok)
     reset_masks(ctx, n);
     if (ctx->run(n, [&](Ctx &c, int first, int count) { return verify_into(ctx, c, first, count, ok, 0, nullptr); })) return -1;
     ctx->masks_n = n;
+    note_verified_keys(ctx, ctx->c->resident_pk_n >= n && ctx->c->keys_from_pk_n >= n ? 1 : 3);
     return 0;
     GUARD_END
 }
@@ -716,6 +728,7 @@ int kosk_verify_resident_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *ok
             return verify_into(ctx, c, first, count, ok, pk ? 1 : 2, pk ? pk + (size_t)first * P.pk_bytes : nullptr);
         })) return -1;
     ctx->masks_n = n;
+    note_verified_keys(ctx, 1);
     return 0;
     GUARD_END
 }
@@ -790,7 +803,7 @@ int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk
         c.host_img_stride = P.proof_bytes;
         return verify_into(ctx, c, first, count, ok, 0, nullptr);
     });
-    if (!rc) ctx->masks_n = n;
+    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
     return rc;
     GUARD_END
 }
@@ -843,7 +856,7 @@ int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uin
         if (stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, pinned)) return -1;
         return verify_into(ctx, c, first, count, ok, 0, nullptr);
     });
-    if (!rc) ctx->masks_n = n;
+    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
     return rc;
     GUARD_END
 }
@@ -914,6 +927,7 @@ int kosk_verify_inst(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *ins
         done += m;
     }
     ctx->masks_n = n;
+    note_verified_keys(ctx, 3);
     return 0;
     GUARD_END
 }
@@ -963,6 +977,79 @@ int kosk_verify_fail_masks(const kosk_ctx *ctx, uint32_t *masks, int n)
     if (!ctx || !masks || n < 0 || n > ctx->masks_n) return bad_args(ctx, __func__);
     memcpy(masks, ctx->masks.data(), sizeof(uint32_t) * (size_t)n);
     return 0;
+}
+
+// ---- Kyber KEM (kosk_kem_kernels.hip) ------------------------------------------------------------------------
+size_t kosk_ct_bytes(int k) { return k == 2 ? 768 : k == 3 ? 1088 : k == 4 ? 1568 : 0; }
+
+// the m of crypto_kem_enc_derand for n items: the caller's, or one 32-byte draw per item, in item order, on the caller's thread
+// (kem.c:117-118)
+static const uint8_t *kem_coins(const kosk_ctx *ctx, int n, const uint8_t *coins, std::vector<uint8_t> &drawn)
+{
+    if (coins) return coins;
+    drawn.resize((size_t)n * 32);
+    draw_seeds(*ctx->c, n, drawn.data());
+    return drawn.data();
+}
+// a KEM call of any n as launch groups of at most KEM_CHUNK items, unmerged, on sub-context 0 (the handle's own stream)
+static int kem_chunks(kosk_ctx *ctx, int n, const std::function<int(Ctx &, int, int)> &fn)
+{
+    ctx->clear_err();
+    Ctx &c = *ctx->c;
+    for (int first = 0; first < n; first += KEM_CHUNK) {
+        const int count = n - first < KEM_CHUNK ? n - first : KEM_CHUNK;
+        if (fn(c, first, count)) { ctx->err = c.err; return -1; }
+    }
+    return 0;
+}
+int kosk_kem_enc_batch(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
+{
+    if (!ctx || n < 1 || !pk || !ct || !ss) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    const size_t ctb = kosk_ct_bytes(P.K);
+    std::vector<uint8_t> drawn;
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_enc(c, count, pk + (size_t)first * P.pk_bytes, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32);
+    });
+    GUARD_END
+}
+int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
+{
+    if (!ctx || n < 1 || !ct || !sk || !ss) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    const size_t ctb = kosk_ct_bytes(P.K);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_dec(c, count, ct + (size_t)first * ctb, sk + (size_t)first * P.sk_bytes, ss + (size_t)first * 32);
+    });
+    GUARD_END
+}
+int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (!ctx || n < 1 || !ct || !ss || !done) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    auto refuse = [&](const char *why) { ctx->err = std::string("kosk_kem_enc_verified: ") + why; ctx->c->err = ctx->err; return -1; };
+    if (ctx->cohort) return refuse("not available with call combining (the handle is a member of a cohort)");
+    if (ctx->sub.size() > 1) return refuse("needs streams = 1 (sub-batches keep separate public keys)");
+    if (ctx->verify_keys == 0 || ctx->masks_n < 1) return refuse("no verify call has completed on this handle");
+    if (ctx->verify_keys == 2) return refuse("the last verify call was a chunked kosk_verify_batch call (n > max_batch): its public keys are not resident as one batch");
+    if (ctx->masks_n < n) return refuse("the last verify call covered fewer than n proofs");
+    if (ctx->verify_keys == 3) return refuse("the last verify call left no public key bytes in HBM (its A and t came from instances)");
+    if (ctx->verify_epoch != ctx->c->pk_epoch || ctx->c->resident_pk_n < n) return refuse("the resident public keys were replaced after the last verify call");
+    // coins are drawn for every position, accepted or not: the draw order does not depend on the outcome
+    std::vector<uint8_t> drawn, bits((size_t)n);
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    for (int b = 0; b < n; b++) bits[(size_t)b] = ctx->masks[(size_t)b] == 0;
+    const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return kem_enc(c, count, nullptr, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32, bits.data() + first, first);
+        })) return -1;
+    if (hipMemcpy(done, bits.data(), (size_t)n, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return refuse("copying the verify bits to `done` failed"); }
+    return 0;
+    GUARD_END
 }
 
 void *kosk_host_alloc(size_t bytes)

@@ -186,7 +186,7 @@ int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_
     });
     c.path_n[direct ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     HIPCHK(hipMemcpyAsync(c.d_pk, c.h_pk, (size_t)n * c.pk_stride, hipMemcpyHostToDevice, c.stream));
-    c.resident_pk_n = n;
+    c.note_pk_written(n);
     if (direct) HIPCHK(hipMemcpy2DAsync(c.d_compact, c.compact_stride, in, c.cplan.bytes, c.cplan.bytes, n, hipMemcpyHostToDevice, c.stream));
     else HIPCHK(hipMemcpyAsync(c.d_compact, c.h_compact, (size_t)n * c.compact_stride, hipMemcpyHostToDevice, c.stream));
     hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_compact, c.compact_stride, c.d_proof, c.image_stride, c.cplan);

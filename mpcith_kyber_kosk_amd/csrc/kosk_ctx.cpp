@@ -60,6 +60,7 @@ Ctx::~Ctx()
         for (auto e : pe)
             if (e) (void)hipEventDestroy(e);
     if (ev_sync) (void)hipEventDestroy(ev_sync);
+    kem_release(*this);
     if (is_view) {
         if (h_err) (void)hipHostFree(h_err);
         // a view owns its events, host workers and compact staging; tables, workspace and the stream belong to the arena
@@ -525,6 +526,8 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     for (int i = 0; i < PR_COUNT; i++) { c.prof_ms[i] = 0; c.prof_n[i] = 0; c.prof_units[i] = 0; c.prof_used[i] = false; }
     c.tape_cur = nullptr;
     c.resident_pk_n = 0;
+    c.keys_from_pk_n = 0;
+    c.kem = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     for (const Ctx::PerProof &pp : arena.per_proof) {
         char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
@@ -553,7 +556,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     return 0;
 }
 
-static bool is_device_pointer(const void *p)
+bool is_device_pointer(const void *p)
 {
     hipPointerAttribute_t at{};
     if (hipPointerGetAttributes(&at, p) != hipSuccess) {
@@ -754,7 +757,7 @@ int issue_keygen(Ctx &c, int n, bool sampled)
     HIPCHK(copy_small(c, c.h_kg, 0, c.d_kg, 0, (size_t)n * c.kg_rec, 1, hipMemcpyDeviceToHost, c.stream)); // pk, NTT(s) bytes, seeds: one copy
     c.kg_on_host_pending = false;
     if (!c.capturing) { HIPCHK(hipEventRecord(c.ev_kg, c.stream)); c.kg_on_host_pending = true; } // (a keygen-in-front call is never captured)
-    c.resident_pk_n = n;
+    c.note_pk_written(n);
     return 0;
 }
 

@@ -72,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -109,6 +109,10 @@ struct CompactPlan {
 CompactPlan make_compact_plan(const Params &P);
 int compact_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a value >= 4096
 void compact_decode(const Params &P, const uint8_t *in, uint8_t *img);
+
+struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
+enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
+       KEM_WAVE_MAX = 1024 }; // launch groups of up to this many items (one wave per SIMD) run their long one-lane-per-item chains on a wave sponge, one wave per item
 
 struct Ctx {
     int device = 0;
@@ -185,6 +189,16 @@ struct Ctx {
     int16_t *d_sehat = nullptr;
     int resident_pk_n = 0; // pk records valid in d_pk (written by the key generation or a verifier staging call): pk_mode 2 needs >= n
     size_t pk_stride = 0, sb_stride = 0;
+    // kosk_kem_enc_verified encapsulates to d_pk with the bits of a verify call that read d_A / d_t: it must know that d_A / d_t were decoded
+    // from d_pk (keys_from_pk_n: how many leading records of d_A / d_t are decodings of the same records of d_pk; 0 once instances were
+    // uploaded, kosk_split.cpp) and that neither changed since (pk_epoch counts every change of either).  EVERY writer of d_pk goes through
+    // note_pk_written(), the instance upload through note_keys_from_inst(), a verify call that decodes the resident d_pk again
+    // (pk_mode 2) through note_pk_decoded()
+    unsigned long pk_epoch = 0;
+    int keys_from_pk_n = 0;
+    void note_pk_written(int n) { resident_pk_n = n; keys_from_pk_n = n; pk_epoch++; }
+    void note_pk_decoded(int n) { if (n > keys_from_pk_n) keys_from_pk_n = n; } // records [0, n) decoded again from d_pk; the others keep their state
+    void note_keys_from_inst() { keys_from_pk_n = 0; pk_epoch++; }
     uint8_t *h_seeds = nullptr, *h_pk = nullptr, *h_sb = nullptr;
     uint16_t *d_t = nullptr; // pk's t, canonical (verifier)
     uint16_t *d_alpha = nullptr, *d_I = nullptr, *d_rest = nullptr;
@@ -299,6 +313,7 @@ struct Ctx {
                                      // record happened inside calls that had just done that, and neither was ever reproduced or explained)
     // which of those paths really ran on this context (kosk_path_count): the tests of the knobs assert on these
     long path_n[PATH_COUNT] = {0};
+    KemWs *kem = nullptr; // allocated at this context's first KEM call, owned by it (a view's is its own, never the arena's)
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -374,6 +389,8 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
 // workers created now (a merged run led by this view uses base_threads x members of them)
 int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx **out, std::string &err);
 
+// p is device memory (hipMalloc); plain, page-locked and unknown pointers are host memory
+bool is_device_pointer(const void *p);
 // host wait for everything queued on the context's stream (spinning, or sleeping with KOSK_BLOCKING_SYNC=1)
 hipError_t stream_sync(Ctx &c);
 // wait for `ev` (recorded on the context's stream); site = which of the pipeline's long waits this is (0..WAIT_SITES-1: napped with
@@ -431,5 +448,12 @@ int stage_verifier_inputs(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, b
 // device memory, n records of pk_bytes) at the head of the first segment (kosk.cpp:94-99: polyvec_frombytes + gen_matrix);
 // 2: decode the pk bytes the key generation left resident in HBM
 int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode = 0, const uint8_t *pk = nullptr, const VerifySeg *segs = nullptr);
+
+// Kyber KEM (kosk_kem_kernels.hip): n <= KEM_CHUNK items, every buffer host or device memory, unmerged on the context's stream.
+// crypto_kem_enc_derand (kem.c:76-96): pk == nullptr encapsulates to the public keys resident in c.d_pk from record resident_first on; mask (host, n bytes, or
+// nullptr): items whose byte is 0 are not encapsulated to, their ct and ss are zero-filled.  crypto_kem_dec (kem.c:140-169).
+int kem_enc(Ctx &c, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask = nullptr, int resident_first = 0);
+int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss);
+void kem_release(Ctx &c);
 
 } // namespace kosk

@@ -1,0 +1,354 @@
+// Kyber KEM on gfx950: crypto_kem_enc_derand / crypto_kem_dec (kyber/kem.c:76-96, :140-169) for batches of items, bit-exact.
+//
+// Three launches per chunk of up to KEM_CHUNK items (plus one wave-sponge launch in a small chunk, below), all on the context's stream:
+//   encapsulate   k_kem_hash    roles  H(pk) + G            one sponge per lane   (K^2 + 1) lanes per item
+//                                      gen_matrix (A^T)
+//                 k_kem_hash    roles  r, e1, e2            one sponge per lane   (2 K + 1) lanes per item
+//                 k_kem_encrypt NTT(r), A^T o r-hat, t-hat o r-hat, inverse NTT, + e, compress, pack   one workgroup per item
+//   decapsulate   k_kem_decrypt decompress, NTT(u), s-hat o u-hat, inverse NTT, tomsg, G(m' || h)     one workgroup per item
+//                 k_kem_hash    roles  rkprf, gen_matrix, r, e1, e2
+//                 k_kem_encrypt the same device function as above, comparing instead of storing; OR-reduction; masked select
+// The roles of k_kem_hash are lane ranges of one launch (task-major: a wave runs one role), longest role first.  Sponge layout by wave
+// count: one state per lane, except the two roles that are ONE lane per item with a chain of 6-12 dependent permutations -- H(pk) of an
+// encapsulation and rkprf of a decapsulation.  In a launch group of up to KEM_WAVE_MAX items such a role would be a few waves at
+// single-wave latency, so it runs as one WAVE per item on the wave sponge (kosk_fs_dev.hpp), launched ahead of k_kem_hash: H(pk) on
+// k_fs_chain<FS_DIGEST> (kosk_fs_kernels.hip), after which the seed role only does G; rkprf on k_kem_rkprf_wave below (SHAKE domain,
+// two-part message).  The device functions are in kosk_kem_dev.hpp; DESIGN.md 19 has the resource figures.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+
+#include "kosk_ctx.hpp"
+#include "kosk_fs_dev.hpp"
+#include "kosk_kem_dev.hpp"
+
+namespace kosk {
+
+using namespace kem;
+
+// HBM workspace of the KEM calls, allocated at a context's first KEM call (a handle that never makes one pays nothing)
+struct KemWs {
+    int cap = 0;
+    uint8_t *d_pk = nullptr, *d_sk = nullptr, *d_ct = nullptr, *d_m = nullptr, *d_kr = nullptr, *d_rk = nullptr, *d_ss = nullptr, *d_mask = nullptr;
+    uint8_t *d_h = nullptr; // [n][32] H(pk) from the wave sponge
+    int16_t *d_A = nullptr, *d_noise = nullptr;
+};
+
+struct KemHashJob {
+    int n, K, eta1;
+    int n_rk, n_seed, n_mat, n_noise; // lanes per item of each role, in launch order
+    const uint8_t *pk;                // records holding t-hat || rho (the pk, or the pk inside the sk)
+    size_t pk_stride;
+    int pk_bytes;
+    const uint8_t *m;                 // [n][32]     seed role: the message
+    const uint8_t *h;                 // [n][32] or nullptr: H(pk) already computed (wave sponge); nullptr: the seed role hashes pk itself
+    uint8_t *kr;                      // [n][64]     seed role writes, noise role reads (coins = kr + 32)
+    int16_t *A, *noise;               // [n][K K][256], [n][2 K + 1][256]
+    const uint8_t *z;                 // rkprf role: z of item b at z + b * z_stride
+    size_t z_stride;
+    const uint8_t *ct;                // [n][ct_bytes]
+    int ct_bytes;
+    uint8_t *rk;                      // [n][32]
+    uint32_t *err;
+    int max_blocks;
+};
+
+__global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const int per = j.n_rk + j.n_seed + j.n_mat + j.n_noise;
+    if (gid >= (long)per * j.n) return;
+    int t = (int)(gid / j.n);
+    const int b = (int)(gid - (long)t * j.n);
+    const uint8_t *pk = j.pk + (size_t)b * j.pk_stride;
+    if (t < j.n_rk) {
+        uint64_t out[4];
+        rkprf(j.z + (size_t)b * j.z_stride, j.ct + (size_t)b * j.ct_bytes, j.ct_bytes, out);
+#pragma unroll
+        for (int l = 0; l < 4; l++) reinterpret_cast<uint64_t *>(j.rk)[4 * (size_t)b + l] = out[l];
+        return;
+    }
+    t -= j.n_rk;
+    if (t < j.n_seed) {
+        uint64_t m[4], h[4], kr[8];
+#pragma unroll
+        for (int l = 0; l < 4; l++) m[l] = ld64(j.m, 4 * b + l);
+        if (j.h) {
+#pragma unroll
+            for (int l = 0; l < 4; l++) h[l] = ld64(j.h, 4 * b + l);
+        } else {
+            sha3_256_words(pk, j.pk_bytes, h);
+        }
+        hash_g64(m, h, kr);
+#pragma unroll
+        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * (size_t)b + l] = kr[l];
+        return;
+    }
+    t -= j.n_seed;
+    if (t < j.n_mat) {
+        uint64_t rho[4];
+#pragma unroll
+        for (int l = 0; l < 4; l++) rho[l] = ld64(pk + j.pk_bytes - 32, l);
+        // A^T[i][j] = XOF(rho, i, j) (indcpa.c:177-178)
+        if (!matrix_entry(rho, t / j.K, t % j.K, j.max_blocks, j.A + ((size_t)b * j.n_mat + t) * 256))
+            if (j.err) *reinterpret_cast<volatile uint32_t *>(j.err) = DEVERR_XOF_BLOCKS;
+        return;
+    }
+    t -= j.n_mat;
+    uint64_t coins[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) coins[l] = ld64(j.kr, 8 * b + 4 + l);
+    noise_poly(coins, t, t < j.K ? j.eta1 : 2, j.noise + ((size_t)b * j.n_noise + t) * 256);
+}
+
+// rkprf = SHAKE256(z[32] || ct) (symmetric-shake.c: kyber_shake256_rkprf), one WAVE per item on the wave sponge: a 32-bit half of a state
+// word per lane, bit-interleaved (kosk_fs_dev.hpp, FsSpongeBperm).  z and ct are 8-byte aligned and 32 + ct_bytes is a multiple of 8, so
+// every block is whole words.  z is secret: it is data only; the addresses are functions of the lane and the block.
+__global__ __launch_bounds__(64) void k_kem_rkprf_wave(const uint8_t *z, size_t z_stride, const uint8_t *ct, int ct_bytes, uint8_t *rk)
+{
+    __shared__ __align__(16) uint32_t st[64];
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    __builtin_amdgcn_s_setprio(3); // a chain is latency, not throughput
+    FsSpongeBperm sp;
+    sp.setup(lane, nullptr);
+    const int word = sp.word();
+    const uint32_t half = sp.half();
+    const uint8_t *zb = z + b * z_stride, *cb = ct + b * (size_t)ct_bytes;
+    const int nwords = 4 + ct_bytes / 8, nfull = nwords / 17, rem = nwords - 17 * nfull;
+    auto fetch = [&](int i) { return *reinterpret_cast<const uint2 *>(i < 4 ? zb + 8 * i : cb + 8 * (i - 4)); };
+    uint32_t a = 0;
+    for (int blk = 0; blk < nfull; blk++) {
+        const uint2 m = word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0);
+        a ^= fs_deinterleave_half(m.x, m.y, half);
+        sp.permute(a);
+    }
+    {
+        uint2 m = word < rem ? fetch(17 * nfull + word) : make_uint2(0, 0);
+        if (word == rem) m.x ^= 0x1Fu;        // rem <= 16: the SHAKE domain byte opens the first free word
+        if (word == 16) m.y ^= 0x80000000u;   // last byte of the 136-byte rate
+        a ^= fs_deinterleave_half(m.x, m.y, half);
+        sp.permute(a);
+    }
+    st[lane] = a;
+    __builtin_amdgcn_wave_barrier();
+    if (lane < 4) { // words 0..3 of the state
+        uint32_t lo, hi;
+        fs_interleave(st[FsSpongeBperm::lane_of(lane, 0, 0)], st[FsSpongeBperm::lane_of(lane, 0, 1)], lo, hi);
+        *reinterpret_cast<uint2 *>(rk + b * 32 + 8 * lane) = make_uint2(lo, hi);
+    }
+}
+
+struct KemEncJob {
+    int K, dec;
+    const uint8_t *pk;
+    size_t pk_stride;
+    const int16_t *A, *noise;
+    const uint8_t *m, *kr, *rk; // [n][32], [n][64], [n][32] (dec)
+    uint8_t *ct;                // [n][ct_bytes]: written (enc) or compared with (dec)
+    uint8_t *ss;                // [n][32]
+    const uint8_t *mask;        // enc: optional [n]; 0 = no encapsulation, ct and ss of the item are zero-filled
+};
+
+__global__ __launch_bounds__(256) void k_kem_encrypt(KemEncJob j)
+{
+    __shared__ alignas(16) uint16_t L[9 * 256];
+    __shared__ uint32_t fail;
+    const Dims D = dims(j.K);
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    uint8_t *ct = j.ct + b * (size_t)D.ct;
+    if (j.mask && !j.mask[b]) { // public: the verifier's bit
+        for (int i = tid; i < D.ct / 16; i += 256) reinterpret_cast<U128 *>(ct)[i] = U128{0, 0, 0, 0};
+        if (tid < 32) j.ss[b * 32 + tid] = 0;
+        return;
+    }
+    if (tid == 0) fail = 0;
+    __syncthreads();
+    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk + b * j.pk_stride, j.A + b * (size_t)(D.K * D.K * 256),
+                                        j.noise + b * (size_t)((2 * D.K + 1) * 256), j.m + b * 32, j.dec ? nullptr : ct, ct);
+    if (!j.dec) {
+        if (tid < 32) j.ss[b * 32 + tid] = j.kr[b * 64 + tid];
+        return;
+    }
+    atomicOr(&fail, diff);
+    __syncthreads();
+    if (tid < 32) j.ss[b * 32 + tid] = select_ss(fail, j.kr[b * 64 + tid], j.rk[b * 32 + tid]);
+}
+
+struct KemDecJob {
+    int K;
+    const uint8_t *ct, *sk;
+    size_t sk_stride;
+    uint8_t *m, *kr;
+};
+
+__global__ __launch_bounds__(256) void k_kem_decrypt(KemDecJob j)
+{
+    __shared__ alignas(16) uint16_t L[6 * 256];
+    __shared__ alignas(16) uint8_t Lb[288];
+    const Dims D = dims(j.K);
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const uint8_t *sk = j.sk + b * j.sk_stride;
+    decrypt_block(D, L, Lb, tid, 256, j.ct + b * (size_t)D.ct, sk);
+    if (tid < 32) j.m[b * 32 + tid] = Lb[256 + tid];
+    if (tid == 0) {
+        uint64_t m[4], h[4], kr[8];
+#pragma unroll
+        for (int l = 0; l < 4; l++) { m[l] = ld64(Lb + 256, l); h[l] = ld64(sk + D.sk - 64, l); }
+        hash_g64(m, h, kr);
+#pragma unroll
+        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * b + l] = kr[l];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host --
+#define HIPCHK(x) KOSK_HIPCHK(x)
+
+void kem_release(Ctx &c)
+{
+    KemWs *w = c.kem;
+    if (!w) return;
+    void *dev[] = {w->d_pk, w->d_sk, w->d_ct, w->d_m, w->d_kr, w->d_rk, w->d_ss, w->d_mask, w->d_h, w->d_A, w->d_noise};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    delete w;
+    c.kem = nullptr;
+}
+
+// the workspace holds the largest launch group the context has seen (rounded up to 1 024 items, at most KEM_CHUNK)
+static int kem_ensure(Ctx &c, int n)
+{
+    if (c.kem && c.kem->cap >= n) return 0;
+    if (c.kem) {
+        KOSK_HIPCHK(stream_sync(c));
+        kem_release(c);
+    }
+    const Dims D = dims(c.P.K);
+    KemWs *w = new KemWs();
+    c.kem = w;
+    const size_t N = (size_t)((n + 1023) / 1024 * 1024 < KEM_CHUNK ? (n + 1023) / 1024 * 1024 : KEM_CHUNK);
+    auto body = [&]() -> int {
+        HIPCHK(hipSetDevice(c.device));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_pk), N * D.pk));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_sk), N * D.sk));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_ct), N * D.ct));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_m), N * 32));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_kr), N * 64));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_rk), N * 32));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_ss), N * 32));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_mask), N));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_h), N * 32));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_A), N * D.K * D.K * 512));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_noise), N * (2 * D.K + 1) * 512));
+        return 0;
+    };
+    if (body()) { kem_release(c); return -1; }
+    w->cap = (int)N;
+    return 0;
+}
+
+static hipError_t kem_copy_in(Ctx &c, void *d_dst, const void *src, size_t bytes)
+{
+    return hipMemcpyAsync(d_dst, src, bytes, is_device_pointer(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream);
+}
+static hipError_t kem_copy_out(Ctx &c, void *dst, const void *d_src, size_t bytes)
+{
+    return hipMemcpyAsync(dst, d_src, bytes, is_device_pointer(dst) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream);
+}
+// KOSK_DEBUG_KEM_WAVE_MAX=n moves the boundary between the two sponge layouts (tests run the per-lane roles on small batches with 0)
+static int kem_wave_max()
+{
+    static const int v = [] { const char *e = getenv("KOSK_DEBUG_KEM_WAVE_MAX"); return e ? atoi(e) : (int)KEM_WAVE_MAX; }();
+    return v;
+}
+static hipError_t kem_launch_hash(const KemHashJob &j, hipStream_t st)
+{
+    const long lanes = (long)(j.n_rk + j.n_seed + j.n_mat + j.n_noise) * j.n;
+    k_kem_hash<<<dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st>>>(j);
+    return hipGetLastError();
+}
+
+int kem_enc(Ctx &c, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask, int resident_first)
+{
+    if (n < 1 || n > KEM_CHUNK || !coins || !ct || !ss) { c.err = "kem_enc: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    const uint8_t *d_pk = w.d_pk;
+    size_t pk_stride = (size_t)D.pk;
+    if (pk) HIPCHK(kem_copy_in(c, w.d_pk, pk, (size_t)n * D.pk));
+    else { d_pk = c.d_pk + (size_t)resident_first * c.pk_stride; pk_stride = c.pk_stride; } // the keys the last verify call left resident (kosk_kem_enc_verified)
+    HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
+    if (mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
+    KemHashJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.pk = d_pk; h.pk_stride = pk_stride; h.pk_bytes = D.pk;
+    h.m = w.d_m; h.kr = w.d_kr; h.A = w.d_A; h.noise = w.d_noise;
+    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
+    if (n <= kem_wave_max()) { // H(pk): one wave per key on the wave sponge
+        FsArgs fa{};
+        fa.in = d_pk; fa.in_stride = pk_stride; fa.len = D.pk; fa.out_digest = w.d_h;
+        HIPCHK(launch_fs_chain(fa, FS_DIGEST, n, c.stream));
+        h.h = w.d_h;
+    }
+    h.n_seed = 1; h.n_mat = D.K * D.K;
+    HIPCHK(kem_launch_hash(h, c.stream));
+    h.n_seed = 0; h.n_mat = 0; h.n_noise = 2 * D.K + 1;
+    HIPCHK(kem_launch_hash(h, c.stream));
+    KemEncJob e{};
+    e.K = D.K; e.dec = 0; e.pk = d_pk; e.pk_stride = pk_stride; e.A = w.d_A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr;
+    e.ct = w.d_ct; e.ss = w.d_ss; e.mask = mask ? w.d_mask : nullptr;
+    k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_ENC]++;
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1; // gen_matrix block limit: no results
+    HIPCHK(kem_copy_out(c, ct, w.d_ct, (size_t)n * D.ct));
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
+{
+    if (n < 1 || n > KEM_CHUNK || !ct || !sk || !ss) { c.err = "kem_dec: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_ct, ct, (size_t)n * D.ct));
+    HIPCHK(kem_copy_in(c, w.d_sk, sk, (size_t)n * D.sk));
+    KemDecJob d{};
+    d.K = D.K; d.ct = w.d_ct; d.sk = w.d_sk; d.sk_stride = (size_t)D.sk; d.m = w.d_m; d.kr = w.d_kr;
+    k_kem_decrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(d);
+    HIPCHK(hipGetLastError());
+    KemHashJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.pk = w.d_sk + D.pvb; h.pk_stride = (size_t)D.sk; h.pk_bytes = D.pk; // sk = s-hat || pk || H(pk) || z
+    h.kr = w.d_kr; h.A = w.d_A; h.noise = w.d_noise;
+    h.z = w.d_sk + D.sk - 32; h.z_stride = (size_t)D.sk; h.ct = w.d_ct; h.ct_bytes = D.ct; h.rk = w.d_rk;
+    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
+    h.n_rk = 1; h.n_mat = D.K * D.K; h.n_noise = 2 * D.K + 1;
+    if (n <= kem_wave_max()) { // rkprf: one wave per item on the wave sponge
+        k_kem_rkprf_wave<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(h.z, h.z_stride, h.ct, h.ct_bytes, h.rk);
+        HIPCHK(hipGetLastError());
+        h.n_rk = 0;
+    }
+    HIPCHK(kem_launch_hash(h, c.stream));
+    KemEncJob e{};
+    e.K = D.K; e.dec = 1; e.pk = h.pk; e.pk_stride = h.pk_stride; e.A = w.d_A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.rk = w.d_rk;
+    e.ct = w.d_ct; e.ss = w.d_ss;
+    k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_DEC]++;
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1;
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+} // namespace kosk

@@ -133,6 +133,7 @@ static int upload_inst(Ctx &c, int n, const uint8_t *inst, bool with_se, bool wi
         for (int i = 0; i < K * 256; i++) t[(size_t)b * K * 256 + i] = (uint16_t)(((int)ts[i] % Q + Q) % Q); // encode_to_gf3329
         memcpy(&se[(size_t)b * c.se_stride], ss, (size_t)2 * K * 512);
     }
+    c.note_keys_from_inst(); // d_A (and d_t) no longer belong to the pk bytes in d_pk
     HIPCHK(hipMemcpyAsync(c.d_A, A.data(), A.size() * 2, hipMemcpyHostToDevice, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
     if (with_se) HIPCHK(hipMemcpyAsync(c.d_se, se.data(), se.size() * 2, hipMemcpyHostToDevice, c.stream));

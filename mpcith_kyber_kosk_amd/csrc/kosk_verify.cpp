@@ -176,7 +176,7 @@ int stage_verifier_inputs(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, b
         if (!registered) memcpy(c.h_proof + (size_t)b * c.image_stride, pi + (size_t)b * P.proof_bytes, P.proof_bytes);
     });
     HIPCHK(hipMemcpyAsync(c.d_pk, c.h_pk, (size_t)n * c.pk_stride, hipMemcpyHostToDevice, c.stream));
-    c.resident_pk_n = n;
+    c.note_pk_written(n);
     c.path_n[registered ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     if (registered) // page-locked caller memory (kosk_capi.cpp): no staging copy
         HIPCHK(hipMemcpy2DAsync(c.d_proof, c.image_stride, pi, P.proof_bytes, P.proof_bytes, n, hipMemcpyHostToDevice, c.stream));
@@ -187,16 +187,6 @@ int stage_verifier_inputs(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, b
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;
     return 0;
-}
-
-static bool is_device_pointer(const void *p)
-{
-    hipPointerAttribute_t at{};
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeDevice;
 }
 
 int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, const VerifySeg *segs)
@@ -241,7 +231,9 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
                 }
                 first += s->count;
             }
-            c.resident_pk_n = n;
+            c.note_pk_written(n);
+        } else {
+            c.note_pk_decoded(n); // pk_mode 2: d_A / d_t of the first n records are decoded again from the resident d_pk by this call
         }
         // the decoding itself (polyvec_frombytes + gen_matrix) is issued with segment V1B: nothing before needs A or t, and
         // there it runs while the host hashes instead of in front of the first digests
