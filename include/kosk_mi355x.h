@@ -290,7 +290,8 @@ int kosk_sha3_256_batch(kosk_ctx *ctx, const uint8_t *d_in, size_t in_stride, si
  * this layout; the pipeline's hashes use one lane per state, which is faster at its wave counts -- DESIGN.md 8) */
 int kosk_sha3_256_batch_pair(kosk_ctx *ctx, const uint8_t *d_in, size_t in_stride, size_t inlen, uint8_t *d_out, int n);
 /* sha3_256 of n LONG messages, one WAVE per message: one Keccak state spread over the 64 lanes
- * of a wave, a 32-bit word of the bit-interleaved state per lane, theta / pi / chi exchanged through LDS (csrc/kosk_fs_dev.hpp) --
+ * of a wave, a 32-bit word of the bit-interleaved state per lane, theta / pi / chi exchanged by DPP and ds_bpermute
+ * (csrc/kosk_keccak_wave_dev.hpp) --
  * the layout for a strictly sequential chain: ~2 us per permutation where the one-state-per-lane sponge needs ~9 us when its wave
  * runs alone.  d_in and in_stride must be multiples of 8.        kyber/fips202.c:745-754 */
 int kosk_sha3_256_batch_wave(kosk_ctx *ctx, const uint8_t *d_in, size_t in_stride, size_t inlen, uint8_t *d_out, int n);

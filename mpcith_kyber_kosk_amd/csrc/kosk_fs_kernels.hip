@@ -6,7 +6,7 @@
 // hashed where the commitment kernels wrote the tables, in HBM: nothing but 32 + 300 bytes per proof would have to reach the host,
 // and with the challenge vectors / opened lists consumed on the device nothing does -- the four 46.5 KB-per-proof device-to-host
 // copies of a step, the host's four hashing rounds and the four host round trips disappear.
-// One wave per proof; the sponge is csrc/kosk_fs_dev.hpp (one state per wave, a word per lane).
+// One wave per proof; the sponge is csrc/kosk_keccak_wave_dev.hpp (one state per wave, a word per lane).
 //   k_fs_chain<FS_DIGEST>  sha3_256 of n long messages (kernel-level entry point kosk_sha3_256_batch_wave; tests, bench)
 //   k_fs_chain<FS_ALPHA>   the challenge vector of every proof, [n][80] u16
 //   k_fs_chain<FS_OPENED>  prover: I, its ascending complement, the window boundaries and the sorted opened list (what
@@ -15,11 +15,8 @@
 // kyber/fips202.c:461-485, :723-734 (shake256), :745-754 (sha3_256); kyber/symmetric-shake.c:41-51 (kyber_shake256_prf).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <cstring>
-
 #include "kosk_device.hpp"
-#include "kosk_fs_dev.hpp"
+#include "kosk_keccak_wave_dev.hpp"
 
 namespace kosk {
 
@@ -32,7 +29,7 @@ __device__ __forceinline__ uint2 fs_load_word(const uint8_t *p)
     return *reinterpret_cast<const uint2 *>(p);
 }
 
-// the last (partial) block's word at byte offset 8 w of the remaining `rem` bytes, padded: dom at byte rem, 0x80 at byte 135
+// the last (partial) block's word at byte offset 8 w of the remaining `rem` bytes, padded for the 136-byte rate
 __device__ __forceinline__ uint2 fs_last_word(const uint8_t *tail, int rem, int w, uint32_t dom)
 {
     uint32_t lo = 0, hi = 0;
@@ -47,19 +44,13 @@ __device__ __forceinline__ uint2 fs_last_word(const uint8_t *tail, int rem, int 
             else hi |= byte << (8 * (i - 4));
         }
     }
-    if ((rem >> 3) == w) {
-        const int sh = 8 * (rem & 7);
-        if (sh < 32) lo ^= dom << sh;
-        else hi ^= dom << (sh - 32);
-    }
-    if (w == 16) hi ^= 0x80000000u;
-    return make_uint2(lo, hi);
+    const uint2 p = WaveSponge::pad(w, rem, dom, 136);
+    return make_uint2(lo ^ p.x, hi ^ p.y);
 }
 
-template <int MODE, class SP>
+template <int MODE>
 __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
 {
-    __shared__ __align__(16) uint32_t xw[FSW_WORDS];
     __shared__ __align__(16) uint32_t st[64];       // the state's words, to be re-interleaved by other lanes
     __shared__ __align__(16) uint8_t sq[3 * 136];   // squeezed PRF bytes
     __shared__ uint16_t pos[MODE >= FS_OPENED ? NPARTY : 1];
@@ -67,10 +58,9 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
 
     const int lane = threadIdx.x, b = blockIdx.x;
     __builtin_amdgcn_s_setprio(3); // a chain is latency, not throughput: its wave issues first wherever it shares a SIMD
-    SP sp;
-    sp.setup(lane, xw);
+    WaveSponge sp;
+    sp.setup(lane);
     const int word = sp.word();
-    const uint32_t half = sp.half();
 
     // ---- sha3_256 of the table
     const uint8_t *src = A.in + (size_t)b * A.in_stride;
@@ -88,50 +78,34 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
                 const uint2 m = pf[j];
                 const int nb = blk + j + FS_PF;
                 pf[j] = (ld && nb < nfull) ? fs_load_word(mine + (size_t)136 * nb) : make_uint2(0, 0);
-                a ^= fs_deinterleave_half(m.x, m.y, half); // (lanes beyond word 16 loaded zeros)
+                sp.absorb(a, m); // (lanes beyond word 16 loaded zeros)
                 sp.permute(a);
             }
         }
     }
-    {
-        const uint2 m = ld ? fs_last_word(src + (size_t)136 * nfull, rem, word, 0x06u) : make_uint2(0, 0);
-        a ^= fs_deinterleave_half(m.x, m.y, half);
-        sp.permute(a);
-    }
-    if (A.out_digest) { // words 0..3 = lanes 6 x (+ 32)
-        st[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 4) {
-            uint32_t lo, hi;
-            fs_interleave(st[SP::lane_of(lane, 0, 0)], st[SP::lane_of(lane, 0, 1)], lo, hi);
-            *reinterpret_cast<uint2 *>(A.out_digest + (size_t)b * 32 + 8 * lane) = make_uint2(lo, hi);
-        }
-        __builtin_amdgcn_wave_barrier();
+    sp.absorb(a, ld ? fs_last_word(src + (size_t)136 * nfull, rem, word, 0x06u) : make_uint2(0, 0));
+    sp.permute(a);
+    if (A.out_digest) {
+        const uint2 w = sp.words(a, st, 4);
+        if (lane < 4) *reinterpret_cast<uint2 *>(A.out_digest + (size_t)b * 32 + 8 * lane) = w;
     }
     if constexpr (MODE == FS_DIGEST) return;
 
     // ---- SHAKE256-PRF(digest, nonce 1): the digest's words are the new block's words 0..3 as they stand (still interleaved)
     {
-        uint32_t lo = 0, hi = 0;
-        if (word == 4) lo = 0x1F01u;      // nonce byte 1, then the SHAKE domain byte (33 bytes absorbed)
-        if (word == 16) hi = 0x80000000u; // last byte of the 136-byte rate
-        const uint32_t pad = fs_deinterleave_half(lo, hi, half);
-        a = (word < 4 ? a : 0u) ^ pad;
+        uint2 m = WaveSponge::pad(word, 33, 0x1Fu, 136); // 33 bytes absorbed, SHAKE domain
+        if (word == 4) m.x |= 0x01u;                     // byte 32: the nonce
+        a = word < 4 ? a : 0u;
+        sp.absorb(a, m);
     }
     constexpr int NSQ = MODE == FS_ALPHA ? 2 : 3;
 #pragma unroll 1
     for (int s = 0; s < NSQ; s++) {
         sp.permute(a);
-        st[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 17) {
-            const int x = lane % 5, y = lane / 5;
-            uint32_t lo, hi;
-            fs_interleave(st[SP::lane_of(x, y, 0)], st[SP::lane_of(x, y, 1)], lo, hi);
-            *reinterpret_cast<uint2 *>(sq + 136 * s + 8 * lane) = make_uint2(lo, hi);
-        }
-        __builtin_amdgcn_wave_barrier();
+        const uint2 w = sp.words(a, st, 17);
+        if (lane < 17) *reinterpret_cast<uint2 *>(sq + 136 * s + 8 * lane) = w;
     }
+    wave_lds_handoff();
 
     if constexpr (MODE == FS_ALPHA) {
         // alpha_i = BE16 % q, i < J (mlwe_prover.cpp:137-142); the entries behind J stay zero
@@ -150,7 +124,7 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
             c[k] = i < NOPEN ? (((uint32_t)sq[2 * i] << 8) | sq[2 * i + 1]) % (uint32_t)NPARTY : 0u;
         }
         for (int p = lane; p < NPARTY; p += 64) pos[p] = 0xFFFF;
-        __builtin_amdgcn_wave_barrier();
+        wave_lds_handoff();
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int cnt = k < 2 ? 64 : NOPEN - 128;
@@ -161,7 +135,7 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
                     pos[v] = (uint16_t)(64 * k + j);
                     il[64 * k + j] = (uint16_t)v;
                 }
-                __builtin_amdgcn_wave_barrier();
+                wave_lds_handoff();
             }
         }
         if constexpr (MODE == FS_CHECK) {
@@ -200,27 +174,16 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
 
 } // namespace
 
-template <class SP>
-static void fs_launch(const FsArgs &A, int mode, int n, hipStream_t st)
-{
-    switch (mode) {
-    case FS_DIGEST: hipLaunchKernelGGL((k_fs_chain<FS_DIGEST, SP>), dim3(n), dim3(64), 0, st, A); break;
-    case FS_ALPHA: hipLaunchKernelGGL((k_fs_chain<FS_ALPHA, SP>), dim3(n), dim3(64), 0, st, A); break;
-    case FS_OPENED: hipLaunchKernelGGL((k_fs_chain<FS_OPENED, SP>), dim3(n), dim3(64), 0, st, A); break;
-    default: hipLaunchKernelGGL((k_fs_chain<FS_CHECK, SP>), dim3(n), dim3(64), 0, st, A); break;
-    }
-}
-
 hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
     if (mode < FS_DIGEST || mode > FS_CHECK) return hipErrorInvalidValue;
-    // variant B of kosk_fs_dev.hpp (DPP column sums + ds_bpermute exchanges).  Variant A (exchanges through LDS memory) measured 4 % slower
-    // (2.26-2.35 against 2.14-2.28 us per permutation, profiles/r06_fs_chain.txt) and is compiled only for tools/fs_chain_time.py's A/B
-    // (KOSK_FS_SPONGE=lds, a debug knob)
-    static const bool lds = getenv("KOSK_FS_SPONGE") && !strcmp(getenv("KOSK_FS_SPONGE"), "lds");
-    if (lds) fs_launch<FsSpongeLds>(A, mode, n, st);
-    else fs_launch<FsSpongeBperm>(A, mode, n, st);
+    switch (mode) {
+    case FS_DIGEST: hipLaunchKernelGGL(k_fs_chain<FS_DIGEST>, dim3(n), dim3(64), 0, st, A); break;
+    case FS_ALPHA: hipLaunchKernelGGL(k_fs_chain<FS_ALPHA>, dim3(n), dim3(64), 0, st, A); break;
+    case FS_OPENED: hipLaunchKernelGGL(k_fs_chain<FS_OPENED>, dim3(n), dim3(64), 0, st, A); break;
+    default: hipLaunchKernelGGL(k_fs_chain<FS_CHECK>, dim3(n), dim3(64), 0, st, A); break;
+    }
     return hipGetLastError();
 }
 

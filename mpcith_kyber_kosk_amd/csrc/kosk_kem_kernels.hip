@@ -11,7 +11,7 @@
 // The roles of k_kem_hash are lane ranges of one launch (task-major: a wave runs one role), longest role first.  Sponge layout by wave
 // count: one state per lane, except the two roles that are ONE lane per item with a chain of 6-12 dependent permutations -- H(pk) of an
 // encapsulation and rkprf of a decapsulation.  In a launch group of up to KEM_WAVE_MAX items such a role would be a few waves at
-// single-wave latency, so it runs as one WAVE per item on the wave sponge (kosk_fs_dev.hpp), launched ahead of k_kem_hash: H(pk) on
+// single-wave latency, so it runs as one WAVE per item on the wave sponge (kosk_keccak_wave_dev.hpp), launched ahead of k_kem_hash: H(pk) on
 // k_fs_chain<FS_DIGEST> (kosk_fs_kernels.hip), after which the seed role only does G; rkprf on k_kem_rkprf_wave below (SHAKE domain,
 // two-part message).  The device functions are in kosk_kem_dev.hpp; DESIGN.md 19 has the resource figures.
 #include <hip/hip_runtime.h>
@@ -19,7 +19,7 @@
 #include <cstdlib>
 
 #include "kosk_ctx.hpp"
-#include "kosk_fs_dev.hpp"
+#include "kosk_keccak_wave_dev.hpp"
 #include "kosk_kem_dev.hpp"
 
 namespace kosk {
@@ -102,7 +102,7 @@ __global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
 }
 
 // rkprf = SHAKE256(z[32] || ct) (symmetric-shake.c: kyber_shake256_rkprf), one WAVE per item on the wave sponge: a 32-bit half of a state
-// word per lane, bit-interleaved (kosk_fs_dev.hpp, FsSpongeBperm).  z and ct are 8-byte aligned and 32 + ct_bytes is a multiple of 8, so
+// word per lane, bit-interleaved (kosk_keccak_wave_dev.hpp, WaveSponge).  z and ct are 8-byte aligned and 32 + ct_bytes is a multiple of 8, so
 // every block is whole words.  z is secret: it is data only; the addresses are functions of the lane and the block.
 __global__ __launch_bounds__(64) void k_kem_rkprf_wave(const uint8_t *z, size_t z_stride, const uint8_t *ct, int ct_bytes, uint8_t *rk)
 {
@@ -110,33 +110,22 @@ __global__ __launch_bounds__(64) void k_kem_rkprf_wave(const uint8_t *z, size_t 
     const int lane = threadIdx.x;
     const size_t b = blockIdx.x;
     __builtin_amdgcn_s_setprio(3); // a chain is latency, not throughput
-    FsSpongeBperm sp;
-    sp.setup(lane, nullptr);
+    WaveSponge sp;
+    sp.setup(lane);
     const int word = sp.word();
-    const uint32_t half = sp.half();
     const uint8_t *zb = z + b * z_stride, *cb = ct + b * (size_t)ct_bytes;
     const int nwords = 4 + ct_bytes / 8, nfull = nwords / 17, rem = nwords - 17 * nfull;
     auto fetch = [&](int i) { return *reinterpret_cast<const uint2 *>(i < 4 ? zb + 8 * i : cb + 8 * (i - 4)); };
     uint32_t a = 0;
     for (int blk = 0; blk < nfull; blk++) {
-        const uint2 m = word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0);
-        a ^= fs_deinterleave_half(m.x, m.y, half);
+        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
         sp.permute(a);
     }
-    {
-        uint2 m = word < rem ? fetch(17 * nfull + word) : make_uint2(0, 0);
-        if (word == rem) m.x ^= 0x1Fu;        // rem <= 16: the SHAKE domain byte opens the first free word
-        if (word == 16) m.y ^= 0x80000000u;   // last byte of the 136-byte rate
-        a ^= fs_deinterleave_half(m.x, m.y, half);
-        sp.permute(a);
-    }
-    st[lane] = a;
-    __builtin_amdgcn_wave_barrier();
-    if (lane < 4) { // words 0..3 of the state
-        uint32_t lo, hi;
-        fs_interleave(st[FsSpongeBperm::lane_of(lane, 0, 0)], st[FsSpongeBperm::lane_of(lane, 0, 1)], lo, hi);
-        *reinterpret_cast<uint2 *>(rk + b * 32 + 8 * lane) = make_uint2(lo, hi);
-    }
+    // rem <= 16 whole words, then the padding: the SHAKE domain byte opens the first free word
+    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, 0x1Fu, 136));
+    sp.permute(a);
+    const uint2 w = sp.words(a, st, 4);
+    if (lane < 4) *reinterpret_cast<uint2 *>(rk + b * 32 + 8 * lane) = w;
 }
 
 struct KemEncJob {

@@ -24,6 +24,7 @@
 #include "kosk_keygen_wave_dev.hpp"
 #include "kosk_math.hpp"
 #include "kosk_limb_dev.hpp"
+#include "kosk_wave_sync_dev.hpp"
 
 namespace kosk {
 
@@ -1692,7 +1693,7 @@ __device__ __forceinline__ void asm_group_block(const AssembleArgs &a, const Asm
     el_s[lane] = el[lane]; // the group's element table (padded to 128 entries), for per-lane row indices
     el_s[lane + 64] = el[lane + 64];
     __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();
     if (lane < nsel) rank_s[my_col] = (int16_t)lane;
     // the gather: all loads first
     int rr[NQ];
@@ -1703,7 +1704,7 @@ __device__ __forceinline__ void asm_group_block(const AssembleArgs &a, const Asm
 #pragma unroll
     for (int q = 0; q < NQ; q++) v[q] = *reinterpret_cast<const uint2 *>(src + (size_t)rr[q] * RS);
     __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0): the rank table is written
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();
     int rk[4];
 #pragma unroll
     for (int m = 0; m < 4; m++) rk[m] = rank_s[4 * cq + m];
@@ -1725,7 +1726,7 @@ __device__ __forceinline__ void asm_group_block(const AssembleArgs &a, const Asm
         }
     }
     __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();
     if (g.sel) {
         for (int s = 0; s < g.nsub; s++) { // one contiguous run per field; its start is only 2-byte aligned in general
             const int width = g.sub_width[s];

@@ -1,5 +1,5 @@
 // gen_matrix on the WAVE sponge (round 6): one matrix entry A[i][j] per 64-lane wave, the Keccak state spread over the wave as in
-// kosk_fs_dev.hpp (variant B: DPP column sums + ds_bpermute exchanges, ~2.1 us per permutation).
+// kosk_keccak_wave_dev.hpp (DPP column sums + ds_bpermute exchanges, ~2.1 us per permutation).
 //
 // Why: an entry is a chain of one seed hash (prover) + three or more SHAKE128 permutations, each followed by a rejection parse whose
 // running count is sequential; on the lane-pair sponge (kosk_keygen_dev.hpp: kp_gen_matrix) that chain is ~9 us per permutation plus
@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kosk_device.hpp"
-#include "kosk_fs_dev.hpp"
+#include "kosk_keccak_wave_dev.hpp"
 
 namespace kosk {
 
@@ -26,46 +26,38 @@ __device__ __forceinline__ void kw_gen_matrix(const uint8_t *seed32, bool hash_d
                                               uint32_t *st, uint8_t *sq)
 {
     const int lane = threadIdx.x & 63;
-    FsSpongeBperm sp;
-    sp.setup(lane, nullptr);
+    WaveSponge sp;
+    sp.setup(lane);
     const int word = sp.word();
-    const uint32_t half = sp.half();
-    // words 0..3 of the first block: the seed
-    uint32_t lo = 0, hi = 0;
+    // the XOF's block behind the 32 bytes of rho: j, i, the SHAKE domain byte; SHAKE128's rate is 168 bytes
+    uint2 mx = WaveSponge::pad(word, 34, 0x1Fu, 168);
+    if (word == 4) mx.x |= (uint32_t)j | ((uint32_t)i << 8);
+    // the first block: the seed in words 0..3; behind it K and sha3_512's padding (rate 72 bytes), or the XOF's block itself
+    uint2 m = mx;
+    if (hash_d) {
+        m = WaveSponge::pad(word, 33, 0x06u, 72);
+        if (word == 4) m.x |= (uint32_t)K;
+    }
     if (word < 4) {
         const uint8_t *p = seed32 + 8 * word;
-        lo = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-        hi = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
+        m.x = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
+        m.y = (uint32_t)p[4] | ((uint32_t)p[5] << 8) | ((uint32_t)p[6] << 16) | ((uint32_t)p[7] << 24);
     }
-    uint32_t a;
-    if (hash_d) { // sha3_512: rate 72 bytes; d || K || 0x06 ... 0x80
-        if (word == 4) lo = (uint32_t)K | (0x06u << 8);
-        if (word == 8) hi = 0x80000000u;
-        a = fs_deinterleave_half(lo, hi, half);
+    uint32_t a = 0;
+    sp.absorb(a, m);
+    if (hash_d) {
         sp.permute(a);
         // rho = words 0..3 of the digest: the next sponge's first words as they stand (still interleaved)
-        lo = 0; hi = 0;
-        if (word == 4) lo = (uint32_t)j | ((uint32_t)i << 8) | (0x1Fu << 16);
-        if (word == 20) hi = 0x80000000u; // byte 167 of SHAKE128's rate
-        a = (word < 4 ? a : 0u) ^ fs_deinterleave_half(lo, hi, half);
-    } else {
-        if (word == 4) lo = (uint32_t)j | ((uint32_t)i << 8) | (0x1Fu << 16);
-        if (word == 20) hi = 0x80000000u;
-        a = fs_deinterleave_half(lo, hi, half);
+        a = word < 4 ? a : 0u;
+        sp.absorb(a, mx);
     }
     int ctr = 0;
 #pragma unroll 1
     for (int blk = 0; blk < xof.max_blocks && ctr < 256; blk++) { // (uniform)
         sp.permute(a);
-        st[lane] = a;
-        __builtin_amdgcn_wave_barrier();
-        if (lane < 21) {
-            const int x = lane % 5, y = lane / 5;
-            uint32_t l2, h2;
-            fs_interleave(st[FsSpongeBperm::lane_of(x, y, 0)], st[FsSpongeBperm::lane_of(x, y, 1)], l2, h2);
-            *reinterpret_cast<uint2 *>(sq + 8 * lane) = make_uint2(l2, h2);
-        }
-        __builtin_amdgcn_wave_barrier();
+        const uint2 w = sp.words(a, st, 21);
+        if (lane < 21) *reinterpret_cast<uint2 *>(sq + 8 * lane) = w;
+        wave_lds_handoff();
         // rej_uniform over the block's 56 three-byte groups: lane t takes group t
         uint32_t v0 = 0xFFFFu, v1 = 0xFFFFu;
         if (lane < 56) {
@@ -80,7 +72,7 @@ __device__ __forceinline__ void kw_gen_matrix(const uint8_t *seed32, bool hash_d
         if (ok0 && at0 < 256) r[at0] = (int16_t)v0;
         if (ok1 && at1 < 256) r[at1] = (int16_t)v1;
         ctr += __popcll(m0) + __popcll(m1);
-        __builtin_amdgcn_wave_barrier(); // the next block's bytes overwrite sq
+        wave_lds_handoff(); // the next block's bytes overwrite sq
     }
     if (ctr < 256) { // block limit reached (XofGuard): what the caller's error check reports, with a defined result
         for (int c = ctr + lane; c < 256; c += 64) r[c] = 0;

@@ -15,6 +15,7 @@
 
 #include <cstdlib>
 #include "kosk_limb_dev.hpp"
+#include "kosk_wave_sync_dev.hpp"
 
 namespace kosk {
 
@@ -149,7 +150,7 @@ __global__ __launch_bounds__(64) void k_disassemble_fields(VerifyArgs v, const F
     else fetch_all(std::integral_constant<int, 40>{});
     if (lane == 1 && head + 2 * body < n16) tile[n16 - 1] = canon(in[n16 - 1]);
     __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
+    wave_lds_handoff();
     const uint16_t *sel = kind ? v.rest + (size_t)b * v.sel_stride : orow;
     if (lane < cnt) {
         const int16_t *rt = rowtab + fd.rowtab_off;

@@ -1,5 +1,5 @@
-"""CPU: the lane-level model of the wave-cooperative sponge (tools/fs_chain_model.py -- the per-lane tables, the two LDS exchanges and
-the bit-interleaved rotations of csrc/kosk_fs_dev.hpp, restated on numpy arrays of 64 lanes) against hashlib; the options struct of
+"""CPU: the lane-level model of the wave-cooperative sponge (tools/fs_chain_model.py -- the per-lane tables, the DPP column sums, the
+gathers and the bit-interleaved rotations of csrc/kosk_keccak_wave_dev.hpp, restated on numpy arrays of 64 lanes) against hashlib; the options struct of
 kosk_create_ex; kosk_create_ex without a GPU."""
 import ctypes as C
 import hashlib
@@ -14,17 +14,12 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 
-def test_lane_model_matches_hashlib():
-    import fs_chain_model as m
-    assert m.self_check()
-
-
-def test_lane_model_of_the_bpermute_variant_matches_hashlib():
-    """variant B of csrc/kosk_fs_dev.hpp (the default): five-lane columns inside 16-lane rows, column sums by three DPP row shifts, both
+def test_wave_sponge_lane_model_matches_hashlib():
+    """csrc/kosk_keccak_wave_dev.hpp (WaveSponge): five-lane columns inside 16-lane rows, column sums by three DPP row shifts, both
     exchanges as ds_bpermute gathers"""
     import fs_chain_model as m
-    assert m.self_check_b()
-    t = m.tables_b()
+    assert m.self_check()
+    t = m.tables()
     act = t["act"] == 1
     assert act.sum() == 50
     for key in ("sCm", "sCp", "s0", "s1", "s2"):  # an active lane never gathers from an idle one
@@ -32,7 +27,7 @@ def test_lane_model_of_the_bpermute_variant_matches_hashlib():
     # a column's five lanes share a 16-lane row (the DPP row shifts never cross one)
     for h in range(2):
         for x in range(5):
-            assert len({m.lane_b(x, y, h) >> 4 for y in range(5)}) == 1
+            assert len({m.lane_of(x, y, h) >> 4 for y in range(5)}) == 1
 
 
 def test_lane_model_of_gen_matrix_on_the_wave_sponge():
@@ -41,26 +36,6 @@ def test_lane_model_of_gen_matrix_on_the_wave_sponge():
     against hashlib + the scalar rej_uniform of kyber/indcpa.c:124-145 -- K = 2, 3, 4, several (i, j), and the block guard"""
     import fs_chain_model as m
     assert m.self_check_gen_matrix()
-
-
-def test_lane_tables_match_the_device_header():
-    """the LDS map constants of csrc/kosk_fs_dev.hpp are the model's"""
-    import fs_chain_model as m
-    hdr = open(os.path.join(ROOT, "mpcith_kyber_kosk_amd", "csrc", "kosk_fs_dev.hpp")).read()
-    got = {k: int(v) for k, v in re.findall(r"constexpr int (FSW_[A-Z]+) = (\d+);", hdr)}
-    assert got == {"FSW_T": m.T_OFF, "FSW_B": m.B_OFF, "FSW_ZERO": m.ZERO_OFF, "FSW_JUNK": m.JUNK_OFF, "FSW_WORDS": m.LDS_WORDS}
-    t = m.tables()
-    act = t["act"] == 1
-    assert act.sum() == 50
-    # 16-byte reads of the theta exchange are 16-byte aligned; the zero pad is too
-    assert not (t["rTm"] % 4).any() and not (t["rTp"] % 4).any() and m.ZERO_OFF % 4 == 0
-    # nobody but the idle lanes touches the zero pad or the junk words; every pi destination (and its ghost) is its own word
-    for key in ("wT", "wB"):
-        assert (t[key][act] < m.ZERO_OFF).all() and (t[key][~act] >= m.JUNK_OFF).all()
-    assert (t["wB"][~act] + 5 < m.LDS_WORDS).all()
-    assert len(set(t["wB"][act])) == 50 and len(set(t["wB"][act] + 5)) == 50 and not set(t["wB"][act]) & set(t["wB"][act] + 5)
-    # a chi read never reaches a scratch word: words x .. x + 2 of a row of (5 values, 2 ghosts, 3 scratch)
-    assert (((t["rB"][act] - m.B_OFF) % 10) + 2 <= 6).all()
 
 
 def test_interleaved_padding_words():

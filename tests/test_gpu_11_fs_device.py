@@ -1,4 +1,4 @@
-"""Fiat-Shamir aggregation on the GPU (round 6; csrc/kosk_fs_kernels.hip, csrc/kosk_fs_dev.hpp): the wave-cooperative sponge against
+"""Fiat-Shamir aggregation on the GPU (round 6; csrc/kosk_fs_kernels.hip, csrc/kosk_keccak_wave_dev.hpp): the wave-cooperative sponge against
 hashlib, the two derivations against the library's host functions, and handles in device mode (kosk_options::fs_mode) against the
 oracle and against host-mode handles, byte for byte.  mlwe_prover.cpp:130-153, :445-474; mlwe_verifier.cpp:37-65, :634-683."""
 import ctypes as C

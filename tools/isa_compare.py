@@ -25,24 +25,25 @@ def kernels(path):
         desc = text[text.index(".amdhsa_kernel %s\n" % name):]
         res["lds"] = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", desc).group(1))
         out[name] = (hist, res)
-    return out
+    # keyed by the demangled name without a template argument a later tree dropped (k_fs_chain<M, FsSpongeBperm> is k_fs_chain<M>)
+    pretty = subprocess.run(["c++filt", "-p"] + list(out), capture_output=True, text=True).stdout.split("\n")
+    return {re.sub(r", kosk::FsSpongeBperm>", ">", p): v for p, v in zip(pretty, out.values())}
 
 
 def main(old_path, new_path):
     old, new = kernels(old_path), kernels(new_path)
     names = sorted(set(old) | set(new))
-    pretty = dict(zip(names, subprocess.run(["c++filt", "-p"] + names, capture_output=True, text=True).stdout.split("\n")))
     print("kernels: %d old, %d new" % (len(old), len(new)))
     grew = False
     for n in names:
         if n not in old or n not in new:
-            print("%-8s %s" % ("removed" if n in old else "added", pretty[n]))
+            print("%-8s %s" % ("removed" if n in old else "added", n))
             continue
         (ho, ro), (hn, rn) = old[n], new[n]
         diff = {m: hn[m] - ho[m] for m in set(ho) | set(hn) if hn[m] != ho[m]}
         rdiff = {r: (ro[r], rn[r]) for r in ro if ro[r] != rn[r]}
         grew |= any(d > 0 for d in diff.values()) or rn["num_vgpr"] > ro["num_vgpr"]
-        print("%-8s %s  %d instructions, vgpr %d agpr %d scratch %d lds %d" % ("changed" if diff or rdiff else "same", pretty[n], sum(hn.values()), *rn.values()))
+        print("%-8s %s  %d instructions, vgpr %d agpr %d scratch %d lds %d" % ("changed" if diff or rdiff else "same", n, sum(hn.values()), *rn.values()))
         if diff or rdiff:
             print("         mnemonics (new - old): %s  resources (old, new): %s" % (dict(sorted(diff.items())), rdiff))
     return 1 if grew else 0

@@ -7,6 +7,8 @@
 #include <cstdlib>
 #include <vector>
 
+#include "../mpcith_kyber_kosk_amd/csrc/kosk_wave_sync_dev.hpp"
+
 constexpr int NP = 138, ROWS = 435, RS = 1728, NWIN = 23, GROUPS = 6, GR = 73; // 6 groups of <= 73 rows cover the 435 rows
 constexpr size_t PSTRIDE = (size_t)ROWS * RS;
 
@@ -104,12 +106,12 @@ __global__ __launch_bounds__(64) void k_transpose(const uint16_t *P, uint16_t *i
     if (PIPE) gather(1);
     put(0);
     __builtin_amdgcn_s_waitcnt(0xC07F); // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
+    kosk::wave_lds_handoff();
     flush(0);
     if (PIPE) {
         put(1);
         __builtin_amdgcn_s_waitcnt(0xC07F);
-        __builtin_amdgcn_wave_barrier();
+        kosk::wave_lds_handoff();
         flush(1);
     }
 }
