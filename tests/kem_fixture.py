@@ -32,9 +32,16 @@ def message(k, i):
 
 def noncanonical_pk(pk, k):
     """every coefficient c < 4096 - q = 767 re-encoded as c + q; returns (pk', number of coefficients changed)"""
-    out = bytearray(pk)
+    body, changed = noncanonical_polyvec(pk[:384 * k])
+    return body + pk[384 * k:], changed
+
+
+def noncanonical_polyvec(body):
+    """the same for any polyvec of 384 K bytes (t-hat of a pk, s-hat of an sk); returns (body', number of coefficients changed)"""
+    assert len(body) % 384 == 0
+    out = bytearray(body)
     changed = 0
-    for t in range(128 * k):  # 3 bytes hold two 12-bit coefficients (poly_tobytes, kyber/poly.c:128-147)
+    for t in range(len(body) // 3):  # 3 bytes hold two 12-bit coefficients (poly_tobytes, kyber/poly.c:128-147)
         b0, b1, b2 = out[3 * t:3 * t + 3]
         c = [b0 | ((b1 & 0x0F) << 8), (b1 >> 4) | (b2 << 4)]
         for j in range(2):

@@ -308,6 +308,9 @@ def test_enc_verified_refuses_keys_that_are_not_the_verified_ones(torch_cuda, or
 
 
 def test_per_lane_sponges_on_small_batches(torch_cuda, gpu_child):
-    out = gpu_child("from tests.gpu_child_kem import per_lane_sponges_on_small_batches; per_lane_sponges_on_small_batches(3)",
+    """K = 2, 3, 4: the per-lane rkprf absorbs 4 + CT_BYTES / 8 = 100 / 140 / 200 words, i.e. 5, 8, 11 full blocks of 17 with 15, 4,
+    13 words left, at a batch size (7) where its wave also holds lanes of the next role"""
+    out = gpu_child("from tests.gpu_child_kem import per_lane_sponges_on_small_batches as f; f(2); f(3); f(4)",
                     env={"KOSK_DEBUG_KEM_WAVE_MAX": "0"})
     assert "per_lane_sponges_on_small_batches ok 3" in out
+    assert "per_lane_sponges_on_small_batches ok 2" in out and "per_lane_sponges_on_small_batches ok 4" in out

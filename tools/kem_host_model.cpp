@@ -78,6 +78,21 @@ extern "C" int kem_model_dec(int K, const uint8_t *ct_in, const uint8_t *sk_in, 
     return 0;
 }
 
+// indcpa_dec alone (kyber/indcpa.c:317-336): m' of any ciphertext under the s-hat of sk.  A decapsulation that rejects returns
+// SHAKE256(z || ct) whatever m' was, so this is where decompress (every code), the s-hat fold and tomsg show on foreign ciphertexts.
+extern "C" int kem_model_indcpa_dec(int K, const uint8_t *ct_in, const uint8_t *sk_in, uint8_t *m)
+{
+    if (K < 2 || K > 4) return -1;
+    const Dims D = dims(K);
+    std::vector<uint64_t> skw((size_t)D.sk / 8), ctw((size_t)D.ct / 8);
+    memcpy(skw.data(), sk_in, (size_t)D.sk);
+    memcpy(ctw.data(), ct_in, (size_t)D.ct);
+    Scratch w;
+    decrypt_block(D, w.L, w.Lb, 0, 1, reinterpret_cast<const uint8_t *>(ctw.data()), reinterpret_cast<const uint8_t *>(skw.data()));
+    memcpy(m, w.Lb + 256, 32);
+    return 0;
+}
+
 // the compression expression over its whole domain, for the test that pins it: out[d_index][x], d in {4, 5, 10, 11}
 extern "C" void kem_model_compress_table(uint16_t *out)
 {
