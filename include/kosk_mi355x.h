@@ -318,7 +318,9 @@ int kosk_commit_hash_lanes(kosk_ctx *ctx, const uint16_t *d_rows, size_t row_str
 /* poly_ntt(r) on n polynomials of 256 int16                  kyber/poly.c:261-265 (ntt.c:80-95 + Barrett) */
 int kosk_ntt256_batch(kosk_ctx *ctx, const int16_t *d_in, int16_t *d_out, int n);
 /* share values of all 1454 parties from the 407 values at points 0..406
- * (recompute_share_secrets_ddeg, ss.cpp:76-99): in  n x 407 u16, out n x 1454 u16 */
+ * (recompute_share_secrets_ddeg, ss.cpp:76-99): in  n x 407 u16, out n x 1454 u16.
+ * Input values >= q are folded mod q where they enter a product; shares 0..127 are the row's own values at points 256..383,
+ * copied as given: a value >= q there comes back unreduced (every computed share, 128..1453, is canonical). */
 int kosk_lagrange_expand(kosk_ctx *ctx, const uint16_t *d_y407, uint16_t *d_shares, int n);
 /* recon_secrets_ddeg / recon_secrets_2ddeg (ss.cpp:37-73): in n x 1454 u16, out n x 256 u16 */
 int kosk_recon_secrets(kosk_ctx *ctx, const uint16_t *d_shares, uint16_t *d_secrets, int n, int two_d);

@@ -219,7 +219,7 @@ int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, in
     ga.src_canonical = s.canonical;
     ga.C = d.C; ga.c_gstride = d.gstride; ga.c_rows = d.rows; ga.c_rstride = d.rstride; ga.c_off = d.off;
     ga.npg = npg; ga.ngroups = ngroups;
-    // the kernels load 16 bytes at a time from the source rows and store 8: checked, not assumed
+    // the kernels load 16 bytes at a time from the source rows and store 16: checked, not assumed
     if (!table_gemm_ok(ga)) { c.err = "internal: table_gemm_ok() refuses the operands of a mod-q product"; return -1; }
     HIPCHK(launch_table_gemm(ga, c.stream));
     if (!c.capturing) c.path_n[PATH_TABLE_GEMM]++;

@@ -404,7 +404,7 @@ hipError_t copy_small(Ctx &c, void *dst, size_t dst_stride, const void *src, siz
 // after the stream has been synchronised: -1 (with c.err set, the word cleared) if a kernel of this context raised an error
 int device_error_check(Ctx &c);
 // C[g][rows_d[i]][off + m] = sum_k T[m][k] * src[g][rows_s[i]][koff + k] mod q on the table kernels; -1 (c.err set) if the operands
-// fail table_gemm_ok() (kosk_device.hpp), which nothing the library itself issues does
+// fail table_gemm_ok() (kosk_device.hpp: 16-byte aligned source and output rows), which nothing the library itself issues does
 int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, int npg, int ngroups);
 
 // tapes (host or device memory, nullptr = callback) -> pk/sk on host, tape + key material resident in HBM

@@ -334,7 +334,7 @@ hipError_t launch_relation_ntt(const NttArgs &na, const int16_t *A, size_t A_str
 hipError_t launch_matvec_ntt(const int16_t *A, size_t A_stride, uint16_t *P, size_t proof_stride, int v_row0, int row0, int K,
                              int nproofs, hipStream_t st);
 // table products (shared table, 407- or 813-wide u16 input rows) with the data rows resident in LDS.  table_gemm_ok: the operands
-// take the kernels' 16-byte loads and 8-byte stores; launch_table_gemm must not be called with operands that fail it
+// take the kernels' 16-byte loads and 16-byte stores; launch_table_gemm must not be called with operands that fail it
 bool table_gemm_ok(const GemmArgs &a);
 hipError_t launch_table_gemm(const GemmArgs &a, hipStream_t st);
 // K3 on the matrix cores (prover): beta / gamma / r / NTT_r rows of every proof from its f / NTT f rows and the alpha-power coefficient

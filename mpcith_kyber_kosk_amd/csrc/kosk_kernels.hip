@@ -845,361 +845,294 @@ __global__ __launch_bounds__(256) void k_relation_ntt(NttArgs na, const int16_t 
 // become limb tiles (kosk_device.hpp) in LDS.
 // =========================================================================
 
-// ---- table products with the DATA ROWS resident in LDS (k_table_gemm) ------------------------------------------
+// ---- table products with the DATA ROWS resident in LDS (k_table_gemm, k_table_gemm_p) --------------------------
 // C[n][c_off + m] = sum_k T[m][k] * X[n][k] mod q for a table T shared by every row: the Lagrange expansion
 // (ss.cpp:23-32, :88-97; T = 1344 x 407), recon_secrets_ddeg (ss.cpp:44-51; T = 256 x 407) and recon_secrets_2ddeg
 // (ss.cpp:63-70; T = 256 x 813).
-// A workgroup owns 48 data rows: they are converted to limbs ONCE, straight from the canonical u16 rows into LDS
+// A workgroup holds a block of 48 data rows: they are converted to limbs ONCE, straight from the u16 rows into LDS
 // (6 KiB per k-step), and stay there while the workgroup's 8 waves walk the table: no limb matrix of the data in HBM,
 // no tile staged again for every k-step of every output tile.  Each wave
-// takes 16-row chunks of the table on its own (no workgroup barrier after the prologue): the chunk's MFMA fragments
+// takes 16-row chunks of the table on its own (no workgroup barrier while a block is worked on): the chunk's MFMA fragments
 // (KS k-steps x 2 limbs x 16 bytes per lane) are loaded from the L2-resident table limb matrix straight into registers -- a
 // fragment is 16 contiguous bytes of a 1 KiB tile, the wave reads each tile exactly once -- and every register set is
 // re-loaded for the NEXT chunk right after its MFMAs have been issued, so a whole chunk of loads is in flight behind
 // the arithmetic.  After the last k-step the wave reduces mod q and stores 16 x 48 outputs.
 // HBM traffic = the data rows once + the output once + the table once (L2-resident afterwards).
-// In-place use (the expansion writes points >= 384 of the rows it reads points < 448 of): the rows are read in the
-// prologue only; with the table split over several workgroups per row block (msplit) another workgroup may already be
+// In-place use (the expansion writes points >= 384 of the rows it reads points < 448 of): a block's rows are read once, before
+// its first chunk; with a block's chunks split over several workgroups another workgroup may already be
 // writing points 384..447 of the same rows -- points < 407 are rewritten with their own values (identity rows of the
 // table) and points >= 407 meet zero table columns, so any value read there is harmless.
 constexpr int TG_WAVES = 8;
-// NBT = data row tiles (of 16) per workgroup.  Both instantiations use 3 (48 rows): k_table_gemm_p<7, 3, .> keeps two row blocks
-// of 42 KiB in LDS, k_table_gemm<13, 1, 3> one of 78 KiB; one workgroup is resident per CU either way.
 
-// TG_RT = table row tiles (of 16) per chunk
-template <int KS, int TG_RT, int NBT>
-__global__ __launch_bounds__(512, (KS <= 7 && NBT == 3) ? 2 : 1) void k_table_gemm(GemmArgs a, int nchunks, int chunks_per_block, int nblk, int msplit, int wide_stores)
-{
-    constexpr int TG_CHUNK = 16 * TG_RT, TG_NB = 16 * NBT;
-    __shared__ __attribute__((aligned(16))) uint8_t ldsB[KS * NBT * 2048]; // [k-step][row tile][limb][1 KiB]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int ntot = a.npg * a.ngroups;
-    // one-dimensional grid in XCD-aware order: the msplit workgroups that share a row block (each converts the same 48 rows) get
-    // consecutive virtual ids, i.e. one XCD and one L2 (as a 2D grid they sat on msplit different XCDs: the rows were fetched
-    // from HBM msplit times)
-    const int vid = xcd_virtual_id();
-    const int bxr = vid / msplit, byr = vid - bxr * msplit;
-    if (bxr >= nblk) return; // grid padding (whole workgroup, before any barrier)
-    const int n0 = bxr * TG_NB;
+// The tile engine of both kernels: everything between a row block in HBM and its outputs in HBM.  The kernels own only how
+// blocks and chunks are dealt to workgroups and waves.
+// KS = k-steps of 64; NBT = data row tiles (of 16) per block.  Both kernels use 3 (48 rows): k_table_gemm_p<7, 3, .> keeps two
+// row blocks of 42 KiB in LDS, k_table_gemm<13, 3> one of 78 KiB; one workgroup is resident per CU either way.
+// BIASED: the reduction's bias comes in with the first MFMA and the last step is packed (kosk_limb_dev.hpp); otherwise the sum starts
+// from zero and gf_reduce_limbs adds the bias (the 13-k-step kernel: its epilogue has only been measured in this form).
+template <int KS, int NBT, bool BIASED>
+struct TableTiles {
+    static constexpr int CHUNK = 16, NB = 16 * NBT;
+    static constexpr int BUF = KS * NBT * 2048;                       // one row block in LDS: [k-step][row tile][limb][1 KiB]
+    static constexpr int ITEMS = NB * KS * 4, PER = (ITEMS + 511) / 512; // 32-byte items of a block's rows; items per thread
 
-    // ---- prologue: this workgroup's data rows, u16 -> limbs, into LDS (every row is read exactly once from HBM);
-    // all loads of a thread are issued before the first conversion
-    constexpr int ITEMS = TG_NB * KS * 4, PER = (ITEMS + 511) / 512;
-    uint4 x0[PER], x1[PER];
-#pragma unroll
-    for (int q = 0; q < PER; q++) {
-        const int item = tid + q * 512;
-        const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
-        const int n = n0 + row_l;
-        x0[q] = make_uint4(0, 0, 0, 0);
-        x1[q] = x0[q];
-        if (item < ITEMS && n < ntot) {
-            const int g = n / a.npg, i = n - g * a.npg;
-            const uint16_t *src = a.src + (size_t)g * a.src_gstride + (size_t)(a.src_rows ? (int)a.src_rows[i] : i) * a.src_rstride + a.src_koff + kc16 * 16;
-            x0[q] = *reinterpret_cast<const uint4 *>(src);
-            x1[q] = *reinterpret_cast<const uint4 *>(src + 8);
-        }
-    }
-#pragma unroll
-    for (int q = 0; q < PER; q++) {
-        const int item = tid + q * 512;
-        if (item < ITEMS) {
-            const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
-            uint4 lo, hi;
-            gm_split16(x0[q], x1[q], lo, hi);
-            uint8_t *d = ldsB + ((kc16 >> 2) * NBT + (row_l >> 4)) * 2048 + (row_l & 15) * 64 + (((kc16 & 3) ^ limb_swz(row_l & 15)) << 4);
-            *reinterpret_cast<uint4 *>(d) = lo;
-            *reinterpret_cast<uint4 *>(d + 1024) = hi;
-        }
+    GemmArgs a;
+    int ntot;
+    uint32_t npg_magic;
+    int lane;
+    int frag; // fragment address inside a 1 KiB LDS tile: row lane & 15, k-chunk lane >> 4 (swizzled)
+    int ART;  // row tiles of the table
+
+    __device__ __forceinline__ TableTiles(const GemmArgs &a_, uint32_t npg_magic_, int lane_)
+        : a(a_), ntot(a_.npg * a_.ngroups), npg_magic(npg_magic_), lane(lane_),
+          frag((lane_ & 15) * 64 + (((lane_ >> 4) ^ limb_swz(lane_ & 15)) << 4)), ART(a_.Mpad / 16)
+    {
     }
 
-    const int c_begin = byr * chunks_per_block;
-    const int c_end = c_begin + chunks_per_block < nchunks ? c_begin + chunks_per_block : nchunks;
-    const int c_first = c_begin + w;
-    const int nmy = c_first < c_end ? (c_end - c_first + TG_WAVES - 1) / TG_WAVES : 0; // chunks c_first, c_first + 8, ...
-    const int ART = a.Mpad / 16;
-    // fragment address inside a 1 KiB LDS tile: row lane & 15, k-chunk lane >> 4 (swizzled)
-    const int frag = (lane & 15) * 64 + (((lane >> 4) ^ limb_swz(lane & 15)) << 4);
-    // this lane's table fragments of chunk c, k-step ks: tiles (row tile TG_RT c + i, limb) of k-step ks; the table copy
-    // a.Afrag keeps every tile in fragment order, so the wave's load of a tile is one linear 1 KiB read
-    v4i fa[KS][2 * TG_RT];
-    auto load_chunk_ks = [&](int c, int ks, v4i (&dst)[2 * TG_RT]) {
-        const uint8_t *src = a.Afrag + ((size_t)(ks * ART + TG_RT * c) * 2) * 1024 + lane * 16;
-#pragma unroll
-        for (int q = 0; q < 2 * TG_RT; q++) dst[q] = *reinterpret_cast<const v4i *>(src + q * 1024);
-    };
-    if (nmy > 0) {
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) load_chunk_ks(c_first, ks, fa[ks]);
-    }
-    __syncthreads(); // the only workgroup barrier: from here on the waves run independently
-    if (nmy == 0) return;
-    // output rows of this lane's NBT columns (n = n0 + 16 j + (lane & 15))
-    uint16_t *crow[NBT];
-#pragma unroll
-    for (int j = 0; j < NBT; j++) {
-        const int n = n0 + j * 16 + (lane & 15);
-        crow[j] = nullptr;
-        if (n < ntot) {
-            const int g = n / a.npg, i = n - g * a.npg;
-            crow[j] = a.C + (size_t)g * a.c_gstride + (size_t)(a.c_rows ? (int)a.c_rows[i] : i) * a.c_rstride + a.c_off + (lane >> 4) * 4;
-        }
-    }
-
-    v4i s0[TG_RT][NBT], s1[TG_RT][NBT], s2[TG_RT][NBT];
-    const v4i zero4 = {0, 0, 0, 0};
-
-    // the data fragments of the next k-step are read from LDS while the current k-step multiplies; the rows are the same
-    // for every chunk, so the last k-step prefetches k-step 0 again (into a buffer of its own: KS is odd)
-    v4i fb[2][2 * NBT], fb0[2 * NBT];
-    auto load_b = [&](int ks, v4i (&dst)[2 * NBT]) {
-        const uint8_t *lb = ldsB + ks * NBT * 2048 + frag;
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            dst[2 * j] = *reinterpret_cast<const v4i *>(lb + j * 2048);
-            dst[2 * j + 1] = *reinterpret_cast<const v4i *>(lb + j * 2048 + 1024);
-        }
-    };
-    // ---- epilogue pieces.  D[row = m: 4 (lane >> 4) + r][col = n: lane & 15]: four consecutive m per lane and block
-    const int grp = lane >> 4;
-    // blocks j, j + 1 of chunk c: with 16-byte aligned rows the odd 16-lane rows of block j's packed values are swapped with the
-    // even rows of block j + 1's (v_permlane16_swap), after which an even-row lane holds EIGHT consecutive m of block j and an
-    // odd-row lane eight of block j + 1: one 16-byte store per lane instead of two 8-byte stores
-    auto store_pair = [&](int j, int c, uint2 pj, uint2 pk) {
-        if (wide_stores) {
-            const auto sx = __builtin_amdgcn_permlane16_swap(pj.x, pk.x, false, false);
-            const auto sy = __builtin_amdgcn_permlane16_swap(pj.y, pk.y, false, false);
-            uint16_t *p = (grp & 1) ? (crow[j + 1] ? crow[j + 1] - 4 : nullptr) : crow[j];
-            if (p) *reinterpret_cast<uint4 *>(p + c * TG_CHUNK) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-        } else {
-            if (crow[j]) *reinterpret_cast<uint2 *>(crow[j] + c * TG_CHUNK) = pj;
-            if (crow[j + 1]) *reinterpret_cast<uint2 *>(crow[j + 1] + c * TG_CHUNK) = pk;
-        }
-    };
-    auto store_one = [&](int j, int c, uint2 pj) {
-        if (crow[j]) *reinterpret_cast<uint2 *>(crow[j] + c * TG_CHUNK) = pj;
-    };
-
-    static_assert(TG_RT == 1, "the epilogue is written for one table row tile per chunk");
-    // (Tried and not kept, profiles/r04_gemm_stamps.txt: the reduction and the stores of chunk c issued inside chunk c + 1's k-steps,
-    // two vector instructions behind every MFMA.  The k-steps grew by exactly what the epilogue shrank -- two waves per SIMD leave
-    // no idle issue slots under the MFMAs -- so the epilogue stays where it was, behind the chunk's last k-step.)
-    load_b(0, fb0);
-    for (int ci = 0; ci < nmy; ci++) {
-        const int c = c_first + ci * TG_WAVES;
-        const int cn = ci + 1 < nmy ? c + TG_WAVES : c; // the chunk to prefetch (the last one re-loads itself: harmless)
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) {
-            v4i(&bc)[2 * NBT] = ks == 0 ? fb0 : fb[ks & 1];
-            v4i(&bn)[2 * NBT] = ks + 1 == KS ? fb0 : fb[(ks & 1) ^ 1];
-            load_b(ks + 1 < KS ? ks + 1 : 0, bn);
-            __builtin_amdgcn_sched_barrier(0); // the reads for the NEXT k-step go out before this k-step's MFMAs, not after them
-            // four limb products per 16 x 16 x 64 block, ordered so that no accumulator is used twice in a row; the first
-            // k-step starts from a zero operand instead of zeroed registers
-#pragma unroll
-            for (int i = 0; i < TG_RT; i++) {
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s0[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][2 * i], bc[2 * j], ks == 0 ? zero4 : s0[i][j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s1[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][2 * i], bc[2 * j + 1], ks == 0 ? zero4 : s1[i][j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s1[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][2 * i + 1], bc[2 * j], s1[i][j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s2[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][2 * i + 1], bc[2 * j + 1], ks == 0 ? zero4 : s2[i][j], 0, 0, 0);
-            }
-            load_chunk_ks(cn, ks, fa[ks]); // in flight for a whole chunk of arithmetic before it is used
-            __builtin_amdgcn_sched_barrier(0); // keep the k-steps apart: hoisting every LDS read of the chunk costs 150 VGPRs
-        }
-        // epilogue of the chunk: combine the limb products, reduce mod q, pack four consecutive m per lane and block, store
-        uint2 pk[NBT];
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            uint32_t v[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) v[r] = gf_reduce_limbs(s0[0][j][r], s1[0][j][r], s2[0][j][r]);
-            pk[j] = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
-            if (j & 1) store_pair(j - 1, c, pk[j - 1], pk[j]);
-            else if (j == NBT - 1) store_one(j, c, pk[j]);
-        }
-    }
-}
-
-// ---- the same product with PERSISTENT workgroups (round 5; default for KS = 7) ----------------------------------------------------
-// k_table_gemm gives every 48-row block a workgroup of its own, one workgroup per CU at a time: a launch takes ceil(blocks / CUs) rounds
-// (29 946 rows = 624 blocks = 2.44 rounds of work in 3 rounds of time; the verifier's and the re-sharing products of a 138-proof step
-// are 1.03 .. 1.6 rounds of work in 2), and every block starts with a prologue -- 43 KB of rows from HBM, their conversion, the first
-// chunk's table fragments -- during which the matrix pipe idles (9-12 k of a block's 55 k cycles, profiles/r04_gemm_stamps.txt).
-// Here the launch is ONE workgroup per CU and the flattened list of (row block, 16-row table chunk) units is dealt evenly over them:
-// a workgroup walks its share block by block (the first and the last may be partial: another workgroup has the block's other
-// chunks and converts the same rows), its eight waves taking the block's chunks round-robin as before.  The NEXT block's rows are
-// fetched and converted inside this block's chunk loop, one 32-byte item per thread and chunk iteration -- loaded at the top of
-// the iteration, converted and written to the OTHER half of the LDS buffer behind its epilogue -- so the only thing between two
-// blocks is a barrier.  Same fragments, same arithmetic, same stores: bit-identical to the one-block-per-workgroup kernel of rounds 2-4 (k_table_gemm, which still serves the 13-k-step product).
-// CANON: the source rows hold canonical values (everything the pipelines produce): packed conversion; otherwise gm_split16 (folds).
-template <int KS, int NBT, bool CANON>
-__global__ __launch_bounds__(512, 1) void k_table_gemm_p(GemmArgs a, int nchunks, int nblk, int wide_stores, uint32_t npg_magic)
-{
     // row n -> (group, index inside the group) by multiply-high with floor(2^32 / npg) and one correction step (as ntt_split)
-    auto split = [&](int n, int &g, int &i) {
+    __device__ __forceinline__ void split(int n, int &g, int &i) const
+    {
         uint32_t gg = __umulhi((uint32_t)n, npg_magic);
         int r = n - (int)gg * a.npg;
         if (r >= a.npg) { gg++; r -= a.npg; }
         g = (int)gg;
         i = r;
-    };
-    constexpr int TG_RT = 1, TG_CHUNK = 16, TG_NB = 16 * NBT, BUF = KS * NBT * 2048;
-    __shared__ __attribute__((aligned(16))) uint8_t ldsB[2 * BUF]; // two row blocks: [buffer][k-step][row tile][limb][1 KiB]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int ntot = a.npg * a.ngroups;
+    }
+
+    // ---- a row block, u16 -> limbs, into LDS.  Item = 16 consecutive k of one row (32 bytes of HBM, 16 + 16 limb bytes of LDS)
+    __device__ __forceinline__ const uint16_t *item_src(int blk, int item) const // nullptr: behind the last row (zero limbs)
+    {
+        const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
+        const int n = blk * NB + row_l;
+        if (item >= ITEMS || n >= ntot) return nullptr;
+        int g, i;
+        split(n, g, i);
+        return a.src + (size_t)g * a.src_gstride + (size_t)(a.src_rows ? (int)a.src_rows[i] : i) * a.src_rstride + a.src_koff + kc16 * 16;
+    }
+    __device__ __forceinline__ void item_get(int blk, int item, uint4 &x0, uint4 &x1) const
+    {
+        const uint16_t *src = item_src(blk, item);
+        x0 = make_uint4(0, 0, 0, 0);
+        x1 = x0;
+        if (src) { x0 = *reinterpret_cast<const uint4 *>(src); x1 = *reinterpret_cast<const uint4 *>(src + 8); }
+    }
+    // CANON: the source rows hold canonical values (everything the pipelines produce): packed conversion; otherwise gm_split16 (folds)
+    template <bool CANON>
+    __device__ __forceinline__ void item_put(uint8_t *lds, int item, const uint4 &x0, const uint4 &x1) const
+    {
+        if (item >= ITEMS) return;
+        const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
+        uint4 lo, hi;
+        if constexpr (CANON) gm_split16_pk(x0, x1, lo, hi);
+        else gm_split16(x0, x1, lo, hi);
+        uint8_t *d = lds + ((kc16 >> 2) * NBT + (row_l >> 4)) * 2048 + (row_l & 15) * 64 + (((kc16 & 3) ^ limb_swz(row_l & 15)) << 4);
+        *reinterpret_cast<uint4 *>(d) = lo;
+        *reinterpret_cast<uint4 *>(d + 1024) = hi;
+    }
+    // a whole block (every row is read exactly once from HBM): all loads of a thread are in flight before the first conversion
+    template <bool CANON>
+    __device__ __forceinline__ void load_block(uint8_t *lds, int blk, int tid) const
+    {
+        uint4 x0[PER], x1[PER];
+#pragma unroll
+        for (int q = 0; q < PER; q++) item_get(blk, tid + q * 512, x0[q], x1[q]);
+#pragma unroll
+        for (int q = 0; q < PER; q++) item_put<CANON>(lds, tid + q * 512, x0[q], x1[q]);
+    }
+
+    // this lane's table fragments of chunk c, k-step ks: tiles (row tile c, limb) of k-step ks; the table copy
+    // a.Afrag keeps every tile in fragment order, so the wave's load of a tile is one linear 1 KiB read
+    __device__ __forceinline__ void load_chunk_ks(int c, int ks, v4i (&dst)[2]) const
+    {
+        const uint8_t *src = a.Afrag + ((size_t)(ks * ART + c) * 2) * 1024 + lane * 16;
+        dst[0] = *reinterpret_cast<const v4i *>(src);
+        dst[1] = *reinterpret_cast<const v4i *>(src + 1024);
+    }
+    __device__ __forceinline__ void load_chunk(int c, v4i (&fa)[KS][2]) const
+    {
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) load_chunk_ks(c, ks, fa[ks]);
+    }
+    // this lane's data fragments of k-step ks: (row tile j, limb) at dst[2 j + limb]
+    __device__ __forceinline__ void load_b(const uint8_t *lds, int ks, v4i (&dst)[2 * NBT]) const
+    {
+        const uint8_t *lb = lds + ks * NBT * 2048 + frag;
+#pragma unroll
+        for (int j = 0; j < NBT; j++) {
+            dst[2 * j] = *reinterpret_cast<const v4i *>(lb + j * 2048);
+            dst[2 * j + 1] = *reinterpret_cast<const v4i *>(lb + j * 2048 + 1024);
+        }
+    }
+
+    // output rows of this lane's NBT columns (n = 16 (NBT blk + j) + (lane & 15)) as element offsets from a.C, with the lane's four
+    // consecutive m of a chunk added; -1: no such row.  (Offsets, not pointers: a.C + offset at the store keeps the global address space.)
+    __device__ __forceinline__ void out_rows(int blk, long (&rows)[NBT]) const
+    {
+#pragma unroll
+        for (int j = 0; j < NBT; j++) {
+            const int n = blk * NB + j * 16 + (lane & 15);
+            rows[j] = -1;
+            if (n < ntot) {
+                int g, i;
+                split(n, g, i);
+                rows[j] = (long)((size_t)g * a.c_gstride + (size_t)(a.c_rows ? (int)a.c_rows[i] : i) * a.c_rstride + a.c_off + (lane >> 4) * 4);
+            }
+        }
+    }
+
+    // One 16-row table chunk c (fragments in fa) against the block in lds: KS k-steps, reduction, stores.  fa is re-loaded with chunk
+    // cn's fragments k-step by k-step; fb0 holds the block's data fragments of k-step 0 on entry and again on return.
+    // (Tried and not kept, profiles/r04_gemm_stamps.txt: the reduction and the stores of chunk c issued inside chunk c + 1's k-steps,
+    // two vector instructions behind every MFMA.  The k-steps grew by exactly what the epilogue shrank -- two waves per SIMD leave
+    // no idle issue slots under the MFMAs -- so the epilogue stays where it is, behind the chunk's last k-step.)
+    __device__ __forceinline__ void chunk(const uint8_t *lds, v4i (&fa)[KS][2], v4i (&fb0)[2 * NBT], int c, int cn, const long (&rows)[NBT]) const
+    {
+        const v4i zero4 = {0, 0, 0, 0}, bias4 = {LIMB_BIAS, LIMB_BIAS, LIMB_BIAS, LIMB_BIAS};
+        // the data fragments of the next k-step are read from LDS while the current k-step multiplies; the rows are the same
+        // for every chunk, so the last k-step prefetches k-step 0 again (into a buffer of its own: KS is odd)
+        static_assert(KS % 2 == 1, "fb0 is free for k-step 0 of the next chunk while the last k-step reads fb[0]");
+        v4i fb[2][2 * NBT];
+        v4i s0[NBT], s1[NBT], s2[NBT];
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+            v4i(&bc)[2 * NBT] = ks == 0 ? fb0 : fb[ks & 1];
+            v4i(&bn)[2 * NBT] = ks + 1 == KS ? fb0 : fb[(ks & 1) ^ 1];
+            load_b(lds, ks + 1 < KS ? ks + 1 : 0, bn);
+            __builtin_amdgcn_sched_barrier(0); // the reads for the NEXT k-step go out before this k-step's MFMAs, not after them
+            // four limb products per 16 x 16 x 64 block, ordered so that no accumulator is used twice in a row; the first
+            // k-step starts from a constant operand instead of initialised registers (s0 with BIASED: the reduction's bias)
+#pragma unroll
+            for (int j = 0; j < NBT; j++) s0[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][0], bc[2 * j], ks == 0 ? (BIASED ? bias4 : zero4) : s0[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NBT; j++) s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][0], bc[2 * j + 1], ks == 0 ? zero4 : s1[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NBT; j++) s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][1], bc[2 * j], s1[j], 0, 0, 0);
+#pragma unroll
+            for (int j = 0; j < NBT; j++) s2[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][1], bc[2 * j + 1], ks == 0 ? zero4 : s2[j], 0, 0, 0);
+            load_chunk_ks(cn, ks, fa[ks]); // in flight for a whole chunk of arithmetic before it is used
+            __builtin_amdgcn_sched_barrier(0); // keep the k-steps apart: hoisting every LDS read of the chunk costs 150 VGPRs
+        }
+        // epilogue: combine the limb products, reduce mod q, pack four consecutive m per lane and block, store.
+        // D[row = m: 4 (lane >> 4) + r][col = n: lane & 15]: four consecutive m per lane and block
+        const int grp = lane >> 4;
+        uint2 pk[NBT];
+#pragma unroll
+        for (int j = 0; j < NBT; j++) {
+            uint32_t v[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) v[r] = BIASED ? gf_reduce_limbs_biased_lazy(s0[j][r], s1[j][r], s2[j][r]) : gf_reduce_limbs(s0[j][r], s1[j][r], s2[j][r]);
+            if constexpr (BIASED) pk[j] = make_uint2(gf_canon_pair(v[0], v[1]), gf_canon_pair(v[2], v[3]));
+            else pk[j] = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
+            if (j & 1) {
+                // blocks j - 1, j: the rows are 16-byte aligned (table_gemm_ok), so the odd 16-lane rows of block j - 1's packed values are
+                // swapped with the even rows of block j's (v_permlane16_swap), after which an even-row lane holds EIGHT consecutive m of
+                // block j - 1 and an odd-row lane eight of block j: one 16-byte store per lane instead of two 8-byte stores
+                const auto sx = __builtin_amdgcn_permlane16_swap(pk[j - 1].x, pk[j].x, false, false);
+                const auto sy = __builtin_amdgcn_permlane16_swap(pk[j - 1].y, pk[j].y, false, false);
+                const long off = (grp & 1) ? (rows[j] >= 0 ? rows[j] - 4 : -1) : rows[j - 1];
+                if (off >= 0) *reinterpret_cast<uint4 *>(a.C + off + c * CHUNK) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
+            } else if (j == NBT - 1) { // the lone last row tile
+                if (rows[j] >= 0) *reinterpret_cast<uint2 *>(a.C + rows[j] + c * CHUNK) = pk[j];
+            }
+        }
+    }
+};
+
+// ---- one workgroup per (row block, share of the table): the 13-k-step product (recon_secrets_2ddeg: few data rows) ----------------
+// The table's chunks are split over msplit workgroups per row block; a wave takes its workgroup's chunks round-robin.  The rows come
+// from the caller (kosk_recon_secrets), so the conversion folds.
+template <int KS, int NBT>
+__global__ __launch_bounds__(512, 1) void k_table_gemm(GemmArgs a, int nchunks, int chunks_per_block, int nblk, int msplit, uint32_t npg_magic)
+{
+    using Tiles = TableTiles<KS, NBT, false>;
+    __shared__ __attribute__((aligned(16))) uint8_t ldsB[Tiles::BUF];
+    const int tid = threadIdx.x, w = tid >> 6;
+    // one-dimensional grid in XCD-aware order: the msplit workgroups that share a row block (each converts the same 48 rows) get
+    // consecutive virtual ids, i.e. one XCD and one L2 (on msplit different XCDs the rows would be fetched from HBM msplit times)
+    const int vid = xcd_virtual_id();
+    const int bxr = vid / msplit, byr = vid - bxr * msplit;
+    if (bxr >= nblk) return; // grid padding (whole workgroup, before any barrier)
+    const Tiles t(a, npg_magic, tid & 63);
+    t.template load_block<false>(ldsB, bxr, tid);
+
+    const int c_begin = byr * chunks_per_block;
+    const int c_end = c_begin + chunks_per_block < nchunks ? c_begin + chunks_per_block : nchunks;
+    const int c_first = c_begin + w;
+    const int nmy = c_first < c_end ? (c_end - c_first + TG_WAVES - 1) / TG_WAVES : 0; // chunks c_first, c_first + 8, ...
+    v4i fa[KS][2];
+    if (nmy > 0) t.load_chunk(c_first, fa);
+    __syncthreads(); // the only workgroup barrier: from here on the waves run independently
+    if (nmy == 0) return;
+    long rows[NBT];
+    t.out_rows(bxr, rows);
+    v4i fb0[2 * NBT];
+    t.load_b(ldsB, 0, fb0);
+    for (int ci = 0; ci < nmy; ci++) {
+        const int c = c_first + ci * TG_WAVES;
+        t.chunk(ldsB, fa, fb0, c, ci + 1 < nmy ? c + TG_WAVES : c, rows); // (the last chunk prefetches itself: harmless)
+    }
+}
+
+// ---- PERSISTENT workgroups: every 7-k-step product ---------------------------------------------------------------------------------
+// With a workgroup per 48-row block, one per CU at a time, a launch takes ceil(blocks / CUs) rounds
+// (29 946 rows = 624 blocks = 2.44 rounds of work in 3 rounds of time; the verifier's and the re-sharing products of a 138-proof step
+// are 1.03 .. 1.6 rounds of work in 2), and every block starts with a prologue -- 43 KB of rows from HBM, their conversion, the first
+// chunk's table fragments -- during which the matrix pipe idles (9-12 k of a block's 55 k cycles, profiles/r04_gemm_stamps.txt).
+// Here the launch is ONE workgroup per CU and the flattened list of (row block, 16-row table chunk) units is dealt evenly over them:
+// a workgroup walks its share block by block (the first and the last may be partial: another workgroup has the block's other
+// chunks and converts the same rows), its eight waves taking the block's chunks round-robin.  The NEXT block's rows are
+// fetched and converted inside this block's chunk loop, one 32-byte item per thread and chunk iteration -- loaded at the top of
+// the iteration, converted and written to the OTHER half of the LDS buffer behind its epilogue -- so the only thing between two
+// blocks is a barrier.
+template <int KS, int NBT, bool CANON>
+__global__ __launch_bounds__(512, 1) void k_table_gemm_p(GemmArgs a, int nchunks, int nblk, uint32_t npg_magic)
+{
+    using Tiles = TableTiles<KS, NBT, true>;
+    __shared__ __attribute__((aligned(16))) uint8_t ldsB[2 * Tiles::BUF]; // two row blocks
+    const int tid = threadIdx.x, w = tid >> 6;
     const long total = (long)nblk * nchunks;
     const long u0 = (long)blockIdx.x * total / gridDim.x, u1 = (long)(blockIdx.x + 1) * total / gridDim.x;
     if (u0 >= u1) return;
     int rb = (int)(u0 / nchunks), ca = (int)(u0 - (long)rb * nchunks);
     long u = u0;
 
-    constexpr int ITEMS = TG_NB * KS * 4, PER = (ITEMS + 511) / 512;
-    auto item_src = [&](int blk, int item) -> const uint16_t * { // nullptr: behind the last row (zero limbs)
-        const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
-        const int n = blk * TG_NB + row_l;
-        if (item >= ITEMS || n >= ntot) return nullptr;
-        int g, i;
-        split(n, g, i);
-        return a.src + (size_t)g * a.src_gstride + (size_t)(a.src_rows ? (int)a.src_rows[i] : i) * a.src_rstride + a.src_koff + kc16 * 16;
-    };
-    auto item_put = [&](int buf, int item, const uint4 &x0, const uint4 &x1) {
-        if (item >= ITEMS) return;
-        const int row_l = item / (KS * 4), kc16 = item - row_l * (KS * 4);
-        uint4 lo, hi;
-        if constexpr (CANON) gm_split16_pk(x0, x1, lo, hi);
-        else gm_split16(x0, x1, lo, hi);
-        uint8_t *d = ldsB + buf * BUF + ((kc16 >> 2) * NBT + (row_l >> 4)) * 2048 + (row_l & 15) * 64 + (((kc16 & 3) ^ limb_swz(row_l & 15)) << 4);
-        *reinterpret_cast<uint4 *>(d) = lo;
-        *reinterpret_cast<uint4 *>(d + 1024) = hi;
-    };
-    { // the first block's rows: every load of a thread in flight before the first conversion
-        uint4 x0[PER], x1[PER];
-#pragma unroll
-        for (int q = 0; q < PER; q++) {
-            const uint16_t *src = item_src(rb, tid + q * 512);
-            x0[q] = make_uint4(0, 0, 0, 0);
-            x1[q] = x0[q];
-            if (src) { x0[q] = *reinterpret_cast<const uint4 *>(src); x1[q] = *reinterpret_cast<const uint4 *>(src + 8); }
-        }
-#pragma unroll
-        for (int q = 0; q < PER; q++) item_put(0, tid + q * 512, x0[q], x1[q]);
-    }
-    const int ART = a.Mpad / 16;
-    const int frag = (lane & 15) * 64 + (((lane >> 4) ^ limb_swz(lane & 15)) << 4);
-    v4i fa[KS][2 * TG_RT];
-    auto load_chunk_ks = [&](int c, int ks, v4i (&dst)[2 * TG_RT]) {
-        const uint8_t *src = a.Afrag + ((size_t)(ks * ART + TG_RT * c) * 2) * 1024 + lane * 16;
-#pragma unroll
-        for (int q = 0; q < 2 * TG_RT; q++) dst[q] = *reinterpret_cast<const v4i *>(src + q * 1024);
-    };
-    {
-        const int c_first = ca + w < nchunks ? ca + w : 0; // (a wave without a chunk in the first block loads a harmless one)
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) load_chunk_ks(c_first, ks, fa[ks]);
-    }
+    const Tiles t(a, npg_magic, tid & 63);
+    t.template load_block<CANON>(ldsB, rb, tid);
+    v4i fa[KS][2];
+    t.load_chunk(ca + w < nchunks ? ca + w : 0, fa); // (a wave without a chunk in the first block loads a harmless one)
     __syncthreads();
-    const v4i zero4 = {0, 0, 0, 0}, bias4 = {LIMB_BIAS, LIMB_BIAS, LIMB_BIAS, LIMB_BIAS};
-    const int grp = lane >> 4;
     int buf = 0;
     while (u < u1) {
         const int cb = (long)(nchunks - ca) <= u1 - u ? nchunks : ca + (int)(u1 - u); // this block's chunks [ca, cb)
         const bool have_next = u + (cb - ca) < u1;
-        const uint8_t *lds_cur = ldsB + buf * BUF;
-        // output rows of this lane's NBT columns (n = n0 + 16 j + (lane & 15))
-        uint16_t *crow[NBT];
-#pragma unroll
-        for (int j = 0; j < NBT; j++) {
-            const int n = rb * TG_NB + j * 16 + (lane & 15);
-            crow[j] = nullptr;
-            if (n < ntot) {
-                int g, i;
-                split(n, g, i);
-                crow[j] = a.C + (size_t)g * a.c_gstride + (size_t)(a.c_rows ? (int)a.c_rows[i] : i) * a.c_rstride + a.c_off + (lane >> 4) * 4;
-            }
-        }
-        auto store_pair = [&](int j, int c, uint2 pj, uint2 pk) {
-            if (wide_stores) {
-                const auto sx = __builtin_amdgcn_permlane16_swap(pj.x, pk.x, false, false);
-                const auto sy = __builtin_amdgcn_permlane16_swap(pj.y, pk.y, false, false);
-                uint16_t *p = (grp & 1) ? (crow[j + 1] ? crow[j + 1] - 4 : nullptr) : crow[j];
-                if (p) *reinterpret_cast<uint4 *>(p + c * TG_CHUNK) = make_uint4(sx[0], sy[0], sx[1], sy[1]);
-            } else {
-                if (crow[j]) *reinterpret_cast<uint2 *>(crow[j] + c * TG_CHUNK) = pj;
-                if (crow[j + 1]) *reinterpret_cast<uint2 *>(crow[j + 1] + c * TG_CHUNK) = pk;
-            }
-        };
-        auto store_one = [&](int j, int c, uint2 pj) {
-            if (crow[j]) *reinterpret_cast<uint2 *>(crow[j] + c * TG_CHUNK) = pj;
-        };
-        v4i fb[2][2 * NBT], fb0[2 * NBT];
-        auto load_b = [&](int ks, v4i (&dst)[2 * NBT]) {
-            const uint8_t *lb = lds_cur + ks * NBT * 2048 + frag;
-#pragma unroll
-            for (int j = 0; j < NBT; j++) {
-                dst[2 * j] = *reinterpret_cast<const v4i *>(lb + j * 2048);
-                dst[2 * j + 1] = *reinterpret_cast<const v4i *>(lb + j * 2048 + 1024);
-            }
-        };
+        const uint8_t *lds_cur = ldsB + buf * Tiles::BUF;
+        uint8_t *lds_next = ldsB + (buf ^ 1) * Tiles::BUF;
+        long rows[NBT];
+        t.out_rows(rb, rows);
+        v4i fb0[2 * NBT];
         int it = 0; // items of the NEXT block's rows this thread has fetched, converted and written so far
         const int c_first = ca + w;
         const int nmy = c_first < cb ? (cb - c_first + TG_WAVES - 1) / TG_WAVES : 0;
-        if (nmy > 0) load_b(0, fb0);
+        if (nmy > 0) t.load_b(lds_cur, 0, fb0);
         for (int ci = 0; ci < nmy; ci++) {
             const int c = c_first + ci * TG_WAVES;
             // the chunk to prefetch: this wave's next one in this block, else its first one of the next block (which starts at chunk
             // 0), else the current one again (harmless)
             const int cn = ci + 1 < nmy ? c + TG_WAVES : (have_next && w < nchunks ? w : c);
             uint4 nx0 = make_uint4(0, 0, 0, 0), nx1 = nx0;
-            const bool fetch = have_next && it < PER;
-            if (fetch) {
-                const uint16_t *src = item_src(rb + 1, tid + it * 512);
-                if (src) { nx0 = *reinterpret_cast<const uint4 *>(src); nx1 = *reinterpret_cast<const uint4 *>(src + 8); }
-            }
-            v4i s0[NBT], s1[NBT], s2[NBT];
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) {
-                v4i(&bc)[2 * NBT] = ks == 0 ? fb0 : fb[ks & 1];
-                v4i(&bn)[2 * NBT] = ks + 1 == KS ? fb0 : fb[(ks & 1) ^ 1];
-                load_b(ks + 1 < KS ? ks + 1 : 0, bn);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s0[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][0], bc[2 * j], ks == 0 ? bias4 : s0[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][0], bc[2 * j + 1], ks == 0 ? zero4 : s1[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][1], bc[2 * j], s1[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < NBT; j++) s2[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(fa[ks][1], bc[2 * j + 1], ks == 0 ? zero4 : s2[j], 0, 0, 0);
-                load_chunk_ks(cn, ks, fa[ks]);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            uint2 pk[NBT];
-#pragma unroll
-            for (int j = 0; j < NBT; j++) {
-                uint32_t v[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) v[r] = gf_reduce_limbs_biased_lazy(s0[j][r], s1[j][r], s2[j][r]); // the bias came in with the first MFMA
-                pk[j] = make_uint2(gf_canon_pair(v[0], v[1]), gf_canon_pair(v[2], v[3]));
-                if (j & 1) store_pair(j - 1, c, pk[j - 1], pk[j]);
-                else if (j == NBT - 1) store_one(j, c, pk[j]);
-            }
-            if (fetch) { item_put(buf ^ 1, tid + it * 512, nx0, nx1); it++; }
+            const bool fetch = have_next && it < Tiles::PER;
+            if (fetch) t.item_get(rb + 1, tid + it * 512, nx0, nx1);
+            t.chunk(lds_cur, fa, fb0, c, cn, rows);
+            if (fetch) { t.template item_put<CANON>(lds_next, tid + it * 512, nx0, nx1); it++; }
         }
         if (have_next) {
-            for (; it < PER; it++) { // a wave with fewer chunk iterations than items (a short first block): the rest here
-                const uint16_t *src = item_src(rb + 1, tid + it * 512);
-                uint4 nx0 = make_uint4(0, 0, 0, 0), nx1 = nx0;
-                if (src) { nx0 = *reinterpret_cast<const uint4 *>(src); nx1 = *reinterpret_cast<const uint4 *>(src + 8); }
-                item_put(buf ^ 1, tid + it * 512, nx0, nx1);
+            for (; it < Tiles::PER; it++) { // a wave with fewer chunk iterations than items (a short first block): the rest here
+                uint4 nx0, nx1;
+                t.item_get(rb + 1, tid + it * 512, nx0, nx1);
+                t.template item_put<CANON>(lds_next, tid + it * 512, nx0, nx1);
             }
-            if (nmy == 0 && w < nchunks) { // this wave sat the block out: its table fragments are those of the clamped chunk, load the next block's
-#pragma unroll
-                for (int ks = 0; ks < KS; ks++) load_chunk_ks(w, ks, fa[ks]);
-            }
+            // this wave sat the block out: its table fragments are those of the clamped chunk, load the next block's
+            if (nmy == 0 && w < nchunks) t.load_chunk(w, fa);
         }
         u += cb - ca;
         rb++;
@@ -1986,40 +1919,45 @@ hipError_t launch_matvec_ntt(const int16_t *A, size_t A_stride, uint16_t *P, siz
 }
 
 // what the table kernels ask of a product: a fragment-order table of 7 k-steps (407-wide inputs) or 13 (813-wide:
-// recon_secrets_2ddeg), whole pairs of 16-row table chunks, source rows that take 16-byte loads, output rows that take 8-byte stores.
+// recon_secrets_2ddeg), whole pairs of 16-row table chunks, source rows that take 16-byte loads, output rows that take 16-byte stores
+// (the kernels have no narrower store for a pair of row tiles).
 // Every product the library issues meets it by construction: its strides and offsets are the constants checked here, its pointers
 // rows of the context's own buffers (a view's are offset by whole proofs of nrows * RS u16).
-static_assert(RS % 8 == 0 && NSEC % 8 == 0 && EXP_OFF % 4 == 0 && EXP_M % 32 == 0 && NSEC % 32 == 0,
+static_assert(RS % 8 == 0 && NSEC % 8 == 0 && EXP_OFF % 8 == 0 && EXP_M % 32 == 0 && NSEC % 32 == 0,
               "row stride, source offsets, output offsets and table heights of the library's own products");
 bool table_gemm_ok(const GemmArgs &a)
 {
     return a.Afrag && (a.KS == 7 || a.KS == 13) && a.M % 32 == 0 && a.src_koff % 8 == 0 && a.src_rstride % 8 == 0 &&
-           a.src_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 && a.c_off % 4 == 0 && a.c_rstride % 4 == 0 &&
-           a.c_gstride % 4 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 7) == 0;
+           a.src_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.src) & 15) == 0 && a.c_off % 8 == 0 && a.c_rstride % 8 == 0 &&
+           a.c_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0;
+}
+
+// CUs of the current device (persistent kernels launch one or two workgroups per CU)
+static int device_cus()
+{
+    static const int ncu = [] {
+        int dev = 0, cus = 256;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
+        return cus;
+    }();
+    return ncu;
 }
 
 hipError_t launch_table_gemm(const GemmArgs &a, hipStream_t st)
 {
     const int ntot = a.npg * a.ngroups;
     if (ntot <= 0) return hipSuccess;
-    static const int ncu = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-        return cus;
-    }();
     const int nblk = (ntot + 47) / 48, nchunks = a.M / 16; // 48 rows per block
-    // eight consecutive outputs per lane and 16-byte stores where the output rows allow it
-    const int ws = a.c_off % 8 == 0 && a.c_rstride % 8 == 0 && a.c_gstride % 8 == 0 && (reinterpret_cast<uintptr_t>(a.C) & 15) == 0;
+    const uint32_t magic = ntt_npg_magic(a.npg);
     if (a.KS == 7) {
-        // persistent workgroups (k_table_gemm_p): one per CU, the (row block, table chunk) units dealt evenly.  (The one-block-per-workgroup
-        // kernel of rounds 2-4, its 64-row variant and the 8-byte-store epilogue are gone since round 6: profiles/r04_sweeps.txt)
+        // persistent workgroups (k_table_gemm_p): one per CU, the (row block, table chunk) units dealt evenly
+        const int ncu = device_cus();
         const long total = (long)nblk * nchunks;
         // at least eight chunks per workgroup where the product is that large (a chunk per wave), never more workgroups than CUs
         long nwg = total / 8 < ncu ? total / 8 : ncu;
         if (nwg < 1) nwg = 1;
-        const uint32_t magic = ntt_npg_magic(a.npg);
-        if (a.src_canonical) hipLaunchKernelGGL((k_table_gemm_p<7, 3, true>), dim3((unsigned)nwg), dim3(512), 0, st, a, nchunks, nblk, ws, magic);
-        else hipLaunchKernelGGL((k_table_gemm_p<7, 3, false>), dim3((unsigned)nwg), dim3(512), 0, st, a, nchunks, nblk, ws, magic);
+        if (a.src_canonical) hipLaunchKernelGGL((k_table_gemm_p<7, 3, true>), dim3((unsigned)nwg), dim3(512), 0, st, a, nchunks, nblk, magic);
+        else hipLaunchKernelGGL((k_table_gemm_p<7, 3, false>), dim3((unsigned)nwg), dim3(512), 0, st, a, nchunks, nblk, magic);
         return hipGetLastError();
     }
     // 13 k-steps (recon_secrets_2ddeg, 24 rows per proof): few data rows, so the table is split over several workgroups per row block
@@ -2028,7 +1966,7 @@ hipError_t launch_table_gemm(const GemmArgs &a, hipStream_t st)
     const int cpb = (nchunks + msplit - 1) / msplit;
     msplit = (nchunks + cpb - 1) / cpb;
     const dim3 grid((unsigned)((nblk * msplit + 7) / 8 * 8));
-    hipLaunchKernelGGL((k_table_gemm<13, 1, 3>), grid, dim3(512), 0, st, a, nchunks, cpb, nblk, msplit, ws);
+    hipLaunchKernelGGL((k_table_gemm<13, 3>), grid, dim3(512), 0, st, a, nchunks, cpb, nblk, msplit, magic);
     return hipGetLastError();
 }
 
@@ -2037,11 +1975,7 @@ hipError_t launch_lincomb_stream(const uint16_t *P, size_t proof_stride, const R
 {
     if (J > 16 * LS_JT || rm.M <= 64 || rm.M > 80) return hipErrorInvalidValue; // (every Kyber parameter set: J = 74..78, M = 75..79)
     // the (group, point block) units dealt evenly over two persistent workgroups per CU
-    static const int ncu = [] {
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) { (void)hipGetLastError(); cus = 256; }
-        return cus;
-    }();
+    const int ncu = device_cus();
     const int total = (NPTS + 127) / 128 * 2 * nproofs;
     const int nwg = total < 2 * ncu ? total : 2 * ncu;
     hipLaunchKernelGGL(k_lincomb_stream, dim3(nwg), dim3(256), 0, st, P, proof_stride, rm.f, rm.tf, rm.M, coef, 2 * nproofs * 8, C, lin_rows, J,

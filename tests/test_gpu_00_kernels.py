@@ -141,7 +141,12 @@ def test_lagrange_expand_and_recon_match_oracle(n, torch, ctx, oracle):
     y[0] = 0; y[1] = 3328
     y[2] = 1664; y[3] = 1665  # the largest centred magnitudes: the limb products' sums are at their extremes for a constant row
     y[4, 0::2] = 1664; y[4, 1::2] = 1665
-    d_y = _dev(torch, y)
+    y_in = y
+    if n == 300:  # one row of values >= q: the folding conversion of the caller-data product
+        y_in = y.copy()
+        y_in[5] = _non_canonical(y[5])
+        y[5] = y_in[5] % 3329
+    d_y = _dev(torch, y_in)
     d_sh = torch.zeros((n, 1454), dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
     ctx.lagrange_expand(d_y.data_ptr(), d_sh.data_ptr(), n)
@@ -158,12 +163,22 @@ def test_lagrange_expand_and_recon_match_oracle(n, torch, ctx, oracle):
     want = expand_exact(oracle, y)
     for i in (0, 1, 2, 3, 4, n // 2, n - 1):
         assert np.array_equal(want[i], oracle.recompute_shares(y[i])), i
-    bad = np.flatnonzero((sh != want).any(axis=1))
+    # shares 0..127 are points 256..383 of the row itself: no product writes them, a value >= q arrives as it was given
+    assert np.array_equal(sh[:, :128], y_in[:, 256:384]) and np.array_equal(sh % 3329, want)
+    bad = np.flatnonzero((sh[:, 128:] != want[:, 128:]).any(axis=1))
     assert not bad.size, ("rows that differ from the oracle's expansion", bad.size, bad[:32].tolist())
     # encode -> erase -> decode round trip on every row: the packed secrets come back
     assert np.array_equal(sec, y[:, :256])
     # degree-2d reconstruction of share-wise products = product of the packed secrets
     prod = (sh.astype(np.uint32)[0::2] * sh.astype(np.uint32)[1::2] % 3329).astype(np.uint16)
+    if n == 300:
+        # constant rows, the largest centred magnitudes (the limb sums of 13 k-steps at their extremes) and values >= q; 156 rows are
+        # no multiple of 16: the last 48-row block is partial
+        extra = np.zeros((6, 1454), dtype=np.uint16)
+        extra[1] = 3328; extra[2] = 1664; extra[3] = 1665
+        extra[4, 0::2] = 1664; extra[4, 1::2] = 1665
+        extra[5] = _non_canonical(rng.integers(0, 3329, size=1454, dtype=np.uint16))
+        prod = np.concatenate([prod, extra])
     d_p = _dev(torch, prod)
     d_s2 = torch.zeros((prod.shape[0], 256), dtype=torch.int16, device="cuda")
     torch.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
@@ -171,8 +186,49 @@ def test_lagrange_expand_and_recon_match_oracle(n, torch, ctx, oracle):
     ctx.synchronize()
     s2 = d_s2.cpu().numpy().view(np.uint16)
     exp = (y[0::2, :256].astype(np.uint32) * y[1::2, :256].astype(np.uint32) % 3329).astype(np.uint16)
-    assert np.array_equal(s2, exp)
+    assert np.array_equal(s2[:exp.shape[0]], exp)
     assert np.array_equal(s2[3], oracle.recon(prod[3], True))
+    for i in range(exp.shape[0], prod.shape[0]):
+        assert np.array_equal(s2[i], oracle.recon(prod[i] % 3329, True)), i
     # all three tables (7 and 13 k-steps), caller data: every product ran on the table kernels
     paths = ctx.path_counts()
     assert paths["table_gemm"] > 0 and paths["limb_gemm"] == 0, paths
+    if n == 300:
+        _recon_2ddeg_two_chunks_per_wave(torch)
+
+
+def _non_canonical(v):
+    """values >= q for a conversion that folds: v + q (it always fits 16 bits), every fifth one 0xFFFF (another residue than v)"""
+    out = v.astype(np.uint16) + np.uint16(3329)
+    out[0::5] = 0xFFFF
+    return out
+
+
+def _recon_2ddeg_two_chunks_per_wave(torch):
+    """7 680 rows = 160 blocks of 48 in ONE 13-k-step launch: the smallest product whose table is not split over workgroups, so
+    that a wave walks two chunks and loads the second one's table fragments behind the first one's arithmetic.  A handle of 18
+    proofs holds 18 x 435 = 7 830 rows."""
+    from mpcith_kyber_kosk_amd import api
+    m = 7680
+    assert m % 48 == 0 and m // 48 == 160  # the launcher stops splitting the table at 160 row blocks
+    y = np.random.default_rng(13).integers(0, 3329, size=(m + 1, 407), dtype=np.uint16)
+    c = api.Kosk(kyber_k=3, max_batch=18)
+    try:
+        d_y = _dev(torch, y)
+        d_sh = torch.zeros((m + 1, 1454), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
+        c.lagrange_expand(d_y.data_ptr(), d_sh.data_ptr(), m + 1)
+        c.synchronize()
+        sh = d_sh.cpu().numpy().view(np.uint16).astype(np.uint32)
+        d_p = _dev(torch, (sh[:-1] * sh[1:] % 3329).astype(np.uint16))  # overlapping pairs
+        d_s2 = torch.zeros((m, 256), dtype=torch.int16, device="cuda")
+        torch.cuda.synchronize()  # torch fills / copies run on the null stream; the library streams are not ordered against it
+        before = c.path_counts()["table_gemm"]
+        c.recon_secrets(d_p.data_ptr(), d_s2.data_ptr(), m, True)
+        c.synchronize()
+        assert c.path_counts()["table_gemm"] == before + 1, "the 7 680 rows must go in ONE launch (a chunked call has fewer than 160 blocks per launch)"
+        s2 = d_s2.cpu().numpy().view(np.uint16)
+    finally:
+        c.close()
+    y32 = y[:, :256].astype(np.uint32)
+    assert np.array_equal(s2, (y32[:-1] * y32[1:] % 3329).astype(np.uint16))

@@ -25,9 +25,10 @@ def kernels(path):
         desc = text[text.index(".amdhsa_kernel %s\n" % name):]
         res["lds"] = int(re.search(r"\.amdhsa_group_segment_fixed_size (\d+)", desc).group(1))
         out[name] = (hist, res)
-    # keyed by the demangled name without a template argument a later tree dropped (k_fs_chain<M, FsSpongeBperm> is k_fs_chain<M>)
+    # keyed by the demangled name without a template argument a later tree dropped (k_fs_chain<M, FsSpongeBperm> is k_fs_chain<M>,
+    # k_table_gemm<13, 1, 3> is k_table_gemm<13, 3>)
     pretty = subprocess.run(["c++filt", "-p"] + list(out), capture_output=True, text=True).stdout.split("\n")
-    return {re.sub(r", kosk::FsSpongeBperm>", ">", p): v for p, v in zip(pretty, out.values())}
+    return {re.sub(r", kosk::FsSpongeBperm>", ">", p).replace("k_table_gemm<13, 1, 3>", "k_table_gemm<13, 3>"): v for p, v in zip(pretty, out.values())}
 
 
 def main(old_path, new_path):
