@@ -175,6 +175,16 @@ inline int crypto_kem_dec(uint8_t *ss, const uint8_t *ct, const uint8_t *sk)
     return 0;
 }
 
+/* ---- a proof for a key pair that already exists (no reference counterpart; kosk_prove_keys_batch on the process-wide handle): one
+ * proof of knowledge of keypair->sk's s, e into pi, the randomness drawn through randombytes as kyber_verifiable_keygen draws it
+ * minus the key generation's 64 bytes.  false (pi all zero) for a record whose s or e is outside the key generation's range. ---- */
+inline bool kyber_kosk_prove_key(const kyber_keypair *keypair, uint8_t *pi)
+{
+    uint8_t ok = 0;
+    kosk_compat::must(kosk_prove_keys_batch(kosk_compat::ctx(), 1, keypair->sk, nullptr, 0, pi, &ok), "kyber_kosk_prove_key");
+    return ok == 1;
+}
+
 /* ---- second-level entry points, used directly by main.cpp:21-47 ---- */
 /* mlwe_prover.hpp:77 */
 inline void prepare_randomness(mpcith_randomness *rand)

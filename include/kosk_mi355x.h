@@ -218,6 +218,38 @@ int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *s
  * by a call that replaced the resident keys (a key generation, a verifier staging call in either wire format); and for a member of a cohort (combine >= 2): "not available with call combining". */
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* ---- Proofs for Kyber keys that already exist.  sk: n consecutive records of kosk_sk_bytes,
+ * NTT(s) bytes || pk || H(pk) || z, from this library or any other Kyber implementation; host or device memory.  H(pk) and z are not read.
+ * The witness is recovered on the device: s = NTT^-1(s-hat), e = NTT^-1(t-hat - A o s-hat) with t-hat and A from the pk INSIDE the record.
+ * 12-bit fields >= q in s-hat and in that pk are folded mod q, as polyvec_frombytes and the KEM calls do (a proof over a pk with such a
+ * field is still refused by the strict-encoding verifier).  ok[b] (host memory) = 1 iff every coefficient of s and e lies in
+ * [-eta1, eta1] (eta1 = 3 for kyber_k 2, else 2), the range the proof is about: true for every honestly generated key, false for a
+ * record whose halves do not belong together or that was tampered with.  Where ok[b] = 0 the witness written for b is all zero.
+ * No branch and no address of the recovery depends on s-hat, s, e or the verdict.  The copy of the sk records, s and e stay in the
+ * handle's HBM workspace until a later call overwrites them or the handle is destroyed.
+ * All five calls return -1 with a kosk_last_error text and start nothing for n out of range, a NULL sk / ok / pi or a stride below
+ * one tape / seed, and -1 ("block limit", no results) if gen_matrix reached its block limit; else 0, and ok[] says which keys were proven.
+ * They run unmerged on the handle's own stream(s): on a member of a cohort (combine >= 2) and with streams > 1 the staging calls and
+ * kosk_witness_from_sk behave as kosk_stage_prover_inputs does (the sub-batches of kosk_prove_resident, on the handle's own view /
+ * lanes), the host-buffer forms as kosk_verifiable_keygen_batch does without combining (chunks dealt to the handle's lanes). */
+/* kernel level: n <= max_batch; se_out (host memory, may be NULL): n x 2 K x 256 int16, s then e per key; leaves A, t, s, e and the pk
+ * bytes resident exactly as kosk_stage_prover_keys does */
+int kosk_witness_from_sk(kosk_ctx *ctx, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok);
+/* The counterpart of kosk_stage_prover_inputs[_seeded] for existing keys, n <= max_batch; then kosk_prove_resident and
+ * kosk_fetch_proofs[_compact].  tapes: the format of every other call (kosk_tape_bytes per proof, host or device memory, a device buffer
+ * read in place under the same alignment rule); the first 64 bytes of a tape, the key seed of a verifiable key generation, are NOT
+ * read -- so on the sk that kosk_verifiable_keygen_batch(tape) returned, the proof is the one that call returned, byte for byte.
+ * tapes / seeds == NULL: the handle's entropy mode (kosk_set_entropy) -- the draws of prepare_randomness, prepare_range_proof and
+ * prove in the reference's order without the key generation's 64-byte draw, or one 32-byte draw per proof.
+ * The proof left in HBM at a position with ok[b] = 0 was made from the all-zero witness (it does not verify); the other positions
+ * are unaffected.  Afterwards the pk bytes, A and t of these keys are resident as after a key generation:
+ * kosk_verify_resident_pk(pk == NULL) and then kosk_kem_enc_verified work on them. */
+int kosk_stage_prover_keys(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *ok);
+int kosk_stage_prover_keys_seeded(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *ok);
+/* host-buffer forms, any n >= 1, chunked by max_batch like kosk_verifiable_keygen_batch: pi receives n proof images, all zero where ok[b] = 0 */
+int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *pi, uint8_t *ok);
+int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok);
+
 /* Which kernel / copy paths ran on this handle since it was created (the tests of the fallbacks and of the Fiat-Shamir mode assert on
  * these).  ids: 0 commitment hash with LDS-DMA staging, 1 without (a layout the staged kernel cannot take: unaligned rows),
  * 2 shared-table products on k_table_gemm / k_table_gemm_p (every mod-q product), 3 retired, always 0 (the generic limb GEMM, which no call

@@ -114,6 +114,16 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_enc_batch")):
         sig.update(kem)
+    # proofs for existing keys; optional under the same rule (and only then)
+    keyproof = {
+        "kosk_witness_from_sk": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_stage_prover_keys": (C.c_int, [vp, C.c_int, vp, vp, sz, vp]),
+        "kosk_stage_prover_keys_seeded": (C.c_int, [vp, C.c_int, vp, vp, sz, vp]),
+        "kosk_prove_keys_batch": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, vp]),
+        "kosk_prove_keys_seeded_batch": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_witness_from_sk")):
+        sig.update(keyproof)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -135,7 +145,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_options_init", "kosk_create_ex", "kosk_sha3_256_batch_wave", "kosk_fs_alpha_device", "kosk_fs_opened_device",
            "kosk_tape_from_seed", "kosk_set_entropy", "kosk_tape_expand_device", "kosk_verifiable_keygen_seeded_batch",
            "kosk_verifiable_keygen_seeded_batch_compact", "kosk_verifiable_keygen_seeded_resident", "kosk_stage_prover_inputs_seeded",
-           "kosk_ct_bytes", "kosk_kem_enc_batch", "kosk_kem_dec_batch", "kosk_kem_enc_verified"]
+           "kosk_ct_bytes", "kosk_kem_enc_batch", "kosk_kem_dec_batch", "kosk_kem_enc_verified",
+           "kosk_witness_from_sk", "kosk_stage_prover_keys", "kosk_stage_prover_keys_seeded", "kosk_prove_keys_batch",
+           "kosk_prove_keys_seeded_batch"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -607,6 +619,58 @@ class Kosk:
         ct = C.create_string_buffer(ctb * n); ss = C.create_string_buffer(SS_BYTES * n); done = C.create_string_buffer(n)
         self._chk(lib.kosk_kem_enc_verified(self._h, n, cp, ct, ss, done), "kem_enc_verified")
         return _cut(ct, ctb, n), _cut(ss, SS_BYTES, n), [bool(x) for x in done.raw[:n]]
+
+    # proofs for keys that already exist
+    def witness_from_sk(self, sks, n=None):
+        """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
+        Returns (se, ok): se an int16 ndarray [n, 2K, 256], s then e per key, all zero where ok is False."""
+        import numpy as np
+        sp, n, _keep = self._records("sk", sks, n, self.sk_bytes)
+        se = np.zeros((n, 2 * self.k, 256), np.int16)
+        ok = C.create_string_buffer(n)
+        self._chk(lib.kosk_witness_from_sk(self._h, n, sp, se.ctypes.data, ok), "witness_from_sk")
+        return se, [b == 1 for b in ok.raw[:n]]
+
+    def _key_rand(self, tapes, seeds, n, seed_stride):
+        """the randomness arguments of the *_keys calls -> (seeded, pointer, stride, keepalive)"""
+        if seeds is not None:
+            sp, ss, ns, keep = self._seed_arg(seeds, n, seed_stride)
+            if ns != n:
+                raise KoskError("seeds for %d proofs, secret keys for %d" % (ns, n))
+            return True, sp, ss, keep
+        if tapes is None:
+            return False, None, 0, None
+        if isinstance(tapes, int):
+            return False, C.c_void_p(tapes), self.tape_bytes, None
+        if len(tapes) != n:
+            raise KoskError("tapes for %d proofs, secret keys for %d" % (len(tapes), n))
+        for t in tapes:
+            if len(t) < self.tape_bytes:
+                raise KoskError("tape shorter than kosk_tape_bytes")
+        blob = b"".join(t[:self.tape_bytes] for t in tapes)
+        return False, C.c_char_p(blob), self.tape_bytes, blob
+
+    def stage_prover_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
+        """kosk_stage_prover_keys[_seeded]: witness and randomness of n existing keys resident for prove_resident(n).  tapes: list of
+        bytes, an int DEVICE pointer (kosk_tape_bytes apart) or None; seeds: see _seed_arg; neither: the handle's entropy mode.
+        Returns ok (list of bool)."""
+        sp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        seeded, rp, stride, _k2 = self._key_rand(tapes, seeds, n, seed_stride)
+        ok = C.create_string_buffer(n)
+        fn = lib.kosk_stage_prover_keys_seeded if seeded else lib.kosk_stage_prover_keys
+        self._chk(fn(self._h, n, sp, rp, stride, ok), "stage_prover_keys")
+        return [b == 1 for b in ok.raw[:n]]
+
+    def prove_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
+        """kosk_prove_keys[_seeded]_batch: one proof per existing key, any n.  Returns (proofs, ok); the image of a key with ok False is
+        all zero."""
+        sp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        seeded, rp, stride, _k2 = self._key_rand(tapes, seeds, n, seed_stride)
+        ok = C.create_string_buffer(n)
+        pi = C.create_string_buffer(self.proof_bytes * n)
+        fn = lib.kosk_prove_keys_seeded_batch if seeded else lib.kosk_prove_keys_batch
+        self._chk(fn(self._h, n, sp, rp, stride, pi, ok), "prove_keys")
+        return _cut(pi, self.proof_bytes, n), [b == 1 for b in ok.raw[:n]]
 
     PATH_IDS = ["hash_dma", "hash_plain", "table_gemm", "limb_gemm", "copy_direct", "copy_staged", "graph_replay", "digest_copy", "small_copy_kernel",
                 "fs_device", "fs_host", "tape_expand", "kem_enc", "kem_dec"]

@@ -1052,6 +1052,111 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
     GUARD_END
 }
 
+// ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----
+int kosk_witness_from_sk(kosk_ctx *ctx, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    return ctx->run(n, [&](Ctx &c, int first, int count) {
+        return witness_from_sk(c, count, sk + (size_t)first * P.sk_bytes, se_out ? se_out + (size_t)first * 2 * P.K * 256 : nullptr, ok + first);
+    });
+    GUARD_END
+}
+
+// the randomness of a proof for an existing key: the draws of prepare_randomness, prepare_range_proof and prove in the reference's order
+// and lengths (mlwe_prover.cpp:9, ss.cpp:5) at their places in the tape; the key generation's 64 bytes in front (kosk.cpp:12) are
+// neither drawn nor read
+static void draw_prover_tapes(const kosk_ctx *ctx, int n, std::vector<uint8_t> &drawn)
+{
+    const Params &P = ctx->c->P;
+    drawn.assign((size_t)n * P.tape_bytes, 0);
+    const Ctx &c0 = *ctx->c;
+    for (int b = 0; b < n; b++) {
+        uint8_t *tp = drawn.data() + (size_t)b * P.tape_bytes + 64;
+        auto draw = [&](size_t len) { if (c0.rb) c0.rb(c0.rb_user, tp, len); else os_randombytes(tp, len); tp += len; };
+        for (int i = 0; i < P.M; i++) draw(32);
+        for (int i = 0; i < P.nfresh; i++) draw(302);
+    }
+}
+static void resolve_for_keys(const kosk_ctx *ctx, int n, RandSrc &src)
+{
+    if (!src.seeded && !src.tapes) {
+        draw_prover_tapes(ctx, n, src.drawn);
+        src.tapes = src.drawn.data();
+        src.tape_stride = ctx->c->P.tape_bytes;
+    } else {
+        src.resolve(ctx, n);
+    }
+}
+static int bad_tape_stride(kosk_ctx *ctx, const char *fn)
+{
+    ctx->clear_err();
+    ctx->err = std::string(fn) + ": tape_stride is smaller than one tape (kosk_tape_bytes)";
+    ctx->c->err = ctx->err;
+    return -1;
+}
+static int stage_prover_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src, uint8_t *ok)
+{
+    const Params &P = ctx->c->P;
+    resolve_for_keys(ctx, n, src); // stateful callback: everything sequentially, in proof order
+    return ctx->run(n, [&](Ctx &c, int first, int count) {
+        return stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
+                                 src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first);
+    });
+}
+int kosk_stage_prover_keys(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
+    if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return stage_prover_keys_from(ctx, n, sk, src, ok);
+    GUARD_END
+}
+int kosk_stage_prover_keys_seeded(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return stage_prover_keys_from(ctx, n, sk, src, ok);
+    GUARD_END
+}
+static int prove_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src, uint8_t *pi, uint8_t *ok)
+{
+    const Params &P = ctx->c->P;
+    resolve_for_keys(ctx, n, src);
+    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
+    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        if (stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
+                              src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first)) return -1;
+        if (prove_resident(c, count)) return -1;
+        if (fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned)) return -1;
+        for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
+            if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
+        return 0;
+    });
+}
+int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *pi, uint8_t *ok)
+{
+    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return prove_keys_from(ctx, n, sk, src, pi, ok);
+    GUARD_END
+}
+int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok)
+{
+    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return prove_keys_from(ctx, n, sk, src, pi, ok);
+    GUARD_END
+}
+
 void *kosk_host_alloc(size_t bytes)
 {
     void *p = nullptr;

@@ -61,6 +61,7 @@ Ctx::~Ctx()
             if (e) (void)hipEventDestroy(e);
     if (ev_sync) (void)hipEventDestroy(ev_sync);
     kem_release(*this);
+    witness_release(*this);
     if (is_view) {
         if (h_err) (void)hipHostFree(h_err);
         // a view owns its events, host workers and compact staging; tables, workspace and the stream belong to the arena
@@ -528,6 +529,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.resident_pk_n = 0;
     c.keys_from_pk_n = 0;
     c.kem = nullptr;
+    c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     for (const Ctx::PerProof &pp : arena.per_proof) {
         char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
@@ -827,6 +829,80 @@ int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride,
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;
     finish_keygen_host(c, n, pk, sk);
+    c.phase_sec[PH_HOST_PRE] = now_sec() - t0;
+    return 0;
+}
+
+// ---- existing keys: the witness from the secret key (kosk_witness_kernels.hip) ----
+void witness_release(Ctx &c)
+{
+    if (c.d_wsk) (void)hipFree(c.d_wsk);
+    if (c.d_wok) (void)hipFree(c.d_wok);
+    if (c.h_wok) (void)hipHostFree(c.h_wok);
+    c.d_wsk = c.d_wok = c.h_wok = nullptr;
+    c.wit_cap = 0;
+}
+
+static int witness_ensure(Ctx &c, int n)
+{
+    if (c.wit_cap >= n) return 0;
+    if (c.wit_cap) {
+        HIPCHK(stream_sync(c));
+        witness_release(c);
+    }
+    auto body = [&]() -> int {
+        HIPCHK(dalloc(&c.d_wsk, (size_t)n * c.P.sk_bytes));
+        HIPCHK(dalloc(&c.d_wok, (size_t)n));
+        HIPCHK(halloc(&c.h_wok, (size_t)n));
+        return 0;
+    };
+    if (body()) { witness_release(c); return -1; }
+    c.wit_cap = n;
+    return 0;
+}
+
+int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
+{
+    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    if (!sk || !ok) { c.err = "sk records and the ok buffer are required"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    if (witness_ensure(c, n)) return -1;
+    const Params &P = c.P;
+    const int K = P.K;
+    HIPCHK(hipMemcpyAsync(c.d_wsk, sk, (size_t)n * P.sk_bytes, is_device_pointer(sk) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    // t-hat (12-bit fields as they stand) and A from the pk inside the record: sk = s-hat || pk || H(pk) || z.  Byte loads only: any stride
+    HIPCHK(launch_decode_pk(c.d_wsk + 384 * K, P.sk_bytes, c.d_t, c.d_A, c.key_stride, K, n, c.stream, c.xof_guard()));
+    WitnessArgs wa{};
+    wa.K = K; wa.sk = c.d_wsk; wa.sk_stride = P.sk_bytes; wa.A = c.d_A; wa.A_stride = c.key_stride; wa.t = c.d_t;
+    wa.se = c.d_se; wa.se_stride = c.se_stride; wa.pk = c.d_pk; wa.pk_stride = c.pk_stride; wa.ok = c.d_wok;
+    if (!witness_args_ok(wa)) { c.err = "internal: witness_args_ok() refuses the operands of the witness kernel"; return -1; }
+    HIPCHK(launch_witness_from_sk(wa, n, c.stream));
+    c.kg_on_host_pending = false;
+    c.note_pk_written(n); // d_pk holds these keys' bytes, d_A / d_t are their decodings
+    HIPCHK(hipMemcpyAsync(c.h_wok, c.d_wok, (size_t)n, hipMemcpyDeviceToHost, c.stream));
+    if (se_out) HIPCHK(hipMemcpyAsync(se_out, c.d_se, (size_t)n * c.se_stride * sizeof(int16_t), hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) { // gen_matrix block limit: no results, and d_A is not a decoding of anything
+        c.resident_pk_n = 0;
+        c.keys_from_pk_n = 0;
+        c.pk_epoch++;
+        return -1;
+    }
+    memcpy(ok, c.h_wok, (size_t)n);
+    return 0;
+}
+
+int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok)
+{
+    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    if (!sk || !ok) { c.err = "sk records and the ok buffer are required"; return -1; }
+    if (!tapes == !seeds) { c.err = "internal: exactly one of tapes / seeds"; return -1; }
+    if (tapes && tape_stride < c.P.tape_bytes) { c.err = "tape_stride smaller than kosk_tape_bytes"; return -1; }
+    if (seeds && seed_stride < SEED_BYTES) { c.err = "seed_stride smaller than KOSK_SEED_BYTES"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    const double t0 = now_sec();
+    if (seeds ? seed_tapes(c, n, seeds, seed_stride) : upload_tapes(c, n, tapes, tape_stride)) return -1;
+    if (witness_from_sk(c, n, sk, nullptr, ok)) return -1; // ends with the stream synchronised: the tapes are resident too
     c.phase_sec[PH_HOST_PRE] = now_sec() - t0;
     return 0;
 }

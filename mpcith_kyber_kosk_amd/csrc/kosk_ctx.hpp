@@ -327,6 +327,11 @@ struct Ctx {
     void prof_end(int id) { if (prof_on && !capturing) { (void)hipEventRecord(prof_ev[id][1], stream); prof_used[id] = true; } }
     void prof_collect(); // call after the stream has been synchronised
 
+    // witness recovery (witness_from_sk): the secret-key records of the largest call so far and their verdicts; allocated at the first
+    // such call and owned by this context like `kem`
+    int wit_cap = 0;
+    uint8_t *d_wsk = nullptr, *d_wok = nullptr, *h_wok = nullptr;
+
     ~Ctx();
 };
 
@@ -420,6 +425,14 @@ void draw_seeds(const Ctx &c, int n, uint8_t *out);
 int upload_tapes(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride);
 int issue_keygen(Ctx &c, int n, bool sampled = false);
 void finish_keygen_host(Ctx &c, int n, uint8_t *pk, uint8_t *sk);
+// Existing keys (kosk_witness_kernels.hip): n <= call_cap secret-key records (host or device memory) -> A, s, e and the embedded pk bytes
+// resident exactly as a key generation leaves them (d_A, d_t, d_se, d_pk; note_pk_written), s and e all zero where ok[b] = 0 (a
+// coefficient outside [-eta1, eta1]).  se_out (host, may be nullptr): n x 2 K x 256 int16, s then e.  Synchronised.
+int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok);
+void witness_release(Ctx &c);
+// the counterpart of stage_prover_inputs for such keys: tapes (exactly one of tapes / seeds; the first 64 bytes of a tape, the key
+// generation's seed, are not read) + witness resident for prove_resident
+int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok);
 // everything from resident inputs to resident proof images (two host Fiat-Shamir round trips)
 enum FrontPart { FRONT_FULL = 0, FRONT_RANDOMNESS, FRONT_RANGE, FRONT_ONLINE };
 int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen = false);

@@ -274,6 +274,25 @@ hipError_t launch_keygen_pack(const int16_t *A, size_t A_stride, const int16_t *
 hipError_t launch_decode_pk(const uint8_t *pk, size_t pk_stride, uint16_t *t_out, int16_t *A, size_t A_stride, int K, int n, hipStream_t st,
                             XofGuard xof = XofGuard());
 
+// ---- witness recovery (kosk_witness_kernels.hip): one workgroup per secret-key record; A and t as launch_decode_pk leaves them for
+// the pk embedded in the record (t: the 12-bit fields as they stand).  se: s then e, centred int16, zero where ok = 0; pk: the
+// embedded pk bytes.  witness_args_ok: the operands take the kernel's 16-byte accesses; launch only operands that pass it
+struct WitnessArgs {
+    int K;
+    const uint8_t *sk;
+    size_t sk_stride;   // bytes
+    const int16_t *A;
+    size_t A_stride;    // int16 per key
+    const uint16_t *t;  // [n][K][256]
+    int16_t *se;
+    size_t se_stride;   // int16 per key
+    uint8_t *pk;
+    size_t pk_stride;   // bytes
+    uint8_t *ok;        // [n]
+};
+bool witness_args_ok(const WitnessArgs &a);
+hipError_t launch_witness_from_sk(const WitnessArgs &a, int n, hipStream_t st);
+
 // the LDS-DMA staged kernel runs where the layout allows it (aligned rows), else the plain kernel; *variant: bit 0 the DMA kernel ran
 hipError_t launch_commit_hash(const HashArgs &a, int ngroups, int K, bool view, hipStream_t st, int *variant = nullptr);
 hipError_t launch_sha3_msgs(const uint8_t *in, size_t in_stride, int len, uint8_t *out, size_t out_stride,
