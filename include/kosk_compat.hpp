@@ -185,6 +185,28 @@ inline bool kyber_kosk_prove_key(const kyber_keypair *keypair, uint8_t *pi)
     return ok == 1;
 }
 
+/* ---- context-bound proofs (no reference counterpart; format kosk-bind-v1): kyber_verifiable_keygen /
+ * kyber_kosk_verify with the proof bound to the public key and the caller's 32-byte context.  The process-wide handle is armed for the
+ * call and disarmed again, so the unbound functions above are untouched by these. ---- */
+inline void kyber_verifiable_keygen_bound(kyber_keypair *keypair, uint8_t *pi, const uint8_t context[32])
+{
+    kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 1, context, 32), "kyber_verifiable_keygen_bound");
+    const int rc = kosk_verifiable_keygen_batch(kosk_compat::ctx(), 1, nullptr, 0, keypair->pk, keypair->sk, pi);
+    if (rc) fprintf(stderr, "kyber_verifiable_keygen_bound: %s\n", kosk_last_error(kosk_compat::ctx()));
+    kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 0, nullptr, 0), "kyber_verifiable_keygen_bound");
+    if (rc) abort();
+}
+inline bool kyber_kosk_verify_bound(const uint8_t *pi, const uint8_t *pk, const uint8_t context[32])
+{
+    uint8_t ok = 0;
+    kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 1, context, 32), "kyber_kosk_verify_bound");
+    const int rc = kosk_verify_batch(kosk_compat::ctx(), 1, pi, pk, &ok);
+    if (rc) fprintf(stderr, "kyber_kosk_verify_bound: %s\n", kosk_last_error(kosk_compat::ctx()));
+    kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 0, nullptr, 0), "kyber_kosk_verify_bound");
+    if (rc) abort();
+    return ok == 1;
+}
+
 /* ---- second-level entry points, used directly by main.cpp:21-47 ---- */
 /* mlwe_prover.hpp:77 */
 inline void prepare_randomness(mpcith_randomness *rand)

@@ -398,6 +398,34 @@ int kosk_host_sha3_256_multi(uint8_t *out, const uint8_t *in, size_t in_stride, 
  * which = 0: share_coeff_ddeg [1303][407], 1: recon_coeff_ddeg [256][407], 2: recon_coeff_2ddeg [256][813] */
 int kosk_lagrange_table(int which, uint16_t *out);
 
+/* ---- context-bound proofs, format kosk-bind-v1 (no reference counterpart) ----
+ * For Kyber parameter K, public key bytes pk and a caller's 32-byte context (a hash of an identity, nonce or message):
+ *   B  = SHA3-256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || SHA3-256(pk) || context)            84 bytes
+ *   h1 = SHA3-256(Tcomm[0..1454) || B)        ch = SHA3-256(view_digest[0..1454) || B)
+ * and everything else as in the reference: alpha from h1, I from ch, the proof image and the tape consumption.  A bound proof verifies
+ * only under the pk and the context it was made for. */
+/* B on the host (no handle) */
+int kosk_bind_value(int kyber_k, const uint8_t *pk, const uint8_t context[32], uint8_t out[32]);
+/* B for n proofs on the device (k_bind_values): pk = n records of kosk_pk_bytes, contexts = n records context_stride >= 32 apart, each
+ * host or device memory; d_out = n x 32 bytes of DEVICE memory, 8-byte aligned; nothing outside them is written.  Synchronised on return. */
+int kosk_bind_device(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *contexts, size_t context_stride, uint8_t *d_out);
+/* kosk_fs_alpha / kosk_fs_opened with the binding value hashed behind the table */
+int kosk_fs_alpha_bound(int kyber_k, const uint8_t *tcomm_all, const uint8_t bind[32], uint16_t *alpha);
+int kosk_fs_opened_bound(const uint8_t *digests_all, const uint8_t bind[32], uint16_t *I, uint16_t *rest);
+/* kosk_fs_alpha_device / kosk_fs_opened_device with d_bind = n x 32 bytes (8-byte aligned), proof b's table followed by d_bind[b] */
+int kosk_fs_alpha_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_stride, int n, const uint8_t *d_bind, uint16_t *d_alpha, uint8_t *d_h1);
+int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_stride, int n, const uint8_t *d_bind,
+                                uint16_t *d_sel, uint16_t *d_rest, int sel_stride, uint8_t *d_ch);
+/* ARM the handle with n contexts (host or device memory, context_stride >= 32 apart; the handle keeps its own copy).  From then on every
+ * first-level entry point that makes or checks proofs on this handle makes or checks BOUND proofs, position b of a call (of the whole call,
+ * when it is chunked) under context b: kosk_verifiable_keygen_* (tape, seeded, compact, resident), kosk_prove_resident after
+ * kosk_stage_prover_inputs* / kosk_stage_prover_keys*, kosk_prove_keys_*, kosk_verify_batch[_compact], kosk_verify_resident after
+ * kosk_stage_verifier_inputs*, kosk_verify_resident_pk.  Refused with -1 and a text, nothing started: a call of more proofs than armed
+ * contexts; kosk_verify_inst / kosk_prove_prepared (no pk bytes exist there); context_stride < 32.  kosk_set_contexts(ctx, 0, NULL, 0)
+ * disarms; a handle never armed, or disarmed, behaves exactly as before.  A cohort member that is armed keeps its calls out of merged
+ * runs.  Not to be called while another thread is inside a call on this handle. */
+int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t context_stride);
+
 #ifdef __cplusplus
 }
 #endif

@@ -124,6 +124,18 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_witness_from_sk")):
         sig.update(keyproof)
+    # context-bound proofs (kosk-bind-v1); optional under the same rule (and only then)
+    bound = {
+        "kosk_bind_value": (C.c_int, [C.c_int, vp, vp, vp]),
+        "kosk_bind_device": (C.c_int, [vp, C.c_int, vp, vp, sz, vp]),
+        "kosk_fs_alpha_bound": (C.c_int, [C.c_int, vp, vp, vp]),
+        "kosk_fs_opened_bound": (C.c_int, [vp, vp, vp, vp]),
+        "kosk_fs_alpha_bound_device": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, vp]),
+        "kosk_fs_opened_bound_device": (C.c_int, [vp, vp, sz, C.c_int, vp, vp, vp, C.c_int, vp]),
+        "kosk_set_contexts": (C.c_int, [vp, C.c_int, vp, sz]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_set_contexts")):
+        sig.update(bound)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -147,7 +159,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_verifiable_keygen_seeded_batch_compact", "kosk_verifiable_keygen_seeded_resident", "kosk_stage_prover_inputs_seeded",
            "kosk_ct_bytes", "kosk_kem_enc_batch", "kosk_kem_dec_batch", "kosk_kem_enc_verified",
            "kosk_witness_from_sk", "kosk_stage_prover_keys", "kosk_stage_prover_keys_seeded", "kosk_prove_keys_batch",
-           "kosk_prove_keys_seeded_batch"]
+           "kosk_prove_keys_seeded_batch",
+           "kosk_bind_value", "kosk_bind_device", "kosk_fs_alpha_bound", "kosk_fs_opened_bound", "kosk_fs_alpha_bound_device",
+           "kosk_fs_opened_bound_device", "kosk_set_contexts"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -179,6 +193,20 @@ def sk_bytes(k): return lib.kosk_sk_bytes(k)
 def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
 def ct_bytes(k): return lib.kosk_ct_bytes(k)
+
+
+CONTEXT_BYTES = 32
+
+
+def bind_value(k, pk, context):
+    """B of format kosk-bind-v1 for one public key and one 32-byte context, on the host (kosk_bind_value)"""
+    pk, context = bytes(pk), bytes(context)
+    if len(pk) != pk_bytes(k) or len(context) != CONTEXT_BYTES:
+        raise KoskError("bind_value: a public key of kosk_pk_bytes and a context of %d bytes" % CONTEXT_BYTES)
+    out = C.create_string_buffer(32)
+    if lib.kosk_bind_value(k, C.c_char_p(pk), C.c_char_p(context), out):
+        raise KoskError("kosk_bind_value: kyber_k outside 2..4")
+    return out.raw
 
 
 def tape_from_seed(k, seed):
@@ -314,6 +342,32 @@ class Kosk:
         """what a call without tapes draws: ENTROPY_TAPE (default) the reference's sequence, a whole tape per proof; ENTROPY_SEED one
         32-byte seed per proof, expanded on the device (kosk_set_entropy)"""
         self._chk(lib.kosk_set_entropy(self._h, int(mode)), "set_entropy")
+
+    def set_contexts(self, contexts, n=None, stride=None):
+        """arm the handle (kosk_set_contexts): from now on position b of every proving / verifying call uses context b.
+        contexts: list of 32-byte bytes, or an int DEVICE pointer (with n, and stride if not 32)"""
+        if isinstance(contexts, int):
+            if n is None:
+                raise KoskError("a device context pointer needs n")
+            self._chk(lib.kosk_set_contexts(self._h, n, C.c_void_p(contexts), CONTEXT_BYTES if stride is None else stride), "set_contexts")
+            return
+        for c_ in contexts:
+            if len(c_) != CONTEXT_BYTES:
+                raise KoskError("a context has %d bytes" % CONTEXT_BYTES)
+        st = CONTEXT_BYTES if stride is None else stride
+        n = len(contexts) if n is None else n
+        blob = b"".join(bytes(c_) + bytes(max(st - CONTEXT_BYTES, 0)) for c_ in contexts)
+        self._chk(lib.kosk_set_contexts(self._h, n, C.c_char_p(blob), st), "set_contexts")
+
+    def clear_contexts(self):
+        """disarm the handle: it behaves exactly as one that was never armed"""
+        self._chk(lib.kosk_set_contexts(self._h, 0, None, 0), "clear_contexts")
+
+    def bind_device(self, n, pk, contexts, d_out, context_stride=CONTEXT_BYTES):
+        """B for n proofs into device memory d_out (int pointer).  pk / contexts: bytes (host) or int device pointers"""
+        a = C.c_void_p(pk) if isinstance(pk, int) else C.c_char_p(bytes(pk))
+        b = C.c_void_p(contexts) if isinstance(contexts, int) else C.c_char_p(bytes(contexts))
+        self._chk(lib.kosk_bind_device(self._h, n, a, b, context_stride, d_out), "bind_device")
 
     def _seed_arg(self, seeds, n, seed_stride):
         """seeds: list of 32-byte bytes, an int DEVICE pointer (with n and seed_stride), or True (the library draws one 32-byte seed
@@ -718,6 +772,12 @@ class Kosk:
 
     def fs_opened_device(self, d_tables, table_stride, n, d_sel, d_rest, sel_stride, d_ch=None):
         self._chk(lib.kosk_fs_opened_device(self._h, d_tables, table_stride, n, d_sel, d_rest, sel_stride, d_ch), "fs_opened_device")
+
+    def fs_alpha_bound_device(self, d_tables, table_stride, n, d_bind, d_alpha, d_h1=None):
+        self._chk(lib.kosk_fs_alpha_bound_device(self._h, d_tables, table_stride, n, d_bind, d_alpha, d_h1), "fs_alpha_bound_device")
+
+    def fs_opened_bound_device(self, d_tables, table_stride, n, d_bind, d_sel, d_rest, sel_stride, d_ch=None):
+        self._chk(lib.kosk_fs_opened_bound_device(self._h, d_tables, table_stride, n, d_bind, d_sel, d_rest, sel_stride, d_ch), "fs_opened_bound_device")
 
     def shake256_batch(self, d_in, in_stride, inlen, d_out, outlen, n):
         self._chk(lib.kosk_shake256_batch(self._h, d_in, in_stride, inlen, d_out, outlen, n), "shake256_batch")

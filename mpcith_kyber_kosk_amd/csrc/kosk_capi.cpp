@@ -65,10 +65,21 @@ struct kosk_ctx {
     unsigned long verify_epoch = 0;
     int verify_keys = 0;
     bool hooks_unmerged = false; // kosk_options::hooks_unmerged: with a round hook set, this handle's resident calls run on their own
+    // kosk_set_contexts (kosk-bind-v1): the handle's own copy of the armed contexts in HBM, 32 bytes each; every sub-context points at it
+    uint8_t *d_contexts = nullptr;
+    int armed = 0;
+    void disarm()
+    {
+        for (Ctx *x : sub) { x->bind_ctx = nullptr; x->bind_n = 0; x->bind_first = 0; }
+        if (d_contexts) (void)hipFree(d_contexts);
+        d_contexts = nullptr;
+        armed = 0;
+    }
 
     ~kosk_ctx()
     {
         lanes.lanes.clear(); // join the lane threads before their sub-contexts go
+        disarm();
         for (Ctx *x : sub) delete x;
         if (cohort) {
             std::lock_guard<std::mutex> lk(g_cohort_mu);
@@ -264,6 +275,22 @@ struct RandSrc {
         return kg;
     }
 };
+// an armed handle (kosk_set_contexts): a call of more proofs than contexts, or one that has no public key bytes to bind, is refused whole
+static int armed_refuse(kosk_ctx *ctx, const char *fn, const char *why)
+{
+    ctx->clear_err();
+    ctx->err = std::string(fn) + ": " + why;
+    ctx->c->err = ctx->err;
+    return -1;
+}
+#define ARMED_CHECK(ctx, n) \
+    if ((ctx)->armed && (n) > (ctx)->armed) return armed_refuse(ctx, __func__, "the handle is armed with fewer contexts than this call has proofs (kosk_set_contexts)")
+// proofs [first, first + count) of the caller's call on sub-context c: position b of the call uses context b
+static int prove_at(Ctx &c, int first, int count, const KeygenIn *kg = nullptr)
+{
+    c.bind_first = first;
+    return prove_resident(c, count, false, kg);
+}
 // seeded entry points: seed_stride below one seed fails the call before anything is started
 static int bad_seed_stride(kosk_ctx *ctx, const char *fn)
 {
@@ -434,6 +461,28 @@ int kosk_set_randombytes(kosk_ctx *ctx, kosk_randombytes_fn fn, void *user)
     return 0;
 }
 
+int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t context_stride)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (n == 0) { ctx->disarm(); return 0; }
+    if (n < 0 || !contexts) return armed_refuse(ctx, __func__, "n contexts need n >= 1 and a pointer (n = 0 disarms)");
+    if (context_stride < 32) return armed_refuse(ctx, __func__, "context_stride is smaller than one context (32 bytes)");
+    Ctx &c = *ctx->c;
+    HIPCHK_C(hipSetDevice(c.device));
+    uint8_t *d = nullptr;
+    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&d), (size_t)n * 32));
+    const hipError_t e = hipMemcpy2D(d, 32, contexts, context_stride, 32, (size_t)n, is_device_pointer(contexts) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); HIPCHK_C(e); }
+    ctx->disarm();
+    ctx->d_contexts = d;
+    ctx->armed = n;
+    for (Ctx *x : ctx->sub) { x->bind_ctx = d; x->bind_n = n; x->bind_first = 0; }
+    return 0;
+    GUARD_END
+}
+
 int kosk_set_entropy(kosk_ctx *ctx, int mode)
 {
     if (!ctx) return -1;
@@ -471,8 +520,9 @@ int kosk_stage_prover_inputs_seeded(kosk_ctx *ctx, int n, const uint8_t *seeds, 
 int kosk_prove_resident(kosk_ctx *ctx, int n)
 {
     if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     GUARD(ctx)
-    return ctx->run(n, [&](Ctx &c, int, int count) { return prove_resident(c, count); });
+    return ctx->run(n, [&](Ctx &c, int first, int count) { return prove_at(c, first, count); });
     GUARD_END
 }
 int kosk_fetch_proofs(kosk_ctx *ctx, int n, uint8_t *pi)
@@ -497,6 +547,7 @@ int kosk_stage_verifier_inputs(kosk_ctx *ctx, int n, const uint8_t *pi, const ui
 // verify `count` resident proofs of sub-context c and file their fail masks at the caller's proof index `first`
 static int verify_into(kosk_ctx *ctx, Ctx &c, int first, int count, uint8_t *ok, int pk_mode, const uint8_t *pk)
 {
+    c.bind_first = first; // an armed handle: position b of the call is checked under context b
     if (verify_resident(c, count, ok + first, pk_mode, pk)) return -1;
     memcpy(ctx->masks.data() + first, c.h_fail, sizeof(uint32_t) * (size_t)count);
     return 0;
@@ -518,6 +569,7 @@ static void note_verified_keys(kosk_ctx *ctx, int kind)
 int kosk_verify_resident(kosk_ctx *ctx, int n, uint8_t *ok)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     GUARD(ctx)
     reset_masks(ctx, n);
     if (ctx->run(n, [&](Ctx &c, int first, int count) { return verify_into(ctx, c, first, count, ok, 0, nullptr); })) return -1;
@@ -588,6 +640,8 @@ static int combined_keygen(kosk_ctx *h, int n, const KeygenCall &call)
     // drawn by its own caller before it got here, and the entropy source is not part of what makes calls mergeable)
     r.kind = (call.tapes || call.seeds) ? CK_KEYGEN : CK_ALONE;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE; // the hook must fire on this caller's own thread (kosk_options::hooks_unmerged)
+    if (h->armed) r.kind = CK_ALONE; // bound proofs (kosk_set_contexts) stay out of merged runs: binding is not part of what makes calls mergeable
+    h->c->bind_first = 0;
     r.n = n;
     r.full = n == co.per;
     r.args = const_cast<KeygenCall *>(&call);
@@ -636,6 +690,8 @@ static int combined_verify(kosk_ctx *h, int n, const VerifyCall &call)
     CombineReq r;
     r.kind = call.pk ? CK_VERIFY_PK_GIVEN : CK_VERIFY_PK_RESIDENT;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE;
+    if (h->armed) r.kind = CK_ALONE; // as in combined_keygen
+    h->c->bind_first = 0;
     r.n = n;
     r.full = n == co.per;
     r.args = const_cast<VerifyCall *>(&call);
@@ -688,12 +744,13 @@ static int keygen_resident_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk,
     const Params &P = ctx->c->P;
     return ctx->run(n, [&](Ctx &c, int first, int count) {
         const KeygenIn kg = src.part(P, first, pk, sk);
-        return prove_resident(c, count, false, &kg);
+        return prove_at(c, first, count, &kg);
     });
 }
 int kosk_verifiable_keygen_resident(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     GUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return keygen_resident_from(ctx, n, src, pk, sk);
@@ -702,6 +759,7 @@ int kosk_verifiable_keygen_resident(kosk_ctx *ctx, int n, const uint8_t *tapes, 
 int kosk_verifiable_keygen_seeded_resident(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     GUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
@@ -720,6 +778,7 @@ int kosk_tape_expand_device(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t s
 int kosk_verify_resident_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *ok)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     GUARD(ctx)
     if (ctx->cohort) return combined_verify(ctx, n, VerifyCall{pk, ok});
     const Params &P = ctx->c->P;
@@ -760,7 +819,7 @@ static int keygen_batch_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, ui
     const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         const KeygenIn kg = src.part(P, first, pk, sk);
-        if (prove_resident(c, count, false, &kg)) return -1;
+        if (prove_at(c, first, count, &kg)) return -1;
         return fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned);
     });
 }
@@ -768,6 +827,7 @@ int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, siz
                                  uint8_t *pk, uint8_t *sk, uint8_t *pi)
 {
     if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (n == 0) return 0;
     GUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
@@ -777,6 +837,7 @@ int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, siz
 int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi)
 {
     if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     if (n == 0) return 0;
     GUARD(ctx)
@@ -788,6 +849,7 @@ int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *see
 int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk, uint8_t *ok)
 {
     if (!ctx || n < 0 || !pi || !pk || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (n == 0) { ctx->masks_n = 0; return 0; }
     GUARD(ctx)
     const Params &P = ctx->c->P;
@@ -818,7 +880,7 @@ static int keygen_batch_compact_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t
     const bool pinned = ctx->c->host_register && span_is_pinned(out, (size_t)n * cb);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         const KeygenIn kg = src.part(P, first, pk, sk);
-        if (prove_resident(c, count, false, &kg)) return -1;
+        if (prove_at(c, first, count, &kg)) return -1;
         return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned);
     });
 }
@@ -826,6 +888,7 @@ int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *ta
                                          uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
     if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (n == 0) return 0;
     GUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
@@ -836,6 +899,7 @@ int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint
                                                 uint8_t *out)
 {
     if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     if (n == 0) return 0;
     GUARD(ctx)
@@ -846,6 +910,7 @@ int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint
 int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
 {
     if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (n == 0) { ctx->masks_n = 0; return 0; }
     GUARD(ctx)
     const Params &P = ctx->c->P;
@@ -900,6 +965,7 @@ int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t
                         const uint8_t *tapes, size_t tape_stride, uint8_t *pi)
 {
     if (!ctx || n < 0 || !inst || !rand_in || !range_in || !pi) return bad_args(ctx, __func__);
+    if (ctx->armed) return armed_refuse(ctx, __func__, "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind");
     GUARD(ctx)
     Ctx &c = *ctx->c;
     ctx->clear_err();
@@ -916,6 +982,7 @@ int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t
 int kosk_verify_inst(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *inst, uint8_t *ok)
 {
     if (!ctx || n < 0 || !pi || !inst || !ok) return bad_args(ctx, __func__);
+    if (ctx->armed) return armed_refuse(ctx, __func__, "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind");
     GUARD(ctx)
     Ctx &c = *ctx->c;
     ctx->clear_err();
@@ -1131,7 +1198,7 @@ static int prove_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         if (stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
                               src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first)) return -1;
-        if (prove_resident(c, count)) return -1;
+        if (prove_at(c, first, count)) return -1;
         if (fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned)) return -1;
         for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
             if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
@@ -1141,6 +1208,7 @@ static int prove_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src
 int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *pi, uint8_t *ok)
 {
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
     GUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
@@ -1150,6 +1218,7 @@ int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t
 int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok)
 {
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     GUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
@@ -1366,6 +1435,61 @@ int kosk_fs_opened_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_s
     GUARD_END
 }
 
+// ---- kosk-bind-v1: the binding values and the bound chains as kernel-level entry points
+int kosk_bind_device(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *contexts, size_t context_stride, uint8_t *d_out)
+{
+    if (!ctx || n < 1 || !pk || !contexts || !d_out || context_stride < 32 || (reinterpret_cast<uintptr_t>(d_out) & 7)) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    Ctx &c = *ctx->c;
+    ctx->clear_err();
+    HIPCHK_C(hipSetDevice(c.device));
+    // pk (n records of pk_bytes) and contexts, host or device memory, into aligned device staging: the kernel loads 8 bytes at a time
+    const size_t pkb = c.P.pk_bytes;
+    uint8_t *stage = nullptr;
+    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&stage), (size_t)n * (pkb + 32)));
+    struct Free { uint8_t *p; ~Free() { (void)hipFree(p); } } fr{stage};
+    uint8_t *d_ctx = stage + (size_t)n * pkb;
+    HIPCHK_C(hipMemcpyAsync(stage, pk, (size_t)n * pkb, is_device_pointer(pk) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    HIPCHK_C(hipMemcpy2DAsync(d_ctx, 32, contexts, context_stride, 32, (size_t)n, is_device_pointer(contexts) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    BindArgs ba{};
+    ba.pk = stage; ba.pk_stride = pkb; ba.pk_bytes = (int)pkb; ba.K = c.P.K; ba.contexts = d_ctx; ba.out = d_out;
+    HIPCHK_C(launch_bind_values(ba, n, c.stream));
+    HIPCHK_C(stream_sync(c)); // the staging buffer goes with the call
+    return 0;
+    GUARD_END
+}
+int kosk_fs_alpha_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_stride, int n, const uint8_t *d_bind, uint16_t *d_alpha, uint8_t *d_h1)
+{
+    if (!ctx || !d_tables || !d_alpha || !d_bind || n < 1 || (reinterpret_cast<uintptr_t>(d_tables) & 7) || (table_stride & 7) ||
+        (reinterpret_cast<uintptr_t>(d_bind) & 7)) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    Ctx &c = *ctx->c;
+    ctx->clear_err();
+    HIPCHK_C(hipSetDevice(c.device));
+    FsArgs fa{};
+    fa.in = d_tables; fa.in_stride = table_stride; fa.len = NPARTY * 32; fa.out_digest = d_h1;
+    fa.alpha = d_alpha; fa.alpha_stride = 80; fa.J = c.P.J; fa.bind = d_bind;
+    HIPCHK_C(launch_fs_chain(fa, FS_ALPHA, n, c.stream));
+    return 0;
+    GUARD_END
+}
+int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_stride, int n, const uint8_t *d_bind, uint16_t *d_sel, uint16_t *d_rest,
+                                int sel_stride, uint8_t *d_ch)
+{
+    if (!ctx || !d_tables || !d_sel || !d_rest || !d_bind || n < 1 || sel_stride < NREST || sel_stride < SEL_OPOS + NOPEN ||
+        (reinterpret_cast<uintptr_t>(d_tables) & 7) || (table_stride & 7) || (reinterpret_cast<uintptr_t>(d_bind) & 7)) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    Ctx &c = *ctx->c;
+    ctx->clear_err();
+    HIPCHK_C(hipSetDevice(c.device));
+    FsArgs fa{};
+    fa.in = d_tables; fa.in_stride = table_stride; fa.len = NPARTY * 32; fa.out_digest = d_ch;
+    fa.I = d_sel; fa.rest = d_rest; fa.sel_stride = sel_stride; fa.bind = d_bind;
+    HIPCHK_C(launch_fs_chain(fa, FS_OPENED, n, c.stream));
+    return 0;
+    GUARD_END
+}
+
 int kosk_commit_hash_lanes(kosk_ctx *ctx, const uint16_t *d_rows, size_t row_stride, int n_lanes,
                            const uint8_t *d_prefix, int with_prefix, uint8_t *d_out)
 {
@@ -1484,6 +1608,33 @@ int kosk_fs_opened(const uint8_t *digests_all, uint16_t *I, uint16_t *rest)
     if (!digests_all || !I || !rest) return -1;
     return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
     fs_opened(digests_all, I, rest);
+    return 0;
+    GUARD_END
+}
+
+int kosk_bind_value(int kyber_k, const uint8_t *pk, const uint8_t context[32], uint8_t out[32])
+{
+    Params P;
+    if (!make_params(kyber_k, P) || !pk || !context || !out) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    bind_value(P, pk, context, out);
+    return 0;
+    GUARD_END
+}
+int kosk_fs_alpha_bound(int kyber_k, const uint8_t *tcomm_all, const uint8_t bind[32], uint16_t *alpha)
+{
+    Params P;
+    if (!make_params(kyber_k, P) || !tcomm_all || !bind || !alpha) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    fs_alpha(P, tcomm_all, alpha, bind);
+    return 0;
+    GUARD_END
+}
+int kosk_fs_opened_bound(const uint8_t *digests_all, const uint8_t bind[32], uint16_t *I, uint16_t *rest)
+{
+    if (!digests_all || !bind || !I || !rest) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    fs_opened(digests_all, I, rest, bind);
     return 0;
     GUARD_END
 }

@@ -79,10 +79,10 @@ Ctx::~Ctx()
     void *dev[] = {t_expand.dfrag, t_recon_d.dfrag, t_recon_2d.dfrag, d_fresh_rows, d_gemm1_rows, d_gemm2_rows, d_off, d_fields, d_asm_groups, d_asm_elems,
                    d_rowtab, d_P, d_tape, d_seedbuf, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_coef, d_lin_rows,
                    d_gather, d_gather2, d_O, d_w, d_ell, d_sec, d_sec_u1, d_sec_u2, d_fail, d_inv, d_invlimb, d_vfields,
-                   d_vrowtab, d_rows_bg, d_rows_isrc, d_rows_idst, d_rows_u, d_fact, d_invfact, d_node_of, d_isort, d_hrange, d_odig};
+                   d_vrowtab, d_rows_bg, d_rows_isrc, d_rows_idst, d_rows_u, d_fact, d_invfact, d_node_of, d_isort, d_hrange, d_odig, d_bind};
     for (void *p : dev)
         if (p) (void)hipFree(p);
-    void *host[] = {h_err, h_tape, h_seedbuf, h_dig, h_dig2, h_proof, h_alpha, h_I, h_fail, h_Iimg, h_kg, h_odig};
+    void *host[] = {h_err, h_tape, h_seedbuf, h_dig, h_dig2, h_proof, h_alpha, h_I, h_fail, h_Iimg, h_kg, h_odig, h_bind};
     for (void *p : host)
         if (p) (void)hipHostFree(p);
     if (d_compact) (void)hipFree(d_compact);
@@ -131,6 +131,28 @@ int device_error_check(Ctx &c)
                                       "probability < 2^-300 with the default limit of 32 blocks): no result was produced"
                                     : "a kernel reported an internal error";
     return -1;
+}
+
+int bind_check(Ctx &c, int n)
+{
+    if (c.bind_n > 0 && (c.bind_first < 0 || c.bind_first + n > c.bind_n)) {
+        c.err = "the handle is armed with fewer contexts than this call has proofs (kosk_set_contexts)";
+        return -1;
+    }
+    return 0;
+}
+
+int issue_bind_values(Ctx &c, int n)
+{
+    if (c.bind_n <= 0) return 0;
+    if (bind_check(c, n)) return -1;
+    BindArgs ba{};
+    ba.pk = c.d_pk; ba.pk_stride = c.pk_stride; ba.pk_bytes = (int)c.P.pk_bytes; ba.K = c.P.K;
+    ba.contexts = c.bind_ctx + (size_t)c.bind_first * 32;
+    ba.out = c.d_bind;
+    HIPCHK(launch_bind_values(ba, n, c.stream));
+    if (!c.fs_device) HIPCHK(copy_small(c, c.h_bind, 0, c.d_bind, 0, (size_t)n * 32, 1, hipMemcpyDeviceToHost, c.stream));
+    return 0;
 }
 
 hipError_t copy_round_table(Ctx &c, uint8_t *h_dst, const uint8_t *d_src, int n)
@@ -477,6 +499,8 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         HIPCHK(dev(&c.d_pwT, (size_t)MAXM * 80));
         HIPCHK(dev(&c.d_coef, 2 * (size_t)8 * 2 * 2048));
         HIPCHK(dev(&c.d_fail, 1));
+        HIPCHK(dev(&c.d_bind, 32));
+        HIPCHK(host(&c.h_bind, 32));
         HIPCHK(host(&c.h_tape, c.tape_stride));
         HIPCHK(host(&c.h_seedbuf, SEED_BYTES));
         HIPCHK(host(&c.h_dig, (size_t)NPARTY * 32));
@@ -531,6 +555,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.kem = nullptr;
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
+    c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
     for (const Ctx::PerProof &pp : arena.per_proof) {
         char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
         *reinterpret_cast<char **>(reinterpret_cast<char *>(&c) + pp.field_off) = base ? base + (size_t)first * pp.stride_bytes : nullptr;
@@ -956,6 +981,11 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         if (!s->pk || !s->sk) { c.err = "pk / sk output buffers are required"; return -1; }
     if (!keygen && !c.tape_cur) { c.err = "no resident prover inputs: call kosk_stage_prover_inputs first"; return -1; }
     if (!keygen) c.tape_segs.count = 0;
+    const bool bound = c.bind_n > 0; // kosk-bind-v1: B of every proof follows both digest tables into their hashes
+    if (bound && online_only) { c.err = "an armed handle (kosk_set_contexts) cannot prove from prepared inputs: there are no public key bytes to bind"; return -1; }
+    if (bound && keygen && (keygen->next || (keygen->count && keygen->count != n))) { c.err = "internal: an armed handle's call in a merged run"; return -1; }
+    if (bind_check(c, n)) return -1;
+    if (bound && !keygen && c.resident_pk_n < n) { c.err = "no resident public keys to bind the proofs to"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     const Params &P = c.P;
     const RowMap &rm = c.rm;
@@ -985,12 +1015,14 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         if (!c.capturing) c.path_n[PATH_DIGEST_COPY]++;
         return 0;
     }, c.tape_cur, c.tape_cur_stride)) return -1; // the tape pointer is baked into the captured launch: part of the graph's key
+    if (issue_bind_values(c, n)) return -1; // the pk bytes are in d_pk (this call's key generation, or the staging call); a plain launch, never captured
     HIPCHK(hipEventRecord(c.ev, st)); // the Tcomm digests are on the host (device Fiat-Shamir: complete in HBM) once this event has passed
     if (c.fs_device) {
         // ---- Fiat-Shamir round 1 on the device: h1 = sha3_256(Tcomm[0..N)), alpha = BE16(PRF(h1, 1)) % q, one wave per proof   :130-153
         FsArgs fa{};
         fa.in = c.d_dig1; fa.in_stride = (size_t)NPARTY * 32; fa.len = NPARTY * 32;
         fa.alpha = c.d_alpha; fa.alpha_stride = 80; fa.J = P.J;
+        fa.bind = bound ? c.d_bind : nullptr;
         c.prof_begin(PR_FS_ALPHA, n);
         HIPCHK(launch_fs_chain(fa, FS_ALPHA, n, st));
         c.prof_end(PR_FS_ALPHA);
@@ -1045,7 +1077,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     // ---- Fiat-Shamir round 1 on the host
     if (keygen && !keys_done) finish_keygen_segs(c, n, *keygen);
     if (!c.fs_device) {
-        fs_alpha_batch(P, n, c.h_dig, (size_t)NPARTY * 32, c.h_alpha, 80, c.nthreads, c.pool);
+        fs_alpha_batch(P, n, c.h_dig, (size_t)NPARTY * 32, c.h_alpha, 80, c.nthreads, c.pool, nullptr, bound ? c.h_bind : nullptr);
         c.path_n[PATH_FS_HOST]++;
     }
     t1 = now_sec(); c.phase_sec[PH_FS_ALPHA] = t1 - t0; t0 = t1;
@@ -1077,6 +1109,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         FsArgs fa{};
         fa.in = c.d_dig2; fa.in_stride = (size_t)NPARTY * 32; fa.len = NPARTY * 32;
         fa.I = c.d_I; fa.rest = c.d_rest; fa.sel_stride = c.sel_stride;
+        fa.bind = bound ? c.d_bind : nullptr;
         c.prof_begin(PR_FS_OPENED, n);
         HIPCHK(launch_fs_chain(fa, FS_OPENED, n, st));
         c.prof_end(PR_FS_OPENED);
@@ -1117,7 +1150,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     // I, its complement, and the complement entries owned by each aligned 64-party window (k_assemble_fields), all derived by
     // the worker that hashed the proof's table
     if (!c.fs_device) {
-        fs_opened_batch(n, c.h_dig2, (size_t)NPARTY * 32, c.h_I, c.h_rest, c.sel_stride, c.nthreads, c.pool, true);
+        fs_opened_batch(n, c.h_dig2, (size_t)NPARTY * 32, c.h_I, c.h_rest, c.sel_stride, c.nthreads, c.pool, true, nullptr, bound ? c.h_bind : nullptr);
         c.path_n[PATH_FS_HOST]++;
     }
     t1 = now_sec(); c.phase_sec[PH_FS_OPEN] = t1 - t0; t0 = t1;

@@ -308,6 +308,14 @@ struct Ctx {
     // table crosses PCIe, the host neither hashes nor waits between segments (kosk_fs_kernels.hip).  Host mode (default)
     // is the path of rounds 1-5
     bool fs_device = false;
+    // kosk-bind-v1 (kosk_set_contexts): while bind_n > 0 the context is ARMED -- prove_resident and verify_resident hash
+    // B_b = k_bind_values(pk_b, context_b) behind both digest tables of proof b.  bind_ctx: the handle's device copy of the armed contexts,
+    // 32 bytes each (owned by the handle, kosk_capi.cpp); bind_first: the position in the caller's whole call of this call's proof 0
+    // (set by the entry point for every chunk / sub-batch).  d_bind / h_bind: the call's binding values, written by k_bind_values in BOTH
+    // Fiat-Shamir modes; in host mode they cross PCIe with the first digest table
+    const uint8_t *bind_ctx = nullptr;
+    int bind_n = 0, bind_first = 0;
+    uint8_t *d_bind = nullptr, *h_bind = nullptr;
     bool host_register = true;       // KOSK_REGISTER=0: staging copies only, even for buffers the caller page-locked itself.  (KOSK_REGISTER=2 of
                                      // rounds 2-4 -- the library page-locking PAGEABLE caller memory for a call -- is gone: both process aborts on
                                      // record happened inside calls that had just done that, and neither was ever reproduced or explained)
@@ -408,6 +416,10 @@ hipError_t copy_round_table(Ctx &c, uint8_t *h_dst, const uint8_t *d_src, int n)
 hipError_t copy_small(Ctx &c, void *dst, size_t dst_stride, const void *src, size_t src_stride, size_t row_bytes, size_t nrows, hipMemcpyKind kind, hipStream_t st);
 // after the stream has been synchronised: -1 (with c.err set, the word cleared) if a kernel of this context raised an error
 int device_error_check(Ctx &c);
+// armed context (bind_n > 0): -1 with c.err set if the call's n proofs reach behind the armed contexts, else the binding values of the
+// n public keys resident in d_pk are queued on the stream (k_bind_values -> d_bind; host Fiat-Shamir: and copied to h_bind).  0 otherwise
+int bind_check(Ctx &c, int n);
+int issue_bind_values(Ctx &c, int n);
 // C[g][rows_d[i]][off + m] = sum_k T[m][k] * src[g][rows_s[i]][koff + k] mod q on the table kernels; -1 (c.err set) if the operands
 // fail table_gemm_ok() (kosk_device.hpp: 16-byte aligned source and output rows), which nothing the library itself issues does
 int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, int npg, int ngroups);

@@ -319,7 +319,20 @@ struct FsArgs {
     size_t image_stride;
     uint32_t off_I;
     uint32_t *fail;
+    // kosk-bind-v1 (nullptr: the reference's transcript): [n][32] binding values, 8-byte aligned; the message hashed for proof b is its
+    // table followed by bind[b].  Not with FS_DIGEST
+    const uint8_t *bind;
 };
+// kosk-bind-v1: out[b] = sha3_256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || sha3_256(pk[b]) || contexts[b]); nothing is written outside
+// out[0 .. 32 n).  pk records pk_stride apart, contexts and out 32 apart; every base and pk_stride multiples of 8 (else hipErrorInvalidValue)
+struct BindArgs {
+    const uint8_t *pk;
+    size_t pk_stride;
+    int pk_bytes, K;
+    const uint8_t *contexts;
+    uint8_t *out;
+};
+hipError_t launch_bind_values(const BindArgs &A, int n, hipStream_t st);
 hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st);
 bool copy_small_ok(const void *src, size_t src_stride, const void *dst, size_t dst_stride, size_t row_bytes);
 hipError_t launch_copy_small(const void *src, size_t src_stride, void *dst, size_t dst_stride, size_t row_bytes, size_t nrows, hipStream_t st);

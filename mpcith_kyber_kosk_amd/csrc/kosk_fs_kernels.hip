@@ -48,7 +48,10 @@ __device__ __forceinline__ uint2 fs_last_word(const uint8_t *tail, int rem, int 
     return make_uint2(lo ^ p.x, hi ^ p.y);
 }
 
-template <int MODE>
+// BOUND (kosk-bind-v1): the 32-byte binding value of the proof follows the table in the hashed message.  The table's
+// tail is a whole number of words (1454 x 32 = 342 x 136 + 16: two words) and tail + 32 bytes stay inside the last block, so the
+// chain has the same number of permutations as the unbound one: the last block's words are the tail's, then four of B, then the padding
+template <int MODE, bool BOUND = false>
 __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
 {
     __shared__ __align__(16) uint32_t st[64];       // the state's words, to be re-interleaved by other lanes
@@ -83,7 +86,19 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
             }
         }
     }
-    sp.absorb(a, ld ? fs_last_word(src + (size_t)136 * nfull, rem, word, 0x06u) : make_uint2(0, 0));
+    if constexpr (BOUND) {
+        uint2 m = make_uint2(0, 0);
+        if (ld) {
+            const int tw = rem >> 3; // (launch_fs_chain: rem is a multiple of 8 and rem + 32 < 136)
+            if (word < tw) m = fs_load_word(src + (size_t)136 * nfull + 8 * word);
+            else if (word < tw + 4) m = fs_load_word(A.bind + (size_t)b * 32 + 8 * (word - tw));
+            const uint2 p = WaveSponge::pad(word, rem + 32, 0x06u, 136);
+            m.x ^= p.x; m.y ^= p.y;
+        }
+        sp.absorb(a, m);
+    } else {
+        sp.absorb(a, ld ? fs_last_word(src + (size_t)136 * nfull, rem, word, 0x06u) : make_uint2(0, 0));
+    }
     sp.permute(a);
     if (A.out_digest) {
         const uint2 w = sp.words(a, st, 4);
@@ -172,12 +187,76 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
     }
 }
 
+// B = sha3_256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || sha3_256(pk) || context), 84 bytes, for proof b = blockIdx.x.  One wave per
+// proof on the wave sponge: 6 / 9 / 12 permutations for the public key and one for the outer message, a 27th of a chain, and as
+// parallel as the chains that wait for it.  pk and contexts: bases and pk_stride multiples of 8 (launch_bind_values)
+__global__ __launch_bounds__(64) void k_bind_values(BindArgs A)
+{
+    __shared__ __align__(16) uint32_t st[64];
+    __shared__ __align__(16) uint32_t msg[34]; // the outer message's only block
+    const int lane = threadIdx.x, b = blockIdx.x;
+    WaveSponge sp;
+    sp.setup(lane);
+    const int word = sp.word();
+    const bool ld = word < 17;
+
+    const uint8_t *src = A.pk + (size_t)b * A.pk_stride;
+    const int nfull = A.pk_bytes / 136, rem = A.pk_bytes - nfull * 136;
+    const uint8_t *mine = src + 8 * (ld ? word : 0);
+    uint32_t a = 0;
+    uint2 nx = (ld && nfull > 0) ? fs_load_word(mine) : make_uint2(0, 0);
+#pragma unroll 1
+    for (int blk = 0; blk < nfull; blk++) {
+        const uint2 m = nx;
+        nx = (ld && blk + 1 < nfull) ? fs_load_word(mine + (size_t)136 * (blk + 1)) : make_uint2(0, 0);
+        sp.absorb(a, m);
+        sp.permute(a);
+    }
+    sp.absorb(a, ld ? fs_last_word(src + (size_t)136 * nfull, rem, word, 0x06u) : make_uint2(0, 0));
+    sp.permute(a);
+    const uint2 hw = sp.words(a, st, 4); // sha3_256(pk): bytes 20..51 of the outer message
+
+    if (lane < 4) { msg[5 + 2 * lane] = hw.x; msg[6 + 2 * lane] = hw.y; }
+    if (lane < 8) msg[13 + lane] = *reinterpret_cast<const uint32_t *>(A.contexts + (size_t)b * 32 + 4 * lane); // bytes 52..83
+    if (lane >= 8 && lane < 21) msg[13 + lane] = lane == 8 ? 0x06u : lane == 20 ? 0x80000000u : 0u; // padding: byte 84, byte 135
+    if (lane >= 21 && lane < 26) {
+        constexpr uint32_t head[5] = {0x6b736f6bu, 0x6e69622du, 0x31762d64u, 0u, 0u}; // "kosk-bind-v1", four zero bytes, then K
+        msg[lane - 21] = lane == 25 ? (uint32_t)A.K : head[lane - 21];
+    }
+    wave_lds_handoff();
+    a = 0;
+    sp.absorb(a, ld ? make_uint2(msg[2 * word], msg[2 * word + 1]) : make_uint2(0, 0));
+    sp.permute(a);
+    const uint2 w = sp.words(a, st, 4);
+    if (lane < 4) *reinterpret_cast<uint2 *>(A.out + (size_t)b * 32 + 8 * lane) = w;
+}
+
 } // namespace
+
+hipError_t launch_bind_values(const BindArgs &A, int n, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; };
+    if (!A.pk || !A.contexts || !A.out || A.pk_bytes < 8 || A.pk_bytes % 8 || A.pk_stride % 8 || A.pk_stride < (size_t)A.pk_bytes ||
+        misaligned(A.pk) || misaligned(A.contexts) || misaligned(A.out)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bind_values, dim3(n), dim3(64), 0, st, A);
+    return hipGetLastError();
+}
 
 hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
     if (mode < FS_DIGEST || mode > FS_CHECK) return hipErrorInvalidValue;
+    if (A.bind) { // kosk-bind-v1: the bound instantiations (the unbound ones below are what they were)
+        const int rem = A.len % 136;
+        if (mode == FS_DIGEST || rem % 8 || rem + 32 >= 136 || (reinterpret_cast<uintptr_t>(A.bind) & 7)) return hipErrorInvalidValue;
+        switch (mode) {
+        case FS_ALPHA: hipLaunchKernelGGL((k_fs_chain<FS_ALPHA, true>), dim3(n), dim3(64), 0, st, A); break;
+        case FS_OPENED: hipLaunchKernelGGL((k_fs_chain<FS_OPENED, true>), dim3(n), dim3(64), 0, st, A); break;
+        default: hipLaunchKernelGGL((k_fs_chain<FS_CHECK, true>), dim3(n), dim3(64), 0, st, A); break;
+        }
+        return hipGetLastError();
+    }
     switch (mode) {
     case FS_DIGEST: hipLaunchKernelGGL(k_fs_chain<FS_DIGEST>, dim3(n), dim3(64), 0, st, A); break;
     case FS_ALPHA: hipLaunchKernelGGL(k_fs_chain<FS_ALPHA>, dim3(n), dim3(64), 0, st, A); break;

@@ -36,7 +36,8 @@ struct Sponge {
     uint64_t s[25];
     size_t rate;
     Sponge(size_t r) : rate(r) { memset(s, 0, sizeof s); }
-    void absorb_once(const uint8_t *in, size_t len, uint8_t dom)
+    // sfx (optional): sfx_len more message bytes behind `in`; they must fit the last block together with in's tail and the domain byte
+    void absorb_once(const uint8_t *in, size_t len, uint8_t dom, const uint8_t *sfx = nullptr, size_t sfx_len = 0)
     {
         while (len >= rate) {
             for (size_t i = 0; i < rate / 8; i++) s[i] ^= load64(in + 8 * i);
@@ -47,6 +48,7 @@ struct Sponge {
         uint8_t last[200];
         memset(last, 0, rate);
         memcpy(last, in, len);
+        if (sfx) { memcpy(last + len, sfx, sfx_len); len += sfx_len; }
         last[len] = dom;
         last[rate - 1] |= 0x80;
         for (size_t i = 0; i < rate / 8; i++) s[i] ^= load64(last + 8 * i);
@@ -66,6 +68,8 @@ struct Sponge {
 } // namespace
 
 void sha3_256(uint8_t out[32], const uint8_t *in, size_t inlen) { Sponge k(136); k.absorb_once(in, inlen, 0x06); k.squeeze(out, 32); }
+// sha3_256(in || sfx[0..32)) without a copy of `in`; inlen % 136 + 32 < 136 (the digest tables: 16)
+static void sha3_256_sfx32(uint8_t out[32], const uint8_t *in, size_t inlen, const uint8_t *sfx) { Sponge k(136); k.absorb_once(in, inlen, 0x06, sfx, sfx ? 32 : 0); k.squeeze(out, 32); }
 void sha3_512(uint8_t out[64], const uint8_t *in, size_t inlen) { Sponge k(72); k.absorb_once(in, inlen, 0x06); k.squeeze(out, 64); }
 void shake128(uint8_t *out, size_t outlen, const uint8_t *in, size_t inlen) { Sponge k(168); k.absorb_once(in, inlen, 0x1F); k.squeeze(out, outlen); }
 void shake256(uint8_t *out, size_t outlen, const uint8_t *in, size_t inlen) { Sponge k(136); k.absorb_once(in, inlen, 0x1F); k.squeeze(out, outlen); }
@@ -226,19 +230,27 @@ void host_decode_pk(const Params &P, const uint8_t *pk, HostKey &key)
 }
 
 // -------------------------------------------------------------- Fiat-Shamir --
-void fs_alpha(const Params &P, const uint8_t *tcomm_all, uint16_t *alpha)
+void bind_value(const Params &P, const uint8_t *pk, const uint8_t context[32], uint8_t out[32])
+{
+    uint8_t m[84] = {'k', 'o', 's', 'k', '-', 'b', 'i', 'n', 'd', '-', 'v', '1', 0, 0, 0, 0, (uint8_t)P.K, 0, 0, 0};
+    sha3_256(m + 20, pk, P.pk_bytes);
+    memcpy(m + 52, context, 32);
+    sha3_256(out, m, sizeof m);
+}
+
+void fs_alpha(const Params &P, const uint8_t *tcomm_all, uint16_t *alpha, const uint8_t *bind)
 {
     uint8_t h[32], a_[2 * MAXJ];
-    sha3_256(h, tcomm_all, (size_t)NPARTY * 32);
+    sha3_256_sfx32(h, tcomm_all, (size_t)NPARTY * 32, bind);
     shake256_prf(a_, (size_t)2 * P.J, h, 1);
     for (int i = 0; i < P.J; i++) alpha[i] = (uint16_t)(((a_[2 * i] << 8) | a_[2 * i + 1]) % Q);
 }
 
 static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t rest[NREST]);
-void fs_opened(const uint8_t *digests_all, uint16_t I[NOPEN], uint16_t rest[NREST])
+void fs_opened(const uint8_t *digests_all, uint16_t I[NOPEN], uint16_t rest[NREST], const uint8_t *bind)
 {
     uint8_t ch[32];
-    sha3_256(ch, digests_all, (size_t)NPARTY * 32);
+    sha3_256_sfx32(ch, digests_all, (size_t)NPARTY * 32, bind);
     opened_from_ch(ch, I, rest);
 }
 
@@ -284,7 +296,7 @@ __attribute__((always_inline)) static inline void vround(const typename VecT<W>:
 
 // W messages of `len` bytes, all of the same length, SHA3-256
 template <int W>
-__attribute__((always_inline)) static inline void sha3_256_xw(uint8_t *const *out, const uint8_t *const *in, size_t len)
+__attribute__((always_inline)) static inline void sha3_256_xw(uint8_t *const *out, const uint8_t *const *in, size_t len, const uint8_t *const *sfx)
 {
     typedef typename VecT<W>::type V;
     V s[25], t[25];
@@ -309,7 +321,8 @@ __attribute__((always_inline)) static inline void sha3_256_xw(uint8_t *const *ou
     for (int i = 0; i < W; i++) {
         memset(last[i], 0, 136);
         memcpy(last[i], in[i] + off, len - off);
-        last[i][len - off] = 0x06;
+        if (sfx) memcpy(last[i] + (len - off), sfx[i], 32); // (the callers see to it that tail + 32 bytes stay inside the block)
+        last[i][len - off + (sfx ? 32 : 0)] = 0x06;
         last[i][135] |= 0x80;
     }
     for (int w = 0; w < 17; w++) {
@@ -333,7 +346,7 @@ __attribute__((always_inline)) static inline void sha3_256_xw(uint8_t *const *ou
 // stack).  Three-way XOR and chi are one vpternlogq each.  The Fiat-Shamir rounds of a step hash 186 KB per proof on the host: this
 // function is the largest single consumer of the host's CPU share.
 #include <immintrin.h>
-__attribute__((target("avx512f"))) void sha3_256_x8_avx512(uint8_t *const *out, const uint8_t *const *in, size_t len)
+__attribute__((target("avx512f"))) void sha3_256_x8_avx512(uint8_t *const *out, const uint8_t *const *in, size_t len, const uint8_t *const *sfx)
 {
     const __m512i zero = _mm512_setzero_si512();
     __m512i s0 = zero, s1 = zero, s2 = zero, s3 = zero, s4 = zero, s5 = zero, s6 = zero, s7 = zero, s8 = zero, s9 = zero, s10 = zero, s11 = zero,
@@ -379,7 +392,8 @@ __attribute__((target("avx512f"))) void sha3_256_x8_avx512(uint8_t *const *out, 
     for (int i = 0; i < 8; i++) {
         memset(last[i], 0, 136);
         memcpy(last[i], in[i] + off, len - off);
-        last[i][len - off] = 0x06;
+        if (sfx) memcpy(last[i] + (len - off), sfx[i], 32);
+        last[i][len - off + (sfx ? 32 : 0)] = 0x06;
         last[i][135] |= 0x80;
         lp[i] = last[i];
     }
@@ -399,8 +413,8 @@ __attribute__((target("avx512f"))) void sha3_256_x8_avx512(uint8_t *const *out, 
 #undef KABSORB
 #undef KABSORB_BLOCK
 }
-__attribute__((target("avx2"))) void sha3_256_x4_avx2(uint8_t *const *out, const uint8_t *const *in, size_t len) { sha3_256_xw<4>(out, in, len); }
-__attribute__((target("avx512f,avx512vl"))) void sha3_256_x4_avx512vl(uint8_t *const *out, const uint8_t *const *in, size_t len) { sha3_256_xw<4>(out, in, len); }
+__attribute__((target("avx2"))) void sha3_256_x4_avx2(uint8_t *const *out, const uint8_t *const *in, size_t len, const uint8_t *const *sfx) { sha3_256_xw<4>(out, in, len, sfx); }
+__attribute__((target("avx512f,avx512vl"))) void sha3_256_x4_avx512vl(uint8_t *const *out, const uint8_t *const *in, size_t len, const uint8_t *const *sfx) { sha3_256_xw<4>(out, in, len, sfx); }
 
 struct CpuCaps {
     bool avx2, avx512f, avx512vl;
@@ -416,20 +430,23 @@ struct CpuCaps {
 const CpuCaps &caps() { static const CpuCaps c; return c; }
 
 // hash group `g` of width w (messages g*w .. g*w+w-1, the tail group re-hashes its first message as padding)
-void sha3_group(uint8_t *out, const uint8_t *const *in, size_t len, int count, int w, int g)
+// sfx (optional): message m is in[m] followed by the 32 bytes at sfx + 32 m (len % 136 + 32 < 136)
+void sha3_group(uint8_t *out, const uint8_t *const *in, size_t len, int count, int w, int g, const uint8_t *sfx = nullptr)
 {
-    const uint8_t *ip[8];
+    const uint8_t *ip[8], *sp[8];
     uint8_t *op[8];
     uint8_t dump[8][32];
     for (int i = 0; i < w; i++) {
         const int m = g * w + i;
         ip[i] = in[m < count ? m : g * w];
+        sp[i] = sfx ? sfx + 32 * (size_t)(m < count ? m : g * w) : nullptr;
         op[i] = m < count ? out + 32 * (size_t)m : dump[i];
     }
-    if (w == 8) sha3_256_x8_avx512(op, ip, len);
-    else if (w == 4 && caps().avx512vl) sha3_256_x4_avx512vl(op, ip, len);
-    else if (w == 4) sha3_256_x4_avx2(op, ip, len);
-    else sha3_256(op[0], ip[0], len);
+    const uint8_t *const *sx = sfx ? sp : nullptr;
+    if (w == 8) sha3_256_x8_avx512(op, ip, len, sx);
+    else if (w == 4 && caps().avx512vl) sha3_256_x4_avx512vl(op, ip, len, sx);
+    else if (w == 4) sha3_256_x4_avx2(op, ip, len, sx);
+    else sha3_256_sfx32(op[0], ip[0], len, sp[0]);
 }
 
 } // namespace
@@ -448,7 +465,7 @@ void sha3_256_multi(uint8_t *out, const uint8_t *const *in, size_t len, int coun
 // derivations (a SHAKE PRF and a few hundred scalar steps each) ride with the hashing instead of forming a serial tail of
 // n of them on the calling thread (r3: that tail was ~60 us of each of the four Fiat-Shamir rounds of a 46-proof step)
 static void sha3_digest_tables(int n, const uint8_t *digs, size_t dig_stride, uint8_t *out, int nthreads, Pool *pool,
-                               const std::function<void(int)> *then = nullptr, const std::function<void(int)> *prep = nullptr)
+                               const std::function<void(int)> *then = nullptr, const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr)
 {
     std::vector<const uint8_t *> in(n);
     for (int b = 0; b < n; b++) in[b] = digs + (size_t)b * dig_stride;
@@ -461,7 +478,7 @@ static void sha3_digest_tables(int n, const uint8_t *digs, size_t dig_stride, ui
     parallel_for(pool, groups, nthreads, [&](int g) {
         if (prep)
             for (int b = g * w; b < n && b < (g + 1) * w; b++) (*prep)(b);
-        sha3_group(out, in.data(), (size_t)NPARTY * 32, n, w, g);
+        sha3_group(out, in.data(), (size_t)NPARTY * 32, n, w, g, bind);
         if (then)
             for (int b = g * w; b < n && b < (g + 1) * w; b++) (*then)(b);
     });
@@ -482,7 +499,7 @@ void assemble_digest_table(uint8_t *table, const uint16_t *I, const uint8_t *uno
 }
 
 void fs_alpha_batch(const Params &P, int n, const uint8_t *digs, size_t dig_stride, uint16_t *alpha, size_t alpha_stride, int nthreads, Pool *pool,
-                    const std::function<void(int)> *prep)
+                    const std::function<void(int)> *prep, const uint8_t *bind)
 {
     std::vector<uint8_t> h((size_t)n * 32);
     const std::function<void(int)> derive = [&](int b) {
@@ -491,7 +508,7 @@ void fs_alpha_batch(const Params &P, int n, const uint8_t *digs, size_t dig_stri
         uint16_t *al = alpha + (size_t)b * alpha_stride;
         for (int i = 0; i < P.J; i++) al[i] = (uint16_t)(((a_[2 * i] << 8) | a_[2 * i + 1]) % Q);
     };
-    sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep);
+    sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep, bind);
 }
 
 static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t rest[NREST])
@@ -512,7 +529,7 @@ static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t res
 }
 
 void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I, uint16_t *rest, size_t sel_stride, int nthreads, Pool *pool,
-                     bool windows, const std::function<void(int)> *prep)
+                     bool windows, const std::function<void(int)> *prep, const uint8_t *bind)
 {
     std::vector<uint8_t> h((size_t)n * 32);
     const std::function<void(int)> derive = [&](int b) {
@@ -533,7 +550,7 @@ void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I,
                 if (pos[p] != 0xFFFF) { Ib[SEL_OSORT + k] = (uint16_t)p; Ib[SEL_OPOS + k] = pos[p]; k++; }
         }
     };
-    sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep);
+    sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep, bind);
 }
 
 // ------------------------------------------------------------------- tables --

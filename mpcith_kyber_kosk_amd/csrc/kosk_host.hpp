@@ -31,9 +31,14 @@ void host_keygen(const Params &P, const uint8_t seed64[64], uint8_t *pk, uint8_t
 void host_decode_pk(const Params &P, const uint8_t *pk, HostKey &key);
 
 // mlwe_prover.cpp:130-142: alpha_j = BE16(SHAKE256(sha3_256(Tcomm) || 1)) % q
-void fs_alpha(const Params &P, const uint8_t *tcomm_all /* [1454][32] */, uint16_t *alpha /* [J] */);
+// bind (fs_alpha, fs_opened and their batch forms; nullptr: the reference's transcript): kosk-bind-v1, the 32-byte binding value follows the
+// table in the hashed message -- a suffix of the multi-buffer hash's last block (46 528 = 342 x 136 + 16), no copy of the table
+void fs_alpha(const Params &P, const uint8_t *tcomm_all /* [1454][32] */, uint16_t *alpha /* [J] */, const uint8_t *bind = nullptr);
+// kosk-bind-v1: B = sha3_256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || sha3_256(pk) || context); the host definition
+// of what k_bind_values (kosk_fs_kernels.hip) computes on the device
+void bind_value(const Params &P, const uint8_t *pk, const uint8_t context[32], uint8_t out[32]);
 // mlwe_prover.cpp:445-474: opened list I (with the linear-probing de-dup) and its complement
-void fs_opened(const uint8_t *digests_all /* [1454][32] */, uint16_t I[NOPEN], uint16_t rest[NREST]);
+void fs_opened(const uint8_t *digests_all /* [1454][32] */, uint16_t I[NOPEN], uint16_t rest[NREST], const uint8_t *bind = nullptr);
 
 // Lagrange basis over n consecutive integer nodes a..a+n-1 evaluated at t
 // (utils/precomputed_kyber.h:10-13; values by the call sites ss.cpp:26-27,:47,:66)
@@ -73,10 +78,10 @@ void assemble_digest_table(uint8_t *table, const uint16_t *I, const uint8_t *uno
 // batch forms of fs_alpha / fs_opened over n proofs whose digest tables are dig_stride bytes apart
 // prep (optional): called for proof b on the worker that hashes it, before the hashing (the verifier assembles the table there)
 void fs_alpha_batch(const Params &P, int n, const uint8_t *digs, size_t dig_stride, uint16_t *alpha, size_t alpha_stride, int nthreads, Pool *pool = nullptr,
-                    const std::function<void(int)> *prep = nullptr);
+                    const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr /* [n][32] */);
 // windows: also write, behind each proof's list I (at I + SEL_WIN), the NWIN + 1 boundaries of the complement's aligned 64-party windows
 void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I, uint16_t *rest, size_t sel_stride, int nthreads, Pool *pool = nullptr,
-                     bool windows = false, const std::function<void(int)> *prep = nullptr);
+                     bool windows = false, const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr /* [n][32] */);
 
 // OS entropy (kyber/randombytes.c:44-57, Linux branch)
 void os_randombytes(uint8_t *out, size_t len);

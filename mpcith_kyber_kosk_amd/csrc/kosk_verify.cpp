@@ -209,6 +209,13 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
         }
         if (total != n) { c.err = "internal: merged call segments do not add up"; return -1; }
     }
+    const bool bound = c.bind_n > 0; // kosk-bind-v1
+    if (bound && segs->next) { c.err = "internal: an armed handle's call in a merged run"; return -1; }
+    if (bind_check(c, n)) return -1;
+    if (bound && pk_mode == 0 && (c.resident_pk_n < n || c.keys_from_pk_n < n)) {
+        c.err = "an armed handle (kosk_set_contexts) cannot verify against instances: there are no public key bytes to bind";
+        return -1;
+    }
     if (pk_mode == 2 && c.resident_pk_n < n) {
         c.err = "no resident public keys for this batch: pk == NULL needs a key generation (or a verifier staging call) of at least n proofs on this context";
         return -1;
@@ -303,12 +310,14 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
     else HIPCHK(copy_round_table(c, c.h_dig, c.d_dig1, n));
     return 0;
     }, c.fs_device ? nullptr : split_tables ? c.h_odig : c.h_dig)) return -1; // which table copy the captured segment holds is part of its graph's key
+    if (issue_bind_values(c, n)) return -1; // the pk bytes are in d_pk in stream order (staging call, the copies above, or resident); never captured
     HIPCHK(hipEventRecord(c.ev, st)); // the opened parties' Tcomm digests are on the host (device Fiat-Shamir: the table is complete in HBM) once this event has passed
     if (c.fs_device) {
         // ---- alpha on the device from the verifier's own table   mlwe_verifier.cpp:37-65
         FsArgs fa{};
         fa.in = c.d_dig1; fa.in_stride = (size_t)NPARTY * 32; fa.len = NPARTY * 32;
         fa.alpha = c.d_alpha; fa.alpha_stride = 80; fa.J = P.J;
+        fa.bind = bound ? c.d_bind : nullptr;
         c.prof_begin(PR_V_FS_ALPHA, n);
         HIPCHK(launch_fs_chain(fa, FS_ALPHA, n, st));
         c.prof_end(PR_V_FS_ALPHA);
@@ -401,7 +410,7 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
     if (!c.fs_device) {
         c.path_n[PATH_FS_HOST]++;
         const std::function<void(int)> prep = table_prep(0);
-        fs_alpha_batch(P, n, c.h_dig, (size_t)NPARTY * 32, c.h_alpha, 80, c.nthreads, c.pool, split_tables ? &prep : nullptr);
+        fs_alpha_batch(P, n, c.h_dig, (size_t)NPARTY * 32, c.h_alpha, 80, c.nthreads, c.pool, split_tables ? &prep : nullptr, bound ? c.h_bind : nullptr);
     }
     t1 = now_sec(); c.phase_sec[PH_V_FS_ALPHA] = t1 - t0; t0 = t1;
     if (run_segment(c, Ctx::SEG_V2, n, [&]() -> int {
@@ -439,6 +448,7 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
         FsArgs fa{};
         fa.in = c.d_dig2; fa.in_stride = (size_t)NPARTY * 32; fa.len = NPARTY * 32;
         fa.proof = c.d_proof; fa.image_stride = c.image_stride; fa.off_I = (uint32_t)P.off[F_I]; fa.fail = c.d_fail;
+        fa.bind = bound ? c.d_bind : nullptr;
         c.prof_begin(PR_V_FS_OPENED, n);
         HIPCHK(launch_fs_chain(fa, FS_CHECK, n, st));
         c.prof_end(PR_V_FS_OPENED);
@@ -504,7 +514,7 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode, const uint8_t *pk, 
     std::vector<uint16_t> &I2 = c.v_I2, &rest2 = c.v_rest2; // every entry that is read below is written by fs_opened_batch first
     {
         const std::function<void(int)> prep = table_prep(1);
-        fs_opened_batch(n, c.h_dig, (size_t)NPARTY * 32, I2.data(), rest2.data(), c.sel_stride, c.nthreads, c.pool, false, split_tables ? &prep : nullptr);
+        fs_opened_batch(n, c.h_dig, (size_t)NPARTY * 32, I2.data(), rest2.data(), c.sel_stride, c.nthreads, c.pool, false, split_tables ? &prep : nullptr, bound ? c.h_bind : nullptr);
     }
     HIPCHK(stream_sync_site(c, 5, n)); // fail masks of V2B
     c.prof_collect();
