@@ -190,6 +190,36 @@ int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uin
 int kosk_fetch_proofs_compact(kosk_ctx *ctx, int n, uint8_t *out);        /* like kosk_fetch_proofs */
 int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk); /* like kosk_stage_verifier_inputs */
 
+/* ---- Dense wire format kosk-dense-v1 (INTEGRATION.md 11 is the normative text; no reference counterpart).  The compact format's
+ * layout -- the 24 fields in order, each on a 16-byte boundary, Tcomm and comm raw, every u16 field 12 bits per value in
+ * poly_tobytes bit order, an odd number of stored values packed with one trailing zero value -- but fields 2, 3, 8, 13, 14, 15, 16
+ * (beta, gamma, t, s+r, e+r, s_eta, e_eta shares of the 1304 unopened parties in ascending order) store rows 0..406 only: their rows
+ * hold evaluations of polynomials of degree <= 406 at the points 256 + party, so rows 407..1303 are the Lagrange interpolation of
+ * rows 0..406 (mod q) through the nodes 256 + rest[j], rest = ascending complement of I.  285 184 / 290 912 / 320 800 bytes for
+ * kyber_k 2 / 3 / 4: 43 % of the image.  The image and the compact format are unchanged; a dense record verifies exactly as the
+ * image it unpacks to (same bit, same fail mask, either strict_encoding mode, armed or not).
+ * Host codec (no device): kosk_proof_dense_pack returns 0, -1 for a stored value >= 4096, -2 for a malformed I (an entry >= 1454 or
+ * repeated) or a row >= 407 of a listed field that is not the refill -- it succeeds iff unpack(pack(image)) == image.
+ * kosk_proof_dense_unpack returns 0, or 1 for a malformed I: rows 407..1303 of the listed fields are then zero (the verifier rejects
+ * every image with such an I); -1 for bad arguments.  Refilled values are canonical; stored values up to 4095 survive unreduced. */
+size_t kosk_dense_proof_bytes(int kyber_k);
+int kosk_proof_dense_pack(int kyber_k, const uint8_t *pi, uint8_t *out);
+int kosk_proof_dense_unpack(int kyber_k, const uint8_t *in, uint8_t *pi);
+/* The compact calls' counterparts: n records of kosk_dense_proof_bytes(), packed on the GPU in front of the D2H copy, unpacked and
+ * refilled on the GPU behind the H2D copy.  Chunking, streams, page-locked and pageable buffers, armed handles and "never merged" as
+ * for the compact calls.  Packing does not check that the resident images are representable: what this library's prover leaves in
+ * HBM is (the zero-witness proof at an ok[b] = 0 position of kosk_stage_prover_keys* included); use the host codec for foreign images. */
+int kosk_verifiable_keygen_batch_dense(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out);
+int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
+                                              uint8_t *out);
+int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok);
+int kosk_fetch_proofs_dense(kosk_ctx *ctx, int n, uint8_t *out);        /* like kosk_fetch_proofs */
+int kosk_stage_verifier_inputs_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk); /* like kosk_stage_verifier_inputs */
+/* kernel level: the refill alone on n >= 1 images in HBM, in place (image b at d_images + b * image_stride; both 16-byte aligned,
+ * image_stride >= kosk_proof_bytes).  d_status (device memory, n x uint32): 0, or 1 for a malformed I, in which case image b is not
+ * written.  Nothing outside rows 407..1303 of the seven listed fields is changed.  Runs on the handle's own stream, synchronised on return. */
+int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+
 /* ---- Kyber KEM on the keys this library makes and vouches for: crypto_kem_enc_derand / crypto_kem_enc / crypto_kem_dec
  * (kyber/kem.c:76-96, :113-121, :140-169; indcpa_enc / indcpa_dec, kyber/indcpa.c:264-336), bit-exact, for kyber_k 2 / 3 / 4, n items
  * per call.  Records are consecutive: kosk_pk_bytes, kosk_sk_bytes (s || pk || H(pk) || z, what kosk_verifiable_keygen_* returns),
@@ -215,7 +245,7 @@ int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *s
  * The public keys are decoded again from their resident bytes (the same result as reusing the verifier's t and A).  Needs
  * streams = 1.  -1 with a text when no verify call has completed, when the last one covered fewer than n proofs, was a
  * chunked kosk_verify_batch call (n > max_batch), verified with A and t from instances (kosk_verify_inst, or kosk_verify_resident after it: no pk bytes were decoded) or was followed
- * by a call that replaced the resident keys (a key generation, a verifier staging call in either wire format); and for a member of a cohort (combine >= 2): "not available with call combining". */
+ * by a call that replaced the resident keys (a key generation, a verifier staging call in any wire format: image, compact (kosk_stage_verifier_inputs_compact, kosk_verify_batch_compact) or dense (kosk_stage_verifier_inputs_dense, kosk_verify_batch_dense)); and for a member of a cohort (combine >= 2): "not available with call combining". */
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
 /* ---- Proofs for Kyber keys that already exist.  sk: n consecutive records of kosk_sk_bytes,
@@ -236,7 +266,7 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
  * bytes resident exactly as kosk_stage_prover_keys does */
 int kosk_witness_from_sk(kosk_ctx *ctx, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok);
 /* The counterpart of kosk_stage_prover_inputs[_seeded] for existing keys, n <= max_batch; then kosk_prove_resident and
- * kosk_fetch_proofs[_compact].  tapes: the format of every other call (kosk_tape_bytes per proof, host or device memory, a device buffer
+ * kosk_fetch_proofs[_compact|_dense].  tapes: the format of every other call (kosk_tape_bytes per proof, host or device memory, a device buffer
  * read in place under the same alignment rule); the first 64 bytes of a tape, the key seed of a verifiable key generation, are NOT
  * read -- so on the sk that kosk_verifiable_keygen_batch(tape) returned, the proof is the one that call returned, byte for byte.
  * tapes / seeds == NULL: the handle's entropy mode (kosk_set_entropy) -- the draws of prepare_randomness, prepare_range_proof and
@@ -257,7 +287,8 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * caller), 5 through the pinned staging buffer (pageable caller memory), 6 hipGraph segment replays (KOSK_GRAPHS=1), 7 commitment rounds
  * whose digest table was copied to the host (host Fiat-Shamir mode), 8 small copies between HBM and the library's own page-locked buffers
  * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded
- * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls. */
+ * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls,
+ * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);
@@ -418,8 +449,8 @@ int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t t
                                 uint16_t *d_sel, uint16_t *d_rest, int sel_stride, uint8_t *d_ch);
 /* ARM the handle with n contexts (host or device memory, context_stride >= 32 apart; the handle keeps its own copy).  From then on every
  * first-level entry point that makes or checks proofs on this handle makes or checks BOUND proofs, position b of a call (of the whole call,
- * when it is chunked) under context b: kosk_verifiable_keygen_* (tape, seeded, compact, resident), kosk_prove_resident after
- * kosk_stage_prover_inputs* / kosk_stage_prover_keys*, kosk_prove_keys_*, kosk_verify_batch[_compact], kosk_verify_resident after
+ * when it is chunked) under context b: kosk_verifiable_keygen_* (tape, seeded, compact, dense, resident), kosk_prove_resident after
+ * kosk_stage_prover_inputs* / kosk_stage_prover_keys*, kosk_prove_keys_*, kosk_verify_batch[_compact|_dense], kosk_verify_resident after
  * kosk_stage_verifier_inputs*, kosk_verify_resident_pk.  Refused with -1 and a text, nothing started: a call of more proofs than armed
  * contexts; kosk_verify_inst / kosk_prove_prepared (no pk bytes exist there); context_stride < 32.  kosk_set_contexts(ctx, 0, NULL, 0)
  * disarms; a handle never armed, or disarmed, behaves exactly as before.  A cohort member that is armed keeps its calls out of merged

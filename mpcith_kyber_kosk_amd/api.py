@@ -136,6 +136,20 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_set_contexts")):
         sig.update(bound)
+    # dense wire format (kosk-dense-v1); optional under the same rule (and only then)
+    dense = {
+        "kosk_dense_proof_bytes": (sz, [C.c_int]),
+        "kosk_proof_dense_pack": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_proof_dense_unpack": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_fetch_proofs_dense": (C.c_int, [vp, C.c_int, vp]),
+        "kosk_stage_verifier_inputs_dense": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_verifiable_keygen_batch_dense": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verifiable_keygen_seeded_batch_dense": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verify_batch_dense": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_dense_fill_device": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_dense_proof_bytes")):
+        sig.update(dense)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -161,7 +175,10 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_witness_from_sk", "kosk_stage_prover_keys", "kosk_stage_prover_keys_seeded", "kosk_prove_keys_batch",
            "kosk_prove_keys_seeded_batch",
            "kosk_bind_value", "kosk_bind_device", "kosk_fs_alpha_bound", "kosk_fs_opened_bound", "kosk_fs_alpha_bound_device",
-           "kosk_fs_opened_bound_device", "kosk_set_contexts"]
+           "kosk_fs_opened_bound_device", "kosk_set_contexts",
+           "kosk_dense_proof_bytes", "kosk_proof_dense_pack", "kosk_proof_dense_unpack", "kosk_fetch_proofs_dense",
+           "kosk_stage_verifier_inputs_dense", "kosk_verifiable_keygen_batch_dense", "kosk_verifiable_keygen_seeded_batch_dense",
+           "kosk_verify_batch_dense", "kosk_dense_fill_device"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -193,6 +210,26 @@ def sk_bytes(k): return lib.kosk_sk_bytes(k)
 def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
 def ct_bytes(k): return lib.kosk_ct_bytes(k)
+def dense_proof_bytes(k): return lib.kosk_dense_proof_bytes(k)
+
+
+def dense_pack(k, pi):
+    """host codec of kosk-dense-v1 (kosk_proof_dense_pack) -> (return code, record): 0, -1 a stored value >= 4096, -2 a malformed I or
+    a dropped row that is not the refill; the record is only meaningful for 0"""
+    if len(pi) != proof_bytes(k):
+        raise KoskError("dense_pack: an image of kosk_proof_bytes")
+    out = C.create_string_buffer(dense_proof_bytes(k))
+    rc = lib.kosk_proof_dense_pack(k, C.c_char_p(bytes(pi)), out)
+    return rc, out.raw
+
+
+def dense_unpack(k, rec):
+    """kosk_proof_dense_unpack -> (status, image): status 1 = malformed opened list (the dropped rows are zero)"""
+    if len(rec) != dense_proof_bytes(k):
+        raise KoskError("dense_unpack: a record of kosk_dense_proof_bytes")
+    out = C.create_string_buffer(proof_bytes(k))
+    rc = lib.kosk_proof_dense_unpack(k, C.c_char_p(bytes(rec)), out)
+    return rc, out.raw
 
 
 CONTEXT_BYTES = 32
@@ -457,6 +494,44 @@ class Kosk:
 
     def stage_verifier_inputs_compact(self, blobs, pks):
         self._chk(lib.kosk_stage_verifier_inputs_compact(self._h, len(blobs), b"".join(blobs), b"".join(pks)), "stage_verifier_inputs_compact")
+
+    # dense wire format (kosk-dense-v1): the compact surface again
+    def verifiable_keygen_dense(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """verifiable_keygen with the proofs in the dense wire format (kosk_verifiable_keygen_[seeded_]batch_dense)"""
+        cb = lib.kosk_dense_proof_bytes(self.k)
+        if seeds is not None:
+            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
+            fn, tp, stride = lib.kosk_verifiable_keygen_seeded_batch_dense, sp, ss
+        elif tapes is not None:
+            n = len(tapes)
+            fn, tp, stride = lib.kosk_verifiable_keygen_batch_dense, C.c_char_p(b"".join(t[:self.tape_bytes] for t in tapes)), self.tape_bytes
+        else:
+            n = 1 if n is None else n
+            fn, tp, stride = lib.kosk_verifiable_keygen_batch_dense, None, 0
+        pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
+        out = C.create_string_buffer(cb * n)
+        self._chk(fn(self._h, n, tp, stride, pk, sk, out), "verifiable_keygen_dense")
+        cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
+        return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(out, cb)
+
+    def verify_dense(self, recs, pks):
+        n = len(recs)
+        ok = C.create_string_buffer(n)
+        self._chk(lib.kosk_verify_batch_dense(self._h, n, C.c_char_p(b"".join(recs)), C.c_char_p(b"".join(pks)), ok), "verify_dense")
+        return [b == 1 for b in ok.raw]
+
+    def fetch_proofs_dense(self, n):
+        size = lib.kosk_dense_proof_bytes(self.k)
+        out = C.create_string_buffer(size * n)
+        self._chk(lib.kosk_fetch_proofs_dense(self._h, n, out), "fetch_proofs_dense")
+        return [out.raw[i * size:(i + 1) * size] for i in range(n)]
+
+    def stage_verifier_inputs_dense(self, recs, pks):
+        self._chk(lib.kosk_stage_verifier_inputs_dense(self._h, len(recs), b"".join(recs), b"".join(pks)), "stage_verifier_inputs_dense")
+
+    def dense_fill_device(self, n, d_images, image_stride, d_status):
+        """kernel level: refill rows 407..1303 of the seven low-degree fields of n images in HBM, in place (int device pointers)"""
+        self._chk(lib.kosk_dense_fill_device(self._h, n, d_images, image_stride, d_status), "dense_fill_device")
 
     # second-level entry points (reference structs as bytes; see include/kosk_mi355x.h)
     def stage_verifier_inputs(self, pis, pks):
@@ -728,6 +803,15 @@ class Kosk:
 
     PATH_IDS = ["hash_dma", "hash_plain", "table_gemm", "limb_gemm", "copy_direct", "copy_staged", "graph_replay", "digest_copy", "small_copy_kernel",
                 "fs_device", "fs_host", "tape_expand", "kem_enc", "kem_dec"]
+
+    # ids behind PATH_IDS (that list is what path_counts() walks and stays as it is)
+    PATH_DENSE_FILL = 14
+
+    def path_count(self, path_id):
+        """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""
+        v = C.c_long()
+        self._chk(lib.kosk_path_count(self._h, int(path_id), C.byref(v)), "path_count")
+        return v.value
 
     def path_counts(self):
         """{name: launches / copies} of the alternative kernel and copy paths on this handle since it was created"""

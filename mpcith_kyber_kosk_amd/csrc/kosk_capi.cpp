@@ -872,16 +872,16 @@ int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk
 
 // The two host-buffer calls with the proofs in the compact wire format: packed / unpacked on the GPU, so PCIe
 // carries 78 % of the image bytes in each direction.  Same chunking and lanes as the calls above.
-static int keygen_batch_compact_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *out)
+static int keygen_batch_compact_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *out, bool dense = false)
 {
     const Params &P = ctx->c->P;
-    const size_t cb = make_compact_plan(P).bytes;
+    const size_t cb = dense ? make_dense_plan(P).bytes : make_compact_plan(P).bytes;
     src.resolve(ctx, n);
     const bool pinned = ctx->c->host_register && span_is_pinned(out, (size_t)n * cb);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         const KeygenIn kg = src.part(P, first, pk, sk);
         if (prove_at(c, first, count, &kg)) return -1;
-        return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned);
+        return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned, dense);
     });
 }
 int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
@@ -907,22 +907,59 @@ int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint
     return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
     GUARD_END
 }
+static int verify_batch_packed(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok, bool dense)
+{
+    const Params &P = ctx->c->P;
+    const size_t cb = dense ? make_dense_plan(P).bytes : make_compact_plan(P).bytes;
+    reset_masks(ctx, n);
+    const bool pinned = ctx->c->host_register && span_is_pinned(in, (size_t)n * cb);
+    const int rc = run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        if (stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, pinned, dense)) return -1;
+        return verify_into(ctx, c, first, count, ok, 0, nullptr);
+    });
+    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
+    return rc;
+}
 int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
 {
     if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (n == 0) { ctx->masks_n = 0; return 0; }
     GUARD(ctx)
-    const Params &P = ctx->c->P;
-    const size_t cb = make_compact_plan(P).bytes;
-    reset_masks(ctx, n);
-    const bool pinned = ctx->c->host_register && span_is_pinned(in, (size_t)n * cb);
-    const int rc = run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        if (stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, pinned)) return -1;
-        return verify_into(ctx, c, first, count, ok, 0, nullptr);
-    });
-    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
-    return rc;
+    return verify_batch_packed(ctx, n, in, pk, ok, false);
+    GUARD_END
+}
+
+// The same three calls in the dense wire format kosk-dense-v1 (kosk_dense.hip): packed by the compact pack kernel on
+// the dense field plan; unpacked and refilled (rows 407..1303 of the seven low-degree fields) on the GPU behind the H2D copy
+int kosk_verifiable_keygen_batch_dense(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
+{
+    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (n == 0) return 0;
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
+    return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
+    GUARD_END
+}
+int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
+{
+    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    if (n == 0) return 0;
+    GUARD(ctx)
+    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
+    return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
+    GUARD_END
+}
+int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
+{
+    if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (n == 0) { ctx->masks_n = 0; return 0; }
+    GUARD(ctx)
+    return verify_batch_packed(ctx, n, in, pk, ok, true);
     GUARD_END
 }
 
@@ -1035,6 +1072,52 @@ int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, 
     return ctx->run(n, [&](Ctx &c, int first, int count) {
         return stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes);
     });
+    GUARD_END
+}
+
+// ---- dense wire format kosk-dense-v1 (kosk_dense.hip) --------------------------------------------------------------
+size_t kosk_dense_proof_bytes(int k) { Params p; return make_params(k, p) ? make_dense_plan(p).bytes : 0; }
+int kosk_proof_dense_pack(int k, const uint8_t *pi, uint8_t *out)
+{
+    Params p;
+    if (!make_params(k, p) || !pi || !out) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    return dense_encode(p, pi, out);
+    GUARD_END
+}
+int kosk_proof_dense_unpack(int k, const uint8_t *in, uint8_t *pi)
+{
+    Params p;
+    if (!make_params(k, p) || !pi || !in) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    return dense_decode(p, in, pi);
+    GUARD_END
+}
+int kosk_fetch_proofs_dense(kosk_ctx *ctx, int n, uint8_t *out)
+{
+    if (!ctx || n < 0 || n > ctx->max_batch || !out) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const size_t cb = make_dense_plan(ctx->c->P).bytes;
+    return ctx->run(n, [&](Ctx &c, int first, int count) { return fetch_proofs_compact(c, count, out + (size_t)first * cb, false, true); });
+    GUARD_END
+}
+int kosk_stage_verifier_inputs_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk)
+{
+    if (!ctx || n < 0 || n > ctx->max_batch || !in || !pk) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    const size_t cb = make_dense_plan(P).bytes;
+    return ctx->run(n, [&](Ctx &c, int first, int count) {
+        return stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, false, true);
+    });
+    GUARD_END
+}
+int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    if (!ctx || n < 1 || !d_images || !d_status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return dense_fill_device(*ctx->c, n, d_images, image_stride, d_status);
     GUARD_END
 }
 

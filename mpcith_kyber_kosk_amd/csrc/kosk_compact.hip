@@ -6,6 +6,7 @@
 // u16 values are below 4096 (every image an honest prover emits; a larger value makes compression fail, not wrap).
 // K=3: 680 980 -> 531 760 bytes (78 %).  Packing runs on the GPU in front of the D2H copy of kosk_fetch_proofs_compact and
 // unpacking behind the H2D copy of kosk_stage_verifier_inputs_compact, so PCIe carries the compact bytes.
+// The dense wire format (kosk_dense.hip) runs the same two kernels on a second field plan with truncated counts.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(256) void k_pack_proofs(const uint8_t *__restrict__
             *reinterpret_cast<uint4 *>(d + 16 * u) = *reinterpret_cast<const uint4 *>(s + 16 * u);
             continue;
         }
-        const uint32_t left = cf.n - 8 * u; // values from here on (even)
+        const uint32_t left = cf.n - 8 * u; // values from here on (odd only at the end of a truncated field of the dense plan)
         if (left >= 8) {
             const uint32_t *sw = reinterpret_cast<const uint32_t *>(s + 16 * u);
             const uint32_t w0 = sw[0], w1 = sw[1], w2 = sw[2], w3 = sw[3];
@@ -100,6 +101,12 @@ __global__ __launch_bounds__(256) void k_pack_proofs(const uint8_t *__restrict__
                 overflow |= (a | b) >= 4096;
                 uint8_t *db = d + 12 * u + 3 * (i / 2);
                 db[0] = (uint8_t)a; db[1] = (uint8_t)((a >> 8) | ((b & 0xF) << 4)); db[2] = (uint8_t)(b >> 4);
+            }
+            if (left & 1) { // the last value, packed with one trailing zero value
+                const uint32_t a = reinterpret_cast<const uint16_t *>(s + 16 * u)[left - 1];
+                overflow |= a >= 4096;
+                uint8_t *db = d + 12 * u + 3 * (left / 2);
+                db[0] = (uint8_t)a; db[1] = (uint8_t)(a >> 8); db[2] = 0;
             }
         }
     }
@@ -133,6 +140,10 @@ __global__ __launch_bounds__(256) void k_unpack_proofs(const uint8_t *__restrict
                 dv[0] = (uint16_t)(sb[0] | ((sb[1] & 0xF) << 8));
                 dv[1] = (uint16_t)((sb[1] >> 4) | (sb[2] << 4));
             }
+            if (left & 1) { // the last value of an odd count; its partner is padding
+                const uint8_t *sb = s + 12 * u + 3 * (left / 2);
+                reinterpret_cast<uint16_t *>(d + 16 * u)[left - 1] = (uint16_t)(sb[0] | ((sb[1] & 0xF) << 8));
+            }
         }
     }
 }
@@ -142,6 +153,8 @@ static int ensure_compact(Ctx &c)
     if (c.d_compact) return 0;
     c.cplan = make_compact_plan(c.P);
     c.compact_stride = (c.cplan.bytes + 63) / 64 * 64;
+    c.dplan = make_dense_plan(c.P); // dense records are shorter and go through the same staging buffers
+    c.dense_stride = (c.dplan.bytes + 63) / 64 * 64;
     // a view keeps its own staging, sized for its own callers' batches (the compact calls are never merged)
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact), (size_t)c.own_batch * c.compact_stride));
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact_bad), sizeof(uint32_t) * c.own_batch));
@@ -150,47 +163,59 @@ static int ensure_compact(Ctx &c)
     return 0;
 }
 
-int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct)
+// dense: the same kernel on the dense plan.  It packs rows 0..406 of the seven low-degree fields and does not look at the rows it drops:
+// what the library's own prover left in HBM is a codeword by construction (kosk_dense.hip; the host codec checks, this call does not)
+int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct, bool dense)
 {
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (ensure_compact(c)) return -1;
-    HIPCHK(hipMemsetAsync(c.d_compact, 0, (size_t)n * c.compact_stride, c.stream)); // padding bytes are zero
+    const CompactPlan &plan = dense ? c.dplan : c.cplan;
+    const size_t stride = dense ? c.dense_stride : c.compact_stride;
+    HIPCHK(hipMemsetAsync(c.d_compact, 0, (size_t)n * stride, c.stream)); // padding bytes are zero
     HIPCHK(hipMemsetAsync(c.d_compact_bad, 0, sizeof(uint32_t) * n, c.stream));
-    hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_proof, c.image_stride, c.d_compact, c.compact_stride,
-                       c.cplan, c.d_compact_bad);
+    hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_proof, c.image_stride, c.d_compact, stride,
+                       plan, c.d_compact_bad);
     HIPCHK(hipGetLastError());
     // direct: `out` is page-locked host memory (the caller's own, or locked for this call by kosk_capi.cpp): no staging copy
-    if (direct) HIPCHK(hipMemcpy2DAsync(out, c.cplan.bytes, c.d_compact, c.compact_stride, c.cplan.bytes, n, hipMemcpyDeviceToHost, c.stream));
-    else HIPCHK(hipMemcpyAsync(c.h_compact, c.d_compact, (size_t)n * c.compact_stride, hipMemcpyDeviceToHost, c.stream));
+    if (direct) HIPCHK(hipMemcpy2DAsync(out, plan.bytes, c.d_compact, stride, plan.bytes, n, hipMemcpyDeviceToHost, c.stream));
+    else HIPCHK(hipMemcpyAsync(c.h_compact, c.d_compact, (size_t)n * stride, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(c.h_compact_bad, c.d_compact_bad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(stream_sync(c));
     c.path_n[direct ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     for (int b = 0; b < n; b++)
         if (c.h_compact_bad[b]) { c.err = "a resident proof holds a value >= 4096: not representable in the compact format"; return -1; }
     if (!direct)
-        parallel_for(c.pool, n, c.nthreads, [&](int b) { memcpy(out + (size_t)b * c.cplan.bytes, c.h_compact + (size_t)b * c.compact_stride, c.cplan.bytes); });
+        parallel_for(c.pool, n, c.nthreads, [&](int b) { memcpy(out + (size_t)b * plan.bytes, c.h_compact + (size_t)b * stride, plan.bytes); });
     return 0;
 }
 
-int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct)
+int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct, bool dense)
 {
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (ensure_verify_workspace(c)) return -1;
     if (ensure_compact(c)) return -1;
+    if (dense && ensure_dense_ws(c)) return -1;
     const Params &P = c.P;
+    const CompactPlan &plan = dense ? c.dplan : c.cplan;
+    const size_t stride = dense ? c.dense_stride : c.compact_stride;
     parallel_for(c.pool, n, c.nthreads, [&](int b) {
         memcpy(c.h_pk + (size_t)b * c.pk_stride, pk + (size_t)b * P.pk_bytes, P.pk_bytes);
-        if (!direct) memcpy(c.h_compact + (size_t)b * c.compact_stride, in + (size_t)b * c.cplan.bytes, c.cplan.bytes);
+        if (!direct) memcpy(c.h_compact + (size_t)b * stride, in + (size_t)b * plan.bytes, plan.bytes);
     });
     c.path_n[direct ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     HIPCHK(hipMemcpyAsync(c.d_pk, c.h_pk, (size_t)n * c.pk_stride, hipMemcpyHostToDevice, c.stream));
     c.note_pk_written(n);
-    if (direct) HIPCHK(hipMemcpy2DAsync(c.d_compact, c.compact_stride, in, c.cplan.bytes, c.cplan.bytes, n, hipMemcpyHostToDevice, c.stream));
-    else HIPCHK(hipMemcpyAsync(c.d_compact, c.h_compact, (size_t)n * c.compact_stride, hipMemcpyHostToDevice, c.stream));
-    hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_compact, c.compact_stride, c.d_proof, c.image_stride, c.cplan);
+    if (direct) HIPCHK(hipMemcpy2DAsync(c.d_compact, stride, in, plan.bytes, plan.bytes, n, hipMemcpyHostToDevice, c.stream));
+    else HIPCHK(hipMemcpyAsync(c.d_compact, c.h_compact, (size_t)n * stride, hipMemcpyHostToDevice, c.stream));
+    if (dense) // the dropped rows start as zero: they stay so where the opened list is malformed (status 1; the verifier rejects such an image)
+        for (int f = 0; f < NFIELDS; f++)
+            if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
+                HIPCHK(hipMemset2DAsync(c.d_proof + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
+    hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_compact, stride, c.d_proof, c.image_stride, plan);
     HIPCHK(hipGetLastError());
+    if (dense && dense_fill_launch(c, n, c.d_proof, c.image_stride, c.d_dense_status)) return -1;
     HIPCHK(launch_decode_pk(c.d_pk, c.pk_stride, c.d_t, c.d_A, c.key_stride, P.K, n, c.stream, c.xof_guard()));
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;

@@ -69,6 +69,8 @@ Ctx::~Ctx()
         if (d_compact_bad) (void)hipFree(d_compact_bad);
         if (h_compact) (void)hipHostFree(h_compact);
         if (h_compact_bad) (void)hipHostFree(h_compact_bad);
+        if (d_dense_ws) (void)hipFree(d_dense_ws);
+        if (d_dense_status) (void)hipFree(d_dense_status);
         if (pool) pool_destroy(pool);
         if (ev) (void)hipEventDestroy(ev);
         if (ev_kg) (void)hipEventDestroy(ev_kg);
@@ -89,6 +91,8 @@ Ctx::~Ctx()
     if (d_compact_bad) (void)hipFree(d_compact_bad);
     if (h_compact) (void)hipHostFree(h_compact);
     if (h_compact_bad) (void)hipHostFree(h_compact_bad);
+    if (d_dense_ws) (void)hipFree(d_dense_ws);
+    if (d_dense_status) (void)hipFree(d_dense_status);
     if (pool) pool_destroy(pool);
     if (ev) (void)hipEventDestroy(ev);
     if (ev_kg) (void)hipEventDestroy(ev_kg);
@@ -546,7 +550,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     for (auto &e : c.timer_ev) e = nullptr;
     for (auto &pe : c.prof_ev) for (auto &e : pe) e = nullptr;
     for (auto &g : c.seg) g = Ctx::SegGraph{};
-    c.d_compact = nullptr; c.h_compact = nullptr; c.d_compact_bad = nullptr; c.h_compact_bad = nullptr;
+    c.d_compact = nullptr; c.h_compact = nullptr; c.d_compact_bad = nullptr; c.h_compact_bad = nullptr; c.d_dense_ws = nullptr; c.d_dense_status = nullptr;
     for (auto &x : c.path_n) x = 0;
     for (int i = 0; i < PR_COUNT; i++) { c.prof_ms[i] = 0; c.prof_n[i] = 0; c.prof_units[i] = 0; c.prof_used[i] = false; }
     c.tape_cur = nullptr;

@@ -72,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -109,6 +109,10 @@ struct CompactPlan {
 CompactPlan make_compact_plan(const Params &P);
 int compact_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a value >= 4096
 void compact_decode(const Params &P, const uint8_t *in, uint8_t *img);
+// dense wire format kosk-dense-v1 (kosk_dense.hip): the compact layout with rows 0..406 only of the seven low-degree fields
+CompactPlan make_dense_plan(const Params &P);
+int dense_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a stored value >= 4096; -2: malformed I, or a dropped row that is not the refill
+int dense_decode(const Params &P, const uint8_t *in, uint8_t *img);  // 0, or 1: malformed I (rows 407..1303 of the seven fields left zero)
 
 struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
 enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
@@ -271,6 +275,11 @@ struct Ctx {
     size_t compact_stride = 0;
     uint8_t *d_compact = nullptr, *h_compact = nullptr;
     uint32_t *d_compact_bad = nullptr, *h_compact_bad = nullptr;
+    // dense wire format: its field plan and record stride in the compact staging buffers; the refill's workspace (allocated on first use)
+    CompactPlan dplan{};
+    size_t dense_stride = 0;
+    uint16_t *d_dense_ws = nullptr;
+    uint32_t *d_dense_status = nullptr;
 
     // pinned host staging
     uint8_t *h_tape = nullptr, *h_dig = nullptr, *h_dig2 = nullptr, *h_proof = nullptr; // h_dig / h_dig2: the host's copies of the two digest tables
@@ -463,8 +472,12 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
 int stage_verifier_inst(Ctx &c, int n, const uint8_t *pi, const uint8_t *inst);
 int ensure_verify_workspace(Ctx &c);
 // direct: the host buffer is page-locked (copied to / from straight, no staging)
-int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct = false);
-int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct = false);
+// dense = true: the same two calls in the dense wire format (stage: unpack, then the refill of kosk_dense.hip)
+int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct = false, bool dense = false);
+int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct = false, bool dense = false);
+int ensure_dense_ws(Ctx &c);
+int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status); // n <= own_batch, on c.stream, not synchronised
+int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status);
 // registered: `pi` is page-locked host memory (hipHostRegister): copied to directly, no staging
 int fetch_proofs(Ctx &c, int n, uint8_t *pi, bool registered = false);
 

@@ -1,0 +1,458 @@
+// Dense wire format kosk-dense-v1: the compact format's layout, but the seven fields whose rows are
+// evaluations of polynomials of degree <= 406 at the points 256 + party (beta, gamma, t, s+r, e+r and the two eta-gate
+// fields of the 1304 unopened parties, ascending) keep only rows 0..406.  Rows 407..1303 are a function of those rows and
+// of the opened list I: Lagrange interpolation through the nodes x_j = 256 + rest[j], j < 407.
+//
+// This file holds the host codec (reference-grade: clarity over speed) and the refill on the GPU, which runs behind the
+// unpack kernel of kosk_compact.hip.  Kernel plan (DESIGN.md "Dense wire format"): the per-proof operator in barycentric form,
+//   out[i][c] = l_i * sum_j inv(x_i - x_j) * (w_j * y[j][c]),
+// k_dense_setup makes rest, the weights w_j and l_i of a proof; k_dense_fill builds the weighted shares of one column group
+// as int8-limb MFMA fragments in LDS, builds the Cauchy operand 1/(x_i - x_j) in registers from a table of the 2907
+// possible differences (as k_interp_apply does) and multiplies with v_mfma_i32_16x16x64_i8.  Every global store is 16 bytes.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <vector>
+
+#include "kosk_ctx.hpp"
+#include "kosk_limb_dev.hpp"
+
+namespace kosk {
+
+#define HIPCHK(x) KOSK_HIPCHK(x)
+
+static const int kDenseFields[7] = {F_BETA, F_GAMMA, F_T, F_SR, F_ER, F_SETA, F_EETA};
+static bool dense_listed(int f)
+{
+    for (int i = 0; i < 7; i++)
+        if (kDenseFields[i] == f) return true;
+    return false;
+}
+static inline uint32_t dense_cols(const Params &P, int f) { return (uint32_t)(P.size[f] / 2 / NREST); }
+
+CompactPlan make_dense_plan(const Params &P)
+{
+    CompactPlan cp{};
+    size_t o = 0;
+    for (int f = 0; f < NFIELDS; f++) {
+        cp.f[f].src_off = (uint32_t)P.off[f];
+        cp.f[f].dst_off = (uint32_t)o;
+        cp.f[f].raw = (f == F_TCOMM || f == F_COMM);
+        if (cp.f[f].raw) cp.f[f].n = (uint32_t)P.size[f];
+        else if (dense_listed(f)) cp.f[f].n = (uint32_t)XLEN * dense_cols(P, f);
+        else cp.f[f].n = (uint32_t)(P.size[f] / 2);
+        const size_t bytes = cp.f[f].raw ? cp.f[f].n : (size_t)(cp.f[f].n + 1) / 2 * 3; // an odd count is packed with one trailing zero value
+        o += (bytes + 15) / 16 * 16;
+    }
+    cp.bytes = o;
+    return cp;
+}
+
+// ---- host codec ----------------------------------------------------------------------------------------------------
+static uint32_t inv_mod_q(uint32_t a)
+{
+    uint32_t r = 1, b = a % Q;
+    for (int e = Q - 2; e; e >>= 1) {
+        if (e & 1) r = r * b % Q;
+        b = b * b % Q;
+    }
+    return r;
+}
+
+// rows 407..1303 of the seven fields from rows 0..406 and I, in place; 1 (nothing written) for a malformed I
+static int dense_refill_host(const Params &P, uint8_t *img)
+{
+    bool opened[NPARTY] = {false};
+    for (int t = 0; t < NOPEN; t++) {
+        const uint32_t v = img[P.off[F_I] + 2 * t] | (img[P.off[F_I] + 2 * t + 1] << 8);
+        if (v >= (uint32_t)NPARTY || opened[v]) return 1;
+        opened[v] = true;
+    }
+    int rest[NREST], nr = 0;
+    for (int p = 0; p < NPARTY; p++)
+        if (!opened[p]) rest[nr++] = p;
+    std::vector<uint32_t> inv(Q, 0);
+    for (int a = 1; a < Q; a++) inv[a] = inv_mod_q((uint32_t)a);
+    auto diff = [&](int a, int b) { return (uint32_t)((a - b) % Q + Q) % Q; };
+    // barycentric weights w_j = 1 / prod_{m != j} (x_j - x_m)
+    uint32_t w[XLEN];
+    for (int j = 0; j < XLEN; j++) {
+        uint32_t pr = 1;
+        for (int m = 0; m < XLEN; m++)
+            if (m != j) pr = pr * diff(rest[j], rest[m]) % Q;
+        w[j] = inv[pr];
+    }
+    std::vector<uint32_t> L(XLEN);
+    std::vector<uint64_t> acc;
+    for (int i = XLEN; i < NREST; i++) {
+        uint32_t l = 1; // l(x_i) = prod_j (x_i - x_j)
+        for (int j = 0; j < XLEN; j++) l = l * diff(rest[i], rest[j]) % Q;
+        for (int j = 0; j < XLEN; j++) L[j] = l * w[j] % Q * inv[diff(rest[i], rest[j])] % Q;
+        for (int fi = 0; fi < 7; fi++) {
+            const int f = kDenseFields[fi];
+            const uint32_t cols = dense_cols(P, f);
+            uint8_t *base = img + P.off[f];
+            acc.assign(cols, 0);
+            for (int j = 0; j < XLEN; j++) {
+                const uint8_t *row = base + (size_t)j * cols * 2;
+                for (uint32_t c = 0; c < cols; c++) acc[c] += (uint64_t)L[j] * ((uint32_t)(row[2 * c] | (row[2 * c + 1] << 8)) % Q);
+            }
+            uint8_t *out = base + (size_t)i * cols * 2;
+            for (uint32_t c = 0; c < cols; c++) {
+                const uint32_t v = (uint32_t)(acc[c] % Q);
+                out[2 * c] = (uint8_t)v; out[2 * c + 1] = (uint8_t)(v >> 8);
+            }
+        }
+    }
+    return 0;
+}
+
+int dense_decode(const Params &P, const uint8_t *in, uint8_t *img)
+{
+    const CompactPlan dp = make_dense_plan(P);
+    memset(img, 0, P.proof_bytes);
+    for (int f = 0; f < NFIELDS; f++) {
+        const CompactField &cf = dp.f[f];
+        if (cf.raw) { memcpy(img + cf.src_off, in + cf.dst_off, cf.n); continue; }
+        const uint8_t *s = in + cf.dst_off;
+        uint8_t *d = img + cf.src_off;
+        for (uint32_t i = 0; i < cf.n; i += 2) {
+            const uint32_t a = s[0] | ((s[1] & 0xF) << 8), b = (s[1] >> 4) | (s[2] << 4);
+            d[2 * i] = (uint8_t)a; d[2 * i + 1] = (uint8_t)(a >> 8);
+            if (i + 1 < cf.n) { d[2 * i + 2] = (uint8_t)b; d[2 * i + 3] = (uint8_t)(b >> 8); }
+            s += 3;
+        }
+    }
+    return dense_refill_host(P, img);
+}
+
+int dense_encode(const Params &P, const uint8_t *img, uint8_t *out)
+{
+    const CompactPlan dp = make_dense_plan(P);
+    memset(out, 0, dp.bytes);
+    for (int f = 0; f < NFIELDS; f++) {
+        const CompactField &cf = dp.f[f];
+        if (cf.raw) { memcpy(out + cf.dst_off, img + cf.src_off, cf.n); continue; }
+        const uint8_t *s = img + cf.src_off;
+        uint8_t *d = out + cf.dst_off;
+        for (uint32_t i = 0; i < cf.n; i += 2) {
+            const uint32_t a = s[2 * i] | (s[2 * i + 1] << 8), b = i + 1 < cf.n ? (uint32_t)(s[2 * i + 2] | (s[2 * i + 3] << 8)) : 0u;
+            if (a >= 4096 || b >= 4096) return -1;
+            d[0] = (uint8_t)a; d[1] = (uint8_t)((a >> 8) | ((b & 0xF) << 4)); d[2] = (uint8_t)(b >> 4);
+            d += 3;
+        }
+    }
+    // representable iff the dropped rows are what unpack makes of the kept ones
+    std::vector<uint8_t> back(P.proof_bytes);
+    if (dense_decode(P, out, back.data())) return -2;
+    return memcmp(back.data(), img, P.proof_bytes) ? -2 : 0;
+}
+
+// ---- the refill on the GPU -----------------------------------------------------------------------------------------
+constexpr int DN_KS = 7, DN_NTMAX = 5, DN_MAXF = 5, DN_NGROUPS = 3; // 448 node slots; a column group has up to 80 columns of up to 5 fields
+constexpr int DN_NTGT = NREST - XLEN;                                 // 897 rows to fill
+constexpr int DN_ITERS = (DN_NTGT + 63) / 64;                         // 15 passes of 64 rows (4 waves x 16)
+constexpr int DN_TAB = 2 * NPARTY - 1;                                // limb pairs of 1/d at index d + NPARTY - 1, |d| <= 1453
+// per-proof workspace, u16: rest[1344] (ascending complement of I, zero behind 1304), w[448] (zero behind 407), l[960] (zero behind 897)
+constexpr int DN_WS_REST = 0, DN_WS_W = 1344, DN_WS_ELL = 1344 + 448, DN_WS = 1344 + 448 + 960;
+constexpr int DN_STAGE = 128 * NCHK + DN_MAXF * 32; // 64 rows of the widest group + per field a carry chunk and a tail chunk
+
+struct DenseFillField { uint32_t start, cols, col0; }; // image offset of row 407 of the field, columns per row, first column in the group
+struct DenseFillGroup { int nf, ncols; DenseFillField f[DN_MAXF]; };
+struct DenseFillArgs { DenseFillGroup g[DN_NGROUPS]; };
+
+__device__ __forceinline__ uint32_t dn_mul(uint32_t a, uint32_t b) { return gf_reduce_u32(__umul24(a, b)); } // a b < 2^32
+__device__ __forceinline__ uint32_t dn_diff(int d) { return (uint32_t)(d < 0 ? d + Q : d); }
+__device__ __forceinline__ uint32_t dn_inv(uint32_t a) // a^(q-2); 0 -> 0
+{
+    uint32_t r = 1, b = a;
+#pragma unroll 1
+    for (int e = Q - 2; e; e >>= 1) {
+        if (e & 1) r = dn_mul(r, b);
+        b = dn_mul(b, b);
+    }
+    return r;
+}
+
+// opened list -> status, rest, w, l of one proof; grid (6, n): block x owns entries [256 x, 256 x + 256) of the complement
+__global__ __launch_bounds__(256) void k_dense_setup(const uint8_t *__restrict__ img, size_t image_stride, uint32_t off_I,
+                                                     uint16_t *__restrict__ ws, uint32_t *__restrict__ status)
+{
+    __shared__ int mark_s[NPARTY];
+    __shared__ int cnt_s[256];
+    __shared__ uint16_t rest_s[NREST + 8];
+    __shared__ int bad_s;
+    const int tid = threadIdx.x, b = blockIdx.y;
+    for (int p = tid; p < NPARTY; p += 256) mark_s[p] = 0;
+    if (tid == 0) bad_s = 0;
+    __syncthreads();
+    if (tid < NOPEN) {
+        const uint32_t v = *reinterpret_cast<const uint16_t *>(img + (size_t)b * image_stride + off_I + 2 * tid);
+        if (v >= (uint32_t)NPARTY) atomicOr(&bad_s, 1);
+        else if (atomicAdd(&mark_s[v], 1) != 0) atomicOr(&bad_s, 1);
+    }
+    __syncthreads();
+    if (bad_s) { // I is public: a uniform branch
+        if (blockIdx.x == 0 && tid == 0) status[b] = 1;
+        return;
+    }
+    constexpr int PER = (NPARTY + 255) / 256; // 6 parties per thread
+    const int p0 = tid * PER, p1 = min(p0 + PER, NPARTY);
+    int cnt = 0;
+    for (int p = p0; p < p1; p++) cnt += mark_s[p] == 0;
+    cnt_s[tid] = cnt;
+    __syncthreads();
+    int base = 0;
+    for (int t = 0; t < tid; t++) base += cnt_s[t];
+    for (int p = p0; p < p1; p++)
+        if (mark_s[p] == 0) rest_s[base++] = (uint16_t)p;
+    __syncthreads();
+    uint16_t *wsb = ws + (size_t)b * DN_WS;
+    if (blockIdx.x == 0) {
+        if (tid == 0) status[b] = 0;
+        for (int r = tid; r < DN_WS_W; r += 256) wsb[DN_WS_REST + r] = r < NREST ? rest_s[r] : (uint16_t)0;
+    }
+    const int r = blockIdx.x * 256 + tid;
+    if (r < NREST) {
+        const int xr = rest_s[r];
+        uint32_t pr = 1;
+        for (int m = 0; m < XLEN; m++) {
+            const uint32_t d = dn_diff(xr - (int)rest_s[m]);
+            pr = dn_mul(pr, m == r ? 1u : d);
+        }
+        if (r < XLEN) wsb[DN_WS_W + r] = (uint16_t)dn_inv(pr); // w_j = 1 / prod_{m != j} (x_j - x_m)
+        else wsb[DN_WS_ELL + r - XLEN] = (uint16_t)pr;          // l(x_i) = prod_j (x_i - x_j)
+    } else {
+        const int z = r - NREST; // the padding both vectors need, written by the last block's idle threads
+        if (z < 448 - XLEN) wsb[DN_WS_W + XLEN + z] = 0;
+        else if (z - (448 - XLEN) < 960 - DN_NTGT) wsb[DN_WS_ELL + DN_NTGT + z - (448 - XLEN)] = 0;
+    }
+}
+
+// One workgroup per (column group, proof).  The rows a field gains are one contiguous byte range of the image; the workgroup
+// walks it 64 rows at a time through an LDS buffer per field and writes it out in aligned 16-byte chunks, carrying the
+// bytes behind the last whole chunk to the next pass.  The first chunk is completed with the kept bytes in front of the range
+// and the last one with the bytes behind it (the next field's kept rows), both read from the image and written back as they
+// are: no other workgroup writes those bytes.
+template <int NT>
+__device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, const DenseFillGroup &g, const uint16_t *tab_s, const uint16_t *rest_s,
+                                                const uint16_t *ell_s, const uint8_t *y_s, uint8_t *stage_s, const uint32_t *cstart_s,
+                                                const uint16_t *ccols_s, const uint16_t *ccf_s, const uint16_t *csb_s)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint16_t *stage16 = reinterpret_cast<uint16_t *>(stage_s);
+#pragma unroll 1
+    for (int it = 0; it < DN_ITERS; it++) {
+        const int m0 = it * 64 + wv * 16;
+        if (m0 < DN_NTGT) { // uniform per wave
+            const int ri = min(XLEN + m0 + (lane & 15), NREST - 1); // rows behind 1303 repeat the last one and are not stored
+            const int kq = (int)rest_s[ri] + NPARTY - 1;
+            v4i s0[NT], s1[NT], s2[NT];
+#pragma unroll
+            for (int j = 0; j < NT; j++) { s0[j] = (v4i){0, 0, 0, 0}; s1[j] = s0[j]; s2[j] = s0[j]; }
+#pragma unroll
+            for (int ks = 0; ks < DN_KS; ks++) {
+                // operand fragment: 1/(x_i - x_j) for the 16 nodes j = 64 ks + 16 (lane >> 4) + q, as (low limb | high limb << 8)
+                const uint16_t *rn = rest_s + ks * 64 + (lane >> 4) * 16;
+                const uint4 r0 = *reinterpret_cast<const uint4 *>(rn), r1 = *reinterpret_cast<const uint4 *>(rn + 8);
+                const uint32_t rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
+                uint32_t e[16];
+#pragma unroll
+                for (int q = 0; q < 16; q++) {
+                    const int xj = (int)((rw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
+                    e[q] = tab_s[kq - xj]; // in [0, 2906]: both are parties below 1454
+                }
+                uint32_t lo[4], hi[4];
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const uint32_t t01 = e[4 * q] | (e[4 * q + 1] << 16), t23 = e[4 * q + 2] | (e[4 * q + 3] << 16);
+                    lo[q] = __builtin_amdgcn_perm(t23, t01, 0x06040200u);
+                    hi[q] = __builtin_amdgcn_perm(t23, t01, 0x07050301u);
+                }
+                const v4i a0 = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3]}, a1 = {(int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
+#pragma unroll
+                for (int j = 0; j < NT; j++) {
+                    const uint8_t *yt = y_s + (size_t)((ks * NT + j) * 2) * 1024 + lane * 16;
+                    const v4i b0 = *reinterpret_cast<const v4i *>(yt), b1 = *reinterpret_cast<const v4i *>(yt + 1024);
+                    s0[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, s0[j], 0, 0, 0);
+                    s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b1, s1[j], 0, 0, 0);
+                    s2[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, s2[j], 0, 0, 0);
+                    s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b0, s1[j], 0, 0, 0);
+                }
+            }
+            // D[row = target m0 + 4 (lane >> 4) + r][col = column 16 j + (lane & 15)]
+            const int tr = m0 + (lane >> 4) * 4;
+#pragma unroll
+            for (int j = 0; j < NT; j++) {
+                const int col = j * 16 + (lane & 15);
+                const uint32_t cols = ccols_s[col];
+                if (cols == 0) continue; // padding column
+                const uint32_t carry = (cstart_s[col] + (uint32_t)it * 128u * cols) & 15u;
+                const uint32_t at = (uint32_t)csb_s[col] + carry + 2u * ccf_s[col];
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    if (tr + r >= DN_NTGT) continue;
+                    const uint32_t v = dn_mul(ell_s[tr + r], gf_reduce_limbs(s0[j][r], s1[j][r], s2[j][r]));
+                    stage16[(at + (uint32_t)(tr + r - it * 64) * cols * 2u) >> 1] = (uint16_t)v;
+                }
+            }
+        }
+        // the tail chunk of the last pass is completed with the image's bytes behind the range
+        const int rows = min(64, DN_NTGT - it * 64);
+        uint32_t keep[DN_MAXF];
+#pragma unroll
+        for (int f = 0; f < DN_MAXF; f++) {
+            keep[f] = 0;
+            if (f >= g.nf) continue;
+            const uint32_t cols = g.f[f].cols, pos = g.f[f].start + (uint32_t)it * 128u * cols, carry = pos & 15u;
+            const uint32_t total = carry + (uint32_t)rows * cols * 2u, sb = csb_s[g.f[f].col0];
+            if (it == DN_ITERS - 1 && (total & 15u) && tid < 8 && total + 2u * tid < ((total + 15u) & ~15u))
+                stage16[(sb + total) / 2 + tid] = *reinterpret_cast<const uint16_t *>(imgb + (pos - carry) + total + 2 * tid);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int f = 0; f < DN_MAXF; f++) {
+            if (f >= g.nf) continue;
+            const uint32_t cols = g.f[f].cols, pos = g.f[f].start + (uint32_t)it * 128u * cols, carry = pos & 15u;
+            const uint32_t total = carry + (uint32_t)rows * cols * 2u, sb = csb_s[g.f[f].col0];
+            const uint32_t nfull = it == DN_ITERS - 1 ? (total + 15u) >> 4 : total >> 4;
+            for (uint32_t k = tid; k < nfull; k += 256)
+                *reinterpret_cast<uint4 *>(imgb + (pos - carry) + 16 * k) = *reinterpret_cast<const uint4 *>(stage_s + sb + 16 * k);
+            // the bytes behind the last whole chunk (bit 16: this thread's pair is one of them)
+            if (2u * tid < (total & 15u) && it < DN_ITERS - 1) keep[f] = stage16[(sb + 16 * nfull) / 2 + tid] | 0x10000u;
+        }
+        __syncthreads();
+        if (tid < 8) {
+#pragma unroll
+            for (int f = 0; f < DN_MAXF; f++)
+                if (f < g.nf && (keep[f] >> 16)) stage16[csb_s[g.f[f].col0] / 2 + tid] = (uint16_t)keep[f];
+        }
+        // the next pass writes behind its carry, i.e. behind these bytes; its flush comes after the next barrier
+    }
+}
+
+__global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, size_t image_stride, DenseFillArgs A, const uint16_t *__restrict__ ws,
+                                                    const uint32_t *__restrict__ status)
+{
+    __shared__ __attribute__((aligned(16))) uint8_t y_s[DN_KS * DN_NTMAX * 2048];
+    __shared__ __attribute__((aligned(16))) uint8_t stage_s[DN_STAGE];
+    __shared__ __attribute__((aligned(16))) uint16_t rest_s[DN_WS_W];
+    __shared__ __attribute__((aligned(4))) uint16_t tab_s[DN_TAB + 1];
+    __shared__ uint16_t ell_s[960];
+    __shared__ uint32_t cstart_s[DN_NTMAX * 16];
+    __shared__ uint16_t ccols_s[DN_NTMAX * 16], ccf_s[DN_NTMAX * 16], csb_s[DN_NTMAX * 16];
+    const int tid = threadIdx.x, b = blockIdx.y;
+    if (status[b]) return; // malformed opened list: nothing is written
+    const DenseFillGroup &g = A.g[blockIdx.x];
+    uint8_t *imgb = img + (size_t)b * image_stride;
+    const uint16_t *wsb = ws + (size_t)b * DN_WS;
+    const int nt = (g.ncols + 15) >> 4;
+
+    for (int i = tid; i < DN_TAB; i += 256) { // limb pairs of 1/d, d = i - 1453 (0 for d = 0: met only by zero shares)
+        const int d = i - (NPARTY - 1);
+        const uint32_t v = dn_inv(dn_diff(d));
+        int c0, c1;
+        limb_split(gf_center(v), c0, c1);
+        tab_s[i] = (uint16_t)((c0 & 0xFF) | ((c1 & 0xFF) << 8));
+    }
+    for (int i = tid; i < DN_WS_W; i += 256) rest_s[i] = wsb[DN_WS_REST + i];
+    for (int i = tid; i < 960; i += 256) ell_s[i] = wsb[DN_WS_ELL + i];
+    if (tid < DN_NTMAX * 16) { // column -> field, column in the field, the field's LDS buffer
+        uint32_t start = 0, cols = 0, cf = 0, sb = 0, o = 0;
+        for (int f = 0; f < g.nf; f++) {
+            if ((uint32_t)tid >= g.f[f].col0 && (uint32_t)tid < g.f[f].col0 + g.f[f].cols) { start = g.f[f].start; cols = g.f[f].cols; cf = tid - g.f[f].col0; sb = o; }
+            o += 128 * g.f[f].cols + 32;
+        }
+        cstart_s[tid] = start; ccols_s[tid] = (uint16_t)cols; ccf_s[tid] = (uint16_t)cf; csb_s[tid] = (uint16_t)sb;
+    }
+    __syncthreads();
+    // weighted shares w_j (y[j][c] mod q) of this group's columns as fragment tiles [k-step][column tile][limb] of 1 KiB: lane
+    // 16 (j / 16 % 4) + c % 16 holds its 16 consecutive nodes.  One thread per (column, 16 nodes), consecutive threads on consecutive columns
+    const int ncp = nt * 16;
+    for (int t = tid; t < ncp * DN_KS * 4; t += 256) {
+        const int c = t % ncp, kc16 = t / ncp;
+        const uint32_t cols = ccols_s[c];
+        uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (cols) {
+            const uint8_t *src = imgb + (cstart_s[c] - (uint32_t)XLEN * cols * 2u) + 2u * ccf_s[c]; // row 0 of the field, this column
+#pragma unroll
+            for (int q = 0; q < 16; q++) {
+                const int j = kc16 * 16 + q;
+                uint32_t v = 0;
+                if (j < XLEN) v = dn_mul(wsb[DN_WS_W + j], *reinterpret_cast<const uint16_t *>(src + (size_t)j * cols * 2)); // w < q, any u16
+                o[q >> 1] |= v << (16 * (q & 1));
+            }
+        }
+        uint4 lo, hi;
+        gm_split16(make_uint4(o[0], o[1], o[2], o[3]), make_uint4(o[4], o[5], o[6], o[7]), lo, hi);
+        uint8_t *d = y_s + (size_t)(((kc16 >> 2) * nt + (c >> 4)) * 2) * 1024 + ((kc16 & 3) * 16 + (c & 15)) * 16;
+        *reinterpret_cast<uint4 *>(d) = lo;
+        *reinterpret_cast<uint4 *>(d + 1024) = hi;
+    }
+    // the bytes between the 16-byte boundary and the first filled row: kept rows, read back from the image
+    if (tid < 8)
+        for (int f = 0; f < g.nf; f++) {
+            const uint32_t carry = g.f[f].start & 15u;
+            if (2u * tid < carry)
+                reinterpret_cast<uint16_t *>(stage_s)[csb_s[g.f[f].col0] / 2 + tid] = *reinterpret_cast<const uint16_t *>(imgb + (g.f[f].start - carry) + 2 * tid);
+        }
+    __syncthreads();
+    if (nt == 5) dense_fill_body<5>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
+    else if (nt == 4) dense_fill_body<4>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
+    else dense_fill_body<3>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
+}
+
+static DenseFillArgs make_fill_args(const Params &P)
+{
+    DenseFillArgs a{};
+    auto put = [&](DenseFillGroup &g, int f) {
+        DenseFillField &d = g.f[g.nf++];
+        d.cols = dense_cols(P, f);
+        d.start = (uint32_t)(P.off[f] + (size_t)XLEN * d.cols * 2);
+        d.col0 = (uint32_t)g.ncols;
+        g.ncols += (int)d.cols;
+    };
+    put(a.g[0], F_BETA);
+    put(a.g[1], F_GAMMA);
+    for (int f : {F_T, F_SR, F_ER, F_SETA, F_EETA}) put(a.g[2], f); // 34 / 39 / 52 columns (K = 2 / 3 / 4)
+    return a;
+}
+
+int ensure_dense_ws(Ctx &c)
+{
+    if (c.d_dense_ws) return 0;
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_ws), (size_t)c.own_batch * DN_WS * sizeof(uint16_t)));
+    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_status), sizeof(uint32_t) * c.own_batch));
+    return 0;
+}
+
+// rows 407..1303 of the seven fields of n <= own_batch images in HBM, in place, on the context's stream (no synchronisation)
+int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
+    if ((reinterpret_cast<uintptr_t>(d_images) | image_stride) & 15) { c.err = "dense fill: images and their stride must be 16-byte aligned"; return -1; }
+    if (image_stride < c.P.proof_bytes) { c.err = "dense fill: image stride below kosk_proof_bytes"; return -1; }
+    if (ensure_dense_ws(c)) return -1;
+    const DenseFillArgs a = make_fill_args(c.P);
+    hipLaunchKernelGGL(k_dense_setup, dim3(6, n), dim3(256), 0, c.stream, d_images, image_stride, (uint32_t)c.P.off[F_I], c.d_dense_ws, d_status);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_dense_fill, dim3(DN_NGROUPS, n), dim3(256), 0, c.stream, d_images, image_stride, a, c.d_dense_ws, d_status);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_DENSE_FILL]++;
+    return 0;
+}
+
+int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    HIPCHK(hipSetDevice(c.device));
+    for (int done = 0; done < n;) {
+        const int m = n - done < c.own_batch ? n - done : c.own_batch;
+        if (dense_fill_launch(c, m, d_images + (size_t)done * image_stride, image_stride, d_status + done)) return -1;
+        done += m;
+    }
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1;
+    return 0;
+}
+
+} // namespace kosk
