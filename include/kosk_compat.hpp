@@ -175,6 +175,19 @@ inline int crypto_kem_dec(uint8_t *ss, const uint8_t *ct, const uint8_t *sk)
     return 0;
 }
 
+/* ---- ordinary key pairs (kyber/kem.h: crypto_kem_keypair_derand, crypto_kem_keypair; kem.c:25-57), one item per call on the
+ * process-wide handle: coins = d || z, 64 bytes; without coins they come from randombytes (one call of 64 bytes) ---- */
+inline int crypto_kem_keypair_derand(uint8_t *pk, uint8_t *sk, const uint8_t *coins)
+{
+    kosk_compat::must(kosk_kem_keypair_batch(kosk_compat::ctx(), 1, coins, pk, sk), "crypto_kem_keypair_derand");
+    return 0;
+}
+inline int crypto_kem_keypair(uint8_t *pk, uint8_t *sk)
+{
+    kosk_compat::must(kosk_kem_keypair_batch(kosk_compat::ctx(), 1, nullptr, pk, sk), "crypto_kem_keypair");
+    return 0;
+}
+
 /* ---- a proof for a key pair that already exists (no reference counterpart; kosk_prove_keys_batch on the process-wide handle): one
  * proof of knowledge of keypair->sk's s, e into pi, the randomness drawn through randombytes as kyber_verifiable_keygen draws it
  * minus the key generation's 64 bytes.  false (pi all zero) for a record whose s or e is outside the key generation's range. ---- */

@@ -248,6 +248,25 @@ int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *s
  * by a call that replaced the resident keys (a key generation, a verifier staging call in any wire format: image, compact (kosk_stage_verifier_inputs_compact, kosk_verify_batch_compact) or dense (kosk_stage_verifier_inputs_dense, kosk_verify_batch_dense)); and for a member of a cohort (combine >= 2): "not available with call combining". */
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
+ * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
+ * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
+ * n records of kosk_pk_bytes / kosk_sk_bytes, sk = tobytes(NTT(s)) || pk || SHA3-256(pk) || z; host or device memory like every KEM
+ * buffer.  The call does not touch the prover's and verifier's resident state (kosk_kem_enc_verified after it behaves as before it).
+ * No branch and no address depends on d, the noise seed, s, e or z (only gen_matrix's rejection sampling, on the public rho, branches
+ * on data); z is copied, never hashed.  The secret scratch (d || z, the noise seed, s, e, the sk records) stays in the handle's HBM
+ * workspace until a later KEM call overwrites it or the handle is destroyed.  -1 with a text and nothing started
+ * for n < 1 or a NULL pk / sk; -1 ("block limit", no results, device outputs untouched) if gen_matrix reached its block limit. */
+int kosk_kem_keypair_batch(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk);
+/* The input checks of FIPS 203 for n >= 1 records, host or device memory; flags: n bytes, host or device memory, flags[b] about
+ * record b alone, 0 = passes.  Read-only: kosk_kem_enc_batch / kosk_kem_dec_batch keep folding fields >= q and trusting the stored
+ * H(pk), whatever these calls say.  The test over s-hat is sign-mask arithmetic and an OR-reduction. */
+#define KOSK_KEYCHK_HASH     1   /* SHA3-256(pk inside sk) != stored H(pk)          FIPS 203 7.3 */
+#define KOSK_KEYCHK_PK_RANGE 2   /* a 12-bit field of t-hat is >= q                 FIPS 203 7.2 */
+#define KOSK_KEYCHK_S_RANGE  4   /* a 12-bit field of s-hat is >= q                 (not in the standard; reported separately) */
+int kosk_kem_check_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *flags);   /* 0 or KOSK_KEYCHK_PK_RANGE */
+int kosk_kem_check_sk(kosk_ctx *ctx, int n, const uint8_t *sk, uint8_t *flags);   /* OR of the three; 0 = passes */
+
 /* ---- Proofs for Kyber keys that already exist.  sk: n consecutive records of kosk_sk_bytes,
  * NTT(s) bytes || pk || H(pk) || z, from this library or any other Kyber implementation; host or device memory.  H(pk) and z are not read.
  * The witness is recovered on the device: s = NTT^-1(s-hat), e = NTT^-1(t-hat - A o s-hat) with t-hat and A from the pk INSIDE the record.
@@ -288,7 +307,8 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * whose digest table was copied to the host (host Fiat-Shamir mode), 8 small copies between HBM and the library's own page-locked buffers
  * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded
  * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls,
- * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch). */
+ * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch),
+ * 15 kem_keypair / 16 kem_check: launch groups of kosk_kem_keypair_batch and of kosk_kem_check_pk / kosk_kem_check_sk. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

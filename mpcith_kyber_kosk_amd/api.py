@@ -150,6 +150,14 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_dense_proof_bytes")):
         sig.update(dense)
+    # KEM key pairs and key checks; optional under the same rule (and only then)
+    keypair = {
+        "kosk_kem_keypair_batch": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_kem_check_pk": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_kem_check_sk": (C.c_int, [vp, C.c_int, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_keypair_batch")):
+        sig.update(keypair)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -178,7 +186,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_fs_opened_bound_device", "kosk_set_contexts",
            "kosk_dense_proof_bytes", "kosk_proof_dense_pack", "kosk_proof_dense_unpack", "kosk_fetch_proofs_dense",
            "kosk_stage_verifier_inputs_dense", "kosk_verifiable_keygen_batch_dense", "kosk_verifiable_keygen_seeded_batch_dense",
-           "kosk_verify_batch_dense", "kosk_dense_fill_device"]
+           "kosk_verify_batch_dense", "kosk_dense_fill_device",
+           "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -193,6 +202,8 @@ FS_HOST, FS_DEVICE = 0, 1
 ENTROPY_TAPE, ENTROPY_SEED = 0, 1  # kosk_set_entropy
 SEED_BYTES = 32
 SS_BYTES = 32  # KOSK_SS_BYTES
+KEYPAIR_COIN_BYTES = 64  # d || z of crypto_kem_keypair_derand
+KEYCHK_HASH, KEYCHK_PK_RANGE, KEYCHK_S_RANGE = 1, 2, 4  # KOSK_KEYCHK_*
 
 
 def options(**fields):
@@ -736,6 +747,36 @@ class Kosk:
             return out
         return _cut(bufs[0], SS_BYTES, n)
 
+    def kem_keypair(self, coins=None, n=None, out=None):
+        """crypto_kem_keypair_derand for n items (kosk_kem_keypair_batch).  coins: a list of 64-byte values (d || z) or an int DEVICE
+        pointer (with n); None: one 64-byte draw per item through the randombytes callback / OS entropy (with n, default 1).  Returns
+        (pks, sks) as lists of bytes, or, with out=(d_pk, d_sk) int device pointers, writes there and returns out."""
+        cp, _k = None, None
+        if coins is not None:
+            cp, n, _k = self._records("coins", coins, n, KEYPAIR_COIN_BYTES)
+        elif n is None:
+            n = 1
+        bufs, host = self._kem_out(out, n, (self.pk_bytes, self.sk_bytes))
+        self._chk(lib.kosk_kem_keypair_batch(self._h, n, cp, bufs[0], bufs[1]), "kem_keypair")
+        if host is None:
+            return out
+        return _cut(bufs[0], self.pk_bytes, n), _cut(bufs[1], self.sk_bytes, n)
+
+    def _kem_check(self, fn, what, recs, n, size):
+        rp, n, _k = self._records(what, recs, n, size)
+        flags = C.create_string_buffer(max(n, 1))
+        self._chk(fn(self._h, n, rp, flags), "kem_check_" + what)
+        return list(flags.raw[:n])
+
+    def kem_check_pk(self, pks, n=None):
+        """kosk_kem_check_pk: per public key 0 or KEYCHK_PK_RANGE (a 12-bit field >= q, FIPS 203 7.2).  pks: list of bytes or an int
+        DEVICE pointer (with n)"""
+        return self._kem_check(lib.kosk_kem_check_pk, "pk", pks, n, self.pk_bytes)
+
+    def kem_check_sk(self, sks, n=None):
+        """kosk_kem_check_sk: per secret key the OR of KEYCHK_HASH (FIPS 203 7.3), KEYCHK_PK_RANGE and KEYCHK_S_RANGE; 0 = passes"""
+        return self._kem_check(lib.kosk_kem_check_sk, "sk", sks, n, self.sk_bytes)
+
     def kem_enc_verified(self, n, coins=None):
         """kosk_kem_enc_verified: encapsulate to the public keys the last completed verify call left in HBM, where its verify bit is 1.
         Returns (cts, sss, done); ct and ss of a rejected position are zero-filled."""
@@ -806,6 +847,8 @@ class Kosk:
 
     # ids behind PATH_IDS (that list is what path_counts() walks and stays as it is)
     PATH_DENSE_FILL = 14
+    PATH_KEM_KEYPAIR = 15
+    PATH_KEM_CHECK = 16
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

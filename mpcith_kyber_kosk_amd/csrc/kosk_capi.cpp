@@ -1176,6 +1176,46 @@ int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *s
     });
     GUARD_END
 }
+// crypto_kem_keypair[_derand] (kem.c:25-57): the caller's coins, or one 64-byte draw (d || z) per item, in item order, on the caller's
+// thread (kem.c:53-54).  Only the KEM workspace is written: pk_epoch, the resident keys and verify_keys stay as they are.
+int kosk_kem_keypair_batch(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk)
+{
+    if (!ctx || n < 1 || !pk || !sk) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    std::vector<uint8_t> drawn;
+    if (!coins) {
+        drawn.resize((size_t)n * 64);
+        const Ctx &c0 = *ctx->c;
+        for (int b = 0; b < n; b++) {
+            uint8_t *dst = drawn.data() + (size_t)b * 64;
+            if (c0.rb) c0.rb(c0.rb_user, dst, 64);
+            else os_randombytes(dst, 64);
+        }
+        coins = drawn.data();
+    }
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_keypair(c, count, coins + (size_t)first * 64, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes);
+    });
+    GUARD_END
+}
+static_assert(KOSK_KEYCHK_HASH == KEYCHK_HASH && KOSK_KEYCHK_PK_RANGE == KEYCHK_PK_RANGE && KOSK_KEYCHK_S_RANGE == KEYCHK_S_RANGE, "kosk_mi355x.h and kosk_ctx.hpp");
+int kosk_kem_check_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *flags)
+{
+    if (!ctx || n < 1 || !pk || !flags) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) { return kem_check(c, count, pk + (size_t)first * P.pk_bytes, 0, flags + first); });
+    GUARD_END
+}
+int kosk_kem_check_sk(kosk_ctx *ctx, int n, const uint8_t *sk, uint8_t *flags)
+{
+    if (!ctx || n < 1 || !sk || !flags) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) { return kem_check(c, count, sk + (size_t)first * P.sk_bytes, 1, flags + first); });
+    GUARD_END
+}
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
 {
     if (!ctx || n < 1 || !ct || !ss || !done) return bad_args(ctx, __func__);

@@ -72,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -492,6 +492,11 @@ int verify_resident(Ctx &c, int n, uint8_t *ok, int pk_mode = 0, const uint8_t *
 // nullptr): items whose byte is 0 are not encapsulated to, their ct and ss are zero-filled.  crypto_kem_dec (kem.c:140-169).
 int kem_enc(Ctx &c, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask = nullptr, int resident_first = 0);
 int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss);
+// crypto_kem_keypair_derand (kem.c:25-35): coins n x 64 bytes, d || z.  Touches the KEM workspace only: not pk_epoch, not the resident keys.
+int kem_keypair(Ctx &c, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk);
+// FIPS 203 7.2 / 7.3 input checks on n pk (is_sk = 0) or sk records: flags[b] = OR of KOSK_KEYCHK_* (kosk_mi355x.h)
+enum { KEYCHK_HASH = 1, KEYCHK_PK_RANGE = 2, KEYCHK_S_RANGE = 4 }; // KOSK_KEYCHK_* (kosk_capi.cpp asserts the equality)
+int kem_check(Ctx &c, int n, const uint8_t *rec, int is_sk, uint8_t *flags);
 void kem_release(Ctx &c);
 
 } // namespace kosk

@@ -123,14 +123,26 @@ KOSK_HD inline void invntt_tile(uint16_t *L, int np, int tid, int nthr)
 
 // eight 12-bit values from 12 bytes at a 4-byte aligned address (poly_frombytes, poly.c:150-158), folded mod q as the reference's
 // arithmetic does with them
-KOSK_HD inline void load12x8(const uint8_t *p, uint32_t (&c)[8])
+KOSK_HD inline void unpack12x8(const uint8_t *p, uint32_t (&c)[8]) // the fields as they stand, in [0, 4096)
 {
     const uint32_t *w = reinterpret_cast<const uint32_t *>(p);
     const uint32_t w0 = w[0], w1 = w[1], w2 = w[2];
     c[0] = w0 & 0xFFF; c[1] = (w0 >> 12) & 0xFFF; c[2] = ((w0 >> 24) | (w1 << 8)) & 0xFFF; c[3] = (w1 >> 4) & 0xFFF;
     c[4] = (w1 >> 16) & 0xFFF; c[5] = ((w1 >> 28) | (w2 << 4)) & 0xFFF; c[6] = (w2 >> 8) & 0xFFF; c[7] = w2 >> 20;
+}
+KOSK_HD inline void load12x8(const uint8_t *p, uint32_t (&c)[8])
+{
+    unpack12x8(p, c);
 #pragma unroll
     for (int i = 0; i < 8; i++) c[i] = csub(c[i]);
+}
+// the inverse for eight canonical residues (poly_tobytes, poly.c:128-147): 12 bytes at a 4-byte aligned address
+KOSK_HD inline void store12x8(uint8_t *p, const uint32_t (&c)[8])
+{
+    uint32_t *w = reinterpret_cast<uint32_t *>(p);
+    w[0] = c[0] | (c[1] << 12) | (c[2] << 24);
+    w[1] = (c[2] >> 8) | (c[3] << 4) | (c[4] << 16) | (c[5] << 28);
+    w[2] = (c[5] >> 4) | (c[6] << 8) | (c[7] << 20);
 }
 KOSK_HD inline void load16x8(const void *p, uint32_t (&c)[8]) // eight u16 at a 16-byte aligned address: one 16-byte load
 {
@@ -434,6 +446,87 @@ KOSK_HD inline void decrypt_block(const Dims &D, uint16_t *L, uint8_t *Lb, int t
     }
     KEM_SYNC();
 }
+
+// ------------------------------------------------------------------------------------------- indcpa_keypair_derand --
+// (rho, sigma) = hash_g (sha3_512) of d[32] || K (indcpa.c:219-221): 33 bytes, rate 72
+KOSK_HD inline void seed_hash_g(const uint64_t (&d)[4], int K, uint64_t (&out)[8])
+{
+    uint64_t s[25];
+    zero(s);
+#pragma unroll
+    for (int l = 0; l < 4; l++) s[l] = d[l];
+    s[4] = (uint64_t)(uint32_t)K | (0x06ULL << 8);
+    s[8] = 0x8000000000000000ULL;
+    perm(s);
+#pragma unroll
+    for (int l = 0; l < 8; l++) out[l] = s[l];
+}
+
+// One workgroup, one key pair (indcpa.c:231-244, kem.c:29-33).  LDS tile L: 2 K polynomials of 256 u16 -- s-hat[K] | e-hat[K], then
+// t-hat[K] in e-hat's place; Lb: the sk record (768 K + 96 bytes, 16-byte aligned) as it will stand, its H(pk) field zero.
+//   A     : A[K][K][256] int16 in [0, q), row-major as multiplied (t-hat_i = sum_j A[i][j] o s-hat_j), 16-byte aligned
+//   noise : s[K] | e[K], int16[256] each, 16-byte aligned             rho, z : 32 bytes each, 4-byte aligned
+// tomont cancels the Montgomery factor of the reference's base multiplication, so on residues t-hat = A o s-hat + e-hat.
+// pk_out and sk_out (16-byte aligned) receive whole records in 16-byte stores; the caller's hash fills sk_out's H(pk) afterwards.
+// Secrets: s, e, s-hat and z are data only; every address is a function of the thread index.
+KOSK_HD inline void keypair_block(const Dims &D, uint16_t *L, uint8_t *Lb, int tid, int nthr, const int16_t *A, const int16_t *noise,
+                                  const uint8_t *rho, const uint8_t *z, uint8_t *pk_out, uint8_t *sk_out)
+{
+    const int K = D.K;
+    for (int w = tid; w < 2 * K * 32; w += nthr) {
+        uint32_t c[8];
+        load16x8(noise + 8 * w, c);
+#pragma unroll
+        for (int i = 0; i < 8; i++) { const int32_t e = (int16_t)c[i]; c[i] = (uint32_t)(e + ((e >> 31) & Q)); }
+        store16x8(L + 8 * w, c);
+    }
+    KEM_SYNC();
+    ntt_tile(L, 2 * K, tid, nthr);
+    // t-hat_i over e-hat_i: group (i, g) of e-hat is read and written by this work item alone, s-hat is only read
+    for (int w = tid; w < K * 32; w += nthr) {
+        const int i = w >> 5, g = w & 31;
+        uint32_t acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, e[8];
+        for (int j = 0; j < K; j++) {
+            uint32_t a[8], b[8];
+            load16x8(A + ((i * K + j) * 256 + 8 * g), a);
+            load16x8(L + j * 256 + 8 * g, b);
+            basemul8_acc(acc, a, b, g);
+        }
+        load16x8(L + (K + i) * 256 + 8 * g, e);
+#pragma unroll
+        for (int c = 0; c < 8; c++) acc[c] = csub(acc[c] + e[c]);
+        store16x8(L + (K + i) * 256 + 8 * g, acc);
+    }
+    KEM_SYNC();
+    // sk = tobytes(s-hat) || tobytes(t-hat) || rho || H(pk) || z: polynomial o of the tile is bytes 384 o .. of the record
+    for (int w = tid; w < 2 * K * 32; w += nthr) {
+        uint32_t c[8];
+        load16x8(L + 8 * w, c);
+        store12x8(Lb + 12 * w, c);
+    }
+    for (int i = tid; i < 8; i += nthr) {
+        uint32_t *tail = reinterpret_cast<uint32_t *>(Lb + 2 * D.pvb);
+        tail[i] = reinterpret_cast<const uint32_t *>(rho)[i];
+        tail[8 + i] = 0;
+        tail[16 + i] = reinterpret_cast<const uint32_t *>(z)[i];
+    }
+    KEM_SYNC();
+    for (int i = tid; i < D.sk / 16; i += nthr) reinterpret_cast<U128 *>(sk_out)[i] = reinterpret_cast<const U128 *>(Lb)[i];
+    for (int i = tid; i < D.pk / 16; i += nthr) reinterpret_cast<U128 *>(pk_out)[i] = reinterpret_cast<const U128 *>(Lb + D.pvb)[i];
+}
+
+// ------------------------------------------------------------------------------------------------------ key checks --
+// non-zero iff one of the eight 12-bit fields at the 4-byte aligned p is >= q (FIPS 203 7.2): the sign bits of q - 1 - c, no branch
+KOSK_HD inline uint32_t range12x8(const uint8_t *p)
+{
+    uint32_t c[8], bad = 0;
+    unpack12x8(p, c);
+#pragma unroll
+    for (int i = 0; i < 8; i++) bad |= ((uint32_t)(Q - 1) - c[i]) >> 31;
+    return bad;
+}
+// 1 iff x != 0, for x < 2^24, without a branch
+KOSK_HD inline uint32_t nonzero_bit(uint32_t x) { return ((x + 0xFFFFFFu) >> 24) & 1u; }
 
 // ss = fail ? rk : kbar without a branch: `diff` is the OR of all byte differences (0 .. 255)
 KOSK_HD inline uint8_t select_ss(uint32_t diff, uint8_t kbar, uint8_t rk)

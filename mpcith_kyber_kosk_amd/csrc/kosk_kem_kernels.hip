@@ -14,6 +14,16 @@
 // single-wave latency, so it runs as one WAVE per item on the wave sponge (kosk_keccak_wave_dev.hpp), launched ahead of k_kem_hash: H(pk) on
 // k_fs_chain<FS_DIGEST> (kosk_fs_kernels.hip), after which the seed role only does G; rkprf on k_kem_rkprf_wave below (SHAKE domain,
 // two-part message).  The device functions are in kosk_kem_dev.hpp; DESIGN.md 19 has the resource figures.
+//
+// crypto_kem_keypair_derand (kem.c:25-35) for batches, in the same shape:
+//   key pair      k_kem_kg_hash role   (rho, sigma) = G(d || K)                      one sponge per lane, one lane per item
+//                 k_kem_kg_hash roles  gen_matrix (A, not transposed), s, e          (K^2 + 2 K) lanes per item
+//                 k_kem_keypair NTT(s), NTT(e), A o s-hat + e-hat, pack pk and sk    one workgroup per item
+//                 k_kem_hpk     H(pk) into the sk record                             one lane per item
+//   key checks    k_kem_hpk     H(pk inside sk)                                      one lane per item
+//                 k_kem_check   12-bit fields >= q, stored H(pk) against the computed one, OR-reduction   one wave per item
+// H(pk) is the third one-lane-per-item chain of this file: in a launch group of up to KEM_WAVE_MAX items it runs on k_fs_chain<FS_DIGEST>
+// like the encapsulation's, and k_kem_hpk only moves the digest into the record (key pair) or is not launched (checks).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -192,6 +202,118 @@ __global__ __launch_bounds__(256) void k_kem_decrypt(KemDecJob j)
     }
 }
 
+// ---- key pairs --------------------------------------------------------------------------------------------------------
+struct KemKgJob {
+    int n, K, eta1;
+    int n_seed, n_mat, n_noise; // lanes per item of each role, in launch order
+    const uint8_t *coins;       // [n][64]  d || z
+    uint8_t *rho, *sigma;       // [n][32] each: the seed role writes, the other two read
+    int16_t *A, *noise;         // [n][K K][256], [n][2 K][256]
+    uint32_t *err;
+    int max_blocks;
+};
+
+__global__ __launch_bounds__(64) void k_kem_kg_hash(KemKgJob j)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const int per = j.n_seed + j.n_mat + j.n_noise;
+    if (gid >= (long)per * j.n) return;
+    int t = (int)(gid / j.n);
+    const int b = (int)(gid - (long)t * j.n);
+    if (t < j.n_seed) {
+        uint64_t d[4], rs[8];
+#pragma unroll
+        for (int l = 0; l < 4; l++) d[l] = ld64(j.coins, 8 * b + l);
+        seed_hash_g(d, j.K, rs);
+#pragma unroll
+        for (int l = 0; l < 4; l++) {
+            reinterpret_cast<uint64_t *>(j.rho)[4 * (size_t)b + l] = rs[l];
+            reinterpret_cast<uint64_t *>(j.sigma)[4 * (size_t)b + l] = rs[4 + l];
+        }
+        return;
+    }
+    t -= j.n_seed;
+    if (t < j.n_mat) {
+        uint64_t rho[4];
+#pragma unroll
+        for (int l = 0; l < 4; l++) rho[l] = ld64(j.rho, 4 * b + l);
+        // A[i][j] = XOF(rho, j, i) (indcpa.c:179-180): entry t = i K + j
+        if (!matrix_entry(rho, t % j.K, t / j.K, j.max_blocks, j.A + ((size_t)b * j.n_mat + t) * 256))
+            if (j.err) *reinterpret_cast<volatile uint32_t *>(j.err) = DEVERR_XOF_BLOCKS;
+        return;
+    }
+    t -= j.n_mat;
+    uint64_t sigma[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) sigma[l] = ld64(j.sigma, 4 * b + l);
+    noise_poly(sigma, t, j.eta1, j.noise + ((size_t)b * j.n_noise + t) * 256); // s_i: nonce i, e_i: nonce K + i (indcpa.c:225-228)
+}
+
+struct KemKeypairJob {
+    int K;
+    const int16_t *A, *noise;
+    const uint8_t *rho, *coins; // [n][32], [n][64]
+    uint8_t *pk, *sk;           // [n][pk_bytes], [n][sk_bytes]
+};
+
+__global__ __launch_bounds__(256) void k_kem_keypair(KemKeypairJob j)
+{
+    __shared__ alignas(16) uint16_t L[8 * 256];
+    __shared__ alignas(16) uint8_t Lb[768 * 4 + 96];
+    const Dims D = dims(j.K);
+    const size_t b = blockIdx.x;
+    keypair_block(D, L, Lb, threadIdx.x, 256, j.A + b * (size_t)(D.K * D.K * 256), j.noise + b * (size_t)(2 * D.K * 256), j.rho + b * 32,
+                  j.coins + b * 64 + 32, j.pk + b * (size_t)D.pk, j.sk + b * (size_t)D.sk);
+}
+
+// sha3_256 of record b (`len` bytes at in + b * in_stride, 8-byte aligned), or h[b] where the wave sponge has computed it already, as two
+// 16-byte stores to out + b * out_stride (16-byte aligned).  One lane per item.
+__global__ __launch_bounds__(64) void k_kem_hpk(int n, const uint8_t *in, size_t in_stride, int len, const uint8_t *h, uint8_t *out, size_t out_stride)
+{
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= n) return;
+    uint64_t d[4];
+    if (h) {
+#pragma unroll
+        for (int l = 0; l < 4; l++) d[l] = ld64(h, 4 * (int)b + l);
+    } else {
+        sha3_256_words(in + (size_t)b * in_stride, len, d);
+    }
+    U128 *o = reinterpret_cast<U128 *>(out + (size_t)b * out_stride);
+    o[0] = U128{(uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32)};
+    o[1] = U128{(uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32)};
+}
+
+// ---- key checks (FIPS 203 7.2, 7.3) -----------------------------------------------------------------------------------
+struct KemCheckJob {
+    int K, is_sk;
+    const uint8_t *rec; // pk records, or sk records (s-hat || pk || H(pk) || z)
+    size_t stride;
+    const uint8_t *h;   // is_sk: [n][32] sha3_256 of the pk inside record b
+    uint8_t *flags;     // [n]
+};
+
+// One wave per record.  Every lane looks at groups of eight 12-bit fields (which group is a function of the lane alone); the range
+// test is sign-mask arithmetic (range12x8) and the verdict an OR over the wave: no branch and no address depends on s-hat.
+__global__ __launch_bounds__(64) void k_kem_check(KemCheckJob j)
+{
+    __shared__ uint32_t verdict;
+    const Dims D = dims(j.K);
+    const int lane = threadIdx.x;
+    const size_t b = blockIdx.x;
+    const uint8_t *rec = j.rec + b * j.stride;
+    if (lane == 0) verdict = 0;
+    __syncthreads();
+    uint32_t f = 0;
+    const int per = D.K * 32; // groups per polyvec; in an sk the pk's follow s-hat's directly
+    for (int w = lane; w < (j.is_sk ? 2 : 1) * per; w += 64)
+        f |= range12x8(rec + 12 * w) * (j.is_sk && w < per ? (uint32_t)KEYCHK_S_RANGE : (uint32_t)KEYCHK_PK_RANGE);
+    if (j.is_sk && lane < 32) f |= nonzero_bit((uint32_t)(j.h[b * 32 + lane] ^ rec[D.sk - 64 + lane])) * (uint32_t)KEYCHK_HASH;
+    atomicOr(&verdict, f);
+    __syncthreads();
+    if (lane == 0) j.flags[b] = (uint8_t)verdict;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host --
 #define HIPCHK(x) KOSK_HIPCHK(x)
 
@@ -336,6 +458,87 @@ int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;
     HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+// H(pk) of n records under the two-layout rule: up to kem_wave_max() items one wave per item into w.d_h (returns true: the caller
+// takes it from there), above that nothing is launched and the caller's one-lane-per-item kernel hashes (returns false)
+static int kem_hpk_wave(Ctx &c, int n, const uint8_t *in, size_t in_stride, int len, bool &done)
+{
+    done = n <= kem_wave_max();
+    if (!done) return 0;
+    FsArgs fa{};
+    fa.in = in; fa.in_stride = in_stride; fa.len = len; fa.out_digest = c.kem->d_h;
+    HIPCHK(launch_fs_chain(fa, FS_DIGEST, n, c.stream));
+    return 0;
+}
+
+int kem_keypair(Ctx &c, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk)
+{
+    if (n < 1 || n > KEM_CHUNK || !coins || !pk || !sk) { c.err = "kem_keypair: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    // workspace roles: d_kr coins (d || z), d_m rho, d_rk sigma, d_A A, d_noise s | e, d_pk / d_sk the records, d_h H(pk)
+    HIPCHK(kem_copy_in(c, w.d_kr, coins, (size_t)n * 64));
+    KemKgJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.coins = w.d_kr; h.rho = w.d_m; h.sigma = w.d_rk; h.A = w.d_A; h.noise = w.d_noise;
+    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
+    auto launch = [&]() {
+        const long lanes = (long)(h.n_seed + h.n_mat + h.n_noise) * n;
+        k_kem_kg_hash<<<dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, c.stream>>>(h);
+        return hipGetLastError();
+    };
+    h.n_seed = 1;
+    HIPCHK(launch());
+    h.n_seed = 0; h.n_mat = D.K * D.K; h.n_noise = 2 * D.K;
+    HIPCHK(launch());
+    KemKeypairJob k{};
+    k.K = D.K; k.A = w.d_A; k.noise = w.d_noise; k.rho = w.d_m; k.coins = w.d_kr; k.pk = w.d_pk; k.sk = w.d_sk;
+    k_kem_keypair<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(k);
+    HIPCHK(hipGetLastError());
+    bool wave = false;
+    if (kem_hpk_wave(c, n, w.d_pk, (size_t)D.pk, D.pk, wave)) return -1;
+    k_kem_hpk<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c.stream>>>(n, w.d_pk, (size_t)D.pk, D.pk, wave ? w.d_h : nullptr, w.d_sk + D.sk - 64, (size_t)D.sk);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_KEYPAIR]++;
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1; // gen_matrix block limit: no results
+    HIPCHK(kem_copy_out(c, pk, w.d_pk, (size_t)n * D.pk));
+    HIPCHK(kem_copy_out(c, sk, w.d_sk, (size_t)n * D.sk));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+int kem_check(Ctx &c, int n, const uint8_t *rec, int is_sk, uint8_t *flags)
+{
+    if (n < 1 || n > KEM_CHUNK || !rec || !flags) { c.err = "kem_check: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    KemCheckJob k{};
+    k.K = D.K; k.is_sk = is_sk; k.flags = w.d_mask;
+    if (is_sk) {
+        HIPCHK(kem_copy_in(c, w.d_sk, rec, (size_t)n * D.sk));
+        k.rec = w.d_sk; k.stride = (size_t)D.sk; k.h = w.d_h;
+        bool wave = false;
+        if (kem_hpk_wave(c, n, w.d_sk + D.pvb, (size_t)D.sk, D.pk, wave)) return -1;
+        if (!wave) {
+            k_kem_hpk<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c.stream>>>(n, w.d_sk + D.pvb, (size_t)D.sk, D.pk, nullptr, w.d_h, 32);
+            HIPCHK(hipGetLastError());
+        }
+    } else {
+        HIPCHK(kem_copy_in(c, w.d_pk, rec, (size_t)n * D.pk));
+        k.rec = w.d_pk; k.stride = (size_t)D.pk;
+    }
+    k_kem_check<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(k);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_CHECK]++;
+    HIPCHK(kem_copy_out(c, flags, w.d_mask, (size_t)n));
     HIPCHK(stream_sync(c));
     return 0;
 }
