@@ -101,6 +101,21 @@ Ctx::~Ctx()
     if (stream) (void)hipStreamDestroy(stream);
 }
 
+// A[m][k] (canonical) as a limb matrix in fragment-linear tile order (kosk_device.hpp: frag_offset): the table products load it
+// straight from global memory
+static void pack_frag_table(const std::vector<uint16_t> &A, int M, int Kdim, int Mpad, int KS, std::vector<uint8_t> &out)
+{
+    const int RT = Mpad / 16;
+    out.assign((size_t)KS * RT * 2048, 0);
+    for (int m = 0; m < M; m++)
+        for (int k = 0; k < Kdim; k++) {
+            int c0, c1;
+            limb_split(gf_center(A[(size_t)m * Kdim + k]), c0, c1);
+            out[frag_offset(m, k, 0, RT)] = (uint8_t)(int8_t)c0;
+            out[frag_offset(m, k, 1, RT)] = (uint8_t)(int8_t)c1;
+        }
+}
+
 static int upload_table(Ctx &c, GemmTable &t, const std::vector<uint16_t> &A, int M, int Kdim)
 {
     t.M = M;

@@ -6,16 +6,17 @@
 // This file holds the host codec (reference-grade: clarity over speed) and the refill on the GPU, which runs behind the
 // unpack kernel of kosk_compact.hip.  Kernel plan (DESIGN.md "Dense wire format"): the per-proof operator in barycentric form,
 //   out[i][c] = l_i * sum_j inv(x_i - x_j) * (w_j * y[j][c]),
-// k_dense_setup makes rest, the weights w_j and l_i of a proof; k_dense_fill builds the weighted shares of one column group
-// as int8-limb MFMA fragments in LDS, builds the Cauchy operand 1/(x_i - x_j) in registers from a table of the 2907
-// possible differences (as k_interp_apply does) and multiplies with v_mfma_i32_16x16x64_i8.  Every global store is 16 bytes.
+// k_dense_setup makes rest, the weights w_j and l_i of a proof; k_dense_fill builds the table of the 2907 possible differences'
+// inverses and the weighted shares of one column group in LDS and hands both to the Cauchy-product engine it shares with
+// k_interp_apply (kosk_cauchy_dev.hpp: operand fragments built in registers, int8-limb MFMA k-steps); its own are the column
+// groups, the 64-row staging and the stores.  Every global store is 16 bytes.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <vector>
 
 #include "kosk_ctx.hpp"
-#include "kosk_limb_dev.hpp"
+#include "kosk_cauchy_dev.hpp"
 
 namespace kosk {
 
@@ -161,19 +162,6 @@ struct DenseFillField { uint32_t start, cols, col0; }; // image offset of row 40
 struct DenseFillGroup { int nf, ncols; DenseFillField f[DN_MAXF]; };
 struct DenseFillArgs { DenseFillGroup g[DN_NGROUPS]; };
 
-__device__ __forceinline__ uint32_t dn_mul(uint32_t a, uint32_t b) { return gf_reduce_u32(__umul24(a, b)); } // a b < 2^32
-__device__ __forceinline__ uint32_t dn_diff(int d) { return (uint32_t)(d < 0 ? d + Q : d); }
-__device__ __forceinline__ uint32_t dn_inv(uint32_t a) // a^(q-2); 0 -> 0
-{
-    uint32_t r = 1, b = a;
-#pragma unroll 1
-    for (int e = Q - 2; e; e >>= 1) {
-        if (e & 1) r = dn_mul(r, b);
-        b = dn_mul(b, b);
-    }
-    return r;
-}
-
 // opened list -> status, rest, w, l of one proof; grid (6, n): block x owns entries [256 x, 256 x + 256) of the complement
 __global__ __launch_bounds__(256) void k_dense_setup(const uint8_t *__restrict__ img, size_t image_stride, uint32_t off_I,
                                                      uint16_t *__restrict__ ws, uint32_t *__restrict__ status)
@@ -217,10 +205,10 @@ __global__ __launch_bounds__(256) void k_dense_setup(const uint8_t *__restrict__
         const int xr = rest_s[r];
         uint32_t pr = 1;
         for (int m = 0; m < XLEN; m++) {
-            const uint32_t d = dn_diff(xr - (int)rest_s[m]);
-            pr = dn_mul(pr, m == r ? 1u : d);
+            const uint32_t d = gf_diff(xr - (int)rest_s[m]);
+            pr = gf_mul_fast(pr, m == r ? 1u : d);
         }
-        if (r < XLEN) wsb[DN_WS_W + r] = (uint16_t)dn_inv(pr); // w_j = 1 / prod_{m != j} (x_j - x_m)
+        if (r < XLEN) wsb[DN_WS_W + r] = (uint16_t)gf_inv_pow(pr); // w_j = 1 / prod_{m != j} (x_j - x_m)
         else wsb[DN_WS_ELL + r - XLEN] = (uint16_t)pr;          // l(x_i) = prod_j (x_i - x_j)
     } else {
         const int z = r - NREST; // the padding both vectors need, written by the last block's idle threads
@@ -228,6 +216,14 @@ __global__ __launch_bounds__(256) void k_dense_setup(const uint8_t *__restrict__
         else if (z - (448 - XLEN) < 960 - DN_NTGT) wsb[DN_WS_ELL + DN_NTGT + z - (448 - XLEN)] = 0;
     }
 }
+
+// the weighted shares of this workgroup's column group, read from LDS where the MFMAs use them
+struct DenseFragsLds {
+    const uint8_t *y_s;
+    int NT, lane;
+    __device__ __forceinline__ void ahead(int) {}
+    __device__ __forceinline__ v4i frag(int ks, int j, int limb) const { return *reinterpret_cast<const v4i *>(y_s + frag_offset(16 * j, 64 * ks, limb, NT) + 16 * lane); }
+};
 
 // One workgroup per (column group, proof).  The rows a field gains are one contiguous byte range of the image; the workgroup
 // walks it 64 rows at a time through an LDS buffer per field and writes it out in aligned 16-byte chunks, carrying the
@@ -247,41 +243,11 @@ __device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, cons
         if (m0 < DN_NTGT) { // uniform per wave
             const int ri = min(XLEN + m0 + (lane & 15), NREST - 1); // rows behind 1303 repeat the last one and are not stored
             const int kq = (int)rest_s[ri] + NPARTY - 1;
-            v4i s0[NT], s1[NT], s2[NT];
-#pragma unroll
-            for (int j = 0; j < NT; j++) { s0[j] = (v4i){0, 0, 0, 0}; s1[j] = s0[j]; s2[j] = s0[j]; }
-#pragma unroll
-            for (int ks = 0; ks < DN_KS; ks++) {
-                // operand fragment: 1/(x_i - x_j) for the 16 nodes j = 64 ks + 16 (lane >> 4) + q, as (low limb | high limb << 8)
-                const uint16_t *rn = rest_s + ks * 64 + (lane >> 4) * 16;
-                const uint4 r0 = *reinterpret_cast<const uint4 *>(rn), r1 = *reinterpret_cast<const uint4 *>(rn + 8);
-                const uint32_t rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-                uint32_t e[16];
-#pragma unroll
-                for (int q = 0; q < 16; q++) {
-                    const int xj = (int)((rw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
-                    e[q] = tab_s[kq - xj]; // in [0, 2906]: both are parties below 1454
-                }
-                uint32_t lo[4], hi[4];
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const uint32_t t01 = e[4 * q] | (e[4 * q + 1] << 16), t23 = e[4 * q + 2] | (e[4 * q + 3] << 16);
-                    lo[q] = __builtin_amdgcn_perm(t23, t01, 0x06040200u);
-                    hi[q] = __builtin_amdgcn_perm(t23, t01, 0x07050301u);
-                }
-                const v4i a0 = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3]}, a1 = {(int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-#pragma unroll
-                for (int j = 0; j < NT; j++) {
-                    const uint8_t *yt = y_s + (size_t)((ks * NT + j) * 2) * 1024 + lane * 16;
-                    const v4i b0 = *reinterpret_cast<const v4i *>(yt), b1 = *reinterpret_cast<const v4i *>(yt + 1024);
-                    s0[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b0, s0[j], 0, 0, 0);
-                    s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, b1, s1[j], 0, 0, 0);
-                    s2[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b1, s2[j], 0, 0, 0);
-                    s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, b0, s1[j], 0, 0, 0);
-                }
-            }
+            DenseFragsLds ld{y_s, NT, lane};
+            CauchySums<DN_KS, NT> cs;
+            cs.template run<0>(rest_s, tab_s, lane, kq, ld); // kq - x_j in [0, 2906]: both are parties below 1454 (the status word)
             // D[row = target m0 + 4 (lane >> 4) + r][col = column 16 j + (lane & 15)]
-            const int tr = m0 + (lane >> 4) * 4;
+            const int lr = wv * 16 + (lane >> 4) * 4, tr = it * 64 + lr; // row of this pass, target
 #pragma unroll
             for (int j = 0; j < NT; j++) {
                 const int col = j * 16 + (lane & 15);
@@ -292,8 +258,8 @@ __device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, cons
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     if (tr + r >= DN_NTGT) continue;
-                    const uint32_t v = dn_mul(ell_s[tr + r], gf_reduce_limbs(s0[j][r], s1[j][r], s2[j][r]));
-                    stage16[(at + (uint32_t)(tr + r - it * 64) * cols * 2u) >> 1] = (uint16_t)v;
+                    const uint32_t v = gf_mul_fast(ell_s[tr + r], cs.value(j, r));
+                    stage16[(at + (uint32_t)(lr + r) * cols * 2u) >> 1] = (uint16_t)v;
                 }
             }
         }
@@ -348,13 +314,7 @@ __global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, s
     const uint16_t *wsb = ws + (size_t)b * DN_WS;
     const int nt = (g.ncols + 15) >> 4;
 
-    for (int i = tid; i < DN_TAB; i += 256) { // limb pairs of 1/d, d = i - 1453 (0 for d = 0: met only by zero shares)
-        const int d = i - (NPARTY - 1);
-        const uint32_t v = dn_inv(dn_diff(d));
-        int c0, c1;
-        limb_split(gf_center(v), c0, c1);
-        tab_s[i] = (uint16_t)((c0 & 0xFF) | ((c1 & 0xFF) << 8));
-    }
+    for (int i = tid; i < DN_TAB; i += 256) tab_s[i] = limb_pair(gf_inv_pow(gf_diff(i - (NPARTY - 1)))); // 1/d, d = i - 1453 (0 for d = 0: met only by zero shares)
     for (int i = tid; i < DN_WS_W; i += 256) rest_s[i] = wsb[DN_WS_REST + i];
     for (int i = tid; i < 960; i += 256) ell_s[i] = wsb[DN_WS_ELL + i];
     if (tid < DN_NTMAX * 16) { // column -> field, column in the field, the field's LDS buffer
@@ -366,28 +326,20 @@ __global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, s
         cstart_s[tid] = start; ccols_s[tid] = (uint16_t)cols; ccf_s[tid] = (uint16_t)cf; csb_s[tid] = (uint16_t)sb;
     }
     __syncthreads();
-    // weighted shares w_j (y[j][c] mod q) of this group's columns as fragment tiles [k-step][column tile][limb] of 1 KiB: lane
-    // 16 (j / 16 % 4) + c % 16 holds its 16 consecutive nodes.  One thread per (column, 16 nodes), consecutive threads on consecutive columns
+    // weighted shares w_j (y[j][c] mod q) of this group's columns: one thread per (column, 16 nodes), consecutive threads on consecutive columns
     const int ncp = nt * 16;
     for (int t = tid; t < ncp * DN_KS * 4; t += 256) {
         const int c = t % ncp, kc16 = t / ncp;
         const uint32_t cols = ccols_s[c];
-        uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        if (cols) {
+        cauchy_weighted_frag(y_s, c, kc16, nt, cols != 0, [&](uint32_t (&y)[16], uint32_t (&w)[16]) {
             const uint8_t *src = imgb + (cstart_s[c] - (uint32_t)XLEN * cols * 2u) + 2u * ccf_s[c]; // row 0 of the field, this column
 #pragma unroll
             for (int q = 0; q < 16; q++) {
                 const int j = kc16 * 16 + q;
-                uint32_t v = 0;
-                if (j < XLEN) v = dn_mul(wsb[DN_WS_W + j], *reinterpret_cast<const uint16_t *>(src + (size_t)j * cols * 2)); // w < q, any u16
-                o[q >> 1] |= v << (16 * (q & 1));
+                w[q] = wsb[DN_WS_W + j]; // zero behind the nodes (k_dense_setup)
+                y[q] = j < XLEN ? *reinterpret_cast<const uint16_t *>(src + (size_t)j * cols * 2) : 0u;
             }
-        }
-        uint4 lo, hi;
-        gm_split16(make_uint4(o[0], o[1], o[2], o[3]), make_uint4(o[4], o[5], o[6], o[7]), lo, hi);
-        uint8_t *d = y_s + (size_t)(((kc16 >> 2) * nt + (c >> 4)) * 2) * 1024 + ((kc16 & 3) * 16 + (c & 15)) * 16;
-        *reinterpret_cast<uint4 *>(d) = lo;
-        *reinterpret_cast<uint4 *>(d + 1024) = hi;
+        });
     }
     // the bytes between the 16-byte boundary and the first filled row: kept rows, read back from the image
     if (tid < 8)

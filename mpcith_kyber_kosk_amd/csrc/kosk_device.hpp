@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kosk_math.hpp"
 #include "kosk_params.hpp"
 
 namespace kosk {
@@ -59,10 +60,23 @@ KOSK_HD inline size_t limb_offset(int r, int k, int limb, int RT)
     const int ks = k >> 6, kc = (k >> 4) & 3, rr = r & 15;
     return ((size_t)(ks * RT + (r >> 4)) * 2 + limb) * 1024 + rr * 64 + ((kc ^ limb_swz(rr)) << 4) + (k & 15);
 }
+// The same tiles in "fragment-linear" order (the table of the table products, the weighted shares of the Cauchy products): lane
+// l = 16 (k % 64 / 16) + r % 16 of the MFMA finds its 16 bytes at offset 16 l of the tile, so a wave reads a tile as one linear 1 KiB access
+KOSK_HD inline size_t frag_offset(int r, int k, int limb, int RT)
+{
+    return ((size_t)((k >> 6) * RT + (r >> 4)) * 2 + limb) * 1024 + (((k >> 4) & 3) * 16 + (r & 15)) * 16 + (k & 15);
+}
 KOSK_HD inline void limb_split(int32_t centred, int &c0, int &c1)
 {
     c0 = ((centred + 32) & 63) - 32;
     c1 = (centred - c0) >> 6;
+}
+// (low limb | high limb << 8) of a canonical value: an entry of the tables the Cauchy products build their operand from
+KOSK_HD inline uint16_t limb_pair(uint32_t v)
+{
+    int c0, c1;
+    limb_split(gf_center(v), c0, c1);
+    return (uint16_t)((c0 & 0xFF) | ((c1 & 0xFF) << 8));
 }
 
 // C[n][c_off + m] = sum_k T[m][k] * X[n][k] mod q (k_table_gemm, k_table_gemm_p)

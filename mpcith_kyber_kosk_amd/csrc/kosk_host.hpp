@@ -45,10 +45,6 @@ void fs_opened(const uint8_t *digests_all /* [1454][32] */, uint16_t I[NOPEN], u
 void lagrange_row(uint16_t *row, int n, int a, int t);
 uint16_t gf_inv_host(uint16_t a);
 
-// pack A[m][k] (canonical) into the limb-matrix operand format of the MFMA GEMM (kosk_device.hpp) with each 1 KiB tile in
-// MFMA-fragment order (lane l's 16 bytes at offset 16 l): operands loaded from global memory
-void pack_frag_table(const std::vector<uint16_t> &A, int M, int Kdim, int Mpad, int KS, std::vector<uint8_t> &out);
-
 // Persistent worker pool.  One per library context: several contexts (pipeline slots) run their
 // Fiat-Shamir rounds concurrently, each on its own few threads.
 class Pool;

@@ -1,5 +1,5 @@
-// Device helpers shared by the mod-q MFMA kernels (kosk_kernels.hip, kosk_verify_kernels.hip): the int8 limb form of
-// field values (kosk_device.hpp: "limb matrix") and the reduction of the recombined accumulators.
+// Device helpers shared by the mod-q MFMA kernels (kosk_kernels.hip, and through kosk_cauchy_dev.hpp kosk_verify_kernels.hip and
+// kosk_dense.hip): the int8 limb form of field values (kosk_device.hpp: "limb matrix") and the reduction of the recombined accumulators.
 #pragma once
 #include <hip/hip_runtime.h>
 

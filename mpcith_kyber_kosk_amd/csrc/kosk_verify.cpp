@@ -64,12 +64,7 @@ int ensure_verify_workspace(Ctx &c)
     { // limb pairs of 1/d for every difference d = k - x_j the interpolation meets (k_interp_apply)
         const int len = interp_table_len(), off = interp_table_off();
         std::vector<uint16_t> il(len, 0);
-        for (int i = 0; i + 2 < len; i++) {
-            const int d = ((i - off) % Q + Q) % Q;
-            int c0, c1;
-            limb_split(gf_center(inv[d]), c0, c1);
-            il[i] = (uint16_t)((c0 & 0xFF) | ((c1 & 0xFF) << 8));
-        }
+        for (int i = 0; i + 2 < len; i++) il[i] = limb_pair(inv[((i - off) % Q + Q) % Q]);
         if (upload_vec(c, &c.d_invlimb, il)) return -1;
     }
     std::vector<uint16_t> fact(Q), invfact(Q);

@@ -14,7 +14,7 @@
 #include "kosk_math.hpp"
 
 #include <cstdlib>
-#include "kosk_limb_dev.hpp"
+#include "kosk_cauchy_dev.hpp"
 #include "kosk_wave_sync_dev.hpp"
 
 namespace kosk {
@@ -295,10 +295,6 @@ hipError_t launch_opened_hash(const OpenedHashArgs &a, int K, bool view, int npr
 
 // ---- interpolation operators over the nodes x_j = 256 + rest[j] (see InterpArgs) ---------------
 __device__ __forceinline__ uint32_t gf_neg_if(uint32_t v, int odd) { return (odd & 1) && v ? (uint32_t)Q - v : v; }
-// a b mod q for a, b < 2^16 with a b < 2^32 in seven full-rate instructions (24-bit multiply + gf_reduce_u32) where `a * b % Q` costs three
-// quarter-rate 32-bit multiplies; the canonical representative of a difference |d| < q
-__device__ __forceinline__ uint32_t gf_mul_fast(uint32_t a, uint32_t b) { return gf_reduce_u32(__umul24(a, b)); }
-__device__ __forceinline__ uint32_t gf_diff(int d) { return (uint32_t)(d < 0 ? d + Q : d); }
 
 // weights of both sets, l(k) and the node map of set 0
 __device__ __forceinline__ void interp_setup_block(const InterpArgs &a, const int bx, const int b, const int set, uint16_t *is)
@@ -363,8 +359,7 @@ __global__ __launch_bounds__(256) void k_interp_setup(InterpArgs a, int nproofs)
 }
 
 // The weighted shares y[r][j] = w[b][set][j] * P[b][rows[r]][256 + rest[b][j]] of both interpolations (degree-d rows, then
-// the u rows of degree 2d), written as the MFMA operand of k_interp_apply: int8 limb tiles [k-step][column tile][limb] of
-// 1 KiB in fragment order (lane 16 (j / 16 % 4) + r % 16 holds its 16 consecutive nodes at byte 16 lane), zero where
+// the u rows of degree 2d), written as the MFMA operand of k_interp_apply (kosk_cauchy_dev.hpp: cauchy_weighted_frag), zero where
 // j >= the node count or r >= the row count.  One thread per (column, 16 nodes).
 constexpr int IA_NT1 = 4, IA_NT2 = 2, IA_KS1 = 7, IA_KS2 = 13; // 64 columns x 448 nodes, 32 columns x 832 nodes (K = 4: 52 and 32)
 constexpr int IA_Y1_BYTES = IA_KS1 * IA_NT1 * 2048, IA_Y2_BYTES = IA_KS2 * IA_NT2 * 2048;
@@ -387,32 +382,20 @@ __global__ __launch_bounds__(256) void k_gather_frags(const uint16_t *__restrict
     // the texture path's line rate: 25 us per 276 proofs for 30 MB.
     const int kc16 = t % (KS * 4), r = t / (KS * 4);
     const int ncols = set ? DEG2 + 1 : DEG + 1, nrows = set ? nrows2 : nrows1;
-    uint4 x0 = make_uint4(0, 0, 0, 0), x1 = x0;
-    if (r < nrows && kc16 * 16 < ncols) {
+    cauchy_weighted_frag(set ? out2 + (size_t)b * IA_Y2_BYTES : out1 + (size_t)b * IA_Y1_BYTES, r, kc16, NT, r < nrows && kc16 * 16 < ncols,
+                         [&](uint32_t (&y)[16], uint32_t (&wq)[16]) {
         const uint16_t *src = P + (size_t)b * proof_stride + (size_t)(set ? rows2 : rows1)[r] * RS + NSEC;
         const uint16_t *wb = w + ((size_t)b * 2 + set) * 832 + kc16 * 16;   // zero behind the nodes (k_interp_setup)
         const uint16_t *rb = rest + (size_t)b * sel_stride + kc16 * 16;
         const uint4 w0 = *reinterpret_cast<const uint4 *>(wb), w1 = *reinterpret_cast<const uint4 *>(wb + 8);
         const uint4 r0 = *reinterpret_cast<const uint4 *>(rb), r1 = *reinterpret_cast<const uint4 *>(rb + 8);
         const uint32_t ww[8] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w}, rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-        uint32_t v[16];
 #pragma unroll
-        for (int q = 0; q < 16; q++) v[q] = src[(rw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu];
-        uint32_t o[8];
-#pragma unroll
-        for (int q = 0; q < 16; q += 2) {
-            const uint32_t lo = gf_mul_fast(ww[q >> 1] & 0xFFFFu, v[q]), hi = gf_mul_fast(ww[q >> 1] >> 16, v[q + 1]); // w < q, v any u16
-            o[q >> 1] = lo | (hi << 16);
+        for (int q = 0; q < 16; q++) {
+            y[q] = src[(rw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu];
+            wq[q] = (ww[q >> 1] >> (16 * (q & 1))) & 0xFFFFu;
         }
-        x0 = make_uint4(o[0], o[1], o[2], o[3]);
-        x1 = make_uint4(o[4], o[5], o[6], o[7]);
-    }
-    uint4 lo, hi;
-    gm_split16(x0, x1, lo, hi);
-    uint8_t *d = (set ? out2 + (size_t)b * IA_Y2_BYTES : out1 + (size_t)b * IA_Y1_BYTES) +
-                 (size_t)(((kc16 >> 2) * NT + (r >> 4)) * 2) * 1024 + ((kc16 & 3) * 16 + (r & 15)) * 16;
-    *reinterpret_cast<uint4 *>(d) = lo;
-    *reinterpret_cast<uint4 *>(d + 1024) = hi;
+    });
 }
 
 // ---- interpolation of the unopened shares, applied without ever storing the operator -------------------------------
@@ -421,11 +404,10 @@ __global__ __launch_bounds__(256) void k_gather_frags(const uint16_t *__restrict
 // In barycentric form the operator of one proof is the Cauchy matrix C[k][j] = 1/(k - x_j) over its nodes
 // x_j = 256 + rest[j] (407 or 813 of them); it differs from proof to proof and multiplies only 34-52 (24-32) vectors, so
 // materialising it (40 MB written and read back per 46 proofs, 17 M table look-ups behind per-element stores) cost more
-// than the product.  Here every lane builds its own MFMA operand fragment -- row = evaluation point lane & 15, sixteen
-// consecutive nodes lane >> 4 -- from the inverse table in LDS, limb-splits it in registers and multiplies right away;
-// the weighted shares (k_gather_cols2) sit in LDS as the other operand.  A wave owns 16 evaluation points, a workgroup
-// 64.  Epilogue: reduce mod q; degree d: times l(k), or the share itself where k is a node (what k_interp_fixup did),
-// into the row matrix; degree 2d: the raw sums for k_check_batch.
+// than the product.  Here every lane builds its own MFMA operand fragment from the inverse table in LDS and multiplies right
+// away (kosk_cauchy_dev.hpp, the engine shared with the dense refill); the weighted shares (k_gather_frags) are the other
+// operand, loaded from global memory one k-step ahead.  A wave owns 16 evaluation points, a workgroup 64.  Epilogue: reduce
+// mod q; degree d: times l(k), or the share itself where k is a node, into the row matrix; degree 2d: the raw sums for k_check_batch.
 // IA_OFF: the table of limb pairs is indexed by k - x_j + IA_OFF with k - 256 in [-256, 150] and x_j in [0, 1453]
 constexpr int IA_OFF = NPARTY - 1 + NSEC, IA_TAB = IA_OFF + (DEG - NSEC) + 1; // 1709, 1860 entries (+ one of padding)
 
@@ -439,6 +421,21 @@ struct InterpApplyArgs {
     int n2;                             // sharings of degree 2d per proof (<= 32)
     const uint8_t *y2;                  // [proof][IA_Y2_BYTES]
     uint16_t *out2;                     // [proof][n2][256]
+};
+
+// the weighted shares of k_gather_frags, read from global memory one k-step ahead of the MFMAs that use them
+template <int KS, int NT>
+struct InterpFragsAhead {
+    const uint8_t *y;
+    int lane;
+    v4i fb[2][2 * NT];
+    __device__ __forceinline__ void ahead(int ks)
+    {
+        if (++ks < KS)
+#pragma unroll
+            for (int q = 0; q < 2 * NT; q++) fb[ks & 1][q] = *reinterpret_cast<const v4i *>(y + frag_offset(16 * (q >> 1), 64 * ks, q & 1, NT) + 16 * lane);
+    }
+    __device__ __forceinline__ v4i frag(int ks, int j, int limb) const { return fb[ks & 1][2 * j + limb]; }
 };
 
 template <int SET>
@@ -470,48 +467,10 @@ __device__ __forceinline__ void interp_apply_block(const InterpApplyArgs &g, con
     const int m0 = (mblk * 4 + wv) * 16;
     if (m0 >= NEVAL) return;
     const int kq = m0 + (lane & 15) - NSEC + IA_OFF; // this lane's evaluation point, offset for the table
-    const uint8_t *yt = (SET ? g.y2 + (size_t)b * IA_Y2_BYTES : g.y1 + (size_t)b * IA_Y1_BYTES) + lane * 16;
-    v4i s0[NT], s1[NT], s2[NT];
-#pragma unroll
-    for (int j = 0; j < NT; j++) { s0[j] = (v4i){0, 0, 0, 0}; s1[j] = s0[j]; s2[j] = s0[j]; }
-    v4i fb[2][2 * NT]; // the other operand's fragments, one k-step ahead
-    auto load_b = [&](int ks, v4i (&dst)[2 * NT]) {
-#pragma unroll
-        for (int q = 0; q < 2 * NT; q++) dst[q] = *reinterpret_cast<const v4i *>(yt + (size_t)(ks * NT * 2 + q) * 1024);
-    };
-    load_b(0, fb[0]);
-#pragma unroll
-    for (int ks = 0; ks < KS; ks++) {
-        if (ks + 1 < KS) load_b(ks + 1, fb[(ks + 1) & 1]);
-        // operand fragment: 1/(k - x_j) for the 16 nodes j = 64 ks + 16 (lane >> 4) + q, as (low limb | high limb << 8)
-        const uint16_t *rn = rest_s + ks * 64 + (lane >> 4) * 16;
-        const uint4 r0 = *reinterpret_cast<const uint4 *>(rn), r1 = *reinterpret_cast<const uint4 *>(rn + 8);
-        const uint32_t rw[8] = {r0.x, r0.y, r0.z, r0.w, r1.x, r1.y, r1.z, r1.w};
-        uint32_t e[16];
-#pragma unroll
-        for (int q = 0; q < 16; q++) {
-            const int xj = (int)((rw[q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
-            e[q] = tab_s[min((uint32_t)(kq - xj), (uint32_t)IA_TAB)]; // the clamp only matters for a malformed list (entry IA_TAB is 0)
-        }
-        uint32_t lo[4], hi[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t t01 = e[4 * q] | (e[4 * q + 1] << 16), t23 = e[4 * q + 2] | (e[4 * q + 3] << 16);
-            lo[q] = __builtin_amdgcn_perm(t23, t01, 0x06040200u);
-            hi[q] = __builtin_amdgcn_perm(t23, t01, 0x07050301u);
-        }
-        const v4i a0 = {(int)lo[0], (int)lo[1], (int)lo[2], (int)lo[3]}, a1 = {(int)hi[0], (int)hi[1], (int)hi[2], (int)hi[3]};
-        v4i(&bc)[2 * NT] = fb[ks & 1];
-#pragma unroll
-        for (int j = 0; j < NT; j++) {
-            s0[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, bc[2 * j], s0[j], 0, 0, 0);
-            s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a0, bc[2 * j + 1], s1[j], 0, 0, 0);
-            s2[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, bc[2 * j + 1], s2[j], 0, 0, 0);
-            s1[j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a1, bc[2 * j], s1[j], 0, 0, 0);
-        }
-    }
-    // D[row = evaluation point m0 + 4 (lane >> 4) + r][col = sharing 16 j + (lane & 15)];
-    // |S0 + 64 S1 + 767 S2| < 2^29 for k <= 832, so adding 90 000 q makes it a positive u32
+    InterpFragsAhead<KS, NT> ld{SET ? g.y2 + (size_t)b * IA_Y2_BYTES : g.y1 + (size_t)b * IA_Y1_BYTES, lane};
+    CauchySums<KS, NT> cs;
+    cs.template run<IA_TAB>(rest_s, tab_s, lane, kq, ld); // the clamp only matters for a malformed list (entry IA_TAB is 0)
+    // D[row = evaluation point m0 + 4 (lane >> 4) + r][col = sharing 16 j + (lane & 15)]
     const int kb = m0 + (lane >> 4) * 4;
     int node[4] = {-1, -1, -1, -1};
     uint32_t ell[4] = {0, 0, 0, 0}, xn[4] = {0, 0, 0, 0};
@@ -529,7 +488,7 @@ __device__ __forceinline__ void interp_apply_block(const InterpApplyArgs &g, con
         if (col >= ncol) continue;
         uint32_t v[4];
 #pragma unroll
-        for (int r = 0; r < 4; r++) v[r] = gf_reduce_limbs(s0[j][r], s1[j][r], s2[j][r]);
+        for (int r = 0; r < 4; r++) v[r] = cs.value(j, r);
         if constexpr (SET) {
             *reinterpret_cast<uint2 *>(g.out2 + ((size_t)b * ncol + col) * NSEC + kb) = make_uint2(v[0] | (v[1] << 16), v[2] | (v[3] << 16));
         } else {
