@@ -780,6 +780,32 @@ int ko_craft_add(int kind, int idx, int party, int mult)
     return 0;
 }
 
+/* ---- test hook: a prover that OPENS A CHOSEN SET -------------------------
+ * No counterpart in the reference.  The verifier's interpolation is keyed by
+ * the opened list I, which an honest prover gets from the Fiat-Shamir hash: a
+ * pseudo-random 150-subset, never an edge case.  While a list is set here,
+ * ko_prove opens that list, in the given order, in place of derive_opened()'s;
+ * view digests and ch stay the honest ones, so the proof is consistent in
+ * every check of ko_verify but the last one, I' == I.                      */
+static uint16_t g_forced_I[KO_OPENED];
+static int g_forced;
+int ko_force_opened(const uint16_t I[KO_OPENED])
+{
+    if (!I) {
+        g_forced = 0;
+        return 0;
+    }
+    uint8_t seen[KO_PARTIES];
+    memset(seen, 0, sizeof seen);
+    for (int i = 0; i < KO_OPENED; i++) {
+        if (I[i] >= KO_PARTIES || seen[I[i]]) return -1;
+        seen[I[i]] = 1;
+    }
+    memcpy(g_forced_I, I, sizeof g_forced_I);
+    g_forced = 1;
+    return 0;
+}
+
 void ko_prove(int K, ko_tape *tp, uint8_t *pi, const ko_mlwe *mlwe, const ko_pre *pre, ko_trace *trace)
 {
     ko_params P;
@@ -980,6 +1006,7 @@ void ko_prove(int K, ko_tape *tp, uint8_t *pi, const ko_mlwe *mlwe, const ko_pre
     uint8_t ch[32];
     uint16_t I[KO_OPENED], rest[KO_REST];
     derive_opened(&vdig[0][0], ch, I);
+    if (g_forced) memcpy(I, g_forced_I, sizeof I); /* test hook, see ko_force_opened */
     uint8_t in_I[KO_PARTIES];
     memset(in_I, 0, sizeof in_I);
     for (int i = 0; i < KO_OPENED; i++) in_I[I[i]] = 1;

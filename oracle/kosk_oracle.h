@@ -160,6 +160,10 @@ int ko_bench(int K, int nproofs, const uint8_t *tapes, size_t tape_stride,
 void ko_craft_clear(void);
 int ko_craft_add(int kind, int idx, int party, int mult);
 
+/* test hook (no reference counterpart): while a list is set, ko_prove opens these 150 parties, in this order, in place of the
+ * Fiat-Shamir list; NULL clears it.  Returns -1 and changes nothing for an entry >= KO_PARTIES or a duplicate (see kosk_oracle.c) */
+int ko_force_opened(const uint16_t I[KO_OPENED]);
+
 #ifdef __cplusplus
 }
 #endif

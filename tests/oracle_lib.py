@@ -33,6 +33,7 @@ lib.ko_zetas.restype = C.POINTER(C.c_int16)
 lib.ko_gf_add.restype = lib.ko_gf_sub.restype = lib.ko_gf_mul.restype = lib.ko_gf_inv.restype = C.c_uint16
 lib.ko_gf_add.argtypes = lib.ko_gf_sub.argtypes = lib.ko_gf_mul.argtypes = [C.c_uint16, C.c_uint16]
 lib.ko_gf_inv.argtypes = [C.c_uint16]
+lib.ko_force_opened.argtypes = [C.c_void_p]
 lib.ko_barrett_reduce.restype = C.c_int16
 lib.ko_barrett_reduce.argtypes = [C.c_int16]
 lib.ko_montgomery_reduce.restype = C.c_int16
@@ -72,6 +73,25 @@ def crafted_verifiable_keygen(k, tape, items):
         return verifiable_keygen(k, tape)[:3]
     finally:
         lib.ko_craft_clear()
+
+
+def force_opened(I):
+    """ko_force_opened: the list the oracle's prover opens from now on (150 parties, in this order), or None to clear it.
+    Returns the oracle's return code: -1 (and nothing changed) for an entry >= 1454 or a duplicate."""
+    if I is None:
+        return lib.ko_force_opened(None)
+    assert len(I) == 150
+    return lib.ko_force_opened((C.c_uint16 * 150)(*I))
+
+
+def forced_verifiable_keygen(k, tape, I):
+    """ko_verifiable_keygen by a prover that opens the list I (kosk_oracle.c: ko_force_opened) in place of the Fiat-Shamir one: every
+    check of the verifier holds on the proof except the last, I' == I.  Returns (pk, sk, pi)."""
+    try:
+        assert force_opened(I) == 0
+        return verifiable_keygen(k, tape)[:3]
+    finally:
+        force_opened(None)
 
 
 def kosk_verify(k, pi, pk):
