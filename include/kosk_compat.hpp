@@ -220,6 +220,21 @@ inline bool kyber_kosk_verify_bound(const uint8_t *pi, const uint8_t *pk, const 
     return ok == 1;
 }
 
+/* ---- the same proof with no entropy source (no reference counterpart; format kosk-keyseed-v1): the randomness is
+ * derived on the device from keypair->sk, K and the context, so the call is a pure function of its inputs and randombytes is not called.
+ * context != NULL: the proof is bound to it (kyber_kosk_verify_bound checks it), the handle armed for the call and disarmed again;
+ * NULL: an unbound proof for kyber_kosk_verify.  false (pi all zero) as kyber_kosk_prove_key. ---- */
+inline bool kyber_kosk_prove_key_derived(const kyber_keypair *keypair, uint8_t *pi, const uint8_t *context)
+{
+    uint8_t ok = 0;
+    if (context) kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 1, context, 32), "kyber_kosk_prove_key_derived");
+    const int rc = kosk_prove_keys_derived_batch(kosk_compat::ctx(), 1, keypair->sk, nullptr, 0, pi, &ok);
+    if (rc) fprintf(stderr, "kyber_kosk_prove_key_derived: %s\n", kosk_last_error(kosk_compat::ctx()));
+    if (context) kosk_compat::must(kosk_set_contexts(kosk_compat::ctx(), 0, nullptr, 0), "kyber_kosk_prove_key_derived");
+    if (rc) abort();
+    return ok == 1;
+}
+
 /* ---- second-level entry points, used directly by main.cpp:21-47 ---- */
 /* mlwe_prover.hpp:77 */
 inline void prepare_randomness(mpcith_randomness *rand)

@@ -308,7 +308,8 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * made by a copy kernel, 9 Fiat-Shamir rounds hashed on the device (k_fs_chain), 10 on the host, 11 launches of k_tape_expand (seeded
  * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls,
  * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch),
- * 15 kem_keypair / 16 kem_check: launch groups of kosk_kem_keypair_batch and of kosk_kem_check_pk / kosk_kem_check_sk. */
+ * 15 kem_keypair / 16 kem_check: launch groups of kosk_kem_keypair_batch and of kosk_kem_check_pk / kosk_kem_check_sk,
+ * 17 launches of k_keyseed (kosk-keyseed-v1: seeds derived from the sk records in HBM). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);
@@ -476,6 +477,29 @@ int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t t
  * disarms; a handle never armed, or disarmed, behaves exactly as before.  A cohort member that is armed keeps its calls out of merged
  * runs.  Not to be called while another thread is inside a call on this handle. */
 int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t context_stride);
+
+/* ---- proof randomness derived from the key, format kosk-keyseed-v1 (no reference counterpart) ----
+ *   seed = SHAKE256("kosk-keyseed-v1" || 00 || LE32(K) || LE32(flags) || context[32] || salt[32] || sk[kosk_sk_bytes(K)])[0 : 32]
+ *   flags bit 0: the proof is context-bound (a context is given / the handle is armed), bit 1: a salt is given; a field whose bit is
+ *   clear is 32 zero bytes.  tape = kosk-seedtape-v1(seed).
+ * The sk record is hashed as it stands.  The proof is byte for byte what kosk_prove_keys_seeded_batch(sk, seed) returns on the same
+ * handle state; the seed is as secret as the key, is made in HBM by k_keyseed and never reaches the host in the handle calls.
+ * Without salts the call is a pure function of (sk, K, armed context): the same inputs give the same proof, any other input an
+ * unrelated tape.  With salts (fresh random bytes per proof) it is the hedged form. */
+/* the seed on the host (no handle); context == NULL: unbound, salt == NULL: none.  -1 for kyber_k outside 2..4, a NULL sk or seed */
+int kosk_keyseed_value(int kyber_k, const uint8_t *sk, const uint8_t *context, const uint8_t *salt, uint8_t seed[32]);
+/* kernel level (k_keyseed), any n >= 1: sk = n records of kosk_sk_bytes; contexts (NULL: unbound) and salts (NULL: none) n records
+ * context_stride / salt_stride >= 32 apart; each host or device memory.  d_seeds = n x 32 bytes of DEVICE memory, 8-byte aligned
+ * (else -1 and a text); nothing outside them is written.  Synchronised on return. */
+int kosk_keyseed_device(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride,
+                        const uint8_t *salts, size_t salt_stride, uint8_t *d_seeds);
+/* kosk_stage_prover_keys_seeded / kosk_prove_keys_seeded_batch with the seeds derived on the device: the context of position b is armed
+ * context b of the whole call (also across max_batch chunks and streams > 1 sub-batches), flag 0 and a zero field on an unarmed handle.
+ * salts == NULL: the deterministic form; else n records salt_stride >= 32 apart, host or device memory.  Everything else -- ok[], zero
+ * images, return codes, the resident state, unmerged on a cohort member -- as the seeded calls above; more proofs
+ * than armed contexts, or salt_stride < 32: -1 and a text, nothing started. */
+int kosk_stage_prover_keys_derived(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *ok);
+int kosk_prove_keys_derived_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *pi, uint8_t *ok);
 
 #ifdef __cplusplus
 }

@@ -158,6 +158,15 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_keypair_batch")):
         sig.update(keypair)
+    # randomness derived from the key (kosk-keyseed-v1); optional under the same rule (and only then)
+    keyseed = {
+        "kosk_keyseed_value": (C.c_int, [C.c_int, vp, vp, vp, vp]),
+        "kosk_keyseed_device": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, sz, vp]),
+        "kosk_stage_prover_keys_derived": (C.c_int, [vp, C.c_int, vp, vp, sz, vp]),
+        "kosk_prove_keys_derived_batch": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_keyseed_value")):
+        sig.update(keyseed)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -187,7 +196,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_dense_proof_bytes", "kosk_proof_dense_pack", "kosk_proof_dense_unpack", "kosk_fetch_proofs_dense",
            "kosk_stage_verifier_inputs_dense", "kosk_verifiable_keygen_batch_dense", "kosk_verifiable_keygen_seeded_batch_dense",
            "kosk_verify_batch_dense", "kosk_dense_fill_device",
-           "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk"]
+           "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk",
+           "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -254,6 +264,27 @@ def bind_value(k, pk, context):
     out = C.create_string_buffer(32)
     if lib.kosk_bind_value(k, C.c_char_p(pk), C.c_char_p(context), out):
         raise KoskError("kosk_bind_value: kyber_k outside 2..4")
+    return out.raw
+
+
+SALT_BYTES = 32
+
+
+def keyseed_value(k, sk, context=None, salt=None):
+    """the seed of format kosk-keyseed-v1 for one secret-key record, on the host (kosk_keyseed_value).  context None: unbound;
+    salt None: the deterministic form.  The seed is as secret as the key."""
+    sk = bytes(sk)
+    if len(sk) != sk_bytes(k):
+        raise KoskError("keyseed_value: a secret key of kosk_sk_bytes")
+    if context is not None and len(context) != CONTEXT_BYTES:
+        raise KoskError("a context has %d bytes" % CONTEXT_BYTES)
+    if salt is not None and len(salt) != SALT_BYTES:
+        raise KoskError("a salt has %d bytes" % SALT_BYTES)
+    out = C.create_string_buffer(SEED_BYTES)
+    cp = None if context is None else C.c_char_p(bytes(context))
+    sp = None if salt is None else C.c_char_p(bytes(salt))
+    if lib.kosk_keyseed_value(k, C.c_char_p(sk), cp, sp, out):
+        raise KoskError("kosk_keyseed_value: kyber_k outside 2..4")
     return out.raw
 
 
@@ -416,6 +447,32 @@ class Kosk:
         a = C.c_void_p(pk) if isinstance(pk, int) else C.c_char_p(bytes(pk))
         b = C.c_void_p(contexts) if isinstance(contexts, int) else C.c_char_p(bytes(contexts))
         self._chk(lib.kosk_bind_device(self._h, n, a, b, context_stride, d_out), "bind_device")
+
+    def keyseed_device(self, n, sk, d_seeds, contexts=None, context_stride=CONTEXT_BYTES, salts=None, salt_stride=SALT_BYTES):
+        """n seeds of format kosk-keyseed-v1 into device memory d_seeds (int pointer, 8-byte aligned; kosk_keyseed_device).
+        sk / contexts / salts: bytes (host) or int device pointers; contexts None: unbound, salts None: none"""
+        def arg(v):
+            return None if v is None else C.c_void_p(v) if isinstance(v, int) else C.c_char_p(bytes(v))
+        self._chk(lib.kosk_keyseed_device(self._h, n, arg(sk), arg(contexts), context_stride, arg(salts), salt_stride, d_seeds), "keyseed_device")
+
+    def _salt_arg(self, salts, n, salt_stride):
+        """salts of the derived calls: None (deterministic), a list of 32-byte bytes, an int DEVICE pointer (salt_stride apart), or True
+        (one os.urandom draw per proof, made here) -> (pointer, stride, keepalive)"""
+        if salts is None:
+            return None, 0, None
+        if isinstance(salts, bool):
+            if not salts:
+                return None, 0, None
+            salts = [os.urandom(SALT_BYTES) for _ in range(n)]
+        if isinstance(salts, int):
+            return C.c_void_p(salts), SALT_BYTES if salt_stride is None else salt_stride, None
+        if len(salts) != n:
+            raise KoskError("salts for %d proofs, secret keys for %d" % (len(salts), n))
+        for s_ in salts:
+            if len(s_) != SALT_BYTES:
+                raise KoskError("a salt has %d bytes" % SALT_BYTES)
+        blob = b"".join(bytes(s_) for s_ in salts)
+        return C.c_char_p(blob), SALT_BYTES, blob
 
     def _seed_arg(self, seeds, n, seed_stride):
         """seeds: list of 32-byte bytes, an int DEVICE pointer (with n and seed_stride), or True (the library draws one 32-byte seed
@@ -820,21 +877,37 @@ class Kosk:
         blob = b"".join(t[:self.tape_bytes] for t in tapes)
         return False, C.c_char_p(blob), self.tape_bytes, blob
 
-    def stage_prover_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
-        """kosk_stage_prover_keys[_seeded]: witness and randomness of n existing keys resident for prove_resident(n).  tapes: list of
-        bytes, an int DEVICE pointer (kosk_tape_bytes apart) or None; seeds: see _seed_arg; neither: the handle's entropy mode.
+    def stage_prover_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None, derived=False, salts=None, salt_stride=None):
+        """kosk_stage_prover_keys[_seeded|_derived]: witness and randomness of n existing keys resident for prove_resident(n).  tapes: list
+        of bytes, an int DEVICE pointer (kosk_tape_bytes apart) or None; seeds: see _seed_arg; neither: the handle's entropy mode.
+        derived=True (kosk-keyseed-v1): the randomness is derived from the keys on the device; salts: see _salt_arg.
         Returns ok (list of bool)."""
         sp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        if derived or salts is not None:
+            if tapes is not None or seeds is not None:
+                raise KoskError("derived=True takes neither tapes nor seeds")
+            rp, stride, _k2 = self._salt_arg(salts, n, salt_stride)
+            ok = C.create_string_buffer(n)
+            self._chk(lib.kosk_stage_prover_keys_derived(self._h, n, sp, rp, stride, ok), "stage_prover_keys")
+            return [b == 1 for b in ok.raw[:n]]
         seeded, rp, stride, _k2 = self._key_rand(tapes, seeds, n, seed_stride)
         ok = C.create_string_buffer(n)
         fn = lib.kosk_stage_prover_keys_seeded if seeded else lib.kosk_stage_prover_keys
         self._chk(fn(self._h, n, sp, rp, stride, ok), "stage_prover_keys")
         return [b == 1 for b in ok.raw[:n]]
 
-    def prove_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
-        """kosk_prove_keys[_seeded]_batch: one proof per existing key, any n.  Returns (proofs, ok); the image of a key with ok False is
-        all zero."""
+    def prove_keys(self, sks, tapes=None, seeds=None, n=None, seed_stride=None, derived=False, salts=None, salt_stride=None):
+        """kosk_prove_keys[_seeded|_derived]_batch: one proof per existing key, any n.  derived / salts: as stage_prover_keys.
+        Returns (proofs, ok); the image of a key with ok False is all zero."""
         sp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        if derived or salts is not None:
+            if tapes is not None or seeds is not None:
+                raise KoskError("derived=True takes neither tapes nor seeds")
+            rp, stride, _k2 = self._salt_arg(salts, n, salt_stride)
+            ok = C.create_string_buffer(n)
+            pi = C.create_string_buffer(self.proof_bytes * n)
+            self._chk(lib.kosk_prove_keys_derived_batch(self._h, n, sp, rp, stride, pi, ok), "prove_keys")
+            return _cut(pi, self.proof_bytes, n), [b == 1 for b in ok.raw[:n]]
         seeded, rp, stride, _k2 = self._key_rand(tapes, seeds, n, seed_stride)
         ok = C.create_string_buffer(n)
         pi = C.create_string_buffer(self.proof_bytes * n)
@@ -849,6 +922,7 @@ class Kosk:
     PATH_DENSE_FILL = 14
     PATH_KEM_KEYPAIR = 15
     PATH_KEM_CHECK = 16
+    PATH_KEYSEED = 17
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

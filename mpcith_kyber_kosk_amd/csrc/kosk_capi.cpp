@@ -1349,6 +1349,59 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
     GUARD_END
 }
 
+// ---- kosk-keyseed-v1: the randomness derived from the key itself.  Position b of the call hashes armed context b (the
+// handle's device copy; chunks and sub-batches pass their offset on as for binding) and salt b
+static int bad_salt_stride(kosk_ctx *ctx, const char *fn)
+{
+    ctx->clear_err();
+    ctx->err = std::string(fn) + ": salt_stride is smaller than one salt (32 bytes)";
+    ctx->c->err = ctx->err;
+    return -1;
+}
+static int stage_derived_at(Ctx &c, const Params &P, int first, int count, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *ok)
+{
+    const DerivedSrc src{salts ? salts + (size_t)first * salt_stride : nullptr, salt_stride};
+    c.bind_first = first;
+    return stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, nullptr, 0, nullptr, 0, ok + first, &src);
+}
+int kosk_stage_prover_keys_derived(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (salts && salt_stride < 32) return bad_salt_stride(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    return ctx->run(n, [&](Ctx &c, int first, int count) { return stage_derived_at(c, P, first, count, sk, salts, salt_stride, ok); });
+    GUARD_END
+}
+int kosk_prove_keys_derived_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *pi, uint8_t *ok)
+{
+    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (salts && salt_stride < 32) return bad_salt_stride(ctx, __func__);
+    GUARD(ctx)
+    const Params &P = ctx->c->P;
+    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
+    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        if (stage_derived_at(c, P, first, count, sk, salts, salt_stride, ok)) return -1;
+        if (prove_at(c, first, count)) return -1;
+        if (fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned)) return -1;
+        for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
+            if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
+        return 0;
+    });
+    GUARD_END
+}
+int kosk_keyseed_device(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride,
+                        uint8_t *d_seeds)
+{
+    if (!ctx || n < 1 || !sk || !d_seeds) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return keyseed_device(*ctx->c, n, sk, contexts, context_stride, salts, salt_stride, d_seeds);
+    GUARD_END
+}
+
 void *kosk_host_alloc(size_t bytes)
 {
     void *p = nullptr;
@@ -1741,6 +1794,15 @@ int kosk_bind_value(int kyber_k, const uint8_t *pk, const uint8_t context[32], u
     if (!make_params(kyber_k, P) || !pk || !context || !out) return -1;
     return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
     bind_value(P, pk, context, out);
+    return 0;
+    GUARD_END
+}
+int kosk_keyseed_value(int kyber_k, const uint8_t *sk, const uint8_t *context, const uint8_t *salt, uint8_t seed[32])
+{
+    Params P;
+    if (!make_params(kyber_k, P) || !sk || !seed) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    keyseed_value(P, sk, context, salt, seed);
     return 0;
     GUARD_END
 }

@@ -572,7 +572,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.resident_pk_n = 0;
     c.keys_from_pk_n = 0;
     c.kem = nullptr;
-    c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr;
+    c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
     for (const Ctx::PerProof &pp : arena.per_proof) {
@@ -883,7 +883,8 @@ void witness_release(Ctx &c)
     if (c.d_wsk) (void)hipFree(c.d_wsk);
     if (c.d_wok) (void)hipFree(c.d_wok);
     if (c.h_wok) (void)hipHostFree(c.h_wok);
-    c.d_wsk = c.d_wok = c.h_wok = nullptr;
+    if (c.d_wsalt) (void)hipFree(c.d_wsalt);
+    c.d_wsk = c.d_wok = c.h_wok = c.d_wsalt = nullptr;
     c.wit_cap = 0;
 }
 
@@ -898,6 +899,7 @@ static int witness_ensure(Ctx &c, int n)
         HIPCHK(dalloc(&c.d_wsk, (size_t)n * c.P.sk_bytes));
         HIPCHK(dalloc(&c.d_wok, (size_t)n));
         HIPCHK(halloc(&c.h_wok, (size_t)n));
+        HIPCHK(dalloc(&c.d_wsalt, (size_t)n * 32));
         return 0;
     };
     if (body()) { witness_release(c); return -1; }
@@ -905,15 +907,11 @@ static int witness_ensure(Ctx &c, int n)
     return 0;
 }
 
-int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
+// the witness of the n records resident in d_wsk; ends with the stream synchronised
+static int witness_from_resident_sk(Ctx &c, int n, int16_t *se_out, uint8_t *ok)
 {
-    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
-    if (!sk || !ok) { c.err = "sk records and the ok buffer are required"; return -1; }
-    HIPCHK(hipSetDevice(c.device));
-    if (witness_ensure(c, n)) return -1;
     const Params &P = c.P;
     const int K = P.K;
-    HIPCHK(hipMemcpyAsync(c.d_wsk, sk, (size_t)n * P.sk_bytes, is_device_pointer(sk) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
     // t-hat (12-bit fields as they stand) and A from the pk inside the record: sk = s-hat || pk || H(pk) || z.  Byte loads only: any stride
     HIPCHK(launch_decode_pk(c.d_wsk + 384 * K, P.sk_bytes, c.d_t, c.d_A, c.key_stride, K, n, c.stream, c.xof_guard()));
     WitnessArgs wa{};
@@ -936,17 +934,94 @@ int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *
     return 0;
 }
 
-int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok)
+static hipError_t copy_sk_records(Ctx &c, int n, const uint8_t *sk)
+{
+    return hipMemcpyAsync(c.d_wsk, sk, (size_t)n * c.P.sk_bytes, is_device_pointer(sk) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream);
+}
+
+int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
 {
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     if (!sk || !ok) { c.err = "sk records and the ok buffer are required"; return -1; }
-    if (!tapes == !seeds) { c.err = "internal: exactly one of tapes / seeds"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    if (witness_ensure(c, n)) return -1;
+    HIPCHK(copy_sk_records(c, n, sk));
+    return witness_from_resident_sk(c, n, se_out, ok);
+}
+
+// kosk-keyseed-v1: the records go to d_wsk FIRST (the seeds are a hash of them), then salts -> d_wsalt, k_keyseed -> d_seedbuf,
+// k_tape_expand -> d_tape, and the witness from the records where they lie.  No seed reaches the host
+static int stage_prover_keys_derived(Ctx &c, int n, const uint8_t *sk, const DerivedSrc &src, uint8_t *ok)
+{
+    if (src.salts && src.salt_stride < 32) { c.err = "salt_stride smaller than one salt (32 bytes)"; return -1; }
+    if (bind_check(c, n)) return -1;
+    if (witness_ensure(c, n)) return -1;
+    HIPCHK(copy_sk_records(c, n, sk));
+    if (src.salts) HIPCHK(hipMemcpy2DAsync(c.d_wsalt, 32, src.salts, src.salt_stride, 32, (size_t)n, is_device_pointer(src.salts) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    KeyseedArgs ka{};
+    ka.sk = c.d_wsk; ka.sk_stride = c.P.sk_bytes; ka.sk_bytes = (int)c.P.sk_bytes; ka.K = c.P.K;
+    if (c.bind_n > 0) { ka.contexts = c.bind_ctx + (size_t)c.bind_first * 32; ka.context_stride = 32; }
+    if (src.salts) { ka.salts = c.d_wsalt; ka.salt_stride = 32; }
+    ka.out = c.d_seedbuf;
+    HIPCHK(launch_keyseed(ka, n, c.stream));
+    c.path_n[PATH_KEYSEED]++;
+    c.tape_segs.count = 0;
+    if (expand_into_own(c, 0, n, c.d_seedbuf, SEED_BYTES)) return -1;
+    c.tape_cur = c.d_tape;
+    c.tape_cur_stride = c.tape_stride;
+    return witness_from_resident_sk(c, n, nullptr, ok);
+}
+
+int keyseed_device(Ctx &c, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride, uint8_t *d_seeds)
+{
+    if (n < 1 || !sk) { c.err = "n >= 1 sk records are required"; return -1; }
+    if ((contexts && context_stride < 32) || (salts && salt_stride < 32)) { c.err = "context_stride / salt_stride smaller than 32 bytes"; return -1; }
+    if (!d_seeds || (reinterpret_cast<uintptr_t>(d_seeds) & 7) || !is_device_pointer(d_seeds)) {
+        c.err = "d_seeds must be device memory with a base that is a multiple of 8";
+        return -1;
+    }
+    HIPCHK(hipSetDevice(c.device));
+    // the kernel loads 8 bytes at a time: device memory with an aligned base and stride is read where it lies, anything else (host memory,
+    // an odd base or stride) goes through aligned device staging that lives as long as the call
+    const size_t skb = c.P.sk_bytes;
+    auto in_place = [](const void *p, size_t stride) { return is_device_pointer(p) && (reinterpret_cast<uintptr_t>(p) & 7) == 0 && stride % 8 == 0; };
+    const bool st_sk = !in_place(sk, skb), st_cx = contexts && !in_place(contexts, context_stride), st_sa = salts && !in_place(salts, salt_stride);
+    const size_t need = (size_t)n * ((st_sk ? skb : 0) + (st_cx ? 32 : 0) + (st_sa ? 32 : 0));
+    uint8_t *stage = nullptr;
+    if (need) HIPCHK(hipMalloc(reinterpret_cast<void **>(&stage), need));
+    struct Free { uint8_t *p; ~Free() { if (p) (void)hipFree(p); } } fr{stage};
+    uint8_t *d_sk = stage, *d_ctx = d_sk + (st_sk ? (size_t)n * skb : 0), *d_salt = d_ctx + (st_cx ? (size_t)n * 32 : 0);
+    auto kind = [](const void *p) { return is_device_pointer(p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; };
+    if (st_sk) HIPCHK(hipMemcpyAsync(d_sk, sk, (size_t)n * skb, kind(sk), c.stream));
+    if (st_cx) HIPCHK(hipMemcpy2DAsync(d_ctx, 32, contexts, context_stride, 32, (size_t)n, kind(contexts), c.stream));
+    if (st_sa) HIPCHK(hipMemcpy2DAsync(d_salt, 32, salts, salt_stride, 32, (size_t)n, kind(salts), c.stream));
+    KeyseedArgs ka{};
+    ka.sk = st_sk ? d_sk : sk; ka.sk_stride = skb; ka.sk_bytes = (int)skb; ka.K = c.P.K;
+    if (contexts) { ka.contexts = st_cx ? d_ctx : contexts; ka.context_stride = st_cx ? 32 : context_stride; }
+    if (salts) { ka.salts = st_sa ? d_salt : salts; ka.salt_stride = st_sa ? 32 : salt_stride; }
+    ka.out = d_seeds;
+    HIPCHK(launch_keyseed(ka, n, c.stream));
+    c.path_n[PATH_KEYSEED]++;
+    HIPCHK(stream_sync(c)); // the staging buffer, if any, goes with the call
+    return 0;
+}
+
+int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok,
+                      const DerivedSrc *derived)
+{
+    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    if (!sk || !ok) { c.err = "sk records and the ok buffer are required"; return -1; }
+    if ((tapes != nullptr) + (seeds != nullptr) + (derived != nullptr) != 1) { c.err = "internal: exactly one of tapes / seeds / derived"; return -1; }
     if (tapes && tape_stride < c.P.tape_bytes) { c.err = "tape_stride smaller than kosk_tape_bytes"; return -1; }
     if (seeds && seed_stride < SEED_BYTES) { c.err = "seed_stride smaller than KOSK_SEED_BYTES"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     const double t0 = now_sec();
-    if (seeds ? seed_tapes(c, n, seeds, seed_stride) : upload_tapes(c, n, tapes, tape_stride)) return -1;
-    if (witness_from_sk(c, n, sk, nullptr, ok)) return -1; // ends with the stream synchronised: the tapes are resident too
+    if (derived) {
+        if (stage_prover_keys_derived(c, n, sk, *derived, ok)) return -1;
+    } else {
+        if (seeds ? seed_tapes(c, n, seeds, seed_stride) : upload_tapes(c, n, tapes, tape_stride)) return -1;
+        if (witness_from_sk(c, n, sk, nullptr, ok)) return -1; // ends with the stream synchronised: the tapes are resident too
+    }
     c.phase_sec[PH_HOST_PRE] = now_sec() - t0;
     return 0;
 }

@@ -72,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -348,6 +348,7 @@ struct Ctx {
     // such call and owned by this context like `kem`
     int wit_cap = 0;
     uint8_t *d_wsk = nullptr, *d_wok = nullptr, *h_wok = nullptr;
+    uint8_t *d_wsalt = nullptr; // kosk-keyseed-v1: the call's salts, 32 bytes per key (allocated with d_wsk)
 
     ~Ctx();
 };
@@ -451,9 +452,19 @@ void finish_keygen_host(Ctx &c, int n, uint8_t *pk, uint8_t *sk);
 // coefficient outside [-eta1, eta1]).  se_out (host, may be nullptr): n x 2 K x 256 int16, s then e.  Synchronised.
 int witness_from_sk(Ctx &c, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok);
 void witness_release(Ctx &c);
-// the counterpart of stage_prover_inputs for such keys: tapes (exactly one of tapes / seeds; the first 64 bytes of a tape, the key
-// generation's seed, are not read) + witness resident for prove_resident
-int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok);
+// the counterpart of stage_prover_inputs for such keys: tapes (exactly one of tapes / seeds / derived; the first 64 bytes of a tape, the
+// key generation's seed, are not read) + witness resident for prove_resident.
+// derived (kosk-keyseed-v1): the seeds come from the records themselves, k_keyseed -> d_seedbuf -> k_tape_expand; an
+// armed context hashes the armed contexts bind_first .. bind_first + n (set by the entry point, as for prove_resident), salts (host or
+// device memory, nullptr: the deterministic form) are salt_stride >= 32 apart
+struct DerivedSrc {
+    const uint8_t *salts = nullptr;
+    size_t salt_stride = 0;
+};
+int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok,
+                      const DerivedSrc *derived = nullptr);
+// kernel level: n seeds of format kosk-keyseed-v1 into DEVICE memory (8-byte aligned), every input host or device memory; synchronised
+int keyseed_device(Ctx &c, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride, uint8_t *d_seeds);
 // everything from resident inputs to resident proof images (two host Fiat-Shamir round trips)
 enum FrontPart { FRONT_FULL = 0, FRONT_RANDOMNESS, FRONT_RANGE, FRONT_ONLINE };
 int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen = false);

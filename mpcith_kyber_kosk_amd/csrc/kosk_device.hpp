@@ -347,6 +347,20 @@ struct BindArgs {
     uint8_t *out;
 };
 hipError_t launch_bind_values(const BindArgs &A, int n, hipStream_t st);
+// kosk-keyseed-v1: out[b] = SHAKE256("kosk-keyseed-v1" || 00 || LE32(K) || LE32(flags) || context_b || salt_b || sk[b])[0:32]; flags bit 0:
+// contexts given, bit 1: salts given (a missing field is hashed as 32 zero bytes).  Nothing is written outside out[0 .. 32 n).  sk records of
+// sk_bytes = 768 K + 96; every base and stride a multiple of 8, context_stride / salt_stride >= 32 (else hipErrorInvalidValue)
+struct KeyseedArgs {
+    const uint8_t *sk;
+    size_t sk_stride;
+    int sk_bytes, K;
+    const uint8_t *contexts; // nullptr: unbound
+    size_t context_stride;
+    const uint8_t *salts;    // nullptr: deterministic
+    size_t salt_stride;
+    uint8_t *out;
+};
+hipError_t launch_keyseed(const KeyseedArgs &A, int n, hipStream_t st);
 hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st);
 bool copy_small_ok(const void *src, size_t src_stride, const void *dst, size_t dst_stride, size_t row_bytes);
 hipError_t launch_copy_small(const void *src, size_t src_stride, void *dst, size_t dst_stride, size_t row_bytes, size_t nrows, hipStream_t st);

@@ -231,6 +231,48 @@ __global__ __launch_bounds__(64) void k_bind_values(BindArgs A)
     if (lane < 4) *reinterpret_cast<uint2 *>(A.out + (size_t)b * 32 + 8 * lane) = w;
 }
 
+// kosk-keyseed-v1: seed_b = SHAKE256("kosk-keyseed-v1" || 00 || LE32(K) || LE32(flags) || context[32] || salt[32] || sk_b)[0:32],
+// one wave per key on the wave sponge, 13 / 19 / 24 permutations for K = 2 / 3 / 4.  Word g = 17 blk + w of the message is word g of
+// the 11-word header for g < 11 (all of it in block 0, built in registers) and word g - 11 of the sk record behind it; the record is a
+// whole number of words, so is the last block (88 / 40 / 128 bytes).  sk, salt and seed are secret: every address and every branch is
+// a function of K, the flags, blk and the lane alone.  Bases and strides multiples of 8 (launch_keyseed)
+__global__ __launch_bounds__(64) void k_keyseed(KeyseedArgs A)
+{
+    __shared__ __align__(16) uint32_t st[64];
+    const int lane = threadIdx.x, b = blockIdx.x;
+    WaveSponge sp;
+    sp.setup(lane);
+    const int word = sp.word();
+    const bool ld = word < 17;
+
+    const uint8_t *sk = A.sk + (size_t)b * A.sk_stride;
+    const int len = 88 + A.sk_bytes, nfull = len / 136, rem = len - nfull * 136; // (launch_keyseed: nfull >= 1, rem % 8 == 0)
+    const uint32_t flags = (A.contexts ? 1u : 0u) | (A.salts ? 2u : 0u);
+    // block 0: the header's words, then the record's first six
+    uint2 nx = make_uint2(0, 0);
+    if (word == 0) nx = make_uint2(0x6b736f6bu, 0x79656b2du);      // "kosk-key"
+    else if (word == 1) nx = make_uint2(0x64656573u, 0x0031762du); // "seed-v1", 00
+    else if (word == 2) nx = make_uint2((uint32_t)A.K, flags);
+    else if (word < 7) { if (A.contexts) nx = fs_load_word(A.contexts + (size_t)b * A.context_stride + 8 * (word - 3)); }
+    else if (word < 11) { if (A.salts) nx = fs_load_word(A.salts + (size_t)b * A.salt_stride + 8 * (word - 7)); }
+    else if (ld) nx = fs_load_word(sk + 8 * (word - 11));
+    const size_t mine = 8 * (size_t)(ld ? word : 0); // word w of block blk >= 1: byte 136 blk - 88 + 8 w of the record
+    uint32_t a = 0;
+#pragma unroll 1
+    for (int blk = 0; blk < nfull; blk++) {
+        const uint2 m = nx;
+        // the next block's word is in flight under this block's permutation; the last block brings the padding (uniform branch)
+        if (blk + 1 < nfull) nx = ld ? fs_load_word(sk + ((size_t)136 * (blk + 1) - 88 + mine)) : make_uint2(0, 0);
+        else nx = ld ? fs_last_word(sk + (size_t)136 * nfull - 88, rem, word, 0x1Fu) : make_uint2(0, 0);
+        sp.absorb(a, m);
+        sp.permute(a);
+    }
+    sp.absorb(a, nx);
+    sp.permute(a);
+    const uint2 w = sp.words(a, st, 4);
+    if (lane < 4) *reinterpret_cast<uint2 *>(A.out + (size_t)b * 32 + 8 * lane) = w;
+}
+
 } // namespace
 
 hipError_t launch_bind_values(const BindArgs &A, int n, hipStream_t st)
@@ -240,6 +282,17 @@ hipError_t launch_bind_values(const BindArgs &A, int n, hipStream_t st)
     if (!A.pk || !A.contexts || !A.out || A.pk_bytes < 8 || A.pk_bytes % 8 || A.pk_stride % 8 || A.pk_stride < (size_t)A.pk_bytes ||
         misaligned(A.pk) || misaligned(A.contexts) || misaligned(A.out)) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bind_values, dim3(n), dim3(64), 0, st, A);
+    return hipGetLastError();
+}
+
+hipError_t launch_keyseed(const KeyseedArgs &A, int n, hipStream_t st)
+{
+    if (n <= 0) return hipSuccess;
+    auto misaligned = [](const void *p) { return (reinterpret_cast<uintptr_t>(p) & 7) != 0; };
+    if (!A.sk || !A.out || A.K < 2 || A.K > 4 || A.sk_bytes != 768 * A.K + 96 || A.sk_stride % 8 || A.sk_stride < (size_t)A.sk_bytes || misaligned(A.sk) ||
+        misaligned(A.out) || (A.contexts && (misaligned(A.contexts) || A.context_stride % 8 || A.context_stride < 32)) ||
+        (A.salts && (misaligned(A.salts) || A.salt_stride % 8 || A.salt_stride < 32))) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_keyseed, dim3(n), dim3(64), 0, st, A);
     return hipGetLastError();
 }
 

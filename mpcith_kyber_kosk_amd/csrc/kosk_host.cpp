@@ -238,6 +238,21 @@ void bind_value(const Params &P, const uint8_t *pk, const uint8_t context[32], u
     sha3_256(out, m, sizeof m);
 }
 
+void keyseed_value(const Params &P, const uint8_t *sk, const uint8_t *context, const uint8_t *salt, uint8_t seed[SEED_BYTES])
+{
+    // one message: the 88-byte header, then the record as it stands (no folding, no look at H(pk))
+    std::vector<uint8_t> m(88 + P.sk_bytes, 0);
+    memcpy(m.data(), "kosk-keyseed-v1", 15);
+    m[16] = (uint8_t)P.K;
+    m[20] = (uint8_t)((context ? 1 : 0) | (salt ? 2 : 0));
+    if (context) memcpy(m.data() + 24, context, 32);
+    if (salt) memcpy(m.data() + 56, salt, 32);
+    memcpy(m.data() + 88, sk, P.sk_bytes);
+    shake256(seed, SEED_BYTES, m.data(), m.size());
+    volatile uint8_t *wipe = m.data(); // the copy of the key does not outlive the call
+    for (size_t i = 0; i < m.size(); i++) wipe[i] = 0;
+}
+
 void fs_alpha(const Params &P, const uint8_t *tcomm_all, uint16_t *alpha, const uint8_t *bind)
 {
     uint8_t h[32], a_[2 * MAXJ];

@@ -37,6 +37,9 @@ void fs_alpha(const Params &P, const uint8_t *tcomm_all /* [1454][32] */, uint16
 // kosk-bind-v1: B = sha3_256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || sha3_256(pk) || context); the host definition
 // of what k_bind_values (kosk_fs_kernels.hip) computes on the device
 void bind_value(const Params &P, const uint8_t *pk, const uint8_t context[32], uint8_t out[32]);
+// kosk-keyseed-v1: seed = SHAKE256("kosk-keyseed-v1" || 00 || LE32(K) || LE32(flags) || context || salt || sk)[0:32], flags
+// bit 0: context given, bit 1: salt given (a missing field is 32 zero bytes); the host definition of what k_keyseed computes on the device
+void keyseed_value(const Params &P, const uint8_t *sk, const uint8_t *context, const uint8_t *salt, uint8_t seed[32]);
 // mlwe_prover.cpp:445-474: opened list I (with the linear-probing de-dup) and its complement
 void fs_opened(const uint8_t *digests_all /* [1454][32] */, uint16_t I[NOPEN], uint16_t rest[NREST], const uint8_t *bind = nullptr);
 
