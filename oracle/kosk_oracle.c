@@ -1098,14 +1098,20 @@ void ko_verifiable_keygen(int K, ko_tape *t, uint8_t *pk, uint8_t *sk, uint8_t *
 /* verify (mlwe_verifier.cpp:4-686)                                         */
 /* ======================================================================== */
 
-#define FAIL(...)                                          \
+/* Every check carries the number of its fail bit ("Verifier fail bits").  ko_verify stops at the first
+ * failed comparison; ko_verify_sites (sites != NULL) counts it in sites[bit] and goes on -- the checks mutate nothing, so what
+ * follows a failed one sees what it would have seen.  Only the malformed list ends both: everything after it indexes with I. */
+#define FAIL(bit, ...)                                     \
     do {                                                   \
-        if (why) snprintf(why, whylen, __VA_ARGS__);       \
         ok = 0;                                            \
-        goto done;                                         \
+        if (sites) sites[bit]++;                           \
+        if (!sites || (bit) == 0) {                        \
+            if (why) snprintf(why, whylen, __VA_ARGS__);   \
+            goto done;                                     \
+        }                                                  \
     } while (0)
 
-int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t whylen)
+static int verify_core(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t whylen, uint32_t *sites)
 {
     ko_params P;
     ko_get_params(K, &P);
@@ -1133,7 +1139,7 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
     memset(in_I, 0, sizeof in_I);
     for (int i = 0; i < T; i++) {
         I[i] = G16(KO_F_I, i);
-        if (I[i] >= N || in_I[I[i]]) FAIL("malformed opened-party list at %d", i);
+        if (I[i] >= N || in_I[I[i]]) FAIL(0, "malformed opened-party list at %d", i);
         in_I[I[i]] = 1;
         pos_of[I[i]] = (uint16_t)i;
     }
@@ -1185,7 +1191,7 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
         for (int k = 0; k < 256; k++) bp[k] = ko_gf_decode(bs[k]);
         ko_poly_ntt(bp);
         for (int k = 0; k < 256; k++)
-            if (bp[k] != ko_gf_decode(gs[k])) FAIL("Check failed for beta[%d] and gamma[%d] relation.", j, j);
+            if (bp[k] != ko_gf_decode(gs[k])) FAIL(1, "Check failed for beta[%d] and gamma[%d] relation.", j, j);
     }
 
     /* V4 :173-247 */
@@ -1207,8 +1213,8 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
         ko_recompute_share_secrets_ddeg(er_sh[i], yval);
         for (int j = 256; j < KO_DEG + 1; j++) er_rnd[i][j] = er_sh[i][j - 256];
         for (int k = 0; k < R; k++) {
-            if (sr_sh[i][rest[k]] != G16(KO_F_SR, k * K + i)) FAIL("s + r share error at %d.", rest[k] + 256);
-            if (er_sh[i][rest[k]] != G16(KO_F_ER, k * K + i)) FAIL("e + r share error at %d.", rest[k] + 256);
+            if (sr_sh[i][rest[k]] != G16(KO_F_SR, k * K + i)) FAIL(2, "s + r share error at %d.", rest[k] + 256);
+            if (er_sh[i][rest[k]] != G16(KO_F_ER, k * K + i)) FAIL(2, "e + r share error at %d.", rest[k] + 256);
         }
     }
 
@@ -1226,9 +1232,9 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
     for (int i = 0; i < K; i++)
         for (int j = 0; j < T; j++) {
             if (G16(KO_F_NTTS, j * K + i) != ko_gf_sub(ntt_sr_sh[i][I[j]], nttr_op[j][i]))
-                FAIL("Check failed for NTT(s[%d]) at view %d.", i, I[j]);
+                FAIL(3, "Check failed for NTT(s[%d]) at view %d.", i, I[j]);
             if (G16(KO_F_NTTE, j * K + i) != ko_gf_sub(ntt_er_sh[i][I[j]], nttr_op[j][i + K]))
-                FAIL("Check failed for NTT(e[%d]) at view %d.", i, I[j]);
+                FAIL(3, "Check failed for NTT(e[%d]) at view %d.", i, I[j]);
         }
 
     /* V6 :287-312 */
@@ -1244,7 +1250,7 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
     for (int i = 0; i < K; i++)
         for (int j = 0; j < T; j++)
             if (ntt_Asr_sh[i][I[j]] != ko_gf_add(G16(KO_F_NTTAS, j * K + i), G16(KO_F_NTTAR, j * K + i)))
-                FAIL("Check failed for NTT(A*(s[%d]+r)) at view %d.", i, I[j]);
+                FAIL(4, "Check failed for NTT(A*(s[%d]+r)) at view %d.", i, I[j]);
 
     /* V7 :316-376 */
     for (int i = 0; i < K; i++) {
@@ -1255,12 +1261,12 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
         ko_recompute_share_secrets_ddeg(t_sh[i], yval);
         ko_poly_reduce(tp); /* :354 */
         for (int j = 0; j < 256; j++)
-            if (ko_gf_encode(tp[j]) != ko_gf_encode(mlwe->t[i][j])) FAIL("Check failed for t[%d] at %d.", i, j);
+            if (ko_gf_encode(tp[j]) != ko_gf_encode(mlwe->t[i][j])) FAIL(5, "Check failed for t[%d] at %d.", i, j);
     }
     for (int i = 0; i < K; i++)
         for (int j = 0; j < T; j++)
             if (t_sh[i][I[j]] != ko_gf_add(G16(KO_F_NTTAS, j * K + i), G16(KO_F_NTTE, j * K + i)))
-                FAIL("Check failed for t = A*s + e at view %d.", I[j]);
+                FAIL(6, "Check failed for t = A*s + e at view %d.", I[j]);
 
     /* V8 :382-466 */
     for (int i = 0; i < K; i++)
@@ -1271,7 +1277,7 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
                 for (int k = 0; k < KO_DEG + 1; k++) ys[k] = G16(fid, (k * K + i) * E + j);
                 interp_eval_range(&nd, ys, yval, 0, KO_DEG + 1);
                 for (int k = 0; k < 256; k++)
-                    if (yval[k] != cur) FAIL("Check failed for %c_eta[%d] at %d (%d != %d).", who ? 'e' : 's', i, k, cur, yval[k]);
+                    if (yval[k] != cur) FAIL(7, "Check failed for %c_eta[%d] at %d (%d != %d).", who ? 'e' : 's', i, k, cur, yval[k]);
                 ko_recompute_share_secrets_ddeg(who ? eeta_sh[i * MAXE + j] : seta_sh[i * MAXE + j], yval);
             }
         }
@@ -1279,9 +1285,9 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
         for (int j = 0; j < T; j++)
             for (int k = 0; k < E; k++) {
                 if (G16(KO_F_SSUB, (j * K + i) * E + k) != ko_gf_sub(G16(KO_F_S, j * K + i), seta_sh[i * MAXE + k][I[j]]))
-                    FAIL("Check failed for s - eta at view %d, eta[%d][%d][%d].", I[j], i, j, k);
+                    FAIL(8, "Check failed for s - eta at view %d, eta[%d][%d][%d].", I[j], i, j, k);
                 if (G16(KO_F_ESUB, (j * K + i) * E + k) != ko_gf_sub(G16(KO_F_E, j * K + i), eeta_sh[i * MAXE + k][I[j]]))
-                    FAIL("Check failed for e - eta at view %d.", I[j]);
+                    FAIL(8, "Check failed for e - eta at view %d.", I[j]);
             }
 
     /* V9 :469-581 */
@@ -1302,12 +1308,12 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
                 for (int k = 0; k < KO_DEG2 + 1; k++) ys[k] = G16(fid, (k * K + i) * Z + j);
                 interp_eval_range(&nd2, ys, z256, 0, 256);
                 for (int k = 0; k < 256; k++)
-                    if (z256[k] != 0) FAIL("Check failed for %c.u[%d] at %d (%d != 0).", who ? 'e' : 's', i, k, z256[k]);
+                    if (z256[k] != 0) FAIL(9, "Check failed for %c.u[%d] at %d (%d != 0).", who ? 'e' : 's', i, k, z256[k]);
                 uint16_t *row = who ? ue_sh[i * MAXZ + j] : us_sh[i * MAXZ + j];
                 for (int k = 0; k < R; k++) row[rest[k]] = G16(fid, (k * K + i) * Z + j);
                 ko_recon_secrets_2ddeg(z256, row);
                 for (int k = 0; k < 256; k++)
-                    if (z256[k] != 0) FAIL("Check failed for inconsistency of %c.u2d[%d] shares at %d.", who ? 'e' : 's', i, k);
+                    if (z256[k] != 0) FAIL(10, "Check failed for inconsistency of %c.u2d[%d] shares at %d.", who ? 'e' : 's', i, k);
             }
         }
 
@@ -1339,7 +1345,7 @@ int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t w
         uint16_t I2[KO_OPENED];
         derive_opened(&vdig[0][0], ch, I2);
         for (int i = 0; i < T; i++)
-            if (I2[i] != I[i]) FAIL("Check failed for reom_I[%d]=%d (pi.I[%d]=%d).", i, I2[i], i, I[i]);
+            if (I2[i] != I[i]) FAIL(11, "Check failed for reom_I[%d]=%d (pi.I[%d]=%d).", i, I2[i], i, I[i]);
     }
     (void)pos_of;
 
@@ -1353,8 +1359,19 @@ done:
     return ok;
 }
 
-/* kosk.cpp:88-117 */
-int ko_kosk_verify(int K, const uint8_t *pi, const uint8_t *pk, char *why, size_t whylen)
+int ko_verify(int K, const uint8_t *pi, const ko_mlwe *mlwe, char *why, size_t whylen)
+{
+    return verify_core(K, pi, mlwe, why, whylen, NULL);
+}
+
+/* test hook (no reference counterpart): the same verifier, every failing comparison counted under its fail bit */
+int ko_verify_sites(int K, const uint8_t *pi, const ko_mlwe *mlwe, uint32_t sites[12])
+{
+    memset(sites, 0, 12 * sizeof sites[0]);
+    return verify_core(K, pi, mlwe, NULL, 0, sites);
+}
+
+static ko_mlwe *mlwe_from_pk(int K, const uint8_t *pk)
 {
     ko_mlwe *raw = (ko_mlwe *)calloc(1, sizeof *raw);
     int16_t A[4 * 4 * 256];
@@ -1362,7 +1379,22 @@ int ko_kosk_verify(int K, const uint8_t *pi, const uint8_t *pk, char *why, size_
     ko_gen_matrix(A, pk + 384 * K, 0, K);
     for (int i = 0; i < K; i++)
         for (int j = 0; j < K; j++) memcpy(raw->A[i][j], A + ((size_t)i * K + j) * 256, 512);
+    return raw;
+}
+
+/* kosk.cpp:88-117 */
+int ko_kosk_verify(int K, const uint8_t *pi, const uint8_t *pk, char *why, size_t whylen)
+{
+    ko_mlwe *raw = mlwe_from_pk(K, pk);
     int ok = ko_verify(K, pi, raw, why, whylen);
+    free(raw);
+    return ok;
+}
+
+int ko_kosk_verify_sites(int K, const uint8_t *pi, const uint8_t *pk, uint32_t sites[12])
+{
+    ko_mlwe *raw = mlwe_from_pk(K, pk);
+    int ok = ko_verify_sites(K, pi, raw, sites);
     free(raw);
     return ok;
 }

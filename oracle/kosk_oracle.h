@@ -164,6 +164,12 @@ int ko_craft_add(int kind, int idx, int party, int mult);
  * Fiat-Shamir list; NULL clears it.  Returns -1 and changes nothing for an entry >= KO_PARTIES or a duplicate (see kosk_oracle.c) */
 int ko_force_opened(const uint16_t I[KO_OPENED]);
 
+/* test hook (no reference counterpart): ko_verify / ko_kosk_verify that do not stop at a failed comparison but count it in
+ * sites[fail bit] (1 NTT(beta) != gamma ... 11 I' != I) and go on; only the malformed list (bit 0) still ends
+ * the run.  Returns the verify bit.  The counts travel through the out-parameter only: callable from several threads at once */
+int ko_verify_sites(int K, const uint8_t *pi, const ko_mlwe *mlwe, uint32_t sites[12]);
+int ko_kosk_verify_sites(int K, const uint8_t *pi, const uint8_t *pk, uint32_t sites[12]);
+
 #ifdef __cplusplus
 }
 #endif

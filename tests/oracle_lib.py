@@ -100,6 +100,14 @@ def kosk_verify(k, pi, pk):
     return bool(ok), why.value.decode()
 
 
+def kosk_verify_sites(k, pi, pk):
+    """ko_kosk_verify_sites: the oracle's verifier going on after a failed comparison -> (verify bit, sites): sites[b] = how many
+    comparisons of fail bit b failed; only a malformed opened list (bit 0) ends the run early"""
+    sites = (C.c_uint32 * 12)()
+    ok = lib.ko_kosk_verify_sites(k, C.c_char_p(pi), C.c_char_p(pk), sites)
+    return bool(ok), list(sites)
+
+
 def sha3_256(data):
     out = C.create_string_buffer(32)
     lib.ko_sha3_256(out, C.c_char_p(bytes(data)), len(data))

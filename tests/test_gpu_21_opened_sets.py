@@ -161,7 +161,7 @@ TAMPER_AT = {13: (0, 406, 407, 1303),  # s + r: every record is compared
              8: (0, 406, 407),         # t
              15: (406, 407),           # s_eta
              21: (0, 812, 813)}        # u_s: degree 2d
-MESSAGE_BIT = (("s + r share error", 2), ("e + r share error", 2), ("for t[", 5), ("_eta[", 7), (".u[", 9), ("u2d[", 10))
+MESSAGE_BIT = (("beta[", 1), ("s + r share error", 2), ("e + r share error", 2), ("for t[", 5), ("_eta[", 7), (".u[", 9), ("u2d[", 10))
 
 
 @pytest.mark.parametrize("name", list(osets.CATALOGUE))
