@@ -88,6 +88,43 @@ int kosk_set_randombytes(kosk_ctx *ctx, kosk_randombytes_fn fn, void *user); /* 
 enum { KOSK_ENTROPY_TAPE = 0, KOSK_ENTROPY_SEED = 1 };
 int kosk_set_entropy(kosk_ctx *ctx, int mode);
 
+/* ---- Erasing secrets.  The handle keeps an inventory of every buffer it owns, in HBM and in page-locked host
+ * memory, and of which of them can hold secret-derived bytes: the row matrix, tapes and seeds, s / e and their NTTs, the NTT(s) bytes
+ * and sha3_512 output of the key records, the sk copies and salts of the calls on existing keys, and the KEM workspace except its
+ * public keys, ciphertexts, A, H(pk) and flags.
+ * kosk_wipe_secrets zeroes all of those now (one launch of k_wipe for the HBM regions, the host for the page-locked staging) and returns
+ * when that is done.  It must not be called while another thread is inside a call on the handle.  Afterwards the handle is as usable
+ * as before, and its PUBLIC resident state is untouched: kosk_fetch_proofs*, kosk_resident_proofs, kosk_resident_digests,
+ * kosk_verify_resident_pk(pk == NULL), kosk_kem_enc_verified and kosk_verify_fail_masks behave exactly as without the wipe.  Staged
+ * prover inputs are gone: kosk_prove_resident returns -1 ("staged inputs were wiped") until a staging call has run again.  Memory of
+ * the caller -- its buffers, device tapes read in place -- is never touched.
+ * kosk_set_wipe(KOSK_WIPE_CALL): every entry point that brings secrets onto the handle ends with that wipe, on success and on every
+ * error return: the key generations in every form, kosk_prove_resident, kosk_prove_prepared, kosk_prepare_*, kosk_kem_enc_batch /
+ * _dec_batch / _enc_verified / _keypair_batch, kosk_kem_check_sk, kosk_keyseed_device, kosk_tape_expand_device and kosk_prove_keys_*;
+ * chunked calls and streams > 1 wipe every sub-context.  Not the staging calls (kosk_stage_prover_inputs*, kosk_stage_prover_keys*,
+ * kosk_witness_from_sk): their secrets are the input of the kosk_prove_resident that follows, which wipes when it ends.  A member of
+ * a cohort (combine >= 2) in this mode keeps its calls out of merged runs, exactly as an armed handle does, and wipes its own block of
+ * the shared workspace.  One difference: kosk_combine_stats counts an armed member's solo runs (calls == members) and leaves the solo
+ * runs of a member in this mode out (0, 0).  KOSK_WIPE_OFF is the default; any other mode: -1, nothing changed.  With the mode off every call returns
+ * the bytes it returned before these calls existed.
+ * kosk_destroy always wipes before it frees; the last member of a cohort to be destroyed wipes the whole shared workspace.
+ * kosk_secret_scan is the audit: *hits = the number of byte positions at which needle[0, len), 16 <= len <= 64, occurs in ANY buffer
+ * of the inventory, secret or public, HBM (k_scan) and page-locked host memory -- so that a buffer filed under the wrong heading
+ * shows.  A diagnostic: unmerged, synchronised, not constant-time in the needle; its own device copy of the needle is cleared before
+ * it returns.  -1 for a NULL argument or len out of range. */
+enum { KOSK_WIPE_OFF = 0, KOSK_WIPE_CALL = 1 };
+int kosk_wipe_secrets(kosk_ctx *ctx);
+int kosk_set_wipe(kosk_ctx *ctx, int mode);
+int kosk_secret_scan(kosk_ctx *ctx, const uint8_t *needle, size_t len, long *hits);
+/* kernel level (tests): k_wipe on the CALLER's device memory, region i = [d_ptrs[i], d_ptrs[i] + bytes[i]), any alignment, any length
+ * (0: skipped), any number of regions; nothing outside the regions is written.  Runs on the handle's own stream, synchronised on return. */
+int kosk_wipe_device(kosk_ctx *ctx, int nregions, void *const *d_ptrs, const size_t *bytes);
+/* UNSTABLE, not part of the supported interface: a diagnostic for tools/wipe_rate.py that may change or go without notice, and that WIPES
+ * THE HANDLE as a side effect (staged inputs included).  It wipes the handle (streams = 1, or sub-batch 0 of it) and then times `reps` launches of k_wipe over its
+ * secret HBM regions and `reps` rounds of the runtime's own fills of the same regions (one hipMemsetAsync per region), each between
+ * two events on the handle's stream.  *bytes / *regions (may be NULL): what one wipe clears in HBM. */
+int kosk_wipe_timing(kosk_ctx *ctx, int reps, double *wipe_ms, double *memset_ms, size_t *bytes, int *regions);
+
 /* void kyber_verifiable_keygen(kyber_keypair *keypair, uint8_t *pi)   kosk.hpp:20-21, kosk.cpp:72-86
  * n independent instances; pk/sk/pi are n consecutive records of kosk_*_bytes().
  * `tapes` == NULL draws randomness through the randombytes callback; otherwise
@@ -231,8 +268,8 @@ int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image
  * Encoding: like the reference's polyvec_frombytes these calls take any 12-bit coefficient in a pk or sk and compute with it mod q
  * (the ciphertext then differs from the canonical key's because H(pk) does); kosk_options::strict_encoding concerns proofs and is
  * not consulted.  Decapsulation has no branch and no address that depends on s, m', the comparison or z; its secret-derived scratch
- * (m', K-bar || coins, r, e1, e2, the rejection key) stays in the handle's HBM workspace until the next KEM call overwrites it or
- * the handle is destroyed.
+ * (m', K-bar || coins, r, e1, e2, the rejection key) stays in the handle's HBM workspace until it is erased: by kosk_wipe_secrets, at the end of the
+ * call under KOSK_WIPE_CALL, or by kosk_destroy.
  * All three calls run unmerged on the handle's own stream, reset and check the HIP error state like every entry point, and return -1
  * ("block limit", no results) if gen_matrix reached its block limit. */
 #define KOSK_SS_BYTES 32
@@ -255,7 +292,7 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
  * buffer.  The call does not touch the prover's and verifier's resident state (kosk_kem_enc_verified after it behaves as before it).
  * No branch and no address depends on d, the noise seed, s, e or z (only gen_matrix's rejection sampling, on the public rho, branches
  * on data); z is copied, never hashed.  The secret scratch (d || z, the noise seed, s, e, the sk records) stays in the handle's HBM
- * workspace until a later KEM call overwrites it or the handle is destroyed.  -1 with a text and nothing started
+ * workspace until it is erased: kosk_wipe_secrets, KOSK_WIPE_CALL or kosk_destroy.  -1 with a text and nothing started
  * for n < 1 or a NULL pk / sk; -1 ("block limit", no results, device outputs untouched) if gen_matrix reached its block limit. */
 int kosk_kem_keypair_batch(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk);
 /* The input checks of FIPS 203 for n >= 1 records, host or device memory; flags: n bytes, host or device memory, flags[b] about
@@ -275,7 +312,7 @@ int kosk_kem_check_sk(kosk_ctx *ctx, int n, const uint8_t *sk, uint8_t *flags); 
  * [-eta1, eta1] (eta1 = 3 for kyber_k 2, else 2), the range the proof is about: true for every honestly generated key, false for a
  * record whose halves do not belong together or that was tampered with.  Where ok[b] = 0 the witness written for b is all zero.
  * No branch and no address of the recovery depends on s-hat, s, e or the verdict.  The copy of the sk records, s and e stay in the
- * handle's HBM workspace until a later call overwrites them or the handle is destroyed.
+ * handle's HBM workspace until they are erased: kosk_wipe_secrets, KOSK_WIPE_CALL or kosk_destroy.
  * All five calls return -1 with a kosk_last_error text and start nothing for n out of range, a NULL sk / ok / pi or a stride below
  * one tape / seed, and -1 ("block limit", no results) if gen_matrix reached its block limit; else 0, and ok[] says which keys were proven.
  * They run unmerged on the handle's own stream(s): on a member of a cohort (combine >= 2) and with streams > 1 the staging calls and
@@ -309,7 +346,8 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * proving: tapes expanded from seeds in HBM), 12 kem_enc / 13 kem_dec: launch groups (up to 16384 items, three or four launches each) of the KEM calls,
  * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch),
  * 15 kem_keypair / 16 kem_check: launch groups of kosk_kem_keypair_batch and of kosk_kem_check_pk / kosk_kem_check_sk,
- * 17 launches of k_keyseed (kosk-keyseed-v1: seeds derived from the sk records in HBM). */
+ * 17 launches of k_keyseed (kosk-keyseed-v1: seeds derived from the sk records in HBM),
+ * 18 launches of k_wipe (kosk_wipe_secrets, the wipe at the end of a call under KOSK_WIPE_CALL, kosk_wipe_device). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -167,6 +167,16 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_keyseed_value")):
         sig.update(keyseed)
+    # erasing secrets and the audit scan; optional under the same rule (and only then)
+    wipe = {
+        "kosk_wipe_secrets": (C.c_int, [vp]),
+        "kosk_set_wipe": (C.c_int, [vp, C.c_int]),
+        "kosk_secret_scan": (C.c_int, [vp, vp, sz, C.POINTER(C.c_long)]),
+        "kosk_wipe_device": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_wipe_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_wipe_secrets")):
+        sig.update(wipe)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -197,7 +207,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_stage_verifier_inputs_dense", "kosk_verifiable_keygen_batch_dense", "kosk_verifiable_keygen_seeded_batch_dense",
            "kosk_verify_batch_dense", "kosk_dense_fill_device",
            "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk",
-           "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch"]
+           "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch",
+           "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -210,6 +221,7 @@ class KoskOptions(C.Structure):
 
 FS_HOST, FS_DEVICE = 0, 1
 ENTROPY_TAPE, ENTROPY_SEED = 0, 1  # kosk_set_entropy
+WIPE_OFF, WIPE_CALL = 0, 1  # kosk_set_wipe
 SEED_BYTES = 32
 SS_BYTES = 32  # KOSK_SS_BYTES
 KEYPAIR_COIN_BYTES = 64  # d || z of crypto_kem_keypair_derand
@@ -421,6 +433,36 @@ class Kosk:
         """what a call without tapes draws: ENTROPY_TAPE (default) the reference's sequence, a whole tape per proof; ENTROPY_SEED one
         32-byte seed per proof, expanded on the device (kosk_set_entropy)"""
         self._chk(lib.kosk_set_entropy(self._h, int(mode)), "set_entropy")
+
+    def wipe_secrets(self):
+        """zero every secret buffer of the handle now, HBM and page-locked staging; public resident state survives (kosk_wipe_secrets)"""
+        self._chk(lib.kosk_wipe_secrets(self._h), "wipe_secrets")
+
+    def set_wipe(self, mode):
+        """WIPE_OFF (default), or WIPE_CALL: every entry point that brings secrets onto the handle ends with the wipe (kosk_set_wipe)"""
+        self._chk(lib.kosk_set_wipe(self._h, int(mode)), "set_wipe")
+
+    def secret_scan(self, needle):
+        """the audit: at how many byte positions of ANY buffer the handle owns, HBM or page-locked, do these 16..64 bytes occur"""
+        needle = bytes(needle)
+        hits = C.c_long()
+        if lib.kosk_secret_scan(self._h, C.c_char_p(needle), len(needle), C.byref(hits)):
+            raise KoskError("secret_scan: " + (lib.kosk_last_error(self._h).decode() or "NULL argument or a needle outside 16..64 bytes"))
+        return hits.value
+
+    def wipe_device(self, d_ptrs, sizes):
+        """kernel level: k_wipe on the caller's device memory, region i = [d_ptrs[i], d_ptrs[i] + sizes[i]) (int pointers)"""
+        n = len(d_ptrs)
+        ptrs = (C.c_void_p * max(n, 1))(*d_ptrs)
+        lens = (C.c_size_t * max(n, 1))(*sizes)
+        self._chk(lib.kosk_wipe_device(self._h, n, ptrs, lens), "wipe_device")
+
+    def wipe_timing(self, reps=20):
+        """diagnostic (kosk_wipe_timing): (ms per k_wipe launch over the secret HBM regions, ms of the runtime's fills of the same regions,
+        bytes, regions)"""
+        a, b, n, r = C.c_double(), C.c_double(), C.c_size_t(), C.c_int()
+        self._chk(lib.kosk_wipe_timing(self._h, reps, C.byref(a), C.byref(b), C.byref(n), C.byref(r)), "wipe_timing")
+        return a.value, b.value, n.value, r.value
 
     def set_contexts(self, contexts, n=None, stride=None):
         """arm the handle (kosk_set_contexts): from now on position b of every proving / verifying call uses context b.
@@ -923,6 +965,7 @@ class Kosk:
     PATH_KEM_KEYPAIR = 15
     PATH_KEM_CHECK = 16
     PATH_KEYSEED = 17
+    PATH_WIPE = 18
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -68,9 +68,11 @@ struct kosk_ctx {
     // kosk_set_contexts (kosk-bind-v1): the handle's own copy of the armed contexts in HBM, 32 bytes each; every sub-context points at it
     uint8_t *d_contexts = nullptr;
     int armed = 0;
+    int wipe_mode = 0; // kosk_set_wipe: KOSK_WIPE_CALL ends every secret-bearing entry point with wipe_secrets() on every sub-context
     void disarm()
     {
         for (Ctx *x : sub) { x->bind_ctx = nullptr; x->bind_n = 0; x->bind_first = 0; }
+        if (c) c->inv_drop(Ctx::INVG_BIND);
         if (d_contexts) (void)hipFree(d_contexts);
         d_contexts = nullptr;
         armed = 0;
@@ -79,6 +81,10 @@ struct kosk_ctx {
     ~kosk_ctx()
     {
         lanes.lanes.clear(); // join the lane threads before their sub-contexts go
+        // nothing secret goes back to the allocator readable: every sub-context (a cohort member: its own block and private buffers)
+        for (Ctx *x : sub) {
+            try { (void)wipe_secrets(*x); } catch (...) {}
+        }
         disarm();
         for (Ctx *x : sub) delete x;
         if (cohort) {
@@ -86,7 +92,8 @@ struct kosk_ctx {
             cohort->member[member_i] = nullptr;
             if (const char *e = getenv("KOSK_COMBINE_TRACE"))
                 if (atoi(e)) fprintf(stderr, "[kosk combine] cohort %p %s\n", (void *)cohort, cohort->comb->trace(member_i).c_str());
-            if (cohort->comb->leave(member_i) == 0) { // the last member frees the arena
+            if (cohort->comb->leave(member_i) == 0) { // the last member wipes the whole arena and frees it
+                try { (void)wipe_secrets(*cohort->arena); } catch (...) {}
                 delete cohort->arena;
                 g_cohorts.erase(std::remove(g_cohorts.begin(), g_cohorts.end(), cohort), g_cohorts.end());
                 delete cohort;
@@ -165,6 +172,32 @@ static int guard(const kosk_ctx *, const char *, F &&body) noexcept // read-only
 #define GUARD(ctx) return guard(ctx, __func__, [&]() -> int {
 #define GUARD_END });
 
+// KOSK_WIPE_CALL (kosk_set_wipe): an entry point that brings secrets onto the handle ends with the wipe of every sub-context, however its
+// body ends -- success, an error return, an exception.  Mode off: one untaken branch
+static int wipe_handle(kosk_ctx *h)
+{
+    int rc = 0;
+    for (Ctx *x : h->sub)
+        if (wipe_secrets(*x)) { h->err = x->err; h->c->err = x->err; rc = -1; }
+    return rc;
+}
+template <typename F>
+static int wiped_call(kosk_ctx *h, F &&body)
+{
+    if (!h->wipe_mode) return body();
+    int rc;
+    try {
+        rc = body();
+    } catch (...) {
+        try { (void)wipe_handle(h); } catch (...) {}
+        throw;
+    }
+    if (wipe_handle(h) && !rc) rc = -1;
+    return rc;
+}
+#define WGUARD(ctx) return guard(ctx, __func__, [&]() -> int { return wiped_call(ctx, [&]() -> int {
+#define WGUARD_END }); });
+
 // argument validation failed: the call has done nothing; kosk_last_error(ctx) says which entry point refused
 static int bad_args(const kosk_ctx *, const char *) { return -1; } // read-only entry points leave the error string alone
 static int bad_args(kosk_ctx *ctx, const char *fn)
@@ -236,6 +269,9 @@ struct RandSrc {
     size_t seed_stride = 0;
     bool seeded = false; // a *_seeded entry point, or tapes == NULL on a handle in KOSK_ENTROPY_SEED mode
     std::vector<uint8_t> drawn;
+    RandSrc() = default;
+    RandSrc(RandSrc &&) = default;
+    ~RandSrc() { host_wipe_vec(drawn); } // drawn tapes / seeds do not go back to the heap readable
 
     static RandSrc from_tapes(const kosk_ctx *ctx, const uint8_t *tapes, size_t tape_stride)
     {
@@ -478,6 +514,7 @@ int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t cont
     ctx->disarm();
     ctx->d_contexts = d;
     ctx->armed = n;
+    c.reg_buf("d_contexts", &ctx->d_contexts, (size_t)n * 32, 0, Ctx::INVG_BIND); // public: the caller's contexts
     for (Ctx *x : ctx->sub) { x->bind_ctx = d; x->bind_n = n; x->bind_first = 0; }
     return 0;
     GUARD_END
@@ -521,9 +558,9 @@ int kosk_prove_resident(kosk_ctx *ctx, int n)
 {
     if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
-    GUARD(ctx)
+    WGUARD(ctx)
     return ctx->run(n, [&](Ctx &c, int first, int count) { return prove_at(c, first, count); });
-    GUARD_END
+    WGUARD_END
 }
 int kosk_fetch_proofs(kosk_ctx *ctx, int n, uint8_t *pi)
 {
@@ -588,8 +625,12 @@ static void run_epilogue(Cohort &co, int first, int count, int rc, const Ctx &le
 {
     for (int k = 0; k < count; k++) {
         kosk_ctx *m = co.member[first + k];
-        m->merged_calls++;
-        m->merged_members += count;
+        // what keeps a member in KOSK_WIPE_CALL out of merged runs is CK_ALONE (combined_keygen / combined_verify); this only keeps its
+        // solo runs out of kosk_combine_stats, which an armed member's solo runs are counted in (header: kosk_set_wipe)
+        if (!(m->wipe_mode && count == 1)) {
+            m->merged_calls++;
+            m->merged_members += count;
+        }
         if (k) memcpy(m->c->phase_sec, lead.phase_sec, sizeof(lead.phase_sec));
         if (rc) { m->err = lead.err; m->c->err = lead.err; }
     }
@@ -641,6 +682,7 @@ static int combined_keygen(kosk_ctx *h, int n, const KeygenCall &call)
     r.kind = (call.tapes || call.seeds) ? CK_KEYGEN : CK_ALONE;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE; // the hook must fire on this caller's own thread (kosk_options::hooks_unmerged)
     if (h->armed) r.kind = CK_ALONE; // bound proofs (kosk_set_contexts) stay out of merged runs: binding is not part of what makes calls mergeable
+    if (h->wipe_mode) r.kind = CK_ALONE; // KOSK_WIPE_CALL: the member wipes its own block when its call ends, so the call is its own run
     h->c->bind_first = 0;
     r.n = n;
     r.full = n == co.per;
@@ -690,7 +732,7 @@ static int combined_verify(kosk_ctx *h, int n, const VerifyCall &call)
     CombineReq r;
     r.kind = call.pk ? CK_VERIFY_PK_GIVEN : CK_VERIFY_PK_RESIDENT;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE;
-    if (h->armed) r.kind = CK_ALONE; // as in combined_keygen
+    if (h->armed || h->wipe_mode) r.kind = CK_ALONE; // as in combined_keygen
     h->c->bind_first = 0;
     r.n = n;
     r.full = n == co.per;
@@ -751,29 +793,29 @@ int kosk_verifiable_keygen_resident(kosk_ctx *ctx, int n, const uint8_t *tapes, 
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return keygen_resident_from(ctx, n, src, pk, sk);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verifiable_keygen_seeded_resident(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
     return keygen_resident_from(ctx, n, src, pk, sk);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_tape_expand_device(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !seeds || !d_tapes) return bad_args(ctx, __func__);
     if (seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     ctx->clear_err();
     return tape_expand_device(*ctx->c, n, seeds, seed_stride, d_tapes, tape_stride);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verify_resident_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *ok)
 {
@@ -829,10 +871,10 @@ int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, siz
     if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return keygen_batch_from(ctx, n, src, pk, sk, pi);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi)
 {
@@ -840,10 +882,10 @@ int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *see
     ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
     return keygen_batch_from(ctx, n, src, pk, sk, pi);
-    GUARD_END
+    WGUARD_END
 }
 
 int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk, uint8_t *ok)
@@ -890,10 +932,10 @@ int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *ta
     if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
                                                 uint8_t *out)
@@ -902,10 +944,10 @@ int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint
     ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
     return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
-    GUARD_END
+    WGUARD_END
 }
 static int verify_batch_packed(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok, bool dense)
 {
@@ -937,10 +979,10 @@ int kosk_verifiable_keygen_batch_dense(kosk_ctx *ctx, int n, const uint8_t *tape
     if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
@@ -948,10 +990,10 @@ int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_
     ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
     if (n == 0) return 0;
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
     return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
 {
@@ -971,7 +1013,7 @@ size_t kosk_mlwe_inst_bytes(int k) { Params p; return make_params(k, p) ? mlwe_i
 int kosk_prepare_randomness(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *rand_out)
 {
     if (!ctx || n < 0 || !rand_out) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     Ctx &c = *ctx->c;
     ctx->clear_err();
     for (int done = 0; done < n;) {
@@ -981,12 +1023,12 @@ int kosk_prepare_randomness(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t t
         done += m;
     }
     return 0;
-    GUARD_END
+    WGUARD_END
 }
 int kosk_prepare_range_proof(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *range_out)
 {
     if (!ctx || n < 0 || !range_out) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     Ctx &c = *ctx->c;
     ctx->clear_err();
     for (int done = 0; done < n;) {
@@ -996,14 +1038,14 @@ int kosk_prepare_range_proof(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t 
         done += m;
     }
     return 0;
-    GUARD_END
+    WGUARD_END
 }
 int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t *rand_in, const uint8_t *range_in,
                         const uint8_t *tapes, size_t tape_stride, uint8_t *pi)
 {
     if (!ctx || n < 0 || !inst || !rand_in || !range_in || !pi) return bad_args(ctx, __func__);
     if (ctx->armed) return armed_refuse(ctx, __func__, "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind");
-    GUARD(ctx)
+    WGUARD(ctx)
     Ctx &c = *ctx->c;
     ctx->clear_err();
     for (int done = 0; done < n;) {
@@ -1014,7 +1056,7 @@ int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t
         done += m;
     }
     return 0;
-    GUARD_END
+    WGUARD_END
 }
 int kosk_verify_inst(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *inst, uint8_t *ok)
 {
@@ -1155,35 +1197,37 @@ static int kem_chunks(kosk_ctx *ctx, int n, const std::function<int(Ctx &, int, 
 int kosk_kem_enc_batch(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
 {
     if (!ctx || n < 1 || !pk || !ct || !ss) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     const Params &P = ctx->c->P;
     const size_t ctb = kosk_ct_bytes(P.K);
     std::vector<uint8_t> drawn;
+    VecWiper<uint8_t> drawn_gone(drawn);
     const uint8_t *m = kem_coins(ctx, n, coins, drawn);
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         return kem_enc(c, count, pk + (size_t)first * P.pk_bytes, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32);
     });
-    GUARD_END
+    WGUARD_END
 }
 int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
 {
     if (!ctx || n < 1 || !ct || !sk || !ss) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     const Params &P = ctx->c->P;
     const size_t ctb = kosk_ct_bytes(P.K);
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         return kem_dec(c, count, ct + (size_t)first * ctb, sk + (size_t)first * P.sk_bytes, ss + (size_t)first * 32);
     });
-    GUARD_END
+    WGUARD_END
 }
 // crypto_kem_keypair[_derand] (kem.c:25-57): the caller's coins, or one 64-byte draw (d || z) per item, in item order, on the caller's
 // thread (kem.c:53-54).  Only the KEM workspace is written: pk_epoch, the resident keys and verify_keys stay as they are.
 int kosk_kem_keypair_batch(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk)
 {
     if (!ctx || n < 1 || !pk || !sk) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     const Params &P = ctx->c->P;
     std::vector<uint8_t> drawn;
+    VecWiper<uint8_t> drawn_gone(drawn);
     if (!coins) {
         drawn.resize((size_t)n * 64);
         const Ctx &c0 = *ctx->c;
@@ -1197,7 +1241,7 @@ int kosk_kem_keypair_batch(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         return kem_keypair(c, count, coins + (size_t)first * 64, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes);
     });
-    GUARD_END
+    WGUARD_END
 }
 static_assert(KOSK_KEYCHK_HASH == KEYCHK_HASH && KOSK_KEYCHK_PK_RANGE == KEYCHK_PK_RANGE && KOSK_KEYCHK_S_RANGE == KEYCHK_S_RANGE, "kosk_mi355x.h and kosk_ctx.hpp");
 int kosk_kem_check_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *flags)
@@ -1211,15 +1255,15 @@ int kosk_kem_check_pk(kosk_ctx *ctx, int n, const uint8_t *pk, uint8_t *flags)
 int kosk_kem_check_sk(kosk_ctx *ctx, int n, const uint8_t *sk, uint8_t *flags)
 {
     if (!ctx || n < 1 || !sk || !flags) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     const Params &P = ctx->c->P;
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) { return kem_check(c, count, sk + (size_t)first * P.sk_bytes, 1, flags + first); });
-    GUARD_END
+    WGUARD_END
 }
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
 {
     if (!ctx || n < 1 || !ct || !ss || !done) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     ctx->clear_err();
     auto refuse = [&](const char *why) { ctx->err = std::string("kosk_kem_enc_verified: ") + why; ctx->c->err = ctx->err; return -1; };
     if (ctx->cohort) return refuse("not available with call combining (the handle is a member of a cohort)");
@@ -1231,6 +1275,7 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
     if (ctx->verify_epoch != ctx->c->pk_epoch || ctx->c->resident_pk_n < n) return refuse("the resident public keys were replaced after the last verify call");
     // coins are drawn for every position, accepted or not: the draw order does not depend on the outcome
     std::vector<uint8_t> drawn, bits((size_t)n);
+    VecWiper<uint8_t> drawn_gone(drawn);
     const uint8_t *m = kem_coins(ctx, n, coins, drawn);
     for (int b = 0; b < n; b++) bits[(size_t)b] = ctx->masks[(size_t)b] == 0;
     const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
@@ -1239,7 +1284,7 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
         })) return -1;
     if (hipMemcpy(done, bits.data(), (size_t)n, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return refuse("copying the verify bits to `done` failed"); }
     return 0;
-    GUARD_END
+    WGUARD_END
 }
 
 // ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----
@@ -1333,20 +1378,20 @@ int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
     return prove_keys_from(ctx, n, sk, src, pi, ok);
-    GUARD_END
+    WGUARD_END
 }
 int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok)
 {
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
     return prove_keys_from(ctx, n, sk, src, pi, ok);
-    GUARD_END
+    WGUARD_END
 }
 
 // ---- kosk-keyseed-v1: the randomness derived from the key itself.  Position b of the call hashes armed context b (the
@@ -1379,7 +1424,7 @@ int kosk_prove_keys_derived_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
     if (salts && salt_stride < 32) return bad_salt_stride(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     const Params &P = ctx->c->P;
     const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
@@ -1390,16 +1435,16 @@ int kosk_prove_keys_derived_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const
             if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
         return 0;
     });
-    GUARD_END
+    WGUARD_END
 }
 int kosk_keyseed_device(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride,
                         uint8_t *d_seeds)
 {
     if (!ctx || n < 1 || !sk || !d_seeds) return bad_args(ctx, __func__);
-    GUARD(ctx)
+    WGUARD(ctx)
     ctx->clear_err();
     return keyseed_device(*ctx->c, n, sk, contexts, context_stride, salts, salt_stride, d_seeds);
-    GUARD_END
+    WGUARD_END
 }
 
 void *kosk_host_alloc(size_t bytes)
@@ -1414,6 +1459,122 @@ void *kosk_host_alloc(size_t bytes)
 void kosk_host_free(void *p)
 {
     if (p && hipHostFree(p) != hipSuccess) (void)hipGetLastError();
+}
+
+// ---- erasure (kosk_wipe.hip) ----
+int kosk_wipe_secrets(kosk_ctx *ctx)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    return wipe_handle(ctx);
+    GUARD_END
+}
+int kosk_set_wipe(kosk_ctx *ctx, int mode)
+{
+    if (!ctx) return -1;
+    if (mode != KOSK_WIPE_OFF && mode != KOSK_WIPE_CALL) return bad_args(ctx, __func__);
+    ctx->wipe_mode = mode;
+    return 0;
+}
+int kosk_secret_scan(kosk_ctx *ctx, const uint8_t *needle, size_t len, long *hits)
+{
+    if (!ctx || !needle || !hits || len < 16 || len > 64) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    Ctx &c = *ctx->c;
+    HIPCHK_C(hipSetDevice(c.device));
+    // the scan's own scratch, outside the inventory: the needle's device copy and the block counters, and their page-locked mirror
+    uint8_t *d = nullptr;
+    unsigned long long *h_slots = nullptr;
+    const size_t slot_bytes = sizeof(unsigned long long) * SCAN_SLOT_COUNT;
+    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&d), 64 + slot_bytes));
+    // however the call ends, the needle's copy is cleared before it is freed (by the runtime's fill: kosk_path_count id 18 counts
+    // wipes, not scans)
+    struct Free {
+        uint8_t *d; unsigned long long *&h; hipStream_t st;
+        ~Free()
+        {
+            if (hipMemsetAsync(d, 0, 64, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+            (void)hipFree(d);
+            if (h) (void)hipHostFree(h);
+        }
+    } fr{d, h_slots, c.stream};
+    HIPCHK_C(hipHostMalloc(reinterpret_cast<void **>(&h_slots), slot_bytes, hipHostMallocDefault));
+    HIPCHK_C(hipMemcpyAsync(d, needle, len, hipMemcpyHostToDevice, c.stream));
+    HIPCHK_C(stream_sync(c));
+    long total = 0;
+    int rc = 0;
+    for (Ctx *x : ctx->sub) {
+        long n = 0;
+        if (secret_scan(*x, needle, len, d, reinterpret_cast<unsigned long long *>(d + 64), h_slots, &n)) { ctx->err = x->err; rc = -1; break; }
+        total += n;
+    }
+    if (rc) return -1;
+    *hits = total;
+    return 0;
+    GUARD_END
+}
+// kernel level (tests): k_wipe on the caller's own device memory, region i = [d_ptrs[i], d_ptrs[i] + bytes[i]); synchronised
+int kosk_wipe_device(kosk_ctx *ctx, int nregions, void *const *d_ptrs, const size_t *bytes)
+{
+    if (!ctx || nregions < 0 || (nregions && (!d_ptrs || !bytes))) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    Ctx &c = *ctx->c;
+    HIPCHK_C(hipSetDevice(c.device));
+    std::vector<WipeRegion> regs;
+    for (int i = 0; i < nregions; i++) {
+        if (!bytes[i]) continue;
+        if (!d_ptrs[i] || !is_device_pointer(d_ptrs[i])) return bad_args(ctx, "kosk_wipe_device");
+        regs.push_back(WipeRegion{static_cast<uint8_t *>(d_ptrs[i]), bytes[i], 0, 1});
+    }
+    if (launch_wipe(c, regs.data(), (int)regs.size())) return -1;
+    HIPCHK_C(stream_sync(c));
+    return 0;
+    GUARD_END
+}
+
+// diagnostic (tools/wipe_rate.py): `reps` wipes of sub-context 0's secret HBM regions by k_wipe, then the same regions by the runtime's
+// own fills (one hipMemsetAsync / hipMemset2DAsync per region), each between two events on the handle's stream
+int kosk_wipe_timing(kosk_ctx *ctx, int reps, double *wipe_ms, double *memset_ms, size_t *bytes, int *regions)
+{
+    if (!ctx || reps < 1 || !wipe_ms || !memset_ms) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    Ctx &c = *ctx->c;
+    HIPCHK_C(hipSetDevice(c.device));
+    std::vector<WipeRegion> regs;
+    wipe_regions_list(c, regs);
+    size_t total = 0;
+    for (const WipeRegion &r : regs) total += r.bytes * r.count;
+    if (bytes) *bytes = total;
+    if (regions) *regions = (int)regs.size();
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    struct Ev { hipEvent_t *e; ~Ev() { for (int i = 0; i < 2; i++) if (e[i]) (void)hipEventDestroy(e[i]); } } evs{ev};
+    HIPCHK_C(hipEventCreate(&ev[0]));
+    HIPCHK_C(hipEventCreate(&ev[1]));
+    float ms = 0;
+    if (wipe_secrets(c)) return -1; // warm: first launch, and whatever staged inputs there were are gone either way
+    HIPCHK_C(hipEventRecord(ev[0], c.stream));
+    for (int i = 0; i < reps; i++)
+        if (launch_wipe(c, regs.data(), (int)regs.size())) return -1;
+    HIPCHK_C(hipEventRecord(ev[1], c.stream));
+    HIPCHK_C(hipEventSynchronize(ev[1]));
+    HIPCHK_C(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    *wipe_ms = ms / reps;
+    HIPCHK_C(hipEventRecord(ev[0], c.stream));
+    for (int i = 0; i < reps; i++)
+        for (const WipeRegion &r : regs) {
+            if (r.count == 1) HIPCHK_C(hipMemsetAsync(r.p, 0, r.bytes, c.stream));
+            else HIPCHK_C(hipMemset2DAsync(r.p, r.stride, 0, r.bytes, r.count, c.stream));
+        }
+    HIPCHK_C(hipEventRecord(ev[1], c.stream));
+    HIPCHK_C(hipEventSynchronize(ev[1]));
+    HIPCHK_C(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    *memset_ms = ms / reps;
+    return 0;
+    GUARD_END
 }
 
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count)
@@ -1759,6 +1920,7 @@ int kosk_keygen(int kyber_k, const uint8_t seed64[64], uint8_t *pk, uint8_t *sk,
     if (!make_params(kyber_k, P) || !seed64 || !pk || !sk) return -1;
     return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
     std::unique_ptr<HostKey> key(new HostKey());
+    struct Gone { HostKey *k; ~Gone() { host_wipe(k, sizeof(HostKey)); } } gone{key.get()}; // s, e: not back to the heap readable, however this ends
     host_keygen(P, seed64, pk, sk, *key);
     const int K = P.K;
     if (A) memcpy(A, key->A, sizeof(int16_t) * K * K * 256);

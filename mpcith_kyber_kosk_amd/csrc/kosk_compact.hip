@@ -160,6 +160,11 @@ static int ensure_compact(Ctx &c)
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact_bad), sizeof(uint32_t) * c.own_batch));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_compact), (size_t)c.own_batch * c.compact_stride, hipHostMallocDefault));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_compact_bad), sizeof(uint32_t) * c.own_batch, hipHostMallocDefault));
+    // the inventory: packed proofs and their flags, public
+    c.reg_buf("d_compact", &c.d_compact, (size_t)c.own_batch * c.compact_stride, 0, Ctx::INVG_COMPACT);
+    c.reg_buf("d_compact_bad", &c.d_compact_bad, sizeof(uint32_t) * c.own_batch, 0, Ctx::INVG_COMPACT);
+    c.reg_buf("h_compact", &c.h_compact, (size_t)c.own_batch * c.compact_stride, Ctx::INV_HOST, Ctx::INVG_COMPACT);
+    c.reg_buf("h_compact_bad", &c.h_compact_bad, sizeof(uint32_t) * c.own_batch, Ctx::INV_HOST, Ctx::INVG_COMPACT);
     return 0;
 }
 

@@ -124,6 +124,7 @@ static int upload_table(Ctx &c, GemmTable &t, const std::vector<uint16_t> &A, in
     std::vector<uint8_t> pk;
     pack_frag_table(A, M, Kdim, t.Mpad, t.KS, pk);
     HIPCHK(dalloc(&t.dfrag, pk.size()));
+    c.reg_buf("table", &t.dfrag, pk.size(), 0);
     HIPCHK(hipMemcpyAsync(t.dfrag, pk.data(), pk.size(), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
     HIPCHK(hipStreamSynchronize(c.stream));
     return 0;
@@ -272,6 +273,7 @@ template <typename T>
 static int upload_vec(Ctx &c, T **d, const std::vector<T> &v)
 {
     HIPCHK(dalloc(d, v.size() ? v.size() : 1));
+    c.reg_buf("table", d, v.size() * sizeof(T), 0);
     if (!v.empty()) {
         HIPCHK(hipMemcpyAsync(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
         HIPCHK(hipStreamSynchronize(c.stream));
@@ -482,12 +484,12 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         // per-proof buffers: allocated for B proofs and registered with their bytes per proof (views, kosk_combine.hpp)
         auto dev = [&](auto **p, size_t per) -> hipError_t {
             const hipError_t e = dalloc(p, B * per);
-            if (e == hipSuccess) c.reg_pp(p, per * sizeof(**p));
+            if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("workspace", p, per * sizeof(**p), Ctx::INV_PER_PROOF); }
             return e;
         };
         auto host = [&](auto **p, size_t per) -> hipError_t {
             const hipError_t e = halloc(p, B * per);
-            if (e == hipSuccess) c.reg_pp(p, per * sizeof(**p));
+            if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("staging", p, per * sizeof(**p), Ctx::INV_PER_PROOF | Ctx::INV_HOST); }
             return e;
         };
         HIPCHK(dev(&c.d_P, c.proof_stride));
@@ -515,6 +517,7 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         HIPCHK(dalloc(&c.d_I, 2 * B * c.sel_stride)); // I rows then complement rows: one upload
         c.d_rest = c.d_I + B * c.sel_stride;
         c.reg_pp(&c.d_I, (size_t)c.sel_stride * 2); c.reg_pp(&c.d_rest, (size_t)c.sel_stride * 2);
+        c.reg_buf("d_I", &c.d_I, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF); c.reg_buf("d_rest", &c.d_rest, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF);
         HIPCHK(dev(&c.d_pwT, (size_t)MAXM * 80));
         HIPCHK(dev(&c.d_coef, 2 * (size_t)8 * 2 * 2048));
         HIPCHK(dev(&c.d_fail, 1));
@@ -529,8 +532,19 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         HIPCHK(halloc(&c.h_I, 2 * B * c.sel_stride));
         c.h_rest = c.h_I + B * c.sel_stride;
         c.reg_pp(&c.h_I, (size_t)c.sel_stride * 2); c.reg_pp(&c.h_rest, (size_t)c.sel_stride * 2);
+        c.reg_buf("h_I", &c.h_I, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF | Ctx::INV_HOST);
+        c.reg_buf("h_rest", &c.h_rest, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF | Ctx::INV_HOST);
         HIPCHK(host(&c.h_fail, 1));
         HIPCHK(halloc(&c.h_err, 16));
+        c.reg_buf("h_err", &c.h_err, 16 * sizeof(uint32_t), Ctx::INV_HOST);
+        // which of the buffers registered above can hold secret-derived bytes (DESIGN.md 26 has the reason for every buffer).  Nothing in
+        // them is written once and assumed later: d_P starts as zeros (above) and a wipe leaves zeros; the public head of a key record
+        // (the pk bytes the resident verifier and kosk_kem_enc_verified read) is not part of the secret span
+        c.inv_secret("d_P", &c.d_P);
+        c.inv_secret("d_tape", &c.d_tape); c.inv_secret("h_tape", &c.h_tape);
+        c.inv_secret("d_seedbuf", &c.d_seedbuf); c.inv_secret("h_seedbuf", &c.h_seedbuf);
+        c.inv_secret("d_se", &c.d_se); c.inv_secret("d_sehat", &c.d_sehat);
+        c.inv_secret("d_kg", &c.d_kg, pkpad, c.kg_rec - pkpad); c.inv_secret("h_kg", &c.h_kg, pkpad, c.kg_rec - pkpad);
         memset(c.h_err, 0, 16 * sizeof(uint32_t));
         memset(c.h_alpha, 0, B * 80 * sizeof(uint16_t));
         HIPCHK(stream_sync(c));
@@ -575,6 +589,13 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
+    c.staged_wiped = false;
+    { // the inventory: a view owns its block of every per-proof buffer; tables and whole buffers are the arena's, private ones come later
+        size_t k = 0;
+        for (size_t i = 0; i < c.inv.size(); i++)
+            if (c.inv[i].flags & Ctx::INV_PER_PROOF) c.inv[k++] = c.inv[i];
+        c.inv.resize(k);
+    }
     for (const Ctx::PerProof &pp : arena.per_proof) {
         char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
         *reinterpret_cast<char **>(reinterpret_cast<char *>(&c) + pp.field_off) = base ? base + (size_t)first * pp.stride_bytes : nullptr;
@@ -589,6 +610,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
         for (auto &pe : c.prof_ev)
             for (auto &e : pe) HIPCHK(hipEventCreate(&e));
         HIPCHK(halloc(&c.h_err, 16)); // a view's kernels report to the view's own word
+        c.reg_buf("h_err", &c.h_err, 16 * sizeof(uint32_t), Ctx::INV_HOST);
         memset(c.h_err, 0, 16 * sizeof(uint32_t));
         return 0;
     };
@@ -867,6 +889,7 @@ int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride,
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     if (!pk || !sk) { c.err = "pk / sk output buffers are required"; return -1; }
     HIPCHK(hipSetDevice(c.device));
+    c.staged_wiped = false;
     const double t0 = now_sec();
     if (seeds ? seed_tapes(c, n, seeds, seed_stride) : upload_tapes(c, n, tapes, tape_stride)) return -1;
     if (issue_keygen(c, n)) return -1;
@@ -886,6 +909,7 @@ void witness_release(Ctx &c)
     if (c.d_wsalt) (void)hipFree(c.d_wsalt);
     c.d_wsk = c.d_wok = c.h_wok = c.d_wsalt = nullptr;
     c.wit_cap = 0;
+    c.inv_drop(Ctx::INVG_WITNESS);
 }
 
 static int witness_ensure(Ctx &c, int n)
@@ -893,6 +917,7 @@ static int witness_ensure(Ctx &c, int n)
     if (c.wit_cap >= n) return 0;
     if (c.wit_cap) {
         HIPCHK(stream_sync(c));
+        if (wipe_group(c, Ctx::INVG_WITNESS)) return -1; // the records of the last call do not go back to the allocator readable
         witness_release(c);
     }
     auto body = [&]() -> int {
@@ -904,6 +929,10 @@ static int witness_ensure(Ctx &c, int n)
     };
     if (body()) { witness_release(c); return -1; }
     c.wit_cap = n;
+    c.reg_buf("d_wsk", &c.d_wsk, (size_t)n * c.P.sk_bytes, Ctx::INV_SECRET, Ctx::INVG_WITNESS);
+    c.reg_buf("d_wsalt", &c.d_wsalt, (size_t)n * 32, Ctx::INV_SECRET, Ctx::INVG_WITNESS);
+    c.reg_buf("d_wok", &c.d_wok, (size_t)n, 0, Ctx::INVG_WITNESS);
+    c.reg_buf("h_wok", &c.h_wok, (size_t)n, Ctx::INV_HOST, Ctx::INVG_WITNESS);
     return 0;
 }
 
@@ -989,7 +1018,16 @@ int keyseed_device(Ctx &c, int n, const uint8_t *sk, const uint8_t *contexts, si
     const size_t need = (size_t)n * ((st_sk ? skb : 0) + (st_cx ? 32 : 0) + (st_sa ? 32 : 0));
     uint8_t *stage = nullptr;
     if (need) HIPCHK(hipMalloc(reinterpret_cast<void **>(&stage), need));
-    struct Free { uint8_t *p; ~Free() { if (p) (void)hipFree(p); } } fr{stage};
+    // the staged copies of the records and salts are zeroed before the buffer goes back to the allocator, however the call ends
+    struct Free {
+        uint8_t *p; size_t n; hipStream_t st;
+        ~Free()
+        {
+            if (!p) return;
+            if (hipMemsetAsync(p, 0, n, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+            (void)hipFree(p);
+        }
+    } fr{stage, need, c.stream};
     uint8_t *d_sk = stage, *d_ctx = d_sk + (st_sk ? (size_t)n * skb : 0), *d_salt = d_ctx + (st_cx ? (size_t)n * 32 : 0);
     auto kind = [](const void *p) { return is_device_pointer(p) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice; };
     if (st_sk) HIPCHK(hipMemcpyAsync(d_sk, sk, (size_t)n * skb, kind(sk), c.stream));
@@ -1015,6 +1053,7 @@ int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, si
     if (tapes && tape_stride < c.P.tape_bytes) { c.err = "tape_stride smaller than kosk_tape_bytes"; return -1; }
     if (seeds && seed_stride < SEED_BYTES) { c.err = "seed_stride smaller than KOSK_SEED_BYTES"; return -1; }
     HIPCHK(hipSetDevice(c.device));
+    c.staged_wiped = false;
     const double t0 = now_sec();
     if (derived) {
         if (stage_prover_keys_derived(c, n, sk, *derived, ok)) return -1;
@@ -1073,7 +1112,11 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     for (const KeygenIn *s = keygen; s; s = s->next)
         if (!s->pk || !s->sk) { c.err = "pk / sk output buffers are required"; return -1; }
-    if (!keygen && !c.tape_cur) { c.err = "no resident prover inputs: call kosk_stage_prover_inputs first"; return -1; }
+    if (!keygen && !c.tape_cur) {
+        c.err = c.staged_wiped ? "staged inputs were wiped: a staging call has to run again before kosk_prove_resident (kosk_wipe_secrets)"
+                               : "no resident prover inputs: call kosk_stage_prover_inputs first";
+        return -1;
+    }
     if (!keygen) c.tape_segs.count = 0;
     const bool bound = c.bind_n > 0; // kosk-bind-v1: B of every proof follows both digest tables into their hashes
     if (bound && online_only) { c.err = "an armed handle (kosk_set_contexts) cannot prove from prepared inputs: there are no public key bytes to bind"; return -1; }

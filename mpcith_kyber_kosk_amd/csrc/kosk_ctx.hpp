@@ -72,7 +72,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -134,6 +134,49 @@ struct Ctx {
     {
         per_proof.push_back({(size_t)(reinterpret_cast<char *>(field) - reinterpret_cast<char *>(this)), stride_bytes});
     }
+    // ---- the buffer inventory (kosk_wipe.hip) ----
+    // Every buffer the context owns is registered where it is allocated: HBM or page-locked host memory, per proof or whole, and whether
+    // it can hold secret-derived bytes (sec_off / sec_bytes: the secret part of each record; the key records keep a public head).
+    // wipe_secrets() zeroes the secret ones, secret_scan() searches ALL of them.  A pointer field of this struct is kept as its offset,
+    // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
+    // buffers that come and go (inv_drop)
+    enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND };
+    struct InvBuf {
+        const char *name;
+        size_t field_off; // (size_t)-1: `abs`
+        void *abs;
+        size_t bytes;     // per proof (INV_PER_PROOF) or of the whole buffer
+        size_t sec_off, sec_bytes;
+        int flags, group;
+    };
+    std::vector<InvBuf> inv;
+    template <class T> void reg_buf(const char *name, T **field, size_t bytes, int flags, int group = INVG_CORE, size_t sec_off = 0, size_t sec_bytes = (size_t)-1)
+    {
+        const char *f = reinterpret_cast<const char *>(field), *me = reinterpret_cast<const char *>(this);
+        const bool mine = f >= me && f < me + sizeof(*this);
+        inv.push_back(InvBuf{name, mine ? (size_t)(f - me) : (size_t)-1, mine ? nullptr : (void *)*field, bytes, sec_off, sec_bytes, flags, group});
+    }
+    // the registered buffer behind pointer field `field` can hold secrets (in bytes [sec_off, sec_off + sec_bytes) of each record)
+    template <class T> void inv_secret(const char *name, T **field, size_t sec_off = 0, size_t sec_bytes = (size_t)-1)
+    {
+        const size_t off = (size_t)(reinterpret_cast<const char *>(field) - reinterpret_cast<const char *>(this));
+        for (InvBuf &b : inv)
+            if (b.field_off == off) { b.name = name; b.flags |= INV_SECRET; b.sec_off = sec_off; b.sec_bytes = sec_bytes; }
+    }
+    void *inv_ptr(const InvBuf &b) const
+    {
+        return b.field_off == (size_t)-1 ? b.abs : *reinterpret_cast<void *const *>(reinterpret_cast<const char *>(this) + b.field_off);
+    }
+    void inv_drop(int group)
+    {
+        size_t k = 0;
+        for (size_t i = 0; i < inv.size(); i++)
+            if (inv[i].group != group) inv[k++] = inv[i];
+        inv.resize(k);
+    }
+    // kosk_wipe_secrets cleared staged prover inputs: kosk_prove_resident refuses until a staging call has run again
+    bool staged_wiped = false;
     bool is_view = false;
     int view_first = 0;
     int own_batch = 0;   // proofs of this context's own callers (a view: its member's kosk_create size; else max_batch)
@@ -509,5 +552,34 @@ int kem_keypair(Ctx &c, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk);
 enum { KEYCHK_HASH = 1, KEYCHK_PK_RANGE = 2, KEYCHK_S_RANGE = 4 }; // KOSK_KEYCHK_* (kosk_capi.cpp asserts the equality)
 int kem_check(Ctx &c, int n, const uint8_t *rec, int is_sk, uint8_t *flags);
 void kem_release(Ctx &c);
+
+// ---- erasure (kosk_wipe.hip) ----
+// `count` records of `bytes` bytes, `stride` apart, in HBM (count 1: one run of bytes)
+struct WipeRegion { uint8_t *p; size_t bytes, stride; uint32_t count; };
+enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches
+enum : unsigned long long { WIPE_MEMSET_BYTES = 320ull << 20 }; // a single run of this many bytes or more is cleared by hipMemsetAsync (kosk_wipe.hip)
+// zero the regions: queued on the context's stream (never while it is capturing), not synchronised; empty regions are skipped
+int launch_wipe(Ctx &c, const WipeRegion *regions, int n);
+// zero every secret buffer of the inventory, HBM by k_wipe and page-locked staging by the host; synchronised.  A view wipes its own block
+// of the per-proof buffers and its private buffers.  Staged prover inputs are gone afterwards (staged_wiped)
+int wipe_secrets(Ctx &c);
+// the HBM regions wipe_secrets() clears (group >= 0: of that owner only)
+int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1);
+// the secret HBM buffers of one owner (Ctx::INVG_*), synchronised: before they are freed to be allocated larger
+int wipe_group(Ctx &c, int group);
+void host_wipe(void *p, size_t bytes); // explicit_bzero: not removed as a dead store
+template <class T> void host_wipe_vec(std::vector<T> &v) { if (!v.empty()) host_wipe(v.data(), v.size() * sizeof(T)); }
+// a host heap temporary that carries secrets is cleared before it is freed, however its scope ends
+template <class T> struct VecWiper {
+    std::vector<T> &v;
+    explicit VecWiper(std::vector<T> &v_) : v(v_) {}
+    ~VecWiper() { host_wipe_vec(v); }
+    VecWiper(const VecWiper &) = delete;
+    VecWiper &operator=(const VecWiper &) = delete;
+};
+// occurrences of needle[0, len) at every byte offset of every buffer of the inventory, secret or public, HBM (k_scan) and page-locked host
+// memory; d_needle / d_slots / h_slots: the caller's scratch (kosk_capi.cpp).  Synchronised
+int secret_scan(Ctx &c, const uint8_t *needle, size_t len, const uint8_t *d_needle, unsigned long long *d_slots, unsigned long long *h_slots, long *hits);
+enum { SCAN_SLOT_COUNT = 1024 };
 
 } // namespace kosk

@@ -375,6 +375,9 @@ int ensure_dense_ws(Ctx &c)
     if (c.d_dense_ws) return 0;
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_ws), (size_t)c.own_batch * DN_WS * sizeof(uint16_t)));
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_status), sizeof(uint32_t) * c.own_batch));
+    // the inventory: rows of proof images and a status word per proof, public
+    c.reg_buf("d_dense_ws", &c.d_dense_ws, (size_t)c.own_batch * DN_WS * sizeof(uint16_t), 0, Ctx::INVG_DENSE);
+    c.reg_buf("d_dense_status", &c.d_dense_status, sizeof(uint32_t) * c.own_batch, 0, Ctx::INVG_DENSE);
     return 0;
 }
 

@@ -215,6 +215,9 @@ void host_keygen(const Params &P, const uint8_t seed64[64], uint8_t *pk, uint8_t
     memcpy(sk + 384 * K, pk, P.pk_bytes);
     sha3_256(sk + P.sk_bytes - 64, pk, P.pk_bytes);
     memcpy(sk + P.sk_bytes - 32, noise_seed, 32); // kosk.cpp:67-69: z is the noise seed
+    // the stack copies of the seeds, the sampler's input and NTT(s), NTT(e) do not outlive the call (as keyseed_value's copy of the key)
+    auto gone = [](void *p, size_t n) { volatile uint8_t *w = static_cast<volatile uint8_t *>(p); for (size_t i = 0; i < n; i++) w[i] = 0; };
+    gone(buf, sizeof buf); gone(in, sizeof in); gone(nb, sizeof nb); gone(shat, sizeof shat); gone(ehat, sizeof ehat);
 }
 
 void host_decode_pk(const Params &P, const uint8_t *pk, HostKey &key)

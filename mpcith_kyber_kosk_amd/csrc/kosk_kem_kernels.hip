@@ -326,6 +326,7 @@ void kem_release(Ctx &c)
         if (p) (void)hipFree(p);
     delete w;
     c.kem = nullptr;
+    c.inv_drop(Ctx::INVG_KEM);
 }
 
 // the workspace holds the largest launch group the context has seen (rounded up to 1 024 items, at most KEM_CHUNK)
@@ -334,6 +335,7 @@ static int kem_ensure(Ctx &c, int n)
     if (c.kem && c.kem->cap >= n) return 0;
     if (c.kem) {
         KOSK_HIPCHK(stream_sync(c));
+        if (wipe_group(c, Ctx::INVG_KEM)) return -1; // the workspace of the earlier calls does not go back to the allocator readable
         kem_release(c);
     }
     const Dims D = dims(c.P.K);
@@ -357,6 +359,19 @@ static int kem_ensure(Ctx &c, int n)
     };
     if (body()) { kem_release(c); return -1; }
     w->cap = (int)N;
+    // the inventory: secret are the records, messages, hashes of them and the noise; public the keys, ciphertexts, A, H(pk), flags
+    const int S = Ctx::INV_SECRET, G = Ctx::INVG_KEM;
+    c.reg_buf("kem.d_sk", &w->d_sk, N * D.sk, S, G);
+    c.reg_buf("kem.d_m", &w->d_m, N * 32, S, G);
+    c.reg_buf("kem.d_kr", &w->d_kr, N * 64, S, G);
+    c.reg_buf("kem.d_rk", &w->d_rk, N * 32, S, G);
+    c.reg_buf("kem.d_ss", &w->d_ss, N * 32, S, G);
+    c.reg_buf("kem.d_noise", &w->d_noise, N * (2 * D.K + 1) * 512, S, G);
+    c.reg_buf("kem.d_pk", &w->d_pk, N * D.pk, 0, G);
+    c.reg_buf("kem.d_ct", &w->d_ct, N * D.ct, 0, G);
+    c.reg_buf("kem.d_mask", &w->d_mask, N, 0, G);
+    c.reg_buf("kem.d_h", &w->d_h, N * 32, 0, G);
+    c.reg_buf("kem.d_A", &w->d_A, N * D.K * D.K * 512, 0, G);
     return 0;
 }
 

@@ -77,6 +77,7 @@ int prepare_randomness(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, 
     HIPCHK(stream_sync(c));
     if (rm.tf != rm.f + M) { c.err = "internal: f / NTT f rows not adjacent"; return -1; }
     std::vector<uint16_t> rows((size_t)2 * M * RS);
+    VecWiper<uint16_t> rows_gone(rows);
     for (int b = 0; b < n; b++) {
         HIPCHK(hipMemcpyAsync(rows.data(), c.d_P + (size_t)b * c.proof_stride + (size_t)rm.f * RS, rows.size() * 2, hipMemcpyDeviceToHost, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
@@ -104,6 +105,7 @@ int prepare_range_proof(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride,
     HIPCHK(stream_sync(c));
     if (rm.eeta != rm.seta + KE) { c.err = "internal: eta rows not adjacent"; return -1; }
     std::vector<uint16_t> rows((size_t)2 * KE * RS);
+    VecWiper<uint16_t> rows_gone(rows);
     for (int b = 0; b < n; b++) {
         HIPCHK(hipMemcpyAsync(rows.data(), c.d_P + (size_t)b * c.proof_stride + (size_t)rm.seta * RS, rows.size() * 2, hipMemcpyDeviceToHost, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
@@ -126,6 +128,7 @@ static int upload_inst(Ctx &c, int n, const uint8_t *inst, bool with_se, bool wi
     const size_t ib = mlwe_inst_bytes(P);
     std::vector<int16_t> A((size_t)n * c.key_stride), se((size_t)n * c.se_stride);
     std::vector<uint16_t> t((size_t)n * K * 256);
+    VecWiper<int16_t> se_gone(se); // s and e
     for (int b = 0; b < n; b++) {
         const int16_t *src = reinterpret_cast<const int16_t *>(inst + (size_t)b * ib);
         for (size_t i = 0; i < (size_t)K * K * 256; i++) A[(size_t)b * c.key_stride + i] = (int16_t)(((int)src[i] % Q + Q) % Q);
@@ -154,6 +157,7 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
     if (upload_inst(c, n, inst, true, false)) return -1;
     // offline rows: secrets at x < 256, party shares at x = 256.., the rest of each row is produced by nothing else
     std::vector<uint16_t> rows((size_t)2 * M * RS), erows((size_t)2 * KE * RS);
+    VecWiper<uint16_t> rows_gone(rows), erows_gone(erows);
     for (int b = 0; b < n; b++) {
         const uint8_t *r = rand_in + (size_t)b * randomness_bytes(P);
         const uint8_t *rf = r, *rntt = r + (size_t)M * 512, *rfs = r + (size_t)M * 1024, *rnfs = rfs + (size_t)M * SHARE_VEC_BYTES;

@@ -40,6 +40,7 @@ template <typename T>
 static int upload_vec(Ctx &c, T **d, const std::vector<T> &v)
 {
     HIPCHK(dalloc(d, v.size()));
+    c.reg_buf("verifier table", d, v.size() * sizeof(T), 0, Ctx::INVG_VERIFY);
     // on the context's own stream (a non-blocking stream is NOT ordered against the legacy null stream that a plain hipMemcpy /
     // hipMemset uses), and complete before `v` goes away: the caller synchronises the stream before it returns
     if (!v.empty()) {
@@ -136,7 +137,7 @@ int ensure_verify_workspace(Ctx &c)
     // per-proof buffers, registered for views like the ones of ctx_create
     auto dev = [&](auto **p, size_t per) -> hipError_t {
         const hipError_t e = dalloc(p, B * per);
-        if (e == hipSuccess) c.reg_pp(p, per * sizeof(**p));
+        if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("verifier workspace", p, per * sizeof(**p), Ctx::INV_PER_PROOF, Ctx::INVG_VERIFY); }
         return e;
     };
     HIPCHK(dev(&c.d_O, c.o_stride));
@@ -153,9 +154,11 @@ int ensure_verify_workspace(Ctx &c)
     HIPCHK(dev(&c.d_sec_u2, (size_t)c.n_interp_2d * 256));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_Iimg), B * 2 * NOPEN, hipHostMallocDefault));
     c.reg_pp(&c.h_Iimg, (size_t)2 * NOPEN);
+    c.reg_buf("h_Iimg", &c.h_Iimg, (size_t)2 * NOPEN, Ctx::INV_PER_PROOF | Ctx::INV_HOST, Ctx::INVG_VERIFY);
     HIPCHK(dev(&c.d_odig, (size_t)NOPEN * 32));
     HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_odig), B * NOPEN * 32, hipHostMallocDefault));
     c.reg_pp(&c.h_odig, (size_t)NOPEN * 32);
+    c.reg_buf("h_odig", &c.h_odig, (size_t)NOPEN * 32, Ctx::INV_PER_PROOF | Ctx::INV_HOST, Ctx::INVG_VERIFY);
     HIPCHK(hipStreamSynchronize(c.stream)); // every table and the zeroed opened matrix are in HBM before the first verifier kernel is queued
     c.verify_ready = true;
     return 0;
