@@ -101,6 +101,7 @@ int kosk_set_entropy(kosk_ctx *ctx, int mode);
  * kosk_set_wipe(KOSK_WIPE_CALL): every entry point that brings secrets onto the handle ends with that wipe, on success and on every
  * error return: the key generations in every form, kosk_prove_resident, kosk_prove_prepared, kosk_prepare_*, kosk_kem_enc_batch /
  * _dec_batch / _enc_verified / _keypair_batch, kosk_kem_check_sk, kosk_keyseed_device, kosk_tape_expand_device and kosk_prove_keys_*;
+ * kosk_kem_enc_key / _dec_key (their per-call scratch; the resident key of kosk_kem_key_set is a long-lived secret and stays);
  * chunked calls and streams > 1 wipe every sub-context.  Not the staging calls (kosk_stage_prover_inputs*, kosk_stage_prover_keys*,
  * kosk_witness_from_sk): their secrets are the input of the kosk_prove_resident that follows, which wipes when it ends.  A member of
  * a cohort (combine >= 2) in this mode keeps its calls out of merged runs, exactly as an armed handle does, and wipes its own block of
@@ -285,6 +286,37 @@ int kosk_kem_dec_batch(kosk_ctx *ctx, int n, const uint8_t *ct, const uint8_t *s
  * by a call that replaced the resident keys (a key generation, a verifier staging call in any wire format: image, compact (kosk_stage_verifier_inputs_compact, kosk_verify_batch_compact) or dense (kosk_stage_verifier_inputs_dense, kosk_verify_batch_dense)); and for a member of a cohort (combine >= 2): "not available with call combining". */
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* ---- KEM with one resident key (INTEGRATION.md 8.2 is the normative text): for a party that owns ONE ML-KEM key and answers many peers
+ * with it.  kosk_kem_key_set loads one record -- exactly one of pk (kosk_pk_bytes) / sk (kosk_sk_bytes) non-NULL, host or device memory
+ * -- into the handle's key slot: the pk bytes, A^T and H(pk) decoded once (one launch of k_kem_key_setup, synchronised), and for an sk
+ * its s-hat, stored H(pk) and z.  The slot is its own HBM allocation (about 1.2 + 0.5 K^2 + 0.8 K KB), made at the first load; a handle
+ * that never loads a key allocates nothing.  A second kosk_kem_key_set replaces the slot, the old one is wiped first;
+ * kosk_kem_key_clear wipes and empties it.  Neither may be called while another thread is inside a call on the handle.
+ * kosk_kem_key_state: KOSK_KEM_KEY_NONE / _PK / _SK; -1 for NULL.
+ * kosk_kem_enc_key(n, coins) returns byte for byte what kosk_kem_enc_batch returns for n copies of the loaded pk record (loaded from an
+ * sk: the pk inside it); kosk_kem_dec_key(n, ct) what kosk_kem_dec_batch returns for n copies of the loaded sk record.  Everything those
+ * calls do holds: 12-bit fields >= q in t-hat / s-hat are folded mod q, decapsulation trusts the H(pk) stored in the sk and re-encrypts
+ * with the pk inside it, the rejection key is SHAKE256(z || ct), encapsulation hashes the pk bytes as given; coins == NULL: one 32-byte
+ * draw per item, in item order, on the caller's thread.  Buffers host or device memory, any n >= 1 in launch groups of 16384 items, which
+ * do only the per-item work (no gen_matrix, no H(pk), no copy of the key).  Unmerged on the handle's own stream (a cohort member as for
+ * kosk_kem_enc_batch); the HIP error state is reset and checked as in every entry point.  No branch and no address depends on s-hat,
+ * m', the comparison or z.
+ * -1 with a text and nothing started: NULL arguments, both or neither of pk / sk, n < 1, kosk_kem_enc_key on an empty slot,
+ * kosk_kem_dec_key on a slot that is not in state SK.  -1 ("block limit"), the slot left empty, if gen_matrix reached its block limit
+ * inside kosk_kem_key_set.
+ * Erasure: s-hat and z are secret buffers of the inventory, the pk bytes, A^T and both H(pk) public ones.
+ * kosk_wipe_secrets, kosk_kem_key_clear and kosk_destroy zero the secret part; after kosk_wipe_secrets a slot in state SK is in state PK,
+ * kosk_kem_enc_key returns the same bytes as before and kosk_kem_dec_key returns -1 ("key was wiped") -- it never decapsulates with
+ * zeros.  Under KOSK_WIPE_CALL the slot is a long-lived secret and NOT part of the wipe at the end of a call: that wipe clears the
+ * per-call scratch (m', K-bar || coins, noise, rejection keys, ss) as before and leaves the slot alone, and kosk_kem_key_set keeps the
+ * slot it just made. */
+enum { KOSK_KEM_KEY_NONE = 0, KOSK_KEM_KEY_PK = 1, KOSK_KEM_KEY_SK = 2 };
+int kosk_kem_key_set(kosk_ctx *ctx, const uint8_t *pk, const uint8_t *sk);
+int kosk_kem_key_state(const kosk_ctx *ctx);
+int kosk_kem_key_clear(kosk_ctx *ctx);
+int kosk_kem_enc_key(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
+int kosk_kem_dec_key(kosk_ctx *ctx, int n, const uint8_t *ct, uint8_t *ss);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -347,7 +379,9 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * 14 refills of the dense wire format (k_dense_setup + k_dense_fill, one per staged chunk or kosk_dense_fill_device sub-batch),
  * 15 kem_keypair / 16 kem_check: launch groups of kosk_kem_keypair_batch and of kosk_kem_check_pk / kosk_kem_check_sk,
  * 17 launches of k_keyseed (kosk-keyseed-v1: seeds derived from the sk records in HBM),
- * 18 launches of k_wipe (kosk_wipe_secrets, the wipe at the end of a call under KOSK_WIPE_CALL, kosk_wipe_device). */
+ * 18 launches of k_wipe (kosk_wipe_secrets, the wipe at the end of a call under KOSK_WIPE_CALL, kosk_wipe_device),
+ * 19 launches of k_kem_key_setup (one per kosk_kem_key_set), 20 kem_enc_key / 21 kem_dec_key: launch groups of kosk_kem_enc_key /
+ * kosk_kem_dec_key (ids 12 / 13 do not move for them). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -177,6 +177,16 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_wipe_secrets")):
         sig.update(wipe)
+    # KEM with one resident key; optional under the same rule (and only then)
+    onekey = {
+        "kosk_kem_key_set": (C.c_int, [vp, vp, vp]),
+        "kosk_kem_key_state": (C.c_int, [vp]),
+        "kosk_kem_key_clear": (C.c_int, [vp]),
+        "kosk_kem_enc_key": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_kem_dec_key": (C.c_int, [vp, C.c_int, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_key_set")):
+        sig.update(onekey)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -208,7 +218,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_verify_batch_dense", "kosk_dense_fill_device",
            "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk",
            "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch",
-           "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing"]
+           "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing",
+           "kosk_kem_key_set", "kosk_kem_key_state", "kosk_kem_key_clear", "kosk_kem_enc_key", "kosk_kem_dec_key"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -226,6 +237,7 @@ SEED_BYTES = 32
 SS_BYTES = 32  # KOSK_SS_BYTES
 KEYPAIR_COIN_BYTES = 64  # d || z of crypto_kem_keypair_derand
 KEYCHK_HASH, KEYCHK_PK_RANGE, KEYCHK_S_RANGE = 1, 2, 4  # KOSK_KEYCHK_*
+KEM_KEY_NONE, KEM_KEY_PK, KEM_KEY_SK = 0, 1, 2  # KOSK_KEM_KEY_*
 
 
 def options(**fields):
@@ -889,6 +901,48 @@ class Kosk:
         self._chk(lib.kosk_kem_enc_verified(self._h, n, cp, ct, ss, done), "kem_enc_verified")
         return _cut(ct, ctb, n), _cut(ss, SS_BYTES, n), [bool(x) for x in done.raw[:n]]
 
+    # one resident key
+    def kem_key_set(self, pk=None, sk=None):
+        """kosk_kem_key_set: load ONE record into the handle's key slot, exactly one of pk / sk (bytes, or an int DEVICE pointer);
+        replaces the slot"""
+        if (pk is None) == (sk is None):
+            raise KoskError("kem_key_set: exactly one of pk / sk")
+        rec, size, what = (pk, self.pk_bytes, "pk") if sk is None else (sk, self.sk_bytes, "sk")
+        ptr, _n, _k = self._records(what, rec if isinstance(rec, int) else [rec], 1, size)
+        self._chk(lib.kosk_kem_key_set(self._h, ptr if sk is None else None, None if sk is None else ptr), "kem_key_set")
+
+    def kem_key_state(self):
+        """KEM_KEY_NONE / KEM_KEY_PK / KEM_KEY_SK (kosk_kem_key_state)"""
+        return lib.kosk_kem_key_state(self._h)
+
+    def kem_key_clear(self):
+        """wipe and empty the key slot (kosk_kem_key_clear)"""
+        self._chk(lib.kosk_kem_key_clear(self._h), "kem_key_clear")
+
+    def kem_enc_key(self, n=None, coins=None, out=None):
+        """kosk_kem_enc_key: n encapsulations to the loaded key; coins / out as in kem_enc (coins=None: n draws, n defaults to 1)"""
+        cp, _k = None, None
+        if coins is not None:
+            cp, n, _k = self._records("coins", coins, n, 32)
+        elif n is None:
+            n = 1
+        ctb = ct_bytes(self.k)
+        bufs, host = self._kem_out(out, n, (ctb, SS_BYTES))
+        self._chk(lib.kosk_kem_enc_key(self._h, n, cp, bufs[0], bufs[1]), "kem_enc_key")
+        if host is None:
+            return out
+        return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n)
+
+    def kem_dec_key(self, cts, n=None, out=None):
+        """kosk_kem_dec_key: decapsulate n ciphertexts with the loaded secret key; cts / out as in kem_dec"""
+        ctb = ct_bytes(self.k)
+        cp, n, _k = self._records("ct", cts, n, ctb)
+        bufs, host = self._kem_out(None if out is None else (out,), n, (SS_BYTES,))
+        self._chk(lib.kosk_kem_dec_key(self._h, n, cp, bufs[0]), "kem_dec_key")
+        if host is None:
+            return out
+        return _cut(bufs[0], SS_BYTES, n)
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -966,6 +1020,9 @@ class Kosk:
     PATH_KEM_CHECK = 16
     PATH_KEYSEED = 17
     PATH_WIPE = 18
+    PATH_KEM_KEY_SETUP = 19
+    PATH_KEM_ENC_KEY = 20
+    PATH_KEM_DEC_KEY = 21
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

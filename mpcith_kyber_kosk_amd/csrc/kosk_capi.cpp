@@ -174,11 +174,11 @@ static int guard(const kosk_ctx *, const char *, F &&body) noexcept // read-only
 
 // KOSK_WIPE_CALL (kosk_set_wipe): an entry point that brings secrets onto the handle ends with the wipe of every sub-context, however its
 // body ends -- success, an error return, an exception.  Mode off: one untaken branch
-static int wipe_handle(kosk_ctx *h)
+static int wipe_handle(kosk_ctx *h, bool keep_key = false)
 {
     int rc = 0;
     for (Ctx *x : h->sub)
-        if (wipe_secrets(*x)) { h->err = x->err; h->c->err = x->err; rc = -1; }
+        if (wipe_secrets(*x, keep_key)) { h->err = x->err; h->c->err = x->err; rc = -1; }
     return rc;
 }
 template <typename F>
@@ -189,10 +189,10 @@ static int wiped_call(kosk_ctx *h, F &&body)
     try {
         rc = body();
     } catch (...) {
-        try { (void)wipe_handle(h); } catch (...) {}
+        try { (void)wipe_handle(h, true); } catch (...) {}
         throw;
     }
-    if (wipe_handle(h) && !rc) rc = -1;
+    if (wipe_handle(h, true) && !rc) rc = -1; // the resident KEM key is a long-lived secret, not per-call scratch: it stays
     return rc;
 }
 #define WGUARD(ctx) return guard(ctx, __func__, [&]() -> int { return wiped_call(ctx, [&]() -> int {
@@ -1284,6 +1284,57 @@ int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *c
         })) return -1;
     if (hipMemcpy(done, bits.data(), (size_t)n, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return refuse("copying the verify bits to `done` failed"); }
     return 0;
+    WGUARD_END
+}
+
+// ---- KEM with one resident key (kosk_kem_kernels.hip) ----
+static_assert((int)KOSK_KEM_KEY_NONE == (int)KEM_KEY_NONE && (int)KOSK_KEM_KEY_PK == (int)KEM_KEY_PK && (int)KOSK_KEM_KEY_SK == (int)KEM_KEY_SK, "kosk_mi355x.h and kosk_ctx.hpp");
+int kosk_kem_key_set(kosk_ctx *ctx, const uint8_t *pk, const uint8_t *sk)
+{
+    if (!ctx || (pk == nullptr) == (sk == nullptr)) return bad_args(ctx, __func__);
+    GUARD(ctx) // under KOSK_WIPE_CALL too: the slot this call makes is what it is for
+    ctx->clear_err();
+    if (kem_key_set(*ctx->c, pk, sk)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+int kosk_kem_key_state(const kosk_ctx *ctx) { return ctx ? kem_key_state(*ctx->c) : -1; }
+int kosk_kem_key_clear(kosk_ctx *ctx)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (kem_key_clear(*ctx->c)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+int kosk_kem_enc_key(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
+{
+    if (!ctx || n < 1 || !ct || !ss) return bad_args(ctx, __func__);
+    WGUARD(ctx)
+    ctx->clear_err();
+    if (kem_key_state(*ctx->c) == KEM_KEY_NONE) { // before any coin is drawn
+        ctx->err = "kosk_kem_enc_key: no key is loaded (kosk_kem_key_set)";
+        ctx->c->err = ctx->err;
+        return -1;
+    }
+    const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
+    std::vector<uint8_t> drawn;
+    VecWiper<uint8_t> drawn_gone(drawn);
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_enc_key(c, count, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32);
+    });
+    WGUARD_END
+}
+int kosk_kem_dec_key(kosk_ctx *ctx, int n, const uint8_t *ct, uint8_t *ss)
+{
+    if (!ctx || n < 1 || !ct || !ss) return bad_args(ctx, __func__);
+    WGUARD(ctx)
+    const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_dec_key(c, count, ct + (size_t)first * ctb, ss + (size_t)first * 32);
+    });
     WGUARD_END
 }
 

@@ -72,7 +72,8 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
               PR_V_LINCOMB, PR_FS_ALPHA, PR_FS_OPENED, PR_V_FS_ALPHA, PR_V_FS_OPENED, PR_COUNT };
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
-              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE, PATH_COUNT };
+              PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -115,6 +116,7 @@ int dense_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a st
 int dense_decode(const Params &P, const uint8_t *in, uint8_t *img);  // 0, or 1: malformed I (rows 407..1303 of the seven fields left zero)
 
 struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
+struct KemKey; // the resident key of the one-key KEM calls (kosk_kem_kernels.hip)
 enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
        KEM_WAVE_MAX = 1024 }; // launch groups of up to this many items (one wave per SIMD) run their long one-lane-per-item chains on a wave sponge, one wave per item
 
@@ -141,7 +143,7 @@ struct Ctx {
     // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
     // buffers that come and go (inv_drop)
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY };
     struct InvBuf {
         const char *name;
         size_t field_off; // (size_t)-1: `abs`
@@ -374,6 +376,7 @@ struct Ctx {
     // which of those paths really ran on this context (kosk_path_count): the tests of the knobs assert on these
     long path_n[PATH_COUNT] = {0};
     KemWs *kem = nullptr; // allocated at this context's first KEM call, owned by it (a view's is its own, never the arena's)
+    KemKey *kem_key = nullptr; // the key slot: allocated at the first kem_key_set, its own allocation (kem_ensure never moves it), owned like `kem`
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -552,6 +555,17 @@ int kem_keypair(Ctx &c, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk);
 enum { KEYCHK_HASH = 1, KEYCHK_PK_RANGE = 2, KEYCHK_S_RANGE = 4 }; // KOSK_KEYCHK_* (kosk_capi.cpp asserts the equality)
 int kem_check(Ctx &c, int n, const uint8_t *rec, int is_sk, uint8_t *flags);
 void kem_release(Ctx &c);
+// One resident key.  kem_key_set: exactly one of pk / sk, one record, host or device memory; replaces the slot (the old one
+// is wiped first); synchronised; -1 ("block limit") leaves the slot empty.  kem_enc_key / kem_dec_key: n <= KEM_CHUNK items on the slot's
+// key, per-item work only; kem_dec_key needs state KEM_KEY_SK and refuses a wiped slot.  kem_key_clear wipes and frees the slot.
+enum { KEM_KEY_NONE = 0, KEM_KEY_PK = 1, KEM_KEY_SK = 2 }; // KOSK_KEM_KEY_* (kosk_capi.cpp asserts the equality)
+int kem_key_set(Ctx &c, const uint8_t *pk, const uint8_t *sk);
+int kem_key_state(const Ctx &c);
+int kem_key_clear(Ctx &c);
+void kem_key_release(Ctx &c); // frees without wiping (the destructor: kosk_destroy has wiped)
+void kem_key_note_wiped(Ctx &c); // wipe_secrets() zeroed the slot's secret part: SK -> PK
+int kem_enc_key(Ctx &c, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
+int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss);
 
 // ---- erasure (kosk_wipe.hip) ----
 // `count` records of `bytes` bytes, `stride` apart, in HBM (count 1: one run of bytes)
@@ -561,10 +575,11 @@ enum : unsigned long long { WIPE_MEMSET_BYTES = 320ull << 20 }; // a single run 
 // zero the regions: queued on the context's stream (never while it is capturing), not synchronised; empty regions are skipped
 int launch_wipe(Ctx &c, const WipeRegion *regions, int n);
 // zero every secret buffer of the inventory, HBM by k_wipe and page-locked staging by the host; synchronised.  A view wipes its own block
-// of the per-proof buffers and its private buffers.  Staged prover inputs are gone afterwards (staged_wiped)
-int wipe_secrets(Ctx &c);
-// the HBM regions wipe_secrets() clears (group >= 0: of that owner only)
-int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1);
+// of the per-proof buffers and its private buffers.  Staged prover inputs are gone afterwards (staged_wiped).  keep_key (the wipe at the end
+// of a call under KOSK_WIPE_CALL): the resident KEM key is a long-lived secret, not per-call scratch, and stays
+int wipe_secrets(Ctx &c, bool keep_key = false);
+// the HBM regions wipe_secrets() clears (group >= 0: of that owner only; skip_group >= 0: all but that owner's)
+int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1, int skip_group = -1);
 // the secret HBM buffers of one owner (Ctx::INVG_*), synchronised: before they are freed to be allocated larger
 int wipe_group(Ctx &c, int group);
 void host_wipe(void *p, size_t bytes); // explicit_bzero: not removed as a dead store

@@ -24,6 +24,15 @@
 //                 k_kem_check   12-bit fields >= q, stored H(pk) against the computed one, OR-reduction   one wave per item
 // H(pk) is the third one-lane-per-item chain of this file: in a launch group of up to KEM_WAVE_MAX items it runs on k_fs_chain<FS_DIGEST>
 // like the encapsulation's, and k_kem_hpk only moves the digest into the record (key pair) or is not launched (checks).
+//
+// One resident key: what depends on the key alone is decoded once into a slot, the n-item calls do the per-item work only:
+//   load          k_kem_key_setup   gen_matrix (A^T), one entry per block; H(pk) on the wave sponge    K^2 + 1 waves, once per key
+//   encapsulate   k_kem_key_hash    role   G(m || h), h from the slot                                 one lane per item
+//                 k_kem_key_hash    roles  r, e1, e2                                                  (2 K + 1) lanes per item
+//                 k_kem_key_encrypt encrypt_block on the slot's pk and A^T                            one workgroup per item
+//   decapsulate   k_kem_key_decrypt decrypt_block on the slot's s-hat, G(m' || stored h)              one workgroup per item
+//                 k_kem_key_hash    roles  rkprf (z from the slot; k_kem_rkprf_wave in a small group), r, e1, e2
+//                 k_kem_key_encrypt comparing
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -314,6 +323,152 @@ __global__ __launch_bounds__(64) void k_kem_check(KemCheckJob j)
     if (lane == 0) j.flags[b] = (uint8_t)verdict;
 }
 
+// ---- one resident key ------------------------------------------------------------------------------------
+// The slot: what depends on the key alone, decoded once by k_kem_key_setup and read by every item of every later call.  Two allocations of
+// its own (kem_ensure frees and reallocates the workspace above; the slot must not move), filed in the inventory under INVG_KEMKEY:
+//   d_pub (public)  pk [384 K + 32] | H(pk) of those bytes [32] | the H(pk) stored in the sk [32] | A^T [K][K][256] int16
+//   d_sec (secret)  s-hat [384 K] | z [32]
+struct KemKey {
+    int state = KEM_KEY_NONE;
+    bool wiped = false; // loaded from an sk, then wipe_secrets() zeroed d_sec: decapsulation refuses, encapsulation goes on
+    uint8_t *d_pub = nullptr, *d_sec = nullptr;
+    uint8_t *pk = nullptr, *h_enc = nullptr, *h_dec = nullptr, *shat = nullptr, *z = nullptr;
+    int16_t *A = nullptr;
+};
+
+// Blocks 0 .. K K - 1: entry (i, j) of A^T, one sponge on lane 0 (three or four dependent permutations; the K K entries run side by side).
+// Block K K: H(pk), the longer chain (6 / 9 / 12 permutations for K = 2 / 3 / 4), on the wave sponge.  One key, one launch: both at
+// single-wave latency, so the long chain gets the layout whose permutation is short.  pk: 16-byte aligned, pk_bytes a multiple of 8.
+__global__ __launch_bounds__(64) void k_kem_key_setup(int K, const uint8_t *pk, int pk_bytes, int16_t *A, uint8_t *h, uint32_t *err, int max_blocks)
+{
+    __shared__ __align__(16) uint32_t st[64];
+    const int lane = threadIdx.x, t = blockIdx.x;
+    if (t < K * K) { // block-uniform
+        if (lane) return;
+        uint64_t rho[4];
+#pragma unroll
+        for (int l = 0; l < 4; l++) rho[l] = ld64(pk + pk_bytes - 32, l);
+        // A^T[i][j] = XOF(rho, i, j) (indcpa.c:177-178), as the matrix role of k_kem_hash
+        if (!matrix_entry(rho, t / K, t % K, max_blocks, A + (size_t)t * 256))
+            if (err) *reinterpret_cast<volatile uint32_t *>(err) = DEVERR_XOF_BLOCKS;
+        return;
+    }
+    __builtin_amdgcn_s_setprio(3);
+    WaveSponge sp;
+    sp.setup(lane);
+    const int word = sp.word();
+    const int nwords = pk_bytes / 8, nfull = nwords / 17, rem = nwords - 17 * nfull;
+    auto fetch = [&](int i) { return *reinterpret_cast<const uint2 *>(pk + 8 * i); };
+    uint32_t a = 0;
+    for (int blk = 0; blk < nfull; blk++) {
+        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
+        sp.permute(a);
+    }
+    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, 0x06u, 136));
+    sp.permute(a);
+    const uint2 w = sp.words(a, st, 4);
+    if (lane < 4) *reinterpret_cast<uint2 *>(h + 8 * lane) = w;
+}
+
+// The per-item hashing of a one-key call, roles as lane ranges like k_kem_hash: rkprf (z of the slot), G(m || h) (h of the slot), noise.
+// No matrix role and no H(pk): the slot has both.  z is data only; every address is a function of the lane.
+struct KemKeyHashJob {
+    int n, K, eta1;
+    int n_rk, n_seed, n_noise; // lanes per item of each role, in launch order
+    const uint8_t *m, *h;      // [n][32], [32]
+    uint8_t *kr;               // [n][64]
+    int16_t *noise;            // [n][2 K + 1][256]
+    const uint8_t *z, *ct;     // [32], [n][ct_bytes]
+    int ct_bytes;
+    uint8_t *rk;               // [n][32]
+};
+
+__global__ __launch_bounds__(64) void k_kem_key_hash(KemKeyHashJob j)
+{
+    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
+    const int per = j.n_rk + j.n_seed + j.n_noise;
+    if (gid >= (long)per * j.n) return;
+    int t = (int)(gid / j.n);
+    const int b = (int)(gid - (long)t * j.n);
+    if (t < j.n_rk) {
+        uint64_t out[4];
+        rkprf(j.z, j.ct + (size_t)b * j.ct_bytes, j.ct_bytes, out);
+#pragma unroll
+        for (int l = 0; l < 4; l++) reinterpret_cast<uint64_t *>(j.rk)[4 * (size_t)b + l] = out[l];
+        return;
+    }
+    t -= j.n_rk;
+    if (t < j.n_seed) {
+        uint64_t m[4], h[4], kr[8];
+#pragma unroll
+        for (int l = 0; l < 4; l++) { m[l] = ld64(j.m, 4 * b + l); h[l] = ld64(j.h, l); }
+        hash_g64(m, h, kr);
+#pragma unroll
+        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * (size_t)b + l] = kr[l];
+        return;
+    }
+    t -= j.n_seed;
+    uint64_t coins[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) coins[l] = ld64(j.kr, 8 * b + 4 + l);
+    noise_poly(coins, t, t < j.K ? j.eta1 : 2, j.noise + ((size_t)b * j.n_noise + t) * 256);
+}
+
+// k_kem_encrypt with the pk and A^T of the slot under every item
+struct KemKeyEncJob {
+    int K, dec;
+    const uint8_t *pk;          // the slot's
+    const int16_t *A, *noise;   // the slot's A^T; [n][2 K + 1][256]
+    const uint8_t *m, *kr, *rk; // [n][32], [n][64], [n][32] (dec)
+    uint8_t *ct, *ss;           // [n][ct_bytes]: written (enc) or compared with (dec); [n][32]
+};
+
+__global__ __launch_bounds__(256) void k_kem_key_encrypt(KemKeyEncJob j)
+{
+    __shared__ alignas(16) uint16_t L[9 * 256];
+    __shared__ uint32_t fail;
+    const Dims D = dims(j.K);
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    uint8_t *ct = j.ct + b * (size_t)D.ct;
+    if (tid == 0) fail = 0;
+    __syncthreads();
+    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk, j.A, j.noise + b * (size_t)((2 * D.K + 1) * 256), j.m + b * 32, j.dec ? nullptr : ct, ct);
+    if (!j.dec) {
+        if (tid < 32) j.ss[b * 32 + tid] = j.kr[b * 64 + tid];
+        return;
+    }
+    atomicOr(&fail, diff);
+    __syncthreads();
+    if (tid < 32) j.ss[b * 32 + tid] = select_ss(fail, j.kr[b * 64 + tid], j.rk[b * 32 + tid]);
+}
+
+// k_kem_decrypt on the slot's s-hat, G with the H(pk) the sk stored.  s-hat is read at addresses that depend on the thread alone.
+struct KemKeyDecJob {
+    int K;
+    const uint8_t *ct, *shat, *h;
+    uint8_t *m, *kr;
+};
+
+__global__ __launch_bounds__(256) void k_kem_key_decrypt(KemKeyDecJob j)
+{
+    __shared__ alignas(16) uint16_t L[6 * 256];
+    __shared__ alignas(16) uint8_t Lb[288];
+    const Dims D = dims(j.K);
+    const int tid = threadIdx.x;
+    const size_t b = blockIdx.x;
+    decrypt_block(D, L, Lb, tid, 256, j.ct + b * (size_t)D.ct, j.shat);
+    if (tid < 32) j.m[b * 32 + tid] = Lb[256 + tid];
+    if (tid == 0) {
+        uint64_t m[4], h[4], kr[8];
+#pragma unroll
+        for (int l = 0; l < 4; l++) { m[l] = ld64(Lb + 256, l); h[l] = ld64(j.h, l); }
+        hash_g64(m, h, kr);
+#pragma unroll
+        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * b + l] = kr[l];
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host --
 #define HIPCHK(x) KOSK_HIPCHK(x)
 
@@ -554,6 +709,153 @@ int kem_check(Ctx &c, int n, const uint8_t *rec, int is_sk, uint8_t *flags)
     HIPCHK(hipGetLastError());
     c.path_n[PATH_KEM_CHECK]++;
     HIPCHK(kem_copy_out(c, flags, w.d_mask, (size_t)n));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+// ---- one resident key ----------------------------------------------------------------------------------------------------
+void kem_key_release(Ctx &c)
+{
+    KemKey *k = c.kem_key;
+    if (!k) return;
+    if (k->d_pub) (void)hipFree(k->d_pub);
+    if (k->d_sec) (void)hipFree(k->d_sec);
+    delete k;
+    c.kem_key = nullptr;
+    c.inv_drop(Ctx::INVG_KEMKEY);
+}
+
+int kem_key_state(const Ctx &c) { return c.kem_key ? c.kem_key->state : (int)KEM_KEY_NONE; }
+
+void kem_key_note_wiped(Ctx &c)
+{
+    KemKey *k = c.kem_key;
+    if (k && k->state == KEM_KEY_SK) { k->state = KEM_KEY_PK; k->wiped = true; }
+}
+
+int kem_key_clear(Ctx &c)
+{
+    if (!c.kem_key) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(stream_sync(c));
+    const int rc = wipe_group(c, Ctx::INVG_KEMKEY); // s-hat and z do not go back to the allocator readable
+    kem_key_release(c);
+    return rc;
+}
+
+int kem_key_set(Ctx &c, const uint8_t *pk, const uint8_t *sk)
+{
+    if ((pk == nullptr) == (sk == nullptr)) { c.err = "kem_key_set: exactly one of pk / sk"; return -1; }
+    if (kem_key_clear(c)) return -1; // a second load replaces the slot: the old one is wiped first
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    KemKey *k = new KemKey();
+    c.kem_key = k;
+    const size_t pub_bytes = (size_t)D.pk + 64 + (size_t)D.K * D.K * 512, sec_bytes = (size_t)D.pvb + 32;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&k->d_pub), pub_bytes));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&k->d_sec), sec_bytes));
+        k->pk = k->d_pub; k->h_enc = k->d_pub + D.pk; k->h_dec = k->h_enc + 32; // D.pk is a multiple of 16: A^T stays 16-byte aligned
+        k->A = reinterpret_cast<int16_t *>(k->h_dec + 32);
+        k->shat = k->d_sec; k->z = k->d_sec + D.pvb;
+        c.reg_buf("kemkey.pub", &k->d_pub, pub_bytes, 0, Ctx::INVG_KEMKEY);
+        c.reg_buf("kemkey.sec", &k->d_sec, sec_bytes, Ctx::INV_SECRET, Ctx::INVG_KEMKEY);
+        HIPCHK(hipMemsetAsync(k->d_pub, 0, pub_bytes, c.stream));
+        HIPCHK(hipMemsetAsync(k->d_sec, 0, sec_bytes, c.stream));
+        if (sk) { // sk = s-hat || pk || H(pk) || z: the pieces go straight to their places, no copy of the record in between
+            HIPCHK(kem_copy_in(c, k->shat, sk, (size_t)D.pvb));
+            HIPCHK(kem_copy_in(c, k->pk, sk + D.pvb, (size_t)D.pk));
+            HIPCHK(kem_copy_in(c, k->h_dec, sk + D.sk - 64, 32));
+            HIPCHK(kem_copy_in(c, k->z, sk + D.sk - 32, 32));
+        } else {
+            HIPCHK(kem_copy_in(c, k->pk, pk, (size_t)D.pk));
+        }
+        k_kem_key_setup<<<dim3((unsigned)(D.K * D.K + 1)), dim3(64), 0, c.stream>>>(D.K, k->pk, D.pk, k->A, k->h_enc, c.h_err, c.xof_max_blocks);
+        HIPCHK(hipGetLastError());
+        c.path_n[PATH_KEM_KEY_SETUP]++;
+        HIPCHK(stream_sync(c));
+        return device_error_check(c); // gen_matrix block limit: no key
+    };
+    if (body()) {
+        const std::string why = c.err;
+        (void)kem_key_clear(c); // the slot stays empty
+        c.err = why;
+        return -1;
+    }
+    k->state = sk ? KEM_KEY_SK : KEM_KEY_PK;
+    return 0;
+}
+
+static hipError_t kem_launch_key_hash(const KemKeyHashJob &j, hipStream_t st)
+{
+    const long lanes = (long)(j.n_rk + j.n_seed + j.n_noise) * j.n;
+    k_kem_key_hash<<<dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st>>>(j);
+    return hipGetLastError();
+}
+
+int kem_enc_key(Ctx &c, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
+{
+    if (n < 1 || n > KEM_CHUNK || !coins || !ct || !ss) { c.err = "kem_enc_key: bad arguments"; return -1; }
+    if (kem_key_state(c) == KEM_KEY_NONE) { c.err = "kem_enc_key: no key is loaded (kosk_kem_key_set)"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const KemKey &k = *c.kem_key;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
+    KemKeyHashJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.m = w.d_m; h.h = k.h_enc; h.kr = w.d_kr; h.noise = w.d_noise;
+    h.n_seed = 1;
+    HIPCHK(kem_launch_key_hash(h, c.stream));
+    h.n_seed = 0; h.n_noise = 2 * D.K + 1;
+    HIPCHK(kem_launch_key_hash(h, c.stream));
+    KemKeyEncJob e{};
+    e.K = D.K; e.dec = 0; e.pk = k.pk; e.A = k.A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.ct = w.d_ct; e.ss = w.d_ss;
+    k_kem_key_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_ENC_KEY]++;
+    HIPCHK(kem_copy_out(c, ct, w.d_ct, (size_t)n * D.ct));
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss)
+{
+    if (n < 1 || n > KEM_CHUNK || !ct || !ss) { c.err = "kem_dec_key: bad arguments"; return -1; }
+    if (kem_key_state(c) != KEM_KEY_SK) {
+        c.err = c.kem_key && c.kem_key->wiped ? "kem_dec_key: key was wiped (kosk_wipe_secrets): load the secret key again"
+                : c.kem_key               ? "kem_dec_key: the loaded key is a public key"
+                                          : "kem_dec_key: no key is loaded (kosk_kem_key_set)";
+        return -1;
+    }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const KemKey &k = *c.kem_key;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_ct, ct, (size_t)n * D.ct));
+    KemKeyDecJob d{};
+    d.K = D.K; d.ct = w.d_ct; d.shat = k.shat; d.h = k.h_dec; d.m = w.d_m; d.kr = w.d_kr;
+    k_kem_key_decrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(d);
+    HIPCHK(hipGetLastError());
+    KemKeyHashJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.kr = w.d_kr; h.noise = w.d_noise; h.z = k.z; h.ct = w.d_ct; h.ct_bytes = D.ct; h.rk = w.d_rk;
+    h.n_rk = 1; h.n_noise = 2 * D.K + 1;
+    if (n <= kem_wave_max()) { // rkprf: one wave per item on the wave sponge, z at stride 0
+        k_kem_rkprf_wave<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(k.z, 0, h.ct, h.ct_bytes, h.rk);
+        HIPCHK(hipGetLastError());
+        h.n_rk = 0;
+    }
+    HIPCHK(kem_launch_key_hash(h, c.stream));
+    KemKeyEncJob e{};
+    e.K = D.K; e.dec = 1; e.pk = k.pk; e.A = k.A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.rk = w.d_rk; e.ct = w.d_ct; e.ss = w.d_ss;
+    k_kem_key_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_KEM_DEC_KEY]++;
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
     HIPCHK(stream_sync(c));
     return 0;
 }
