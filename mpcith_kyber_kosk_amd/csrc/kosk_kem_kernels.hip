@@ -27,12 +27,14 @@
 //
 // One resident key: what depends on the key alone is decoded once into a slot, the n-item calls do the per-item work only:
 //   load          k_kem_key_setup   gen_matrix (A^T), one entry per block; H(pk) on the wave sponge    K^2 + 1 waves, once per key
-//   encapsulate   k_kem_key_hash    role   G(m || h), h from the slot                                 one lane per item
-//                 k_kem_key_hash    roles  r, e1, e2                                                  (2 K + 1) lanes per item
-//                 k_kem_key_encrypt encrypt_block on the slot's pk and A^T                            one workgroup per item
-//   decapsulate   k_kem_key_decrypt decrypt_block on the slot's s-hat, G(m' || stored h)              one workgroup per item
-//                 k_kem_key_hash    roles  rkprf (z from the slot; k_kem_rkprf_wave in a small group), r, e1, e2
-//                 k_kem_key_encrypt comparing
+//   encapsulate   k_kem_hash        role   G(m || h), h from the slot                                 one lane per item
+//                 k_kem_hash        roles  r, e1, e2                                                  (2 K + 1) lanes per item
+//                 k_kem_encrypt     encrypt_block on the slot's pk and A^T                            one workgroup per item
+//   decapsulate   k_kem_decrypt     decrypt_block on the slot's s-hat, G(m' || stored h)              one workgroup per item
+//                 k_kem_hash        roles  rkprf (z from the slot; k_kem_rkprf_wave in a small group), r, e1, e2
+//                 k_kem_encrypt     comparing
+// These are the per-item kernels and the per-item host bodies: a one-key call is the per-item call with every key-side stride 0 (KemKeySide),
+// no matrix role and no H(pk).
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -56,11 +58,12 @@ struct KemWs {
 struct KemHashJob {
     int n, K, eta1;
     int n_rk, n_seed, n_mat, n_noise; // lanes per item of each role, in launch order
-    const uint8_t *pk;                // records holding t-hat || rho (the pk, or the pk inside the sk)
+    const uint8_t *pk;                // records holding t-hat || rho (the pk, or the pk inside the sk); not read where h is given and n_mat = 0
     size_t pk_stride;
     int pk_bytes;
     const uint8_t *m;                 // [n][32]     seed role: the message
-    const uint8_t *h;                 // [n][32] or nullptr: H(pk) already computed (wave sponge); nullptr: the seed role hashes pk itself
+    const uint8_t *h;                 // seed role: H(pk) of item b at h + b * h_stride (wave sponge, or the slot's); nullptr: it hashes pk itself
+    size_t h_stride;
     uint8_t *kr;                      // [n][64]     seed role writes, noise role reads (coins = kr + 32)
     int16_t *A, *noise;               // [n][K K][256], [n][2 K + 1][256]
     const uint8_t *z;                 // rkprf role: z of item b at z + b * z_stride
@@ -94,7 +97,7 @@ __global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
         for (int l = 0; l < 4; l++) m[l] = ld64(j.m, 4 * b + l);
         if (j.h) {
 #pragma unroll
-            for (int l = 0; l < 4; l++) h[l] = ld64(j.h, 4 * b + l);
+            for (int l = 0; l < 4; l++) h[l] = ld64(j.h + (size_t)b * j.h_stride, l);
         } else {
             sha3_256_words(pk, j.pk_bytes, h);
         }
@@ -120,6 +123,21 @@ __global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
     noise_poly(coins, t, t < j.K ? j.eta1 : 2, j.noise + ((size_t)b * j.n_noise + t) * 256);
 }
 
+// The whole-word message of a wave sponge at rate 136 (17 words a block): absorbs words fetch(0 .. nwords - 1) and the padding behind them,
+// domain byte `dom` (0x06 SHA3, 0x1F SHAKE), through the last permutation.  Which word a lane fetches is a function of the lane and the block.
+template <class Fetch>
+__device__ __forceinline__ void wave_absorb_words(const WaveSponge &sp, uint32_t &a, Fetch fetch, int nwords, uint32_t dom)
+{
+    const int word = sp.word(), nfull = nwords / 17, rem = nwords - 17 * nfull;
+    for (int blk = 0; blk < nfull; blk++) {
+        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
+        sp.permute(a);
+    }
+    // rem <= 16 whole words, then the padding: the domain byte opens the first free word
+    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, dom, 136));
+    sp.permute(a);
+}
+
 // rkprf = SHAKE256(z[32] || ct) (symmetric-shake.c: kyber_shake256_rkprf), one WAVE per item on the wave sponge: a 32-bit half of a state
 // word per lane, bit-interleaved (kosk_keccak_wave_dev.hpp, WaveSponge).  z and ct are 8-byte aligned and 32 + ct_bytes is a multiple of 8, so
 // every block is whole words.  z is secret: it is data only; the addresses are functions of the lane and the block.
@@ -131,27 +149,20 @@ __global__ __launch_bounds__(64) void k_kem_rkprf_wave(const uint8_t *z, size_t 
     __builtin_amdgcn_s_setprio(3); // a chain is latency, not throughput
     WaveSponge sp;
     sp.setup(lane);
-    const int word = sp.word();
     const uint8_t *zb = z + b * z_stride, *cb = ct + b * (size_t)ct_bytes;
-    const int nwords = 4 + ct_bytes / 8, nfull = nwords / 17, rem = nwords - 17 * nfull;
-    auto fetch = [&](int i) { return *reinterpret_cast<const uint2 *>(i < 4 ? zb + 8 * i : cb + 8 * (i - 4)); };
     uint32_t a = 0;
-    for (int blk = 0; blk < nfull; blk++) {
-        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
-        sp.permute(a);
-    }
-    // rem <= 16 whole words, then the padding: the SHAKE domain byte opens the first free word
-    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, 0x1Fu, 136));
-    sp.permute(a);
+    wave_absorb_words(sp, a, [&](int i) { return *reinterpret_cast<const uint2 *>(i < 4 ? zb + 8 * i : cb + 8 * (i - 4)); }, 4 + ct_bytes / 8, 0x1Fu);
     const uint2 w = sp.words(a, st, 4);
     if (lane < 4) *reinterpret_cast<uint2 *>(rk + b * 32 + 8 * lane) = w;
 }
 
+// pk and A^T of item b at pk + b * pk_stride and A + b * A_stride (int16_t elements): one of each per item, or the slot's at stride 0
 struct KemEncJob {
     int K, dec;
     const uint8_t *pk;
     size_t pk_stride;
     const int16_t *A, *noise;
+    size_t A_stride;
     const uint8_t *m, *kr, *rk; // [n][32], [n][64], [n][32] (dec)
     uint8_t *ct;                // [n][ct_bytes]: written (enc) or compared with (dec)
     uint8_t *ss;                // [n][32]
@@ -173,7 +184,7 @@ __global__ __launch_bounds__(256) void k_kem_encrypt(KemEncJob j)
     }
     if (tid == 0) fail = 0;
     __syncthreads();
-    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk + b * j.pk_stride, j.A + b * (size_t)(D.K * D.K * 256),
+    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk + b * j.pk_stride, j.A + b * j.A_stride,
                                         j.noise + b * (size_t)((2 * D.K + 1) * 256), j.m + b * 32, j.dec ? nullptr : ct, ct);
     if (!j.dec) {
         if (tid < 32) j.ss[b * 32 + tid] = j.kr[b * 64 + tid];
@@ -184,10 +195,13 @@ __global__ __launch_bounds__(256) void k_kem_encrypt(KemEncJob j)
     if (tid < 32) j.ss[b * 32 + tid] = select_ss(fail, j.kr[b * 64 + tid], j.rk[b * 32 + tid]);
 }
 
+// s-hat of item b at shat + b * shat_stride and the H(pk) its sk stored at h + b * h_stride: both inside the item's sk record, or the slot's at
+// stride 0.  s-hat, z, m and kr are data only: every address built from them (here and in k_kem_hash, k_kem_rkprf_wave, k_kem_encrypt) is a
+// function of the block, the lane and a launch-time stride, whichever caller launched.
 struct KemDecJob {
     int K;
-    const uint8_t *ct, *sk;
-    size_t sk_stride;
+    const uint8_t *ct, *shat, *h;
+    size_t shat_stride, h_stride;
     uint8_t *m, *kr;
 };
 
@@ -198,13 +212,12 @@ __global__ __launch_bounds__(256) void k_kem_decrypt(KemDecJob j)
     const Dims D = dims(j.K);
     const int tid = threadIdx.x;
     const size_t b = blockIdx.x;
-    const uint8_t *sk = j.sk + b * j.sk_stride;
-    decrypt_block(D, L, Lb, tid, 256, j.ct + b * (size_t)D.ct, sk);
+    decrypt_block(D, L, Lb, tid, 256, j.ct + b * (size_t)D.ct, j.shat + b * j.shat_stride);
     if (tid < 32) j.m[b * 32 + tid] = Lb[256 + tid];
     if (tid == 0) {
         uint64_t m[4], h[4], kr[8];
 #pragma unroll
-        for (int l = 0; l < 4; l++) { m[l] = ld64(Lb + 256, l); h[l] = ld64(sk + D.sk - 64, l); }
+        for (int l = 0; l < 4; l++) { m[l] = ld64(Lb + 256, l); h[l] = ld64(j.h + b * j.h_stride, l); }
         hash_g64(m, h, kr);
 #pragma unroll
         for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * b + l] = kr[l];
@@ -356,117 +369,10 @@ __global__ __launch_bounds__(64) void k_kem_key_setup(int K, const uint8_t *pk, 
     __builtin_amdgcn_s_setprio(3);
     WaveSponge sp;
     sp.setup(lane);
-    const int word = sp.word();
-    const int nwords = pk_bytes / 8, nfull = nwords / 17, rem = nwords - 17 * nfull;
-    auto fetch = [&](int i) { return *reinterpret_cast<const uint2 *>(pk + 8 * i); };
     uint32_t a = 0;
-    for (int blk = 0; blk < nfull; blk++) {
-        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
-        sp.permute(a);
-    }
-    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, 0x06u, 136));
-    sp.permute(a);
+    wave_absorb_words(sp, a, [&](int i) { return *reinterpret_cast<const uint2 *>(pk + 8 * i); }, pk_bytes / 8, 0x06u);
     const uint2 w = sp.words(a, st, 4);
     if (lane < 4) *reinterpret_cast<uint2 *>(h + 8 * lane) = w;
-}
-
-// The per-item hashing of a one-key call, roles as lane ranges like k_kem_hash: rkprf (z of the slot), G(m || h) (h of the slot), noise.
-// No matrix role and no H(pk): the slot has both.  z is data only; every address is a function of the lane.
-struct KemKeyHashJob {
-    int n, K, eta1;
-    int n_rk, n_seed, n_noise; // lanes per item of each role, in launch order
-    const uint8_t *m, *h;      // [n][32], [32]
-    uint8_t *kr;               // [n][64]
-    int16_t *noise;            // [n][2 K + 1][256]
-    const uint8_t *z, *ct;     // [32], [n][ct_bytes]
-    int ct_bytes;
-    uint8_t *rk;               // [n][32]
-};
-
-__global__ __launch_bounds__(64) void k_kem_key_hash(KemKeyHashJob j)
-{
-    const long gid = (long)blockIdx.x * 64 + threadIdx.x;
-    const int per = j.n_rk + j.n_seed + j.n_noise;
-    if (gid >= (long)per * j.n) return;
-    int t = (int)(gid / j.n);
-    const int b = (int)(gid - (long)t * j.n);
-    if (t < j.n_rk) {
-        uint64_t out[4];
-        rkprf(j.z, j.ct + (size_t)b * j.ct_bytes, j.ct_bytes, out);
-#pragma unroll
-        for (int l = 0; l < 4; l++) reinterpret_cast<uint64_t *>(j.rk)[4 * (size_t)b + l] = out[l];
-        return;
-    }
-    t -= j.n_rk;
-    if (t < j.n_seed) {
-        uint64_t m[4], h[4], kr[8];
-#pragma unroll
-        for (int l = 0; l < 4; l++) { m[l] = ld64(j.m, 4 * b + l); h[l] = ld64(j.h, l); }
-        hash_g64(m, h, kr);
-#pragma unroll
-        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * (size_t)b + l] = kr[l];
-        return;
-    }
-    t -= j.n_seed;
-    uint64_t coins[4];
-#pragma unroll
-    for (int l = 0; l < 4; l++) coins[l] = ld64(j.kr, 8 * b + 4 + l);
-    noise_poly(coins, t, t < j.K ? j.eta1 : 2, j.noise + ((size_t)b * j.n_noise + t) * 256);
-}
-
-// k_kem_encrypt with the pk and A^T of the slot under every item
-struct KemKeyEncJob {
-    int K, dec;
-    const uint8_t *pk;          // the slot's
-    const int16_t *A, *noise;   // the slot's A^T; [n][2 K + 1][256]
-    const uint8_t *m, *kr, *rk; // [n][32], [n][64], [n][32] (dec)
-    uint8_t *ct, *ss;           // [n][ct_bytes]: written (enc) or compared with (dec); [n][32]
-};
-
-__global__ __launch_bounds__(256) void k_kem_key_encrypt(KemKeyEncJob j)
-{
-    __shared__ alignas(16) uint16_t L[9 * 256];
-    __shared__ uint32_t fail;
-    const Dims D = dims(j.K);
-    const int tid = threadIdx.x;
-    const size_t b = blockIdx.x;
-    uint8_t *ct = j.ct + b * (size_t)D.ct;
-    if (tid == 0) fail = 0;
-    __syncthreads();
-    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk, j.A, j.noise + b * (size_t)((2 * D.K + 1) * 256), j.m + b * 32, j.dec ? nullptr : ct, ct);
-    if (!j.dec) {
-        if (tid < 32) j.ss[b * 32 + tid] = j.kr[b * 64 + tid];
-        return;
-    }
-    atomicOr(&fail, diff);
-    __syncthreads();
-    if (tid < 32) j.ss[b * 32 + tid] = select_ss(fail, j.kr[b * 64 + tid], j.rk[b * 32 + tid]);
-}
-
-// k_kem_decrypt on the slot's s-hat, G with the H(pk) the sk stored.  s-hat is read at addresses that depend on the thread alone.
-struct KemKeyDecJob {
-    int K;
-    const uint8_t *ct, *shat, *h;
-    uint8_t *m, *kr;
-};
-
-__global__ __launch_bounds__(256) void k_kem_key_decrypt(KemKeyDecJob j)
-{
-    __shared__ alignas(16) uint16_t L[6 * 256];
-    __shared__ alignas(16) uint8_t Lb[288];
-    const Dims D = dims(j.K);
-    const int tid = threadIdx.x;
-    const size_t b = blockIdx.x;
-    decrypt_block(D, L, Lb, tid, 256, j.ct + b * (size_t)D.ct, j.shat);
-    if (tid < 32) j.m[b * 32 + tid] = Lb[256 + tid];
-    if (tid == 0) {
-        uint64_t m[4], h[4], kr[8];
-#pragma unroll
-        for (int l = 0; l < 4; l++) { m[l] = ld64(Lb + 256, l); h[l] = ld64(j.h, l); }
-        hash_g64(m, h, kr);
-#pragma unroll
-        for (int l = 0; l < 8; l++) reinterpret_cast<uint64_t *>(j.kr)[8 * b + l] = kr[l];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host --
@@ -551,6 +457,131 @@ static hipError_t kem_launch_hash(const KemHashJob &j, hipStream_t st)
     return hipGetLastError();
 }
 
+// H(pk) of n records under the two-layout rule: up to kem_wave_max() items one wave per item into w.d_h (returns true: the caller
+// takes it from there), above that nothing is launched and the caller's one-lane-per-item kernel hashes (returns false)
+static int kem_hpk_wave(Ctx &c, int n, const uint8_t *in, size_t in_stride, int len, bool &done)
+{
+    done = n <= kem_wave_max();
+    if (!done) return 0;
+    FsArgs fa{};
+    fa.in = in; fa.in_stride = in_stride; fa.len = len; fa.out_digest = c.kem->d_h;
+    HIPCHK(launch_fs_chain(fa, FS_DIGEST, n, c.stream));
+    return 0;
+}
+
+// The key side of a KEM call: item b's piece of the key lies at base + b * stride.  The per-item calls point it into the workspace (or at
+// the resident verified keys), where A^T and H(pk) are still to be computed; a one-key call points it at the slot, every stride 0.
+struct KemKeySide {
+    const uint8_t *pk, *h_enc, *shat, *h_dec, *z; // h_enc: H(pk) for G of an encapsulation; h_dec: the H(pk) stored in the sk
+    const int16_t *A;
+    size_t pk_stride, h_enc_stride, shat_stride, h_dec_stride, z_stride, A_stride; // A_stride in int16_t elements
+    bool derive;                                  // A^T (matrix role, into A) and H(pk) (kem_wave_max() rule, into h_enc) belong to the call
+};
+
+// n records at `rec`, `stride` bytes apart: public keys, or (is_sk) secret keys s-hat || pk || H(pk) || z
+static KemKeySide kem_side_items(const KemWs &w, const Dims &D, const uint8_t *rec, size_t stride, bool is_sk)
+{
+    KemKeySide k{};
+    k.pk = is_sk ? rec + D.pvb : rec; k.pk_stride = stride;
+    k.A = w.d_A; k.A_stride = (size_t)D.K * D.K * 256;
+    k.h_enc = w.d_h; k.h_enc_stride = 32;
+    if (is_sk) {
+        k.shat = rec; k.h_dec = rec + D.sk - 64; k.z = rec + D.sk - 32;
+        k.shat_stride = k.h_dec_stride = k.z_stride = stride;
+    }
+    k.derive = true;
+    return k;
+}
+
+static KemKeySide kem_side_slot(const KemKey &s)
+{
+    KemKeySide k{};
+    k.pk = s.pk; k.A = s.A; k.h_enc = s.h_enc; k.shat = s.shat; k.h_dec = s.h_dec; k.z = s.z;
+    return k;
+}
+
+static KemHashJob kem_hash_job(Ctx &c, int n, const KemKeySide &k)
+{
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    KemHashJob h{};
+    h.n = n; h.K = D.K; h.eta1 = D.eta1;
+    h.pk = k.pk; h.pk_stride = k.pk_stride; h.pk_bytes = D.pk;
+    h.kr = w.d_kr; h.A = w.d_A; h.noise = w.d_noise;
+    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
+    return h;
+}
+
+static hipError_t kem_launch_encrypt(Ctx &c, int n, const KemKeySide &k, int dec, const uint8_t *d_mask)
+{
+    KemWs &w = *c.kem;
+    KemEncJob e{};
+    e.K = c.P.K; e.dec = dec; e.pk = k.pk; e.pk_stride = k.pk_stride; e.A = k.A; e.A_stride = k.A_stride; e.noise = w.d_noise;
+    e.m = w.d_m; e.kr = w.d_kr; e.rk = dec ? w.d_rk : nullptr; e.ct = w.d_ct; e.ss = w.d_ss; e.mask = d_mask;
+    k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
+    return hipGetLastError();
+}
+
+// Encapsulation under either key side (the workspace holds n items): `path` is the caller's path_n[] counter
+static int kem_enc_body(Ctx &c, int n, const KemKeySide &k, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask, int path)
+{
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
+    if (mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
+    KemHashJob h = kem_hash_job(c, n, k);
+    h.m = w.d_m; h.h = k.h_enc; h.h_stride = k.h_enc_stride;
+    if (k.derive) {
+        bool wave = false; // H(pk): one wave per key on the wave sponge, or the seed role hashes pk itself
+        if (kem_hpk_wave(c, n, k.pk, k.pk_stride, D.pk, wave)) return -1;
+        if (!wave) h.h = nullptr;
+        h.n_mat = D.K * D.K;
+    }
+    h.n_seed = 1;
+    HIPCHK(kem_launch_hash(h, c.stream));
+    h.n_seed = 0; h.n_mat = 0; h.n_noise = 2 * D.K + 1;
+    HIPCHK(kem_launch_hash(h, c.stream));
+    HIPCHK(kem_launch_encrypt(c, n, k, 0, mask ? w.d_mask : nullptr));
+    c.path_n[path]++;
+    if (k.derive) {
+        HIPCHK(stream_sync(c));
+        if (device_error_check(c)) return -1; // gen_matrix block limit: no results
+    }
+    HIPCHK(kem_copy_out(c, ct, w.d_ct, (size_t)n * D.ct));
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+// Decapsulation of the n ciphertexts in w.d_ct under either key side
+static int kem_dec_body(Ctx &c, int n, const KemKeySide &k, uint8_t *ss, int path)
+{
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    KemDecJob d{};
+    d.K = D.K; d.ct = w.d_ct; d.shat = k.shat; d.shat_stride = k.shat_stride; d.h = k.h_dec; d.h_stride = k.h_dec_stride; d.m = w.d_m; d.kr = w.d_kr;
+    k_kem_decrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(d);
+    HIPCHK(hipGetLastError());
+    KemHashJob h = kem_hash_job(c, n, k);
+    h.z = k.z; h.z_stride = k.z_stride; h.ct = w.d_ct; h.ct_bytes = D.ct; h.rk = w.d_rk;
+    h.n_rk = 1; h.n_mat = k.derive ? D.K * D.K : 0; h.n_noise = 2 * D.K + 1;
+    if (n <= kem_wave_max()) { // rkprf: one wave per item on the wave sponge
+        k_kem_rkprf_wave<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(h.z, h.z_stride, h.ct, h.ct_bytes, h.rk);
+        HIPCHK(hipGetLastError());
+        h.n_rk = 0;
+    }
+    HIPCHK(kem_launch_hash(h, c.stream));
+    HIPCHK(kem_launch_encrypt(c, n, k, 1, nullptr));
+    c.path_n[path]++;
+    if (k.derive) {
+        HIPCHK(stream_sync(c));
+        if (device_error_check(c)) return -1;
+    }
+    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
 int kem_enc(Ctx &c, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask, int resident_first)
 {
     if (n < 1 || n > KEM_CHUNK || !coins || !ct || !ss) { c.err = "kem_enc: bad arguments"; return -1; }
@@ -562,35 +593,7 @@ int kem_enc(Ctx &c, int n, const uint8_t *pk, const uint8_t *coins, uint8_t *ct,
     size_t pk_stride = (size_t)D.pk;
     if (pk) HIPCHK(kem_copy_in(c, w.d_pk, pk, (size_t)n * D.pk));
     else { d_pk = c.d_pk + (size_t)resident_first * c.pk_stride; pk_stride = c.pk_stride; } // the keys the last verify call left resident (kosk_kem_enc_verified)
-    HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
-    if (mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
-    KemHashJob h{};
-    h.n = n; h.K = D.K; h.eta1 = D.eta1;
-    h.pk = d_pk; h.pk_stride = pk_stride; h.pk_bytes = D.pk;
-    h.m = w.d_m; h.kr = w.d_kr; h.A = w.d_A; h.noise = w.d_noise;
-    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
-    if (n <= kem_wave_max()) { // H(pk): one wave per key on the wave sponge
-        FsArgs fa{};
-        fa.in = d_pk; fa.in_stride = pk_stride; fa.len = D.pk; fa.out_digest = w.d_h;
-        HIPCHK(launch_fs_chain(fa, FS_DIGEST, n, c.stream));
-        h.h = w.d_h;
-    }
-    h.n_seed = 1; h.n_mat = D.K * D.K;
-    HIPCHK(kem_launch_hash(h, c.stream));
-    h.n_seed = 0; h.n_mat = 0; h.n_noise = 2 * D.K + 1;
-    HIPCHK(kem_launch_hash(h, c.stream));
-    KemEncJob e{};
-    e.K = D.K; e.dec = 0; e.pk = d_pk; e.pk_stride = pk_stride; e.A = w.d_A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr;
-    e.ct = w.d_ct; e.ss = w.d_ss; e.mask = mask ? w.d_mask : nullptr;
-    k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
-    HIPCHK(hipGetLastError());
-    c.path_n[PATH_KEM_ENC]++;
-    HIPCHK(stream_sync(c));
-    if (device_error_check(c)) return -1; // gen_matrix block limit: no results
-    HIPCHK(kem_copy_out(c, ct, w.d_ct, (size_t)n * D.ct));
-    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
-    HIPCHK(stream_sync(c));
-    return 0;
+    return kem_enc_body(c, n, kem_side_items(w, D, d_pk, pk_stride, false), coins, ct, ss, mask, PATH_KEM_ENC);
 }
 
 int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
@@ -602,46 +605,7 @@ int kem_dec(Ctx &c, int n, const uint8_t *ct, const uint8_t *sk, uint8_t *ss)
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(kem_copy_in(c, w.d_ct, ct, (size_t)n * D.ct));
     HIPCHK(kem_copy_in(c, w.d_sk, sk, (size_t)n * D.sk));
-    KemDecJob d{};
-    d.K = D.K; d.ct = w.d_ct; d.sk = w.d_sk; d.sk_stride = (size_t)D.sk; d.m = w.d_m; d.kr = w.d_kr;
-    k_kem_decrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(d);
-    HIPCHK(hipGetLastError());
-    KemHashJob h{};
-    h.n = n; h.K = D.K; h.eta1 = D.eta1;
-    h.pk = w.d_sk + D.pvb; h.pk_stride = (size_t)D.sk; h.pk_bytes = D.pk; // sk = s-hat || pk || H(pk) || z
-    h.kr = w.d_kr; h.A = w.d_A; h.noise = w.d_noise;
-    h.z = w.d_sk + D.sk - 32; h.z_stride = (size_t)D.sk; h.ct = w.d_ct; h.ct_bytes = D.ct; h.rk = w.d_rk;
-    h.err = c.h_err; h.max_blocks = c.xof_max_blocks;
-    h.n_rk = 1; h.n_mat = D.K * D.K; h.n_noise = 2 * D.K + 1;
-    if (n <= kem_wave_max()) { // rkprf: one wave per item on the wave sponge
-        k_kem_rkprf_wave<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(h.z, h.z_stride, h.ct, h.ct_bytes, h.rk);
-        HIPCHK(hipGetLastError());
-        h.n_rk = 0;
-    }
-    HIPCHK(kem_launch_hash(h, c.stream));
-    KemEncJob e{};
-    e.K = D.K; e.dec = 1; e.pk = h.pk; e.pk_stride = h.pk_stride; e.A = w.d_A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.rk = w.d_rk;
-    e.ct = w.d_ct; e.ss = w.d_ss;
-    k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
-    HIPCHK(hipGetLastError());
-    c.path_n[PATH_KEM_DEC]++;
-    HIPCHK(stream_sync(c));
-    if (device_error_check(c)) return -1;
-    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
-    HIPCHK(stream_sync(c));
-    return 0;
-}
-
-// H(pk) of n records under the two-layout rule: up to kem_wave_max() items one wave per item into w.d_h (returns true: the caller
-// takes it from there), above that nothing is launched and the caller's one-lane-per-item kernel hashes (returns false)
-static int kem_hpk_wave(Ctx &c, int n, const uint8_t *in, size_t in_stride, int len, bool &done)
-{
-    done = n <= kem_wave_max();
-    if (!done) return 0;
-    FsArgs fa{};
-    fa.in = in; fa.in_stride = in_stride; fa.len = len; fa.out_digest = c.kem->d_h;
-    HIPCHK(launch_fs_chain(fa, FS_DIGEST, n, c.stream));
-    return 0;
+    return kem_dec_body(c, n, kem_side_items(w, D, w.d_sk, (size_t)D.sk, true), ss, PATH_KEM_DEC);
 }
 
 int kem_keypair(Ctx &c, int n, const uint8_t *coins, uint8_t *pk, uint8_t *sk)
@@ -786,39 +750,13 @@ int kem_key_set(Ctx &c, const uint8_t *pk, const uint8_t *sk)
     return 0;
 }
 
-static hipError_t kem_launch_key_hash(const KemKeyHashJob &j, hipStream_t st)
-{
-    const long lanes = (long)(j.n_rk + j.n_seed + j.n_noise) * j.n;
-    k_kem_key_hash<<<dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, st>>>(j);
-    return hipGetLastError();
-}
-
 int kem_enc_key(Ctx &c, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
 {
     if (n < 1 || n > KEM_CHUNK || !coins || !ct || !ss) { c.err = "kem_enc_key: bad arguments"; return -1; }
     if (kem_key_state(c) == KEM_KEY_NONE) { c.err = "kem_enc_key: no key is loaded (kosk_kem_key_set)"; return -1; }
     if (kem_ensure(c, n)) return -1;
-    KemWs &w = *c.kem;
-    const KemKey &k = *c.kem_key;
-    const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
-    HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
-    KemKeyHashJob h{};
-    h.n = n; h.K = D.K; h.eta1 = D.eta1;
-    h.m = w.d_m; h.h = k.h_enc; h.kr = w.d_kr; h.noise = w.d_noise;
-    h.n_seed = 1;
-    HIPCHK(kem_launch_key_hash(h, c.stream));
-    h.n_seed = 0; h.n_noise = 2 * D.K + 1;
-    HIPCHK(kem_launch_key_hash(h, c.stream));
-    KemKeyEncJob e{};
-    e.K = D.K; e.dec = 0; e.pk = k.pk; e.A = k.A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.ct = w.d_ct; e.ss = w.d_ss;
-    k_kem_key_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
-    HIPCHK(hipGetLastError());
-    c.path_n[PATH_KEM_ENC_KEY]++;
-    HIPCHK(kem_copy_out(c, ct, w.d_ct, (size_t)n * D.ct));
-    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
-    HIPCHK(stream_sync(c));
-    return 0;
+    return kem_enc_body(c, n, kem_side_slot(*c.kem_key), coins, ct, ss, nullptr, PATH_KEM_ENC_KEY);
 }
 
 int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss)
@@ -831,33 +769,9 @@ int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss)
         return -1;
     }
     if (kem_ensure(c, n)) return -1;
-    KemWs &w = *c.kem;
-    const KemKey &k = *c.kem_key;
-    const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
-    HIPCHK(kem_copy_in(c, w.d_ct, ct, (size_t)n * D.ct));
-    KemKeyDecJob d{};
-    d.K = D.K; d.ct = w.d_ct; d.shat = k.shat; d.h = k.h_dec; d.m = w.d_m; d.kr = w.d_kr;
-    k_kem_key_decrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(d);
-    HIPCHK(hipGetLastError());
-    KemKeyHashJob h{};
-    h.n = n; h.K = D.K; h.eta1 = D.eta1;
-    h.kr = w.d_kr; h.noise = w.d_noise; h.z = k.z; h.ct = w.d_ct; h.ct_bytes = D.ct; h.rk = w.d_rk;
-    h.n_rk = 1; h.n_noise = 2 * D.K + 1;
-    if (n <= kem_wave_max()) { // rkprf: one wave per item on the wave sponge, z at stride 0
-        k_kem_rkprf_wave<<<dim3((unsigned)n), dim3(64), 0, c.stream>>>(k.z, 0, h.ct, h.ct_bytes, h.rk);
-        HIPCHK(hipGetLastError());
-        h.n_rk = 0;
-    }
-    HIPCHK(kem_launch_key_hash(h, c.stream));
-    KemKeyEncJob e{};
-    e.K = D.K; e.dec = 1; e.pk = k.pk; e.A = k.A; e.noise = w.d_noise; e.m = w.d_m; e.kr = w.d_kr; e.rk = w.d_rk; e.ct = w.d_ct; e.ss = w.d_ss;
-    k_kem_key_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
-    HIPCHK(hipGetLastError());
-    c.path_n[PATH_KEM_DEC_KEY]++;
-    HIPCHK(kem_copy_out(c, ss, w.d_ss, (size_t)n * 32));
-    HIPCHK(stream_sync(c));
-    return 0;
+    HIPCHK(kem_copy_in(c, c.kem->d_ct, ct, (size_t)n * dims(c.P.K).ct));
+    return kem_dec_body(c, n, kem_side_slot(*c.kem_key), ss, PATH_KEM_DEC_KEY);
 }
 
 } // namespace kosk

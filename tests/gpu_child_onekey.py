@@ -49,8 +49,8 @@ def check_parity(ctx, k, n, dec):
 
 
 def per_lane_rkprf_on_small_batches(k=3):
-    """run with KOSK_DEBUG_KEM_WAVE_MAX=0: the rkprf of small batches on the per-lane role of k_kem_key_hash (what batches above
-    KEM_WAVE_MAX use), against the fixture, valid and tampered ciphertexts"""
+    """run with KOSK_DEBUG_KEM_WAVE_MAX=0: the rkprf of small batches on the per-lane role of k_kem_hash, z at stride 0 (what batches
+    above KEM_WAVE_MAX use), against the fixture, valid and tampered ciphertexts"""
     assert os.environ.get("KOSK_DEBUG_KEM_WAVE_MAX") == "0"
     from mpcith_kyber_kosk_amd import api
     v = vectors(k)
@@ -63,6 +63,35 @@ def per_lane_rkprf_on_small_batches(k=3):
     assert [s.hex() for s in ctx.kem_dec_key(bad)] == [t["dec_ss"] for t in v["raw"]["tampered"]]
     ctx.close()
     print("per_lane_rkprf_on_small_batches ok %d" % k)
+
+
+def both_paths_on_one_handle(k=3, n=65):
+    """the per-item and the one-key calls share their kernels and their host bodies: with fixture key 3 in the slot, twice over,
+    kosk_kem_enc_batch + kosk_kem_dec_batch on n items of tests/golden/kem_vectors_v1.json (each its own key, none of them key 3), then
+    kosk_kem_enc_key + kosk_kem_dec_key on n items -- every ct and ss against its fixture.  65 items: a second, partial wave in every role.
+    Rejected in the per-item dec: item 2 (the fixture stores its rejection key) and a tampered ciphertext in the second wave
+    (SHAKE256(z || ct) of that item's own z); in the one-key dec: the fixture's tampered ciphertext of item 5, put in the second wave"""
+    from mpcith_kyber_kosk_amd import api
+    v, items = vectors(k), kf.load()["k"]["k%d" % k]
+    idx = [i for i in range(n + 1) if i != KEY]
+    pks, sks, ms = [kf.enc_pk(k, i) for i in idx], [kf.keypair(k, i)[1] for i in idx], [kf.message(k, i) for i in idx]
+    t = v["raw"]["tampered"][1]
+    bad5 = kf.tampered(bytes.fromhex(v["raw"]["ct5_hex"]), t["byte"])
+    ctx = api.Kosk(kyber_k=k, max_batch=3)
+    ctx.kem_key_set(sk=v["sk"])
+    for _ in range(2):
+        cts, sss = ctx.kem_enc(pks, ms)
+        assert [kf.sha3(c) for c in cts] == [items[i]["ct"] for i in idx] and [s.hex() for s in sss] == [items[i]["ss"] for i in idx]
+        cts[n - 1] = kf.tampered(cts[n - 1], kf.U_BYTES[k] - 1)
+        want = [items[i]["dec_ss"] if i == 2 else items[i]["ss"] for i in idx]
+        want[n - 1] = rejection_key(sks[n - 1], cts[n - 1]).hex()
+        assert [s.hex() for s in ctx.kem_dec(cts, sks)] == want
+        cts, sss = check_parity(ctx, k, n, False)
+        cts[n - 1] = bad5
+        assert [s.hex() for s in ctx.kem_dec_key(cts)] == [x[1] for x in v["items"][:n - 1]] + [t["dec_ss"]]
+    assert ctx.path_count(api.Kosk.PATH_KEM_ENC_KEY) == 2 and ctx.path_count(api.Kosk.PATH_KEM_DEC_KEY) == 2
+    ctx.close()
+    print("both_paths_on_one_handle ok %d" % k)
 
 
 def cohort_member_uses_the_calls_unmerged(k=2):

@@ -274,6 +274,15 @@ def test_per_lane_rkprf_on_small_batches(torch_cuda, gpu_child):
         assert "per_lane_rkprf_on_small_batches ok %d" % k in out
 
 
+def test_both_paths_on_one_handle(torch_cuda, gpu_child):
+    """10. the slot's pointers and the workspace's under the shared kernels: per-item calls on 65 keys that are not the slot's and
+    one-key calls on 65 items, alternating twice on one handle, every ct and ss against its fixture, one rejected ciphertext in the second
+    wave of each dec; again with KOSK_DEBUG_KEM_WAVE_MAX=0 (H(pk) and rkprf on the per-lane roles)"""
+    ok.both_paths_on_one_handle(3)
+    out = gpu_child("from tests.gpu_child_onekey import both_paths_on_one_handle as f; f(3)", env={"KOSK_DEBUG_KEM_WAVE_MAX": "0"})
+    assert "both_paths_on_one_handle ok 3" in out
+
+
 def test_block_limit_inside_key_set(torch_cuda, gpu_child):
     """6. -1 ("block limit") with the slot left empty when gen_matrix reaches its limit inside kosk_kem_key_set"""
     out = gpu_child("from tests.gpu_child_onekey import block_limit_leaves_the_slot_empty as f; f(3)", env={"KOSK_DEBUG_XOF_BLOCKS": "1"})
