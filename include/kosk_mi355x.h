@@ -550,6 +550,23 @@ int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t t
  * runs.  Not to be called while another thread is inside a call on this handle. */
 int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t context_stride);
 
+/* ---- TESTS ONLY: the prover at a chosen opened list ----
+ * While n lists are set (cand: host memory, n x 150 entries, each < 1454; the handle keeps its own copies), Fiat-Shamir round 2 of this
+ * handle's PROVER takes cand[b][i] for proof b of a call (of the whole call, when it is chunked) in place of the candidates BE16 % 1454
+ * it reads from the PRF output.  The probing (duplicates are allowed: they are what reaches it), the complement and the derived tables
+ * are the code the honest path runs, in both Fiat-Shamir modes; ch and the view digests stay the honest ones, so the proof fails the
+ * verifier's last check, I' == I, and no other.  kosk_fs_opened_device / kosk_fs_opened_bound_device obey it for tables b < n.  The
+ * verifier never does.  -1 with a text, and the lists that were set stay: an entry >= 1454; n < 1 or n > KOSK_FORCE_MAX_LISTS; a handle
+ * that replays captured graphs (KOSK_GRAPHS=1); a cohort member (combine).  A proving call of more proofs than lists fails with -1 (a
+ * chunked call: at the first chunk that reaches behind the lists).  cand == NULL clears; kosk_destroy clears too.  Not to be called
+ * while another thread is inside a call on this handle. */
+#define KOSK_FORCE_MAX_LISTS 4096
+int kosk_force_opened_candidates(kosk_ctx *ctx, int n, const uint16_t *cand);
+/* the host's round-2 function behind the PRF on one candidate list, no handle: sel[0..150) = I, sel[160..184) the window boundaries,
+ * sel[192..342) the opened parties ascending, sel[352..502) their positions in I; rest[0..1304) the ascending complement.  Nothing else
+ * of the two rows is written.  -1: a NULL pointer, an entry >= 1454, sel_stride < 1304 (a row of the opened-list tables) */
+int kosk_opened_tables(const uint16_t cand[150], uint16_t *sel, uint16_t *rest, int sel_stride);
+
 /* ---- proof randomness derived from the key, format kosk-keyseed-v1 (no reference counterpart) ----
  *   seed = SHAKE256("kosk-keyseed-v1" || 00 || LE32(K) || LE32(flags) || context[32] || salt[32] || sk[kosk_sk_bytes(K)])[0 : 32]
  *   flags bit 0: the proof is context-bound (a context is given / the handle is armed), bit 1: a salt is given; a field whose bit is

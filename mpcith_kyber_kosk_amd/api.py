@@ -187,6 +187,13 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_kem_key_set")):
         sig.update(onekey)
+    # tests: the prover at forced opened lists; optional under the same rule (and only then)
+    forced = {
+        "kosk_force_opened_candidates": (C.c_int, [vp, C.c_int, vp]),
+        "kosk_opened_tables": (C.c_int, [vp, vp, vp, C.c_int]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_opened_tables")):
+        sig.update(forced)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -219,7 +226,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_kem_keypair_batch", "kosk_kem_check_pk", "kosk_kem_check_sk",
            "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch",
            "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing",
-           "kosk_kem_key_set", "kosk_kem_key_state", "kosk_kem_key_clear", "kosk_kem_enc_key", "kosk_kem_dec_key"]
+           "kosk_kem_key_set", "kosk_kem_key_state", "kosk_kem_key_clear", "kosk_kem_enc_key", "kosk_kem_dec_key",
+           "kosk_force_opened_candidates", "kosk_opened_tables"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -310,6 +318,23 @@ def keyseed_value(k, sk, context=None, salt=None):
     if lib.kosk_keyseed_value(k, C.c_char_p(sk), cp, sp, out):
         raise KoskError("kosk_keyseed_value: kyber_k outside 2..4")
     return out.raw
+
+
+SEL_STRIDE = 1312  # entries of a row of the opened-list tables as the handles lay them out (>= 1304)
+
+
+def opened_tables(cand, sel_stride=SEL_STRIDE, fill=0):
+    """tests (kosk_opened_tables): the host's round-2 function behind the PRF on 150 candidates, no handle -> (sel, rest), two rows of
+    sel_stride u16 that held `fill` everywhere before the call: sel = I, the window boundaries at 160, the opened parties ascending at
+    192 and their positions in I at 352; rest = the ascending complement"""
+    cand = [int(c) for c in cand]
+    if len(cand) != 150 or any(not 0 <= c < 65536 for c in cand):
+        raise KoskError("opened_tables: 150 candidates")
+    rows = max(int(sel_stride), 1)
+    sel, rest = (C.c_uint16 * rows)(*([fill] * rows)), (C.c_uint16 * rows)(*([fill] * rows))
+    if lib.kosk_opened_tables((C.c_uint16 * 150)(*cand), sel, rest, sel_stride):
+        raise KoskError("kosk_opened_tables: an entry >= 1454, or sel_stride below a row of the tables")
+    return list(sel), list(rest)
 
 
 def tape_from_seed(k, seed):
@@ -495,6 +520,19 @@ class Kosk:
     def clear_contexts(self):
         """disarm the handle: it behaves exactly as one that was never armed"""
         self._chk(lib.kosk_set_contexts(self._h, 0, None, 0), "clear_contexts")
+
+    def force_opened_candidates(self, lists, n=None):
+        """tests (kosk_force_opened_candidates): lists = a list of lists of 150 candidates below 1454, proof b of every proving call on
+        this handle then takes lists[b] where it would read its candidates from the PRF output; None clears.  n: the count handed to
+        the library, if not len(lists)"""
+        if lists is None:
+            self._chk(lib.kosk_force_opened_candidates(self._h, 0, None), "force_opened_candidates")
+            return
+        flat = [int(c) for row in lists for c in row]
+        if any(len(row) != 150 for row in lists) or any(not 0 <= c < 65536 for c in flat):
+            raise KoskError("force_opened_candidates: lists of 150 candidates")
+        arr = (C.c_uint16 * max(len(flat), 1))(*flat)
+        self._chk(lib.kosk_force_opened_candidates(self._h, len(lists) if n is None else n, arr), "force_opened_candidates")
 
     def bind_device(self, n, pk, contexts, d_out, context_stride=CONTEXT_BYTES):
         """B for n proofs into device memory d_out (int pointer).  pk / contexts: bytes (host) or int device pointers"""

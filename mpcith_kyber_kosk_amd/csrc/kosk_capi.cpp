@@ -77,6 +77,18 @@ struct kosk_ctx {
         d_contexts = nullptr;
         armed = 0;
     }
+    // kosk_force_opened_candidates (tests): the handle's lists, 150 candidates each, in HBM for the chain kernel and on the host for the
+    // host's round; every sub-context points at both
+    uint16_t *d_force = nullptr;
+    std::vector<uint16_t> h_force;
+    void unforce()
+    {
+        for (Ctx *x : sub) { x->force_d = nullptr; x->force_h = nullptr; x->force_n = 0; }
+        if (c) c->inv_drop(Ctx::INVG_FORCE);
+        if (d_force) (void)hipFree(d_force);
+        d_force = nullptr;
+        h_force.clear();
+    }
 
     ~kosk_ctx()
     {
@@ -86,6 +98,7 @@ struct kosk_ctx {
             try { (void)wipe_secrets(*x); } catch (...) {}
         }
         disarm();
+        unforce();
         for (Ctx *x : sub) delete x;
         if (cohort) {
             std::lock_guard<std::mutex> lk(g_cohort_mu);
@@ -518,6 +531,46 @@ int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t cont
     for (Ctx *x : ctx->sub) { x->bind_ctx = d; x->bind_n = n; x->bind_first = 0; }
     return 0;
     GUARD_END
+}
+
+// tests: candidate lists for round 2 of this handle's prover (header).  Refusals leave the lists that were set as they are
+int kosk_force_opened_candidates(kosk_ctx *ctx, int n, const uint16_t *cand)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!cand) { ctx->unforce(); return 0; }
+    if (n < 1 || n > KOSK_FORCE_MAX_LISTS) return armed_refuse(ctx, __func__, "n lists need 1 <= n <= KOSK_FORCE_MAX_LISTS (cand == NULL clears)");
+    for (size_t i = 0; i < (size_t)n * NOPEN; i++)
+        if (cand[i] >= NPARTY) return armed_refuse(ctx, __func__, "a candidate is not a party (every entry must be below 1454)");
+    Ctx &c = *ctx->c;
+    if (c.use_graphs) return armed_refuse(ctx, __func__, "not on a handle that replays captured graphs (KOSK_GRAPHS=1): their kernel arguments are frozen");
+    if (ctx->cohort) return armed_refuse(ctx, __func__, "not on a cohort member (combine): its proofs may run in another member's call");
+    HIPCHK_C(hipSetDevice(c.device));
+    std::vector<uint16_t> h(cand, cand + (size_t)n * NOPEN);
+    uint16_t *d = nullptr;
+    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&d), h.size() * sizeof(uint16_t)));
+    const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { (void)hipFree(d); HIPCHK_C(e); }
+    ctx->unforce();
+    ctx->d_force = d;
+    ctx->h_force.swap(h);
+    c.reg_buf("d_force", &ctx->d_force, ctx->h_force.size() * sizeof(uint16_t), 0, Ctx::INVG_FORCE); // public: the test's candidate lists
+    for (Ctx *x : ctx->sub) { x->force_d = d; x->force_h = ctx->h_force.data(); x->force_n = n; }
+    return 0;
+    GUARD_END
+}
+// the host's function behind the PRF on one list, no handle (tests that run without a GPU)
+int kosk_opened_tables(const uint16_t cand[150], uint16_t *sel, uint16_t *rest, int sel_stride)
+{
+    if (!cand || !sel || !rest || sel_stride < NREST || sel_stride < SEL_OPOS + NOPEN) return -1;
+    for (int i = 0; i < NOPEN; i++)
+        if (cand[i] >= NPARTY) return -1;
+    try {
+        opened_from_candidates(cand, sel, rest);
+        opened_derived_tables(sel, rest);
+    } catch (...) { return -1; }
+    return 0;
 }
 
 int kosk_set_entropy(kosk_ctx *ctx, int mode)
@@ -1050,6 +1103,7 @@ int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t
     ctx->clear_err();
     for (int done = 0; done < n;) {
         const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
+        c.bind_first = done; // (forced candidate lists are indexed by the position in the call)
         if (prove_prepared(c, m, inst + (size_t)done * mlwe_inst_bytes(c.P), rand_in + (size_t)done * randomness_bytes(c.P),
                            range_in + (size_t)done * range_proof_bytes(c.P), tapes ? tapes + (size_t)done * tape_stride : nullptr,
                            tape_stride, pi + (size_t)done * c.P.proof_bytes)) return -1;
@@ -1818,6 +1872,7 @@ int kosk_fs_opened_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t table_s
     FsArgs fa{};
     fa.in = d_tables; fa.in_stride = table_stride; fa.len = NPARTY * 32; fa.out_digest = d_ch;
     fa.I = d_sel; fa.rest = d_rest; fa.sel_stride = sel_stride;
+    if (c.force_n > 0) { fa.cand = c.force_d; fa.cand_n = c.force_n; } // tests: tables b < force_n take the handle's candidate lists
     HIPCHK_C(launch_fs_chain(fa, FS_OPENED, n, c.stream));
     return 0;
     GUARD_END
@@ -1873,6 +1928,7 @@ int kosk_fs_opened_bound_device(kosk_ctx *ctx, const uint8_t *d_tables, size_t t
     FsArgs fa{};
     fa.in = d_tables; fa.in_stride = table_stride; fa.len = NPARTY * 32; fa.out_digest = d_ch;
     fa.I = d_sel; fa.rest = d_rest; fa.sel_stride = sel_stride; fa.bind = d_bind;
+    if (c.force_n > 0) { fa.cand = c.force_d; fa.cand_n = c.force_n; } // tests: tables b < force_n take the handle's candidate lists
     HIPCHK_C(launch_fs_chain(fa, FS_OPENED, n, c.stream));
     return 0;
     GUARD_END

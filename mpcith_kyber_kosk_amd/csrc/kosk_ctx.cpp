@@ -591,6 +591,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
+    c.force_d = nullptr; c.force_h = nullptr; c.force_n = 0;
     c.staged_wiped = false;
     { // the inventory: a view owns its block of every per-proof buffer; tables and whole buffers are the arena's, private ones come later
         size_t k = 0;
@@ -1124,6 +1125,12 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     if (bound && online_only) { c.err = "an armed handle (kosk_set_contexts) cannot prove from prepared inputs: there are no public key bytes to bind"; return -1; }
     if (bound && keygen && (keygen->next || (keygen->count && keygen->count != n))) { c.err = "internal: an armed handle's call in a merged run"; return -1; }
     if (bind_check(c, n)) return -1;
+    const bool forced = c.force_n > 0; // tests: round 2 takes its candidates from the handle's lists (kosk_force_opened_candidates)
+    if (forced && (c.bind_first < 0 || c.bind_first + n > c.force_n)) {
+        c.err = "the handle holds fewer forced candidate lists than this call has proofs (kosk_force_opened_candidates)";
+        return -1;
+    }
+    if (forced && (c.use_graphs || (keygen && keygen->next))) { c.err = "internal: forced candidate lists under graph replay or in a merged run"; return -1; }
     if (bound && !keygen && c.resident_pk_n < n) { c.err = "no resident public keys to bind the proofs to"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     const Params &P = c.P;
@@ -1249,6 +1256,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         fa.in = c.d_dig2; fa.in_stride = (size_t)NPARTY * 32; fa.len = NPARTY * 32;
         fa.I = c.d_I; fa.rest = c.d_rest; fa.sel_stride = c.sel_stride;
         fa.bind = bound ? c.d_bind : nullptr;
+        if (forced) { fa.cand = c.force_d + (size_t)c.bind_first * NOPEN; fa.cand_n = n; }
         c.prof_begin(PR_FS_OPENED, n);
         HIPCHK(launch_fs_chain(fa, FS_OPENED, n, st));
         c.prof_end(PR_FS_OPENED);
@@ -1289,7 +1297,8 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     // I, its complement, and the complement entries owned by each aligned 64-party window (k_assemble_fields), all derived by
     // the worker that hashed the proof's table
     if (!c.fs_device) {
-        fs_opened_batch(n, c.h_dig2, (size_t)NPARTY * 32, c.h_I, c.h_rest, c.sel_stride, c.nthreads, c.pool, true, nullptr, bound ? c.h_bind : nullptr);
+        fs_opened_batch(n, c.h_dig2, (size_t)NPARTY * 32, c.h_I, c.h_rest, c.sel_stride, c.nthreads, c.pool, true, nullptr, bound ? c.h_bind : nullptr,
+                        forced ? c.force_h + (size_t)c.bind_first * NOPEN : nullptr, forced ? n : 0);
         c.path_n[PATH_FS_HOST]++;
     }
     t1 = now_sec(); c.phase_sec[PH_FS_OPEN] = t1 - t0; t0 = t1;

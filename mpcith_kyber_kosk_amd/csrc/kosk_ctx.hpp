@@ -143,7 +143,7 @@ struct Ctx {
     // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
     // buffers that come and go (inv_drop)
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE };
     struct InvBuf {
         const char *name;
         size_t field_off; // (size_t)-1: `abs`
@@ -370,6 +370,11 @@ struct Ctx {
     const uint8_t *bind_ctx = nullptr;
     int bind_n = 0, bind_first = 0;
     uint8_t *d_bind = nullptr, *h_bind = nullptr;
+    // tests (kosk_force_opened_candidates): while force_n > 0 round 2 of prove_resident takes the candidates of proof b from list
+    // bind_first + b -- force_d in HBM for the chain kernel, force_h for the host's round; both owned by the handle (kosk_capi.cpp).  The
+    // verifier never looks at them
+    const uint16_t *force_d = nullptr, *force_h = nullptr;
+    int force_n = 0;
     bool host_register = true;       // KOSK_REGISTER=0: staging copies only, even for buffers the caller page-locked itself.  (KOSK_REGISTER=2 of
                                      // rounds 2-4 -- the library page-locking PAGEABLE caller memory for a call -- is gone: both process aborts on
                                      // record happened inside calls that had just done that, and neither was ever reproduced or explained)

@@ -336,6 +336,10 @@ struct FsArgs {
     // kosk-bind-v1 (nullptr: the reference's transcript): [n][32] binding values, 8-byte aligned; the message hashed for proof b is its
     // table followed by bind[b].  Not with FS_DIGEST
     const uint8_t *bind;
+    // FS_OPENED, tests (kosk_force_opened_candidates; nullptr: the honest kernels): proofs b < cand_n take cand[b][0..150), every entry
+    // < NPARTY, as their candidates in place of BE16 % NPARTY of the PRF output; the hashing, the probing and the tables are the same code
+    const uint16_t *cand;
+    int cand_n;
 };
 // kosk-bind-v1: out[b] = sha3_256("kosk-bind-v1" || 00 00 00 00 || LE32(K) || sha3_256(pk[b]) || contexts[b]); nothing is written outside
 // out[0 .. 32 n).  pk records pk_stride apart, contexts and out 32 apart; every base and pk_stride multiples of 8 (else hipErrorInvalidValue)

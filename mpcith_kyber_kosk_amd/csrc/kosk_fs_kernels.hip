@@ -51,7 +51,9 @@ __device__ __forceinline__ uint2 fs_last_word(const uint8_t *tail, int rem, int 
 // BOUND (kosk-bind-v1): the 32-byte binding value of the proof follows the table in the hashed message.  The table's
 // tail is a whole number of words (1454 x 32 = 342 x 136 + 16: two words) and tail + 32 bytes stay inside the last block, so the
 // chain has the same number of permutations as the unbound one: the last block's words are the tail's, then four of B, then the padding
-template <int MODE, bool BOUND = false>
+// FORCED (tests, kosk_force_opened_candidates; FS_OPENED only): proofs b < A.cand_n read their 150 candidates from A.cand in place of the
+// squeezed bytes; everything else is the same code, and the instantiations without it are what they were
+template <int MODE, bool BOUND = false, bool FORCED = false>
 __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
 {
     __shared__ __align__(16) uint32_t st[64];       // the state's words, to be re-interleaved by other lanes
@@ -137,6 +139,9 @@ __global__ __launch_bounds__(64) void k_fs_chain(FsArgs A)
         for (int k = 0; k < 3; k++) {
             const int i = lane + 64 * k;
             c[k] = i < NOPEN ? (((uint32_t)sq[2 * i] << 8) | sq[2 * i + 1]) % (uint32_t)NPARTY : 0u;
+            if constexpr (FORCED) {
+                if (b < A.cand_n && i < NOPEN) c[k] = A.cand[(size_t)b * NOPEN + i]; // (launch_fs_chain's callers: every entry < NPARTY)
+            }
         }
         for (int p = lane; p < NPARTY; p += 64) pos[p] = 0xFFFF;
         wave_lds_handoff();
@@ -300,12 +305,17 @@ hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st)
 {
     if (n <= 0) return hipSuccess;
     if (mode < FS_DIGEST || mode > FS_CHECK) return hipErrorInvalidValue;
+    const bool forced = A.cand && A.cand_n > 0;
+    if (forced && mode != FS_OPENED) return hipErrorInvalidValue;
     if (A.bind) { // kosk-bind-v1: the bound instantiations (the unbound ones below are what they were)
         const int rem = A.len % 136;
         if (mode == FS_DIGEST || rem % 8 || rem + 32 >= 136 || (reinterpret_cast<uintptr_t>(A.bind) & 7)) return hipErrorInvalidValue;
         switch (mode) {
         case FS_ALPHA: hipLaunchKernelGGL((k_fs_chain<FS_ALPHA, true>), dim3(n), dim3(64), 0, st, A); break;
-        case FS_OPENED: hipLaunchKernelGGL((k_fs_chain<FS_OPENED, true>), dim3(n), dim3(64), 0, st, A); break;
+        case FS_OPENED:
+            if (forced) hipLaunchKernelGGL((k_fs_chain<FS_OPENED, true, true>), dim3(n), dim3(64), 0, st, A);
+            else hipLaunchKernelGGL((k_fs_chain<FS_OPENED, true>), dim3(n), dim3(64), 0, st, A);
+            break;
         default: hipLaunchKernelGGL((k_fs_chain<FS_CHECK, true>), dim3(n), dim3(64), 0, st, A); break;
         }
         return hipGetLastError();
@@ -313,7 +323,10 @@ hipError_t launch_fs_chain(const FsArgs &A, int mode, int n, hipStream_t st)
     switch (mode) {
     case FS_DIGEST: hipLaunchKernelGGL(k_fs_chain<FS_DIGEST>, dim3(n), dim3(64), 0, st, A); break;
     case FS_ALPHA: hipLaunchKernelGGL(k_fs_chain<FS_ALPHA>, dim3(n), dim3(64), 0, st, A); break;
-    case FS_OPENED: hipLaunchKernelGGL(k_fs_chain<FS_OPENED>, dim3(n), dim3(64), 0, st, A); break;
+    case FS_OPENED:
+        if (forced) hipLaunchKernelGGL((k_fs_chain<FS_OPENED, false, true>), dim3(n), dim3(64), 0, st, A);
+        else hipLaunchKernelGGL(k_fs_chain<FS_OPENED>, dim3(n), dim3(64), 0, st, A);
+        break;
     default: hipLaunchKernelGGL(k_fs_chain<FS_CHECK>, dim3(n), dim3(64), 0, st, A); break;
     }
     return hipGetLastError();

@@ -529,15 +529,13 @@ void fs_alpha_batch(const Params &P, int n, const uint8_t *digs, size_t dig_stri
     sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep, bind);
 }
 
-static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t rest[NREST])
+void opened_from_candidates(const uint16_t cand[NOPEN], uint16_t I[NOPEN], uint16_t rest[NREST])
 {
-    uint8_t I_[2 * NOPEN];
-    shake256_prf(I_, sizeof I_, ch, 1);
     bool used[NPARTY] = {false};
     for (int i = 0; i < NOPEN; i++) {
         // first candidate, then the reference's "+inc, rescan" probing: the smallest
         // inc >= 0 such that (I[i] + inc) % N is not among I[0..i)
-        int v = ((I_[2 * i] << 8) | I_[2 * i + 1]) % NPARTY;
+        int v = cand[i];
         while (used[v]) v = (v + 1) % NPARTY;
         used[v] = true;
         I[i] = (uint16_t)v;
@@ -546,27 +544,41 @@ static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t res
         if (!used[p]) rest[j++] = (uint16_t)p;
 }
 
+static void opened_from_ch(const uint8_t ch[32], uint16_t I[NOPEN], uint16_t rest[NREST])
+{
+    uint8_t I_[2 * NOPEN];
+    shake256_prf(I_, sizeof I_, ch, 1);
+    uint16_t cand[NOPEN];
+    for (int i = 0; i < NOPEN; i++) cand[i] = (uint16_t)(((I_[2 * i] << 8) | I_[2 * i + 1]) % NPARTY);
+    opened_from_candidates(cand, I, rest);
+}
+
+void opened_derived_tables(uint16_t *Ib, const uint16_t rb[NREST])
+{
+    // complement entries owned by each aligned 64-party window (k_assemble_fields), stored behind the list I
+    uint16_t *win = Ib + SEL_WIN;
+    for (int w = 0, j = 0; w <= NWIN; w++) {
+        while (j < NREST && rb[j] < 64 * w) j++;
+        win[w] = (uint16_t)j;
+    }
+    // the opened parties ascending and where each sits in I (the grouped image kernel writes an opened party's records
+    // from the window its column lies in)
+    uint16_t pos[NPARTY];
+    for (int p = 0; p < NPARTY; p++) pos[p] = 0xFFFF;
+    for (int i = 0; i < NOPEN; i++) pos[Ib[i]] = (uint16_t)i;
+    for (int p = 0, k = 0; p < NPARTY; p++)
+        if (pos[p] != 0xFFFF) { Ib[SEL_OSORT + k] = (uint16_t)p; Ib[SEL_OPOS + k] = pos[p]; k++; }
+}
+
 void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I, uint16_t *rest, size_t sel_stride, int nthreads, Pool *pool,
-                     bool windows, const std::function<void(int)> *prep, const uint8_t *bind)
+                     bool windows, const std::function<void(int)> *prep, const uint8_t *bind, const uint16_t *cand, int cand_n)
 {
     std::vector<uint8_t> h((size_t)n * 32);
     const std::function<void(int)> derive = [&](int b) {
         uint16_t *Ib = I + (size_t)b * sel_stride, *rb = rest + (size_t)b * sel_stride;
-        opened_from_ch(&h[(size_t)b * 32], Ib, rb);
-        if (windows) { // complement entries owned by each aligned 64-party window (k_assemble_fields), stored behind the list I
-            uint16_t *win = Ib + SEL_WIN;
-            for (int w = 0, j = 0; w <= NWIN; w++) {
-                while (j < NREST && rb[j] < 64 * w) j++;
-                win[w] = (uint16_t)j;
-            }
-            // the opened parties ascending and where each sits in I (the grouped image kernel writes an opened party's records
-            // from the window its column lies in)
-            uint16_t pos[NPARTY];
-            for (int p = 0; p < NPARTY; p++) pos[p] = 0xFFFF;
-            for (int i = 0; i < NOPEN; i++) pos[Ib[i]] = (uint16_t)i;
-            for (int p = 0, k = 0; p < NPARTY; p++)
-                if (pos[p] != 0xFFFF) { Ib[SEL_OSORT + k] = (uint16_t)p; Ib[SEL_OPOS + k] = pos[p]; k++; }
-        }
+        if (cand && b < cand_n) opened_from_candidates(cand + (size_t)b * NOPEN, Ib, rb);
+        else opened_from_ch(&h[(size_t)b * 32], Ib, rb);
+        if (windows) opened_derived_tables(Ib, rb);
     };
     sha3_digest_tables(n, digs, dig_stride, h.data(), nthreads, pool, &derive, prep, bind);
 }

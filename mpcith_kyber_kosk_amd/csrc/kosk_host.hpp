@@ -79,8 +79,15 @@ void assemble_digest_table(uint8_t *table, const uint16_t *I, const uint8_t *uno
 void fs_alpha_batch(const Params &P, int n, const uint8_t *digs, size_t dig_stride, uint16_t *alpha, size_t alpha_stride, int nthreads, Pool *pool = nullptr,
                     const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr /* [n][32] */);
 // windows: also write, behind each proof's list I (at I + SEL_WIN), the NWIN + 1 boundaries of the complement's aligned 64-party windows
+// cand (tests, kosk_force_opened_candidates): proofs b < cand_n take cand[b][0..150), every entry < NPARTY, in place of the candidates
+// BE16 % NPARTY of the PRF output; the table is hashed all the same
 void fs_opened_batch(int n, const uint8_t *digs, size_t dig_stride, uint16_t *I, uint16_t *rest, size_t sel_stride, int nthreads, Pool *pool = nullptr,
-                     bool windows = false, const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr /* [n][32] */);
+                     bool windows = false, const std::function<void(int)> *prep = nullptr, const uint8_t *bind = nullptr /* [n][32] */,
+                     const uint16_t *cand = nullptr /* [cand_n][NOPEN] */, int cand_n = 0);
+// what lies behind the PRF in fs_opened / fs_opened_batch: the probing of 150 candidates (each < NPARTY) into the list I and its ascending
+// complement, and the tables derived from them behind I (SEL_WIN, SEL_OSORT, SEL_OPOS of kosk_params.hpp; `Ib` is a row of >= SEL_OPOS + NOPEN entries)
+void opened_from_candidates(const uint16_t cand[NOPEN], uint16_t I[NOPEN], uint16_t rest[NREST]);
+void opened_derived_tables(uint16_t *Ib, const uint16_t rest[NREST]);
 
 // OS entropy (kyber/randombytes.c:44-57, Linux branch)
 void os_randombytes(uint8_t *out, size_t len);

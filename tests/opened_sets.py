@@ -74,3 +74,67 @@ CATALOGUE = {
 }
 
 HI_MAX = (DEG + NOPEN, DEG2 + NOPEN)  # 556, 962: every opened party below the last node
+
+
+# ---- the prover's side: from 150 candidates to the list I and the tables the wire-image kernel reads (kosk_params.hpp)
+NWIN = (NPARTY + 63) // 64                                # 23 aligned windows of 64 parties, the last one 46 wide
+SEL_WIN, SEL_OSORT, SEL_OPOS = 160, 192, 352              # where a row of the opened-list table holds win, osort, opos behind I
+SEL_ENTRIES = SEL_OPOS + NOPEN                            # 502 documented entries of a sel row; a rest row has NREST
+
+
+def probe(cand):
+    """The opened list of the candidates: entry i is (cand[i] + inc) % 1454 for the smallest inc >= 0 at which that party is not
+    among the entries before it."""
+    assert len(cand) == NOPEN and all(0 <= int(c) < NPARTY for c in cand)
+    I, taken = [], set()
+    for c in cand:
+        inc = 0
+        while (int(c) + inc) % NPARTY in taken:
+            inc += 1
+        I.append((int(c) + inc) % NPARTY)
+        taken.add(I[-1])
+    return I
+
+
+def chain_shape(cand):
+    """(longest, total, wrapped): the largest inc of an entry, the sum of all inc, and how many entries went past party 1453 to get
+    to their place."""
+    I = probe(cand)
+    inc = [(p - int(c)) % NPARTY for p, c in zip(I, cand)]
+    return max(inc), sum(inc), sum(int(c) + d >= NPARTY for c, d in zip(cand, inc))
+
+
+def tables(I):
+    """(rest, win, osort, opos) of the list I: the ascending complement (1304 parties); win[w], w = 0..23: how many unopened parties
+    lie below party 64 w; the opened parties ascending; and the position in I of each of those."""
+    rest = complement(I)
+    where = {int(p): i for i, p in enumerate(I)}
+    win = [sum(p < 64 * w for p in rest) for w in range(NWIN + 1)]
+    osort = sorted(where)
+    return rest, win, osort, [where[p] for p in osort]
+
+
+def windows(I):
+    """opened parties in each of the 23 aligned 64-party windows (nk of the wire-image kernel; cnt = the window's width - nk)"""
+    opened = set(int(p) for p in I)
+    return [sum(p in opened for p in range(w, min(w + 64, NPARTY))) for w in range(0, NPARTY, 64)]
+
+
+def sel_row(I):
+    """the documented entries of a sel row as {index: value}"""
+    _, win, osort, opos = tables(I)
+    row = {i: int(p) for i, p in enumerate(I)}
+    row.update({SEL_WIN + w: v for w, v in enumerate(win)})
+    row.update({SEL_OSORT + k: v for k, v in enumerate(osort)})
+    row.update({SEL_OPOS + k: v for k, v in enumerate(opos)})
+    return row
+
+
+# name -> 150 candidates; duplicates are what reaches the probing.  probe(CANDIDATES[name]) is the list the prover opens
+CANDIDATES = {
+    "all_1453": [1453] * 150,                                      # I = 1453, 0, 1, .., 148: entry i probes i steps, all but the first wrap
+    "zigzag": [0, 1453] * 75,                                      # I = 0, 1453, 1, 2, .., 148: chains from both ends of the party range
+    "top_then_1400": list(range(1354, 1454)) + [1400] * 50,        # 50 chains through the filled top 1400..1453 and over the wrap to 0..49
+    "tail_chain": list(range(500, 649)) + [500],                   # one chain of 149 steps in the middle, no wrap: I = 500..649
+    "pairs": [v for v in range(7, 7 + 19 * 75, 19) for _ in (0, 1)],  # 75 chains of one step; opened parties in every window
+}

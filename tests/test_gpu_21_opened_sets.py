@@ -41,14 +41,15 @@ def _oracle_verify_many(oracle, cases):
 def forced(oracle):
     """{k: {"honest": (pk, pi), "sets": {name: (pk, pi)}}}: the forced proofs, made once by the oracle (its hook is process-wide, so
     one after the other) and never changed; the oracle's verdict on every forced proof is taken here."""
+    from tests import forced_proofs  # the same proofs serve the forcing prover's tests: made once per process
     t0 = time.time()
     out = {}
     for k in (2, 3, 4):
         names = list(osets.CATALOGUE) if k == 3 else list(FEW)
-        hpk, _, hpi = oracle.verifiable_keygen(k, oracle.tape_bytes_for(k, 2100))[:3]
+        hpk, _, hpi = forced_proofs.honest(k)
         sets = {}
-        for i, name in enumerate(names):
-            pk, _, pi = oracle.forced_verifiable_keygen(k, oracle.tape_bytes_for(k, 2101 + i), osets.CATALOGUE[name])
+        for name in names:
+            pk, _, pi = forced_proofs.forced(k, name)
             sets[name] = (pk, pi)
         out[k] = {"honest": (hpk, hpi), "sets": sets}
     out["prove_seconds"] = time.time() - t0
