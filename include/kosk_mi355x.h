@@ -187,10 +187,23 @@ size_t kosk_mlwe_inst_bytes(int kyber_k);   /* sizeof(mlwe_inst)          */
 int kosk_prepare_randomness(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *rand_out);
 /* prepare_range_proof, mlwe_prover.cpp:41-59 */
 int kosk_prepare_range_proof(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *range_out);
-/* prove + encode_mpcith_proof, mlwe_prover.cpp:81-543: pi receives n proof images */
+/* prove + encode_mpcith_proof, mlwe_prover.cpp:81-543: pi receives n proof images.  What the call reads, as the reference's prove():
+ *   mpcith_randomness   share_y of f_shares[] and NTT_f_shares[] only.  f and NTT_f are NOT read (prove() computes everything from the
+ *                       shares; the opened s + r is recon_secrets_ddeg of parties 0..406, and so it is here: the packed secrets of the 2M
+ *                       rows are reconstructed on the GPU from those parties).  A caller may bank the shares and drop, zero or overwrite
+ *                       the two secret members; rows that lie on no degree-406 polynomial give the reference's bytes too.
+ *   mpcith_range_proof  share_y of every sharing.  PRECONDITION: s_eta_shares[i][j] and e_eta_shares[i][j] are valid sharings (degree
+ *                       406) of the constant j - eta1 at all 256 packed positions, as prepare_range_proof makes them, with any 151 free
+ *                       points; the struct has no secrets member to check them against, and other contents are not supported.
+ *   mlwe_inst           A (any int16 representative mod q), s and e.  t is not read.  s and e must lie in [-(q - 1), q - 1] = [-3328,
+ *                       3328]: outside it encode_to_gf3329 is not canonical and nothing downstream is defined; the call refuses (-1).
+ *   share_vec           len and share_x are implied (1454, 256 + party) and ignored.
+ * Every share_y must be canonical (< q = 3329): the call returns -1 with a text (kosk_last_error) otherwise. */
 int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t *rand_in, const uint8_t *range_in,
                         const uint8_t *tapes, size_t tape_stride, uint8_t *pi);
-/* decode_mpcith_proof + verify, mlwe_verifier.cpp:4-686, with A and t from the instance (s, e are not read) */
+/* decode_mpcith_proof + verify, mlwe_verifier.cpp:4-686, with A and t from the instance (s, e are not read).  A: any int16 representative
+ * mod q.  t: compared as the reference compares it, encode_to_gf3329(t) (q + t for t < 0, else t; nothing reduced) against the canonical
+ * t of the proof (:358), so a coefficient outside [-q, q - 1] fails check 5 whatever its residue */
 int kosk_verify_inst(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *inst, uint8_t *ok);
 
 /* Device-resident split of the two calls above, for callers that keep inputs

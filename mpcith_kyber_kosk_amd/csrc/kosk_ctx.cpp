@@ -8,7 +8,8 @@
 //                         -> view hash P16 -> [host] I P17 -> [GPU] wire image P18.
 // All linear steps act on whole evaluation-point rows (secrets included), so the
 // values the reference obtains by recon_secrets_ddeg/2ddeg are simply the x < 256
-// part of the same rows.
+// part of the same rows.  (Rows that come from a caller's structs get that part by
+// the same reconstruction first: prove_prepared, kosk_split.cpp.)
 #include "kosk_ctx.hpp"
 
 #include <atomic>

@@ -133,8 +133,14 @@ static int upload_inst(Ctx &c, int n, const uint8_t *inst, bool with_se, bool wi
         const int16_t *src = reinterpret_cast<const int16_t *>(inst + (size_t)b * ib);
         for (size_t i = 0; i < (size_t)K * K * 256; i++) A[(size_t)b * c.key_stride + i] = (int16_t)(((int)src[i] % Q + Q) % Q);
         const int16_t *ts = src + (size_t)K * K * 256, *ss = ts + (size_t)K * 256; // t, then s, e (mlwe_prover.hpp:34-37)
-        for (int i = 0; i < K * 256; i++) t[(size_t)b * K * 256 + i] = (uint16_t)(((int)ts[i] % Q + Q) % Q); // encode_to_gf3329
+        // encode_to_gf3329 as it is (q + a for a < 0, else a: nothing is reduced): the reference compares this u16 with the canonical t
+        // of the proof (mlwe_verifier.cpp:358), so a coefficient outside [-q, q - 1] fails the check whatever its residue
+        for (int i = 0; i < K * 256; i++) t[(size_t)b * K * 256 + i] = (uint16_t)(ts[i] < 0 ? Q + ts[i] : ts[i]);
         memcpy(&se[(size_t)b * c.se_stride], ss, (size_t)2 * K * 512);
+        // encode_to_gf3329 (q + a for a < 0, else a) leaves [0, q) outside [-(q - 1), q - 1], and nothing downstream is defined for that
+        if (with_se)
+            for (int i = 0; i < 2 * K * 256; i++)
+                if (ss[i] <= -Q || ss[i] >= Q) { c.err = "mlwe_inst holds an s or e coefficient outside [-(q - 1), q - 1]"; return -1; }
     }
     c.note_keys_from_inst(); // d_A (and d_t) no longer belong to the pk bytes in d_pk
     HIPCHK(hipMemcpyAsync(c.d_A, A.data(), A.size() * 2, hipMemcpyHostToDevice, c.stream));
@@ -155,21 +161,22 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
     const RowMap &rm = c.rm;
     const int M = P.M, K = P.K, E = P.E, KE = K * E;
     if (upload_inst(c, n, inst, true, false)) return -1;
-    // offline rows: secrets at x < 256, party shares at x = 256.., the rest of each row is produced by nothing else
+    // offline rows: party shares at x = 256.., the rest of each row is produced by nothing else.  The packed secrets at x < 256 of the
+    // f / NTT f rows are what recon_secrets_ddeg makes of parties 0..406 of the same rows, as in the reference's prove(), which
+    // never reads rand->f or rand->NTT_f (mlwe_prover.cpp:222-245 reconstructs s + r from the shares): they are filled on the device
+    // below, and the struct's two secret members do not cross to the GPU
     std::vector<uint16_t> rows((size_t)2 * M * RS), erows((size_t)2 * KE * RS);
     VecWiper<uint16_t> rows_gone(rows), erows_gone(erows);
     for (int b = 0; b < n; b++) {
         const uint8_t *r = rand_in + (size_t)b * randomness_bytes(P);
-        const uint8_t *rf = r, *rntt = r + (size_t)M * 512, *rfs = r + (size_t)M * 1024, *rnfs = rfs + (size_t)M * SHARE_VEC_BYTES;
+        const uint8_t *rfs = r + (size_t)M * 1024, *rnfs = rfs + (size_t)M * SHARE_VEC_BYTES; // behind f[M][256] and NTT_f[M][256]
         std::fill(rows.begin(), rows.end(), 0);
         for (int i = 0; i < M; i++) {
-            memcpy(&rows[(size_t)i * RS], rf + (size_t)i * 512, 512);
-            memcpy(&rows[(size_t)(M + i) * RS], rntt + (size_t)i * 512, 512);
             get_share_vec(&rows[(size_t)i * RS], rfs + (size_t)i * SHARE_VEC_BYTES);
             get_share_vec(&rows[(size_t)(M + i) * RS], rnfs + (size_t)i * SHARE_VEC_BYTES);
         }
         for (uint16_t v : rows)
-            if (v >= Q) { c.err = "mpcith_randomness holds a non-canonical value"; return -1; }
+            if (v >= Q) { c.err = "mpcith_randomness holds a non-canonical share value"; return -1; }
         HIPCHK(hipMemcpyAsync(c.d_P + (size_t)b * c.proof_stride + (size_t)rm.f * RS, rows.data(), rows.size() * 2, hipMemcpyHostToDevice, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
         const uint8_t *g = range_in + (size_t)b * range_proof_bytes(P);
@@ -181,9 +188,15 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
             get_share_vec(&erows[(size_t)q * RS], g + (size_t)q * SHARE_VEC_BYTES);
         }
         for (uint16_t v : erows)
-            if (v >= Q) { c.err = "mpcith_range_proof holds a non-canonical value"; return -1; }
+            if (v >= Q) { c.err = "mpcith_range_proof holds a non-canonical share value"; return -1; }
         HIPCHK(hipMemcpyAsync(c.d_P + (size_t)b * c.proof_stride + (size_t)rm.seta * RS, erows.data(), erows.size() * 2, hipMemcpyHostToDevice, c.stream));
         HIPCHK(hipStreamSynchronize(c.stream));
+    }
+    { // recon_secrets_ddeg of the 2M f / NTT f rows of every proof: columns 0..255 from the shares of parties 0..406 (ss.cpp:44-51).  The
+      // first 2M fresh rows of the tape order are exactly these rows (build_tables)
+        const GemmSrc gs{c.d_P, c.proof_stride, c.d_gemm1_rows, RS, NSEC};
+        const GemmDst gd{c.d_P, c.proof_stride, c.d_gemm1_rows, RS, 0};
+        if (gemm_modq(c, c.t_recon_d, gs, gd, 2 * M, n)) return -1;
     }
     if (fill_tape_part(c, n, false, 2 * M + 2 * KE, P.nfresh, tapes, tape_stride)) return -1;
     if (prove_resident(c, n, true)) return -1;

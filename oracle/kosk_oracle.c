@@ -593,6 +593,44 @@ const uint16_t *ko_pre_ntt_f_shares(const ko_pre *p, int i) { return p->ntt_f_sh
 const uint16_t *ko_pre_s_eta_shares(const ko_pre *p, int i, int j) { return p->s_eta_sh[i][j]; }
 const uint16_t *ko_pre_e_eta_shares(const ko_pre *p, int i, int j) { return p->e_eta_sh[i][j]; }
 
+/* test hook (no reference counterpart): the reference's two structs as byte images (include/kosk_mi355x.h: share_vec = u64 len, u16
+ * share_x[1454], u16 share_y[1454]; mpcith_randomness = f[M][256], NTT_f[M][256], f_shares[M], NTT_f_shares[M]; mpcith_range_proof =
+ * s_eta_shares[K][E], e_eta_shares[K][E]) -> ko_pre, every value as it stands (nothing is reduced).  -1 for a len other than 1454 or a
+ * share_x[p] other than 256 + p */
+#define KO_SHARE_VEC_BYTES (8 + 4 * KO_PARTIES)
+static int share_vec_from_image(uint16_t y[KO_PARTIES], const uint8_t *img)
+{
+    uint64_t len;
+    uint16_t x[KO_PARTIES];
+    memcpy(&len, img, 8);
+    memcpy(x, img + 8, 2 * KO_PARTIES);
+    if (len != KO_PARTIES) return -1;
+    for (int p = 0; p < KO_PARTIES; p++)
+        if (x[p] != KO_NSEC + p) return -1;
+    memcpy(y, img + 8 + 2 * KO_PARTIES, 2 * KO_PARTIES);
+    return 0;
+}
+
+int ko_pre_from_images(int K, ko_pre *pre, const uint8_t *rand_img, const uint8_t *range_img)
+{
+    ko_params P;
+    if (ko_get_params(K, &P) || !pre || !rand_img || !range_img) return -1;
+    const uint8_t *f = rand_img, *nf = f + (size_t)P.M * 512, *fs = nf + (size_t)P.M * 512, *nfs = fs + (size_t)P.M * KO_SHARE_VEC_BYTES;
+    for (int i = 0; i < P.M; i++) {
+        memcpy(pre->f[i], f + (size_t)i * 512, 512);
+        memcpy(pre->ntt_f[i], nf + (size_t)i * 512, 512);
+        if (share_vec_from_image(pre->f_sh[i], fs + (size_t)i * KO_SHARE_VEC_BYTES)) return -1;
+        if (share_vec_from_image(pre->ntt_f_sh[i], nfs + (size_t)i * KO_SHARE_VEC_BYTES)) return -1;
+    }
+    const uint8_t *es = range_img + (size_t)K * P.E * KO_SHARE_VEC_BYTES;
+    for (int i = 0; i < K; i++)
+        for (int j = 0; j < P.E; j++) {
+            if (share_vec_from_image(pre->s_eta_sh[i][j], range_img + (size_t)(i * P.E + j) * KO_SHARE_VEC_BYTES)) return -1;
+            if (share_vec_from_image(pre->e_eta_sh[i][j], es + (size_t)(i * P.E + j) * KO_SHARE_VEC_BYTES)) return -1;
+        }
+    return 0;
+}
+
 /* mlwe_prover.cpp:4-39 */
 void ko_prepare_randomness(int K, ko_tape *t, ko_pre *pre)
 {

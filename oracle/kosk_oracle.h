@@ -130,6 +130,11 @@ const uint16_t *ko_pre_ntt_f_shares(const ko_pre *, int i);
 const uint16_t *ko_pre_s_eta_shares(const ko_pre *, int i, int j);
 const uint16_t *ko_pre_e_eta_shares(const ko_pre *, int i, int j);
 
+/* test hook (no reference counterpart): fill a ko_pre from the byte images of the reference's mpcith_randomness and mpcith_range_proof
+ * (the bytes kosk_prove_prepared gets; layout in include/kosk_mi355x.h).  Values are copied as they are, never reduced.  Returns -1 for
+ * a share_vec whose len is not 1454 or whose share_x[p] is not 256 + p */
+int ko_pre_from_images(int K, ko_pre *pre, const uint8_t *rand_img, const uint8_t *range_img);
+
 /* optional stage outputs of prove(), for stage-level parity tests */
 typedef struct {
     uint8_t tcomm[KO_PARTIES][32];

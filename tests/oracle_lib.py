@@ -209,3 +209,49 @@ def main_order(k, tape):
     lib.ko_pre_free(pre)
     return {"rand": rand, "range": rng, "inst": mlwe_inst_bytes(k, raw), "pk": pk.raw, "sk": sk.raw, "pi": pi.raw, "verify": ok,
             "used": used}
+
+
+lib.ko_pre_from_images.argtypes = [C.c_int, C.c_void_p, C.c_char_p, C.c_char_p]
+lib.ko_verify_sites.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_void_p]
+
+
+def mlwe_from_inst_bytes(k, inst):
+    """the inverse of mlwe_inst_bytes: the reference's mlwe_inst image for KYBER_K = k -> ko_mlwe, every int16 as it stands"""
+    a = np.frombuffer(inst, dtype=np.int16)
+    assert a.size == (k * k + 3 * k) * 256
+    raw = Mlwe()
+    np.ctypeslib.as_array(raw.A).reshape(4, 4, 256)[:k, :k] = a[:k * k * 256].reshape(k, k, 256)
+    for i, f in enumerate(("t", "s", "e")):
+        np.ctypeslib.as_array(getattr(raw, f)).reshape(4, 256)[:k] = a[(k * k + i * k) * 256:(k * k + (i + 1) * k) * 256].reshape(k, 256)
+    return raw
+
+
+def pre_from_images(k, pre, rand, rng):
+    """ko_pre_from_images on an allocated ko_pre: 0, or -1 for a len other than 1454 or a share_x[p] other than 256 + p"""
+    p = params(k)
+    assert len(rand) == p.M * (1024 + 2 * 5824) and len(rng) == 2 * k * p.E * 5824
+    return lib.ko_pre_from_images(k, pre, rand, rng)
+
+
+def prove_images(k, inst, rand, rng, tape):
+    """the oracle's prove() on the three struct images kosk_prove_prepared gets (include/kosk_mi355x.h) and the online tape -> pi"""
+    p = params(k)
+    pre = lib.ko_pre_alloc()
+    try:
+        assert pre_from_images(k, pre, rand, rng) == 0
+        raw = mlwe_from_inst_bytes(k, inst)
+        t = Tape(tape, len(tape), 0, 0, 0)
+        pi = C.create_string_buffer(p.proof_bytes)
+        lib.ko_prove(k, C.byref(t), pi, C.byref(raw), pre, None)
+        assert not t.overrun
+        return pi.raw
+    finally:
+        lib.ko_pre_free(pre)
+
+
+def verify_inst_sites(k, pi, inst):
+    """ko_verify_sites with A and t of an mlwe_inst image -> (verify bit, sites), as kosk_verify_sites"""
+    raw = mlwe_from_inst_bytes(k, inst)
+    sites = (C.c_uint32 * 12)()
+    ok = lib.ko_verify_sites(k, pi, C.byref(raw), sites)
+    return bool(ok), list(sites)
