@@ -259,7 +259,8 @@ int kosk_proof_dense_unpack(int kyber_k, const uint8_t *in, uint8_t *pi);
 /* The compact calls' counterparts: n records of kosk_dense_proof_bytes(), packed on the GPU in front of the D2H copy, unpacked and
  * refilled on the GPU behind the H2D copy.  Chunking, streams, page-locked and pageable buffers, armed handles and "never merged" as
  * for the compact calls.  Packing does not check that the resident images are representable: what this library's prover leaves in
- * HBM is (the zero-witness proof at an ok[b] = 0 position of kosk_stage_prover_keys* included); use the host codec for foreign images. */
+ * HBM is (the zero-witness proof at an ok[b] = 0 position of kosk_stage_prover_keys* included); foreign images go through
+ * kosk_transcode_batch below, which checks. */
 int kosk_verifiable_keygen_batch_dense(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out);
 int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
                                               uint8_t *out);
@@ -270,6 +271,38 @@ int kosk_stage_verifier_inputs_dense(kosk_ctx *ctx, int n, const uint8_t *in, co
  * image_stride >= kosk_proof_bytes).  d_status (device memory, n x uint32): 0, or 1 for a malformed I, in which case image b is not
  * written.  Nothing outside rows 407..1303 of the seven listed fields is changed.  Runs on the handle's own stream, synchronised on return. */
 int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+
+/* ---- Transcoding between the three wire formats on the GPU: image <-> compact <-> dense, n >= 1 records per call
+ * (chunked by max_batch), for a party that stores, forwards or translates proofs and holds no keys.  `in` is n consecutive records of
+ * kosk_format_bytes(k, from), `out` n consecutive records of kosk_format_bytes(k, to); each of the two is host memory (pageable or
+ * page-locked) or device memory of ANY alignment, told apart per pointer as the KEM calls do (the library copies into its own aligned
+ * workspace); they must not overlap.  `status` is host memory, n entries.  from == to is refused.
+ * The contract is the composition of the host codecs, per record b:
+ *   1. decode `from` into an image: compact kosk_proof_decompress; dense kosk_proof_dense_unpack (result 1: a malformed I, rows 407..1303
+ *      of the listed fields left zero); an image decodes to itself;
+ *   2. encode that image into `to`: compact kosk_proof_compress (-1: a value >= 4096); dense kosk_proof_dense_pack (-1 or -2, with the host
+ *      code's precedence: -1 concerns STORED values only and wins over -2; a value >= 4096 in a dropped row is -2, not -1); an image
+ *      encodes to itself;
+ *   3. status[b] = the encoder's result if it is nonzero, otherwise the decoder's.
+ * For status[b] >= 0 (status 1 included) `out` record b is byte for byte what the host codecs produce; for status[b] < 0 it is all zero
+ * (the host codecs leave it unspecified; this call defines it).  Other positions are unaffected.
+ * Returns 0 when it ran, whatever the statuses are; -1 with a kosk_last_error text, nothing started, for NULL arguments, n < 1, a bad
+ * format, from == to or overlapping buffers.
+ * The call touches none of the prover's, verifier's or KEM's resident state: kosk_fetch_proofs*, kosk_resident_proofs,
+ * kosk_verify_resident_pk(pk == NULL) and kosk_kem_enc_verified behave after it as before it.  Its workspace (max_batch images, the
+ * records of both sides, two status words per record) is allocated at the handle's first such call and filed in the buffer inventory as
+ * PUBLIC buffers: kosk_secret_scan sees them, kosk_wipe_secrets leaves them, kosk_destroy frees them.  It brings no secret onto the
+ * handle and is not one of the entry points that wipe under KOSK_WIPE_CALL.  It runs unmerged on a cohort member, and with streams > 1
+ * on sub-batch 0's stream. */
+enum { KOSK_FMT_IMAGE = 0, KOSK_FMT_COMPACT = 1, KOSK_FMT_DENSE = 2 };
+size_t kosk_format_bytes(int kyber_k, int fmt);      /* kosk_proof_bytes / kosk_compact_proof_bytes / kosk_dense_proof_bytes; 0 for a bad k or fmt */
+int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status);
+/* kernel level: the codeword check alone on n >= 1 images in the caller's HBM (alignment rules of kosk_dense_fill_device; -1 and a text
+ * otherwise).  Strictly read-only on the images.  d_status[b] (device memory, n x uint32): 0; 1 a malformed I; 2 some u16 in rows
+ * 407..1303 of a listed field differs from the refill of rows 0..406 -- the refill is canonical, so a congruent value v + q in a dropped
+ * row is a difference.  It says nothing about values >= 4096 in kept rows (the pack kernel's overflow word does).  Runs on the handle's
+ * own stream, synchronised on return. */
+int kosk_dense_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_t image_stride, uint32_t *d_status);
 
 /* ---- Kyber KEM on the keys this library makes and vouches for: crypto_kem_enc_derand / crypto_kem_enc / crypto_kem_dec
  * (kyber/kem.c:76-96, :113-121, :140-169; indcpa_enc / indcpa_dec, kyber/indcpa.c:264-336), bit-exact, for kyber_k 2 / 3 / 4, n items
@@ -394,7 +427,8 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * 17 launches of k_keyseed (kosk-keyseed-v1: seeds derived from the sk records in HBM),
  * 18 launches of k_wipe (kosk_wipe_secrets, the wipe at the end of a call under KOSK_WIPE_CALL, kosk_wipe_device),
  * 19 launches of k_kem_key_setup (one per kosk_kem_key_set), 20 kem_enc_key / 21 kem_dec_key: launch groups of kosk_kem_enc_key /
- * kosk_kem_dec_key (ids 12 / 13 do not move for them). */
+ * kosk_kem_dec_key (ids 12 / 13 do not move for them),
+ * 22 launches of k_dense_check (the codeword check: one per chunk of kosk_transcode_batch to dense or kosk_dense_check_device sub-batch). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -194,6 +194,14 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_opened_tables")):
         sig.update(forced)
+    # transcoding between the wire formats; optional under the same rule (and only then)
+    transcode = {
+        "kosk_format_bytes": (sz, [C.c_int, C.c_int]),
+        "kosk_transcode_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+        "kosk_dense_check_device": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_transcode_batch")):
+        sig.update(transcode)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -227,7 +235,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_keyseed_value", "kosk_keyseed_device", "kosk_stage_prover_keys_derived", "kosk_prove_keys_derived_batch",
            "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing",
            "kosk_kem_key_set", "kosk_kem_key_state", "kosk_kem_key_clear", "kosk_kem_enc_key", "kosk_kem_dec_key",
-           "kosk_force_opened_candidates", "kosk_opened_tables"]
+           "kosk_force_opened_candidates", "kosk_opened_tables",
+           "kosk_format_bytes", "kosk_transcode_batch", "kosk_dense_check_device"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -246,6 +255,7 @@ SS_BYTES = 32  # KOSK_SS_BYTES
 KEYPAIR_COIN_BYTES = 64  # d || z of crypto_kem_keypair_derand
 KEYCHK_HASH, KEYCHK_PK_RANGE, KEYCHK_S_RANGE = 1, 2, 4  # KOSK_KEYCHK_*
 KEM_KEY_NONE, KEM_KEY_PK, KEM_KEY_SK = 0, 1, 2  # KOSK_KEM_KEY_*
+FMT_IMAGE, FMT_COMPACT, FMT_DENSE = 0, 1, 2  # KOSK_FMT_*
 
 
 def options(**fields):
@@ -264,6 +274,7 @@ def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
 def ct_bytes(k): return lib.kosk_ct_bytes(k)
 def dense_proof_bytes(k): return lib.kosk_dense_proof_bytes(k)
+def format_bytes(k, fmt): return lib.kosk_format_bytes(k, fmt)
 
 
 def dense_pack(k, pi):
@@ -693,6 +704,30 @@ class Kosk:
         """kernel level: refill rows 407..1303 of the seven low-degree fields of n images in HBM, in place (int device pointers)"""
         self._chk(lib.kosk_dense_fill_device(self._h, n, d_images, image_stride, d_status), "dense_fill_device")
 
+    def dense_check_device(self, n, d_images, image_stride, d_status):
+        """kernel level: the codeword check on n images in HBM, read only (int device pointers); d_status[b] 0, 1 malformed I, 2 a row
+        407..1303 of a listed field that is not the refill of rows 0..406"""
+        self._chk(lib.kosk_dense_check_device(self._h, n, d_images, image_stride, d_status), "dense_check_device")
+
+    def transcode(self, records, from_fmt, to_fmt, n=None, out=None):
+        """kosk_transcode_batch: records of format from_fmt into format to_fmt (FMT_IMAGE / FMT_COMPACT / FMT_DENSE) -> (statuses, records).
+        records: a list of bytes; or an int pointer (host or device memory, any alignment) to n consecutive records, with out an int
+        pointer to room for n records of to_fmt -- then (statuses, None).  A record with a negative status is all zero."""
+        ib, ob = lib.kosk_format_bytes(self.k, from_fmt), lib.kosk_format_bytes(self.k, to_fmt)
+        if isinstance(records, int):
+            if n is None or out is None:
+                raise KoskError("transcode: a pointer needs n and out")
+            st = (C.c_int32 * n)()
+            self._chk(lib.kosk_transcode_batch(self._h, n, from_fmt, records, to_fmt, out, st), "transcode")
+            return list(st), None
+        n = len(records)
+        if any(len(r) != ib for r in records):
+            raise KoskError("transcode: records of kosk_format_bytes(k, from_fmt)")
+        st = (C.c_int32 * max(n, 1))()
+        buf = C.create_string_buffer(max(ob * n, 1))
+        self._chk(lib.kosk_transcode_batch(self._h, n, from_fmt, C.c_char_p(b"".join(records)), to_fmt, buf, st), "transcode")
+        return list(st)[:n], _cut(buf, ob, n)
+
     # second-level entry points (reference structs as bytes; see include/kosk_mi355x.h)
     def stage_verifier_inputs(self, pis, pks):
         """proof images and public keys into HBM for verify_resident (kosk_stage_verifier_inputs)"""
@@ -1061,6 +1096,7 @@ class Kosk:
     PATH_KEM_KEY_SETUP = 19
     PATH_KEM_ENC_KEY = 20
     PATH_KEM_DEC_KEY = 21
+    PATH_DENSE_CHECK = 22
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -1216,6 +1216,44 @@ int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image
     return dense_fill_device(*ctx->c, n, d_images, image_stride, d_status);
     GUARD_END
 }
+int kosk_dense_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    if (!ctx || n < 1 || !d_images || !d_status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return dense_fill_device(*ctx->c, n, const_cast<uint8_t *>(d_images), image_stride, d_status, true); // the check kernel takes them const
+    GUARD_END
+}
+
+// ---- transcoding between the wire formats (kosk_compact.hip: transcode) -----------------------------------------------------------
+static_assert((int)KOSK_FMT_IMAGE == (int)FMT_IMAGE && (int)KOSK_FMT_COMPACT == (int)FMT_COMPACT && (int)KOSK_FMT_DENSE == (int)FMT_DENSE, "kosk_mi355x.h and kosk_ctx.hpp");
+size_t kosk_format_bytes(int k, int fmt)
+{
+    return fmt == KOSK_FMT_IMAGE ? kosk_proof_bytes(k) : fmt == KOSK_FMT_COMPACT ? kosk_compact_proof_bytes(k) : fmt == KOSK_FMT_DENSE ? kosk_dense_proof_bytes(k) : 0;
+}
+// unmerged, on sub-context 0 (the handle's own stream), chunks of its batch size; brings no secret onto the handle (no wipe under KOSK_WIPE_CALL)
+int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status)
+{
+    if (!ctx) return -1;
+    auto refuse = [&](const char *why) { ctx->clear_err(); ctx->err = std::string("kosk_transcode_batch: ") + why; ctx->c->err = ctx->err; return -1; };
+    if (!in || !out || !status) return refuse("null pointer");
+    if (n < 1) return refuse("n must be at least 1");
+    const size_t ib = kosk_format_bytes(ctx->c->P.K, from), ob = kosk_format_bytes(ctx->c->P.K, to);
+    if (!ib || !ob) return refuse("unknown format (KOSK_FMT_IMAGE, KOSK_FMT_COMPACT, KOSK_FMT_DENSE)");
+    if (from == to) return refuse("from and to are the same format");
+    const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
+    if (i0 < o0 + (size_t)n * ob && o0 < i0 + (size_t)n * ib) return refuse("in and out overlap");
+    GUARD(ctx)
+    ctx->clear_err();
+    Ctx &c = *ctx->c;
+    for (int done = 0; done < n;) {
+        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
+        if (transcode(c, m, from, in + (size_t)done * ib, to, out + (size_t)done * ob, status + done)) { ctx->err = c.err; return -1; }
+        done += m;
+    }
+    return 0;
+    GUARD_END
+}
 
 int kosk_verify_fail_masks(const kosk_ctx *ctx, uint32_t *masks, int n)
 {

@@ -227,4 +227,116 @@ int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_
     return 0;
 }
 
+// ---- transcoding between the three wire formats (kosk_transcode_batch) ----------------------------------------
+// Its own workspace, so that nothing resident moves: own_batch 16-byte-aligned images, the records of either side, two status words per
+// proof (the refill's / check's, the pack kernel's overflow flag) and their page-locked mirror.  All public: proofs are
+struct TcWs {
+    uint8_t *d_img = nullptr, *d_in = nullptr, *d_out = nullptr;
+    uint32_t *d_words = nullptr, *h_words = nullptr; // [2][own_batch]: dense status, then overflow
+};
+
+void transcode_release(Ctx &c)
+{
+    TcWs *w = c.tc;
+    if (!w) return;
+    for (void *p : {(void *)w->d_img, (void *)w->d_in, (void *)w->d_out, (void *)w->d_words})
+        if (p) (void)hipFree(p);
+    if (w->h_words) (void)hipHostFree(w->h_words);
+    delete w;
+    c.tc = nullptr;
+    c.inv_drop(Ctx::INVG_TRANSCODE);
+}
+
+static int transcode_ensure(Ctx &c)
+{
+    if (c.tc) return 0;
+    if (!c.cplan.bytes) { // the plans and strides of ensure_compact, without its buffers
+        c.cplan = make_compact_plan(c.P);
+        c.compact_stride = (c.cplan.bytes + 63) / 64 * 64;
+        c.dplan = make_dense_plan(c.P);
+        c.dense_stride = (c.dplan.bytes + 63) / 64 * 64;
+    }
+    TcWs *w = new TcWs();
+    c.tc = w;
+    const size_t N = (size_t)c.own_batch;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_img), N * c.image_stride));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_in), N * c.compact_stride));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_out), N * c.compact_stride));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_words), 2 * N * sizeof(uint32_t)));
+        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&w->h_words), 2 * N * sizeof(uint32_t), hipHostMallocDefault));
+        return 0;
+    };
+    if (body()) { transcode_release(c); return -1; }
+    const int G = Ctx::INVG_TRANSCODE;
+    c.reg_buf("tc.d_img", &w->d_img, N * c.image_stride, 0, G);
+    c.reg_buf("tc.d_in", &w->d_in, N * c.compact_stride, 0, G);
+    c.reg_buf("tc.d_out", &w->d_out, N * c.compact_stride, 0, G);
+    c.reg_buf("tc.d_words", &w->d_words, 2 * N * sizeof(uint32_t), 0, G);
+    c.reg_buf("tc.h_words", &w->h_words, 2 * N * sizeof(uint32_t), Ctx::INV_HOST, G);
+    return 0;
+}
+
+// records whose encoder failed (overflow flag, or with use_st a nonzero dense status) become all zero; stride is a multiple of 16
+__global__ __launch_bounds__(256) void k_zero_failed(uint8_t *__restrict__ out, size_t stride, const uint32_t *__restrict__ st,
+                                                     const uint32_t *__restrict__ bad, int use_st)
+{
+    const int b = blockIdx.y;
+    if (!(bad[b] | (use_st ? st[b] : 0u))) return; // public: a uniform branch
+    uint4 *p = reinterpret_cast<uint4 *>(out + (size_t)b * stride);
+    for (size_t i = blockIdx.x * 256 + threadIdx.x; i < stride / 16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0, 0, 0, 0);
+}
+
+// n <= own_batch records `from` -> `to` (FMT_*), in / out host (pageable or page-locked) or device memory of any alignment, status on the
+// host: the composition of the host codecs per record (kosk_mi355x.h).  On the context's stream, synchronised
+int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status)
+{
+    if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    if (transcode_ensure(c)) return -1;
+    if ((from == FMT_DENSE || to == FMT_DENSE) && ensure_dense_ws(c)) return -1;
+    const Params &P = c.P;
+    TcWs &w = *c.tc;
+    uint32_t *d_st = w.d_words, *d_bad = w.d_words + c.own_batch;
+    auto plan_of = [&](int fmt) -> const CompactPlan & { return fmt == FMT_DENSE ? c.dplan : c.cplan; };
+    auto stride_of = [&](int fmt) { return fmt == FMT_IMAGE ? c.image_stride : fmt == FMT_DENSE ? c.dense_stride : c.compact_stride; };
+    auto bytes_of = [&](int fmt) { return fmt == FMT_IMAGE ? P.proof_bytes : plan_of(fmt).bytes; };
+    HIPCHK(hipMemsetAsync(w.d_words, 0, 2 * (size_t)c.own_batch * sizeof(uint32_t), c.stream));
+    // in
+    uint8_t *d_src = from == FMT_IMAGE ? w.d_img : w.d_in;
+    HIPCHK(hipMemcpy2DAsync(d_src, stride_of(from), in, bytes_of(from), bytes_of(from), n, is_device_pointer(in) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    if (from != FMT_IMAGE) {
+        const CompactPlan &plan = plan_of(from);
+        if (from == FMT_DENSE) // the dropped rows start as zero and stay so under a malformed I (status 1)
+            for (int f = 0; f < NFIELDS; f++)
+                if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
+                    HIPCHK(hipMemset2DAsync(w.d_img + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
+        hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, w.d_in, stride_of(from), w.d_img, c.image_stride, plan);
+        HIPCHK(hipGetLastError());
+        if (from == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st)) return -1;
+    }
+    // out
+    const uint8_t *d_dst = w.d_img;
+    if (to != FMT_IMAGE) {
+        if (to == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st, true)) return -1;
+        HIPCHK(hipMemsetAsync(w.d_out, 0, (size_t)n * stride_of(to), c.stream)); // padding bytes are zero
+        hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, w.d_img, c.image_stride, w.d_out, stride_of(to), plan_of(to), d_bad);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(k_zero_failed, dim3(8, n), dim3(256), 0, c.stream, w.d_out, stride_of(to), d_st, d_bad, to == FMT_DENSE ? 1 : 0);
+        HIPCHK(hipGetLastError());
+        d_dst = w.d_out;
+    }
+    HIPCHK(hipMemcpy2DAsync(out, bytes_of(to), d_dst, stride_of(to), bytes_of(to), n, is_device_pointer(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpyAsync(w.h_words, w.d_words, 2 * (size_t)c.own_batch * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1;
+    const uint32_t *st = w.h_words, *bad = w.h_words + c.own_batch;
+    for (int b = 0; b < n; b++) {
+        const int32_t dec = from == FMT_DENSE ? (int32_t)st[b] : 0; // the decoder's: 1 a malformed I
+        const int32_t enc = to == FMT_IMAGE ? 0 : bad[b] ? -1 : (to == FMT_DENSE && st[b]) ? -2 : 0;
+        status[b] = enc ? enc : dec;
+    }
+    return 0;
+}
+
 } // namespace kosk

@@ -62,6 +62,7 @@ Ctx::~Ctx()
             if (e) (void)hipEventDestroy(e);
     if (ev_sync) (void)hipEventDestroy(ev_sync);
     kem_release(*this);
+    transcode_release(*this);
     kem_key_release(*this);
     witness_release(*this);
     if (is_view) {
@@ -588,6 +589,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.resident_pk_n = 0;
     c.keys_from_pk_n = 0;
     c.kem = nullptr;
+    c.tc = nullptr;
     c.kem_key = nullptr;
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;

@@ -73,7 +73,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
-              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_COUNT };
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -115,6 +115,7 @@ CompactPlan make_dense_plan(const Params &P);
 int dense_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a stored value >= 4096; -2: malformed I, or a dropped row that is not the refill
 int dense_decode(const Params &P, const uint8_t *in, uint8_t *img);  // 0, or 1: malformed I (rows 407..1303 of the seven fields left zero)
 
+struct TcWs;  // HBM workspace of kosk_transcode_batch (kosk_compact.hip)
 struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
 struct KemKey; // the resident key of the one-key KEM calls (kosk_kem_kernels.hip)
 enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
@@ -143,7 +144,7 @@ struct Ctx {
     // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
     // buffers that come and go (inv_drop)
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE };
     struct InvBuf {
         const char *name;
         size_t field_off; // (size_t)-1: `abs`
@@ -325,6 +326,7 @@ struct Ctx {
     size_t dense_stride = 0;
     uint16_t *d_dense_ws = nullptr;
     uint32_t *d_dense_status = nullptr;
+    TcWs *tc = nullptr; // kosk_transcode_batch: allocated at this context's first such call, owned by it like `kem`
 
     // pinned host staging
     uint8_t *h_tape = nullptr, *h_dig = nullptr, *h_dig2 = nullptr, *h_proof = nullptr; // h_dig / h_dig2: the host's copies of the two digest tables
@@ -538,8 +540,15 @@ int ensure_verify_workspace(Ctx &c);
 int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct = false, bool dense = false);
 int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct = false, bool dense = false);
 int ensure_dense_ws(Ctx &c);
-int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status); // n <= own_batch, on c.stream, not synchronised
-int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+// check = true: the codeword check (k_dense_check): the refill compared with the images' own rows 407..1303 instead of stored, the images only read
+// (the pointer is not const because the fill shares the signature); d_status 0, 1 malformed I, 2 a dropped row that is not the refill
+int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false); // n <= own_batch, on c.stream, not synchronised
+int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false);
+// transcoding between the wire formats (kosk_compact.hip): n <= own_batch records, `in` / `out` host or device memory of any alignment,
+// status[b] (host) the host codecs' composition (kosk_mi355x.h); touches nothing but its own workspace and the refill's scratch.  Synchronised
+enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality)
+int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status);
+void transcode_release(Ctx &c);
 // registered: `pi` is page-locked host memory (hipHostRegister): copied to directly, no staging
 int fetch_proofs(Ctx &c, int n, uint8_t *pi, bool registered = false);
 

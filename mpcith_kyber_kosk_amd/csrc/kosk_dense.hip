@@ -10,9 +10,12 @@
 // inverses and the weighted shares of one column group in LDS and hands both to the Cauchy-product engine it shares with
 // k_interp_apply (kosk_cauchy_dev.hpp: operand fragments built in registers, int8-limb MFMA k-steps); its own are the column
 // groups, the 64-row staging and the stores.  Every global store is 16 bytes.
+// k_dense_check (DESIGN.md "Transcoding between the wire formats") is the same body with the other epilogue: the refilled chunks are
+// compared with the image's own instead of stored, which is the representability check of the host codec's pack.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "kosk_ctx.hpp"
@@ -230,12 +233,19 @@ struct DenseFragsLds {
 // bytes behind the last whole chunk to the next pass.  The first chunk is completed with the kept bytes in front of the range
 // and the last one with the bytes behind it (the next field's kept rows), both read from the image and written back as they
 // are: no other workgroup writes those bytes.
-template <int NT>
-__device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, const DenseFillGroup &g, const uint16_t *tab_s, const uint16_t *rest_s,
+// CHECK (k_dense_check, the codeword check of kosk_transcode_batch): the same product with the other epilogue.  Where the fill stores a
+// chunk the check loads it from the image and compares; any difference ends as bit 1 of the proof's status word.  The carry and tail
+// bytes come from the image in both, so they compare equal and only a filled row can differ.  The image is read only.
+template <bool CHECK> using dense_img_t = std::conditional_t<CHECK, const uint8_t, uint8_t>;
+template <bool CHECK> using dense_status_t = std::conditional_t<CHECK, uint32_t, const uint32_t>;
+
+template <int NT, bool CHECK>
+__device__ __forceinline__ void dense_fill_body(dense_img_t<CHECK> *__restrict__ imgb, const DenseFillGroup &g, const uint16_t *tab_s, const uint16_t *rest_s,
                                                 const uint16_t *ell_s, const uint8_t *y_s, uint8_t *stage_s, const uint32_t *cstart_s,
-                                                const uint16_t *ccols_s, const uint16_t *ccf_s, const uint16_t *csb_s)
+                                                const uint16_t *ccols_s, const uint16_t *ccf_s, const uint16_t *csb_s, dense_status_t<CHECK> *status_b)
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    uint32_t differs = 0; // CHECK: OR of image chunk ^ recomputed chunk over this thread's chunks
     uint16_t *stage16 = reinterpret_cast<uint16_t *>(stage_s);
 #pragma unroll 1
     for (int it = 0; it < DN_ITERS; it++) {
@@ -282,8 +292,15 @@ __device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, cons
             const uint32_t cols = g.f[f].cols, pos = g.f[f].start + (uint32_t)it * 128u * cols, carry = pos & 15u;
             const uint32_t total = carry + (uint32_t)rows * cols * 2u, sb = csb_s[g.f[f].col0];
             const uint32_t nfull = it == DN_ITERS - 1 ? (total + 15u) >> 4 : total >> 4;
-            for (uint32_t k = tid; k < nfull; k += 256)
-                *reinterpret_cast<uint4 *>(imgb + (pos - carry) + 16 * k) = *reinterpret_cast<const uint4 *>(stage_s + sb + 16 * k);
+            for (uint32_t k = tid; k < nfull; k += 256) {
+                const uint4 mine = *reinterpret_cast<const uint4 *>(stage_s + sb + 16 * k);
+                if constexpr (CHECK) {
+                    const uint4 theirs = *reinterpret_cast<const uint4 *>(imgb + (pos - carry) + 16 * k);
+                    differs |= (mine.x ^ theirs.x) | (mine.y ^ theirs.y) | (mine.z ^ theirs.z) | (mine.w ^ theirs.w);
+                } else {
+                    *reinterpret_cast<uint4 *>(imgb + (pos - carry) + 16 * k) = mine;
+                }
+            }
             // the bytes behind the last whole chunk (bit 16: this thread's pair is one of them)
             if (2u * tid < (total & 15u) && it < DN_ITERS - 1) keep[f] = stage16[(sb + 16 * nfull) / 2 + tid] | 0x10000u;
         }
@@ -295,10 +312,13 @@ __device__ __forceinline__ void dense_fill_body(uint8_t *__restrict__ imgb, cons
         }
         // the next pass writes behind its carry, i.e. behind these bytes; its flush comes after the next barrier
     }
+    if constexpr (CHECK)
+        if (differs) atomicOr(status_b, 2u); // images are public, and so is what the check says about them
 }
 
-__global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, size_t image_stride, DenseFillArgs A, const uint16_t *__restrict__ ws,
-                                                    const uint32_t *__restrict__ status)
+template <bool CHECK>
+__device__ __forceinline__ void dense_fill_kernel(dense_img_t<CHECK> *__restrict__ img, size_t image_stride, const DenseFillArgs &A,
+                                                  const uint16_t *__restrict__ ws, dense_status_t<CHECK> *__restrict__ status)
 {
     __shared__ __attribute__((aligned(16))) uint8_t y_s[DN_KS * DN_NTMAX * 2048];
     __shared__ __attribute__((aligned(16))) uint8_t stage_s[DN_STAGE];
@@ -308,9 +328,10 @@ __global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, s
     __shared__ uint32_t cstart_s[DN_NTMAX * 16];
     __shared__ uint16_t ccols_s[DN_NTMAX * 16], ccf_s[DN_NTMAX * 16], csb_s[DN_NTMAX * 16];
     const int tid = threadIdx.x, b = blockIdx.y;
-    if (status[b]) return; // malformed opened list: nothing is written
+    // malformed opened list: nothing is written (the check looks at bit 0 only: bit 1 is its own, set by a workgroup that is done)
+    if (CHECK ? (status[b] & 1u) != 0 : status[b] != 0) return;
     const DenseFillGroup &g = A.g[blockIdx.x];
-    uint8_t *imgb = img + (size_t)b * image_stride;
+    dense_img_t<CHECK> *imgb = img + (size_t)b * image_stride;
     const uint16_t *wsb = ws + (size_t)b * DN_WS;
     const int nt = (g.ncols + 15) >> 4;
 
@@ -349,9 +370,21 @@ __global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, s
                 reinterpret_cast<uint16_t *>(stage_s)[csb_s[g.f[f].col0] / 2 + tid] = *reinterpret_cast<const uint16_t *>(imgb + (g.f[f].start - carry) + 2 * tid);
         }
     __syncthreads();
-    if (nt == 5) dense_fill_body<5>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
-    else if (nt == 4) dense_fill_body<4>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
-    else dense_fill_body<3>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s);
+    if (nt == 5) dense_fill_body<5, CHECK>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s, status + b);
+    else if (nt == 4) dense_fill_body<4, CHECK>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s, status + b);
+    else dense_fill_body<3, CHECK>(imgb, g, tab_s, rest_s, ell_s, y_s, stage_s, cstart_s, ccols_s, ccf_s, csb_s, status + b);
+}
+
+__global__ __launch_bounds__(256) void k_dense_fill(uint8_t *__restrict__ img, size_t image_stride, DenseFillArgs A, const uint16_t *__restrict__ ws,
+                                                    const uint32_t *__restrict__ status)
+{
+    dense_fill_kernel<false>(img, image_stride, A, ws, status);
+}
+// d_status[b]: 0, 1 (k_dense_setup: malformed I) or 2 (a u16 of rows 407..1303 of a listed field is not the refill of rows 0..406)
+__global__ __launch_bounds__(256) void k_dense_check(const uint8_t *__restrict__ img, size_t image_stride, DenseFillArgs A, const uint16_t *__restrict__ ws,
+                                                     uint32_t *__restrict__ status)
+{
+    dense_fill_kernel<true>(img, image_stride, A, ws, status);
 }
 
 static DenseFillArgs make_fill_args(const Params &P)
@@ -381,28 +414,30 @@ int ensure_dense_ws(Ctx &c)
     return 0;
 }
 
-// rows 407..1303 of the seven fields of n <= own_batch images in HBM, in place, on the context's stream (no synchronisation)
-int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+// rows 407..1303 of the seven fields of n <= own_batch images in HBM, in place, on the context's stream (no synchronisation);
+// check: compared with what is there instead of stored (d_status 0 / 1 / 2, the images are only read)
+int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check)
 {
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
-    if ((reinterpret_cast<uintptr_t>(d_images) | image_stride) & 15) { c.err = "dense fill: images and their stride must be 16-byte aligned"; return -1; }
-    if (image_stride < c.P.proof_bytes) { c.err = "dense fill: image stride below kosk_proof_bytes"; return -1; }
+    if ((reinterpret_cast<uintptr_t>(d_images) | image_stride) & 15) { c.err = check ? "dense check: images and their stride must be 16-byte aligned" : "dense fill: images and their stride must be 16-byte aligned"; return -1; }
+    if (image_stride < c.P.proof_bytes) { c.err = check ? "dense check: image stride below kosk_proof_bytes" : "dense fill: image stride below kosk_proof_bytes"; return -1; }
     if (ensure_dense_ws(c)) return -1;
     const DenseFillArgs a = make_fill_args(c.P);
     hipLaunchKernelGGL(k_dense_setup, dim3(6, n), dim3(256), 0, c.stream, d_images, image_stride, (uint32_t)c.P.off[F_I], c.d_dense_ws, d_status);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_dense_fill, dim3(DN_NGROUPS, n), dim3(256), 0, c.stream, d_images, image_stride, a, c.d_dense_ws, d_status);
+    if (check) hipLaunchKernelGGL(k_dense_check, dim3(DN_NGROUPS, n), dim3(256), 0, c.stream, d_images, image_stride, a, c.d_dense_ws, d_status);
+    else hipLaunchKernelGGL(k_dense_fill, dim3(DN_NGROUPS, n), dim3(256), 0, c.stream, d_images, image_stride, a, c.d_dense_ws, d_status);
     HIPCHK(hipGetLastError());
-    c.path_n[PATH_DENSE_FILL]++;
+    c.path_n[check ? PATH_DENSE_CHECK : PATH_DENSE_FILL]++;
     return 0;
 }
 
-int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check)
 {
     HIPCHK(hipSetDevice(c.device));
     for (int done = 0; done < n;) {
         const int m = n - done < c.own_batch ? n - done : c.own_batch;
-        if (dense_fill_launch(c, m, d_images + (size_t)done * image_stride, image_stride, d_status + done)) return -1;
+        if (dense_fill_launch(c, m, d_images + (size_t)done * image_stride, image_stride, d_status + done, check)) return -1;
         done += m;
     }
     HIPCHK(stream_sync(c));
