@@ -54,8 +54,9 @@ int kosk_create(kosk_ctx **ctx, int device, int kyber_k, int max_batch);
 /* ---- Per-handle options (round 6).  The reference has no run-time configuration at all (kosk.hpp:18-24 takes pointers, nothing
  * else); what a HOST must decide per handle -- how its calls are batched, what the verifier accepts, where the Fiat-Shamir rounds
  * run, how its threads wait -- is this struct, not the process environment.  kosk_options_init() fills in "not given" for every
- * field (the library's defaults apply); kosk_create_ex() with opt == NULL is kosk_create().  Fields the caller sets win over the
- * environment variables of the same name, which kosk_create() still honours. */
+ * field (the library's defaults apply); kosk_create_ex() with opt == NULL is kosk_create().  The environment variables of the same
+ * names that earlier rounds read at kosk_create() (KOSK_STREAMS, KOSK_COMBINE, KOSK_FS_DEVICE, ...) are no longer read by either call;
+ * only debug knobs remain in the environment. */
 enum { KOSK_FS_HOST = 0, KOSK_FS_DEVICE = 1 };
 typedef struct kosk_options {
     uint32_t size;              /* sizeof(kosk_options) as the caller compiled it (set by kosk_options_init) */

@@ -420,7 +420,7 @@ class Kosk:
 
     def __init__(self, kyber_k=2, max_batch=1, device=0, entropy=None, **opts):
         """opts: fields of kosk_options (streams, combine, strict_encoding, fs_mode, host_threads, blocking_sync, ...): the handle is
-        then created with kosk_create_ex; without any, with kosk_create (library defaults and the KOSK_* environment).
+        then created with kosk_create_ex; without any, with kosk_create (library defaults; no KOSK_* variable stands in for an option).
         entropy: ENTROPY_TAPE / ENTROPY_SEED, handed to set_entropy() once the handle exists (a setter, not an options field)"""
         self.k = kyber_k
         self.max_batch = max_batch
@@ -599,106 +599,82 @@ class Kosk:
         sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
         self._chk(lib.kosk_tape_expand_device(self._h, n, sp, ss, d_tapes, tape_stride), "tape_expand_device")
 
-    def verifiable_keygen_compact(self, tapes=None, n=None, seeds=None, seed_stride=None):
-        """verifiable_keygen with the proofs in the compact wire format (kosk_verifiable_keygen_[seeded_]batch_compact)"""
-        cb = lib.kosk_compact_proof_bytes(self.k)
+    # ---- the three wire formats (FMT_IMAGE / FMT_COMPACT / FMT_DENSE): one body per operation, the library's functions by format ----
+    # format -> (suffix of the public names, size function, then the library's keygen, seeded keygen, verify, fetch and stage functions)
+    _FMT = {fmt: (sfx, size) + tuple(name + sfx for name in ("kosk_verifiable_keygen_batch", "kosk_verifiable_keygen_seeded_batch", "kosk_verify_batch",
+                                                              "kosk_fetch_proofs", "kosk_stage_verifier_inputs"))
+            for fmt, sfx, size in ((FMT_IMAGE, "", "kosk_proof_bytes"), (FMT_COMPACT, "_compact", "kosk_compact_proof_bytes"),
+                                   (FMT_DENSE, "_dense", "kosk_dense_proof_bytes"))}
+    _KEYGEN, _KEYGEN_SEEDED, _VERIFY, _FETCH, _STAGE = 2, 3, 4, 5, 6
+
+    def _fmt(self, fmt, op):
+        """(suffix, record size, the library's function for `op`) of a format"""
+        row = self._FMT[fmt]
+        return row[0], getattr(lib, row[1])(self.k), getattr(lib, row[op])
+
+    def _keygen(self, fmt, tapes, n, seeds, seed_stride):
         if seeds is not None:
-            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
-            fn, tp, stride = lib.kosk_verifiable_keygen_seeded_batch_compact, sp, ss
+            tp, stride, n, _keep = self._seed_arg(seeds, n, seed_stride)
         elif tapes is not None:
-            n = len(tapes)
-            fn, tp, stride = lib.kosk_verifiable_keygen_batch_compact, C.c_char_p(b"".join(t[:self.tape_bytes] for t in tapes)), self.tape_bytes
+            n, stride = len(tapes), self.tape_bytes
+            if any(len(t) < stride for t in tapes):
+                raise KoskError("tape shorter than kosk_tape_bytes")
+            tp = C.c_char_p(b"".join(t[:stride] for t in tapes))
         else:
-            n = 1 if n is None else n
-            fn, tp, stride = lib.kosk_verifiable_keygen_batch_compact, None, 0
+            n, stride, tp = 1 if n is None else n, 0, None
+        sfx, size, fn = self._fmt(fmt, self._KEYGEN if seeds is None else self._KEYGEN_SEEDED)
         pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
-        out = C.create_string_buffer(cb * n)
-        self._chk(fn(self._h, n, tp, stride, pk, sk, out), "verifiable_keygen_compact")
-        cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
-        return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(out, cb)
+        out = C.create_string_buffer(size * n)
+        self._chk(fn(self._h, n, tp, stride, pk, sk, out), "verifiable_keygen" + sfx)
+        return _cut(pk, self.pk_bytes, n), _cut(sk, self.sk_bytes, n), _cut(out, size, n)
+
+    def _verify(self, fmt, recs, pks):
+        sfx, _size, fn = self._fmt(fmt, self._VERIFY)
+        n = len(recs)
+        ok = C.create_string_buffer(n)
+        self._chk(fn(self._h, n, C.c_char_p(b"".join(recs)), C.c_char_p(b"".join(pks)), ok), "verify" + sfx)
+        return [b == 1 for b in ok.raw]
+
+    def _fetch(self, fmt, n):
+        sfx, size, fn = self._fmt(fmt, self._FETCH)
+        out = C.create_string_buffer(size * n)
+        self._chk(fn(self._h, n, out), "fetch_proofs" + sfx)
+        return _cut(out, size, n)
+
+    def _stage(self, fmt, recs, pks):
+        sfx, _size, fn = self._fmt(fmt, self._STAGE)
+        self._chk(fn(self._h, len(recs), b"".join(recs), b"".join(pks)), "stage_verifier_inputs" + sfx)
 
     def verifiable_keygen(self, tapes=None, n=None, seeds=None, seed_stride=None):
         """tapes: list of bytes (one randomness tape per instance) or None (callback / OS entropy).
         seeds (instead of tapes): seeded proving, see _seed_arg."""
-        if seeds is not None:
-            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
-            pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
-            pi = C.create_string_buffer(self.proof_bytes * n)
-            self._chk(lib.kosk_verifiable_keygen_seeded_batch(self._h, n, sp, ss, pk, sk, pi), "verifiable_keygen")
-            cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
-            return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(pi, self.proof_bytes)
-        if tapes is not None:
-            n = len(tapes)
-            stride = self.tape_bytes
-            blob = b"".join(t[:stride].ljust(stride, b"\0") for t in tapes)
-            for t in tapes:
-                if len(t) < stride:
-                    raise KoskError("tape shorter than kosk_tape_bytes")
-            tp = C.c_char_p(blob)
-        else:
-            if n is None:
-                n = 1
-            stride, tp = 0, None
-        pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
-        pi = C.create_string_buffer(self.proof_bytes * n)
-        self._chk(lib.kosk_verifiable_keygen_batch(self._h, n, tp, stride, pk, sk, pi), "verifiable_keygen")
-        cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
-        return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(pi, self.proof_bytes)
+        return self._keygen(FMT_IMAGE, tapes, n, seeds, seed_stride)
 
-    def verify(self, pis, pks):
-        n = len(pis)
-        ok = C.create_string_buffer(n)
-        self._chk(lib.kosk_verify_batch(self._h, n, C.c_char_p(b"".join(pis)), C.c_char_p(b"".join(pks)), ok), "verify")
-        return [b == 1 for b in ok.raw]
+    def verifiable_keygen_compact(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """verifiable_keygen with the proofs in the compact wire format (kosk_verifiable_keygen_[seeded_]batch_compact)"""
+        return self._keygen(FMT_COMPACT, tapes, n, seeds, seed_stride)
+
+    def verifiable_keygen_dense(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """verifiable_keygen with the proofs in the dense wire format kosk-dense-v1 (kosk_verifiable_keygen_[seeded_]batch_dense)"""
+        return self._keygen(FMT_DENSE, tapes, n, seeds, seed_stride)
+
+    def verify(self, pis, pks): return self._verify(FMT_IMAGE, pis, pks)
+    def verify_dense(self, recs, pks): return self._verify(FMT_DENSE, recs, pks)
+    def fetch_proofs(self, n): return self._fetch(FMT_IMAGE, n)
+    def fetch_proofs_compact(self, n): return self._fetch(FMT_COMPACT, n)
+    def fetch_proofs_dense(self, n): return self._fetch(FMT_DENSE, n)
+
+    def stage_verifier_inputs(self, pis, pks):
+        """proof images and public keys into HBM for verify_resident (kosk_stage_verifier_inputs)"""
+        self._stage(FMT_IMAGE, pis, pks)
+
+    def stage_verifier_inputs_compact(self, blobs, pks): self._stage(FMT_COMPACT, blobs, pks)
+    def stage_verifier_inputs_dense(self, recs, pks): self._stage(FMT_DENSE, recs, pks)
 
     def fail_masks(self, n):
         m = (C.c_uint32 * n)()
         self._chk(lib.kosk_verify_fail_masks(self._h, m, n), "fail_masks")
         return list(m)
-
-    # compact wire format
-    def fetch_proofs_compact(self, n):
-        size = lib.kosk_compact_proof_bytes(self.k)
-        out = C.create_string_buffer(size * n)
-        self._chk(lib.kosk_fetch_proofs_compact(self._h, n, out), "fetch_proofs_compact")
-        return [out.raw[i * size:(i + 1) * size] for i in range(n)]
-
-    def stage_verifier_inputs_compact(self, blobs, pks):
-        self._chk(lib.kosk_stage_verifier_inputs_compact(self._h, len(blobs), b"".join(blobs), b"".join(pks)), "stage_verifier_inputs_compact")
-
-    # dense wire format (kosk-dense-v1): the compact surface again
-    def verifiable_keygen_dense(self, tapes=None, n=None, seeds=None, seed_stride=None):
-        """verifiable_keygen with the proofs in the dense wire format (kosk_verifiable_keygen_[seeded_]batch_dense)"""
-        cb = lib.kosk_dense_proof_bytes(self.k)
-        if seeds is not None:
-            sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
-            fn, tp, stride = lib.kosk_verifiable_keygen_seeded_batch_dense, sp, ss
-        elif tapes is not None:
-            n = len(tapes)
-            fn, tp, stride = lib.kosk_verifiable_keygen_batch_dense, C.c_char_p(b"".join(t[:self.tape_bytes] for t in tapes)), self.tape_bytes
-        else:
-            n = 1 if n is None else n
-            fn, tp, stride = lib.kosk_verifiable_keygen_batch_dense, None, 0
-        pk = C.create_string_buffer(self.pk_bytes * n); sk = C.create_string_buffer(self.sk_bytes * n)
-        out = C.create_string_buffer(cb * n)
-        self._chk(fn(self._h, n, tp, stride, pk, sk, out), "verifiable_keygen_dense")
-        cut = lambda b, s: [b.raw[i * s:(i + 1) * s] for i in range(n)]
-        return cut(pk, self.pk_bytes), cut(sk, self.sk_bytes), cut(out, cb)
-
-    def verify_dense(self, recs, pks):
-        n = len(recs)
-        ok = C.create_string_buffer(n)
-        self._chk(lib.kosk_verify_batch_dense(self._h, n, C.c_char_p(b"".join(recs)), C.c_char_p(b"".join(pks)), ok), "verify_dense")
-        return [b == 1 for b in ok.raw]
-
-    def fetch_proofs_dense(self, n):
-        size = lib.kosk_dense_proof_bytes(self.k)
-        out = C.create_string_buffer(size * n)
-        self._chk(lib.kosk_fetch_proofs_dense(self._h, n, out), "fetch_proofs_dense")
-        return [out.raw[i * size:(i + 1) * size] for i in range(n)]
-
-    def stage_verifier_inputs_dense(self, recs, pks):
-        self._chk(lib.kosk_stage_verifier_inputs_dense(self._h, len(recs), b"".join(recs), b"".join(pks)), "stage_verifier_inputs_dense")
 
     def dense_fill_device(self, n, d_images, image_stride, d_status):
         """kernel level: refill rows 407..1303 of the seven low-degree fields of n images in HBM, in place (int device pointers)"""
@@ -729,10 +705,6 @@ class Kosk:
         return list(st)[:n], _cut(buf, ob, n)
 
     # second-level entry points (reference structs as bytes; see include/kosk_mi355x.h)
-    def stage_verifier_inputs(self, pis, pks):
-        """proof images and public keys into HBM for verify_resident (kosk_stage_verifier_inputs)"""
-        self._chk(lib.kosk_stage_verifier_inputs(self._h, len(pis), b"".join(pis), b"".join(pks)), "stage_verifier_inputs")
-
     def prepare_randomness(self, tapes=None, n=None):
         n = len(tapes) if tapes is not None else n
         size = lib.kosk_randomness_bytes(self.k)
@@ -784,11 +756,6 @@ class Kosk:
         ok = C.create_string_buffer(n)
         self._chk(lib.kosk_verify_resident(self._h, n, ok), "verify_resident")
         return [b == 1 for b in ok.raw]
-
-    def fetch_proofs(self, n):
-        pi = C.create_string_buffer(self.proof_bytes * n)
-        self._chk(lib.kosk_fetch_proofs(self._h, n, pi), "fetch_proofs")
-        return [pi.raw[i * self.proof_bytes:(i + 1) * self.proof_bytes] for i in range(n)]
 
     def verifiable_keygen_resident(self, tapes=None, n=None, tape_stride=None, seeds=None, seed_stride=None):
         """kyber_verifiable_keygen as one resident call: key generation + prove, pk/sk returned, proofs stay in HBM.

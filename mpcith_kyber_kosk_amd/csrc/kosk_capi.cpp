@@ -211,17 +211,28 @@ static int wiped_call(kosk_ctx *h, F &&body)
 #define WGUARD(ctx) return guard(ctx, __func__, [&]() -> int { return wiped_call(ctx, [&]() -> int {
 #define WGUARD_END }); });
 
-// argument validation failed: the call has done nothing; kosk_last_error(ctx) says which entry point refused
+// The one way a call is refused with a message: it has done nothing, and kosk_last_error(ctx) says "<fn>: <why>" (fn == nullptr: `why` alone)
+static int refuse(kosk_ctx *ctx, const char *fn, const char *why)
+{
+    ctx->clear_err();
+    ctx->err = fn ? std::string(fn) + ": " + why : std::string(why);
+    ctx->c->err = ctx->err;
+    return -1;
+}
+// argument validation failed
 static int bad_args(const kosk_ctx *, const char *) { return -1; } // read-only entry points leave the error string alone
 static int bad_args(kosk_ctx *ctx, const char *fn)
 {
-    if (ctx) {
-        ctx->clear_err();
-        ctx->err = std::string(fn) + ": invalid argument (null pointer, batch size out of range, or unsupported for this context)";
-        ctx->c->err = ctx->err;
-    }
-    return -1;
+    return ctx ? refuse(ctx, fn, "invalid argument (null pointer, batch size out of range, or unsupported for this context)") : -1;
 }
+// refusals that several entry points share (after bad_args, in this order: armed, stride)
+static const char *const WHY_ARMED = "the handle is armed with fewer contexts than this call has proofs (kosk_set_contexts)"; // the call is refused whole
+static const char *const WHY_NO_PK_TO_BIND = "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind";
+static const char *const WHY_SEED_STRIDE = "seed_stride is smaller than one seed (KOSK_SEED_BYTES)";
+static const char *const WHY_TAPE_STRIDE = "tape_stride is smaller than one tape (kosk_tape_bytes)";
+static const char *const WHY_SALT_STRIDE = "salt_stride is smaller than one salt (32 bytes)";
+#define ARMED_CHECK(ctx, n) \
+    if ((ctx)->armed && (n) > (ctx)->armed) return refuse(ctx, __func__, WHY_ARMED)
 
 // Batches larger than a sub-context: the chunks (of a sub-context's capacity each) are dealt round-robin to the S
 // sub-contexts, which work through theirs concurrently on the handle's lane threads.  With KOSK_STREAMS >= 2 one chunk's
@@ -235,6 +246,16 @@ static int run_chunks(kosk_ctx *h, int n, F &&fn)
     std::vector<std::function<int()>> jobs;
     deal_chunks((int)h->sub.size(), h->sub[0]->own_batch, n, on_lane, jobs); // own_batch: a cohort member's max_batch spans its neighbours' blocks
     return h->run_lanes(jobs);
+}
+// A call of any n on sub-context 0 alone (the handle's own stream, unmerged), its batch size at a time: fn(c, first, count)
+template <typename F>
+static int serial_chunks(kosk_ctx *h, int n, F &&fn)
+{
+    h->clear_err();
+    Ctx &c = *h->c;
+    for (int first = 0; first < n; first += c.own_batch)
+        if (fn(c, first, std::min(n - first, c.own_batch))) return -1;
+    return 0;
 }
 
 // [p, p + bytes) is page-locked host memory already (kosk_host_alloc, hipHostMalloc, hipHostRegister by the caller): the
@@ -254,6 +275,8 @@ static bool span_is_pinned(const void *p, size_t bytes)
     if (!a0.devicePointer || !a1.devicePointer) return false;
     return static_cast<const uint8_t *>(a1.devicePointer) - static_cast<const uint8_t *>(a0.devicePointer) == (ptrdiff_t)(bytes - 1);
 }
+// records go straight to / from a buffer the CALLER page-locked (KOSK_REGISTER=0: never), else through the pinned staging buffers
+static bool copy_direct(const kosk_ctx *ctx, const void *p, size_t bytes) { return ctx->c->host_register && span_is_pinned(p, bytes); }
 
 // draw n proofs' worth of randomness through the (stateful) callback / OS entropy, sequentially in proof order and in the
 // reference's call order and lengths (kosk.cpp:12, mlwe_prover.cpp:9, ss.cpp:5)
@@ -302,6 +325,11 @@ struct RandSrc {
         r.seeded = true;
         return r;
     }
+    // the tape-taking entry point, or its *_seeded twin
+    static RandSrc of(const kosk_ctx *ctx, bool seeded_call, const uint8_t *rand, size_t stride)
+    {
+        return seeded_call ? from_seeds(rand, stride) : from_tapes(ctx, rand, stride);
+    }
     // draw_tapes_too: false leaves a NULL tape pointer alone (the callee draws inside a single sub-context's call)
     void resolve(const kosk_ctx *ctx, int n, bool draw_tapes_too = true)
     {
@@ -324,29 +352,11 @@ struct RandSrc {
         return kg;
     }
 };
-// an armed handle (kosk_set_contexts): a call of more proofs than contexts, or one that has no public key bytes to bind, is refused whole
-static int armed_refuse(kosk_ctx *ctx, const char *fn, const char *why)
-{
-    ctx->clear_err();
-    ctx->err = std::string(fn) + ": " + why;
-    ctx->c->err = ctx->err;
-    return -1;
-}
-#define ARMED_CHECK(ctx, n) \
-    if ((ctx)->armed && (n) > (ctx)->armed) return armed_refuse(ctx, __func__, "the handle is armed with fewer contexts than this call has proofs (kosk_set_contexts)")
 // proofs [first, first + count) of the caller's call on sub-context c: position b of the call uses context b
 static int prove_at(Ctx &c, int first, int count, const KeygenIn *kg = nullptr)
 {
     c.bind_first = first;
     return prove_resident(c, count, false, kg);
-}
-// seeded entry points: seed_stride below one seed fails the call before anything is started
-static int bad_seed_stride(kosk_ctx *ctx, const char *fn)
-{
-    ctx->clear_err();
-    ctx->err = std::string(fn) + ": seed_stride is smaller than one seed (KOSK_SEED_BYTES)";
-    ctx->c->err = ctx->err;
-    return -1;
 }
 
 static thread_local std::string g_create_err; // error text of the last failed kosk_create on this thread
@@ -516,8 +526,8 @@ int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t cont
     GUARD(ctx)
     ctx->clear_err();
     if (n == 0) { ctx->disarm(); return 0; }
-    if (n < 0 || !contexts) return armed_refuse(ctx, __func__, "n contexts need n >= 1 and a pointer (n = 0 disarms)");
-    if (context_stride < 32) return armed_refuse(ctx, __func__, "context_stride is smaller than one context (32 bytes)");
+    if (n < 0 || !contexts) return refuse(ctx, __func__, "n contexts need n >= 1 and a pointer (n = 0 disarms)");
+    if (context_stride < 32) return refuse(ctx, __func__, "context_stride is smaller than one context (32 bytes)");
     Ctx &c = *ctx->c;
     HIPCHK_C(hipSetDevice(c.device));
     uint8_t *d = nullptr;
@@ -540,12 +550,12 @@ int kosk_force_opened_candidates(kosk_ctx *ctx, int n, const uint16_t *cand)
     GUARD(ctx)
     ctx->clear_err();
     if (!cand) { ctx->unforce(); return 0; }
-    if (n < 1 || n > KOSK_FORCE_MAX_LISTS) return armed_refuse(ctx, __func__, "n lists need 1 <= n <= KOSK_FORCE_MAX_LISTS (cand == NULL clears)");
+    if (n < 1 || n > KOSK_FORCE_MAX_LISTS) return refuse(ctx, __func__, "n lists need 1 <= n <= KOSK_FORCE_MAX_LISTS (cand == NULL clears)");
     for (size_t i = 0; i < (size_t)n * NOPEN; i++)
-        if (cand[i] >= NPARTY) return armed_refuse(ctx, __func__, "a candidate is not a party (every entry must be below 1454)");
+        if (cand[i] >= NPARTY) return refuse(ctx, __func__, "a candidate is not a party (every entry must be below 1454)");
     Ctx &c = *ctx->c;
-    if (c.use_graphs) return armed_refuse(ctx, __func__, "not on a handle that replays captured graphs (KOSK_GRAPHS=1): their kernel arguments are frozen");
-    if (ctx->cohort) return armed_refuse(ctx, __func__, "not on a cohort member (combine): its proofs may run in another member's call");
+    if (c.use_graphs) return refuse(ctx, __func__, "not on a handle that replays captured graphs (KOSK_GRAPHS=1): their kernel arguments are frozen");
+    if (ctx->cohort) return refuse(ctx, __func__, "not on a cohort member (combine): its proofs may run in another member's call");
     HIPCHK_C(hipSetDevice(c.device));
     std::vector<uint16_t> h(cand, cand + (size_t)n * NOPEN);
     uint16_t *d = nullptr;
@@ -581,31 +591,50 @@ int kosk_set_entropy(kosk_ctx *ctx, int mode)
     return 0;
 }
 
-static int stage_prover_inputs_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk)
+// The tape-taking entry points and their *_seeded twins differ in one stride check and in the RandSrc they make: one body per pair, with
+// the entry point's name for the messages.  `rand`: tapes or seeds
+static int stage_prover_inputs_src(kosk_ctx *ctx, const char *fn, int n, bool seeded, const uint8_t *rand, size_t stride, uint8_t *pk, uint8_t *sk)
 {
-    const Params &P = ctx->c->P;
-    src.resolve(ctx, n); // the randombytes callback is stateful: draw everything sequentially, then stage in parallel
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg = src.part(P, first, pk, sk);
-        return stage_prover_inputs(c, count, kg.tapes, kg.tape_stride, kg.pk, kg.sk, kg.seeds, kg.seed_stride);
+    if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, fn);
+    if (seeded && rand && stride < SEED_BYTES) return refuse(ctx, fn, WHY_SEED_STRIDE);
+    return guard(ctx, fn, [&]() -> int {
+        const Params &P = ctx->c->P;
+        RandSrc src = RandSrc::of(ctx, seeded, rand, stride);
+        src.resolve(ctx, n); // the randombytes callback is stateful: draw everything sequentially, then stage in parallel
+        return ctx->run(n, [&](Ctx &c, int first, int count) {
+            const KeygenIn kg = src.part(P, first, pk, sk);
+            return stage_prover_inputs(c, count, kg.tapes, kg.tape_stride, kg.pk, kg.sk, kg.seeds, kg.seed_stride);
+        });
+    });
+}
+// The resident fetch / stage calls in wire format `fmt`.  (The image calls have always refused n = 0 and the packed ones taken it as
+// nothing to do; the table of every entry point's checks is in DESIGN.md 31)
+static int fetch_fmt(kosk_ctx *ctx, const char *fn, int n, int fmt, uint8_t *out)
+{
+    if (!ctx || n < (fmt == FMT_IMAGE ? 1 : 0) || n > ctx->max_batch || !out) return bad_args(ctx, fn);
+    return guard(ctx, fn, [&]() -> int {
+        const size_t rb = format_bytes(ctx->c->P, fmt);
+        return ctx->run(n, [&](Ctx &c, int first, int count) { return fetch_proofs(c, count, fmt, out + (size_t)first * rb); });
+    });
+}
+static int stage_fmt(kosk_ctx *ctx, const char *fn, int n, int fmt, const uint8_t *in, const uint8_t *pk)
+{
+    if (!ctx || n < (fmt == FMT_IMAGE ? 1 : 0) || n > ctx->max_batch || !in || !pk) return bad_args(ctx, fn);
+    return guard(ctx, fn, [&]() -> int {
+        const Params &P = ctx->c->P;
+        const size_t rb = format_bytes(P, fmt);
+        return ctx->run(n, [&](Ctx &c, int first, int count) {
+            return stage_verifier_inputs(c, count, fmt, in + (size_t)first * rb, pk + (size_t)first * P.pk_bytes);
+        });
     });
 }
 int kosk_stage_prover_inputs(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
 {
-    if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return stage_prover_inputs_from(ctx, n, src, pk, sk);
-    GUARD_END
+    return stage_prover_inputs_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk);
 }
 int kosk_stage_prover_inputs_seeded(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
 {
-    if (!ctx || n < 1 || n > ctx->max_batch) return bad_args(ctx, __func__);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    GUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return stage_prover_inputs_from(ctx, n, src, pk, sk);
-    GUARD_END
+    return stage_prover_inputs_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk);
 }
 int kosk_prove_resident(kosk_ctx *ctx, int n)
 {
@@ -615,24 +644,12 @@ int kosk_prove_resident(kosk_ctx *ctx, int n)
     return ctx->run(n, [&](Ctx &c, int first, int count) { return prove_at(c, first, count); });
     WGUARD_END
 }
-int kosk_fetch_proofs(kosk_ctx *ctx, int n, uint8_t *pi)
-{
-    if (!ctx || n < 1 || n > ctx->max_batch || !pi) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const Params &P = ctx->c->P;
-    return ctx->run(n, [&](Ctx &c, int first, int count) { return fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes); });
-    GUARD_END
-}
-int kosk_stage_verifier_inputs(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk)
-{
-    if (!ctx || n < 1 || n > ctx->max_batch || !pi || !pk) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const Params &P = ctx->c->P;
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        return stage_verifier_inputs(c, count, pi + (size_t)first * P.proof_bytes, pk + (size_t)first * P.pk_bytes);
-    });
-    GUARD_END
-}
+int kosk_fetch_proofs(kosk_ctx *ctx, int n, uint8_t *pi) { return fetch_fmt(ctx, __func__, n, FMT_IMAGE, pi); }
+int kosk_fetch_proofs_compact(kosk_ctx *ctx, int n, uint8_t *out) { return fetch_fmt(ctx, __func__, n, FMT_COMPACT, out); }
+int kosk_fetch_proofs_dense(kosk_ctx *ctx, int n, uint8_t *out) { return fetch_fmt(ctx, __func__, n, FMT_DENSE, out); }
+int kosk_stage_verifier_inputs(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk) { return stage_fmt(ctx, __func__, n, FMT_IMAGE, pi, pk); }
+int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk) { return stage_fmt(ctx, __func__, n, FMT_COMPACT, in, pk); }
+int kosk_stage_verifier_inputs_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk) { return stage_fmt(ctx, __func__, n, FMT_DENSE, in, pk); }
 
 // verify `count` resident proofs of sub-context c and file their fail masks at the caller's proof index `first`
 static int verify_into(kosk_ctx *ctx, Ctx &c, int first, int count, uint8_t *ok, int pk_mode, const uint8_t *pk)
@@ -724,11 +741,7 @@ static int combined_keygen(kosk_ctx *h, int n, const KeygenCall &call)
     Cohort &co = *h->cohort;
     h->clear_err();
     // a caller's bad arguments fail THAT caller, here, not the run it would have joined (and every innocent member of it)
-    if (call.tapes && call.tape_stride < h->c->P.tape_bytes) {
-        h->err = "tape_stride is smaller than one proof's tape (kosk_tape_bytes)";
-        h->c->err = h->err;
-        return -1;
-    }
+    if (call.tapes && call.tape_stride < h->c->P.tape_bytes) return refuse(h, nullptr, "tape_stride is smaller than one proof's tape (kosk_tape_bytes)");
     CombineReq r;
     // the stateful randombytes callback is per handle: a call that draws whole tapes through it runs alone (a seeded call's seeds were
     // drawn by its own caller before it got here, and the entropy source is not part of what makes calls mergeable)
@@ -777,11 +790,8 @@ static int combined_verify(kosk_ctx *h, int n, const VerifyCall &call)
     Cohort &co = *h->cohort;
     h->clear_err();
     h->masks_n = 0;
-    if (!call.pk && h->c->resident_pk_n < n) {
-        h->err = "no resident public keys for this batch: pk == NULL needs a key generation (or a verifier staging call) of at least n proofs on this context";
-        h->c->err = h->err;
-        return -1;
-    }
+    if (!call.pk && h->c->resident_pk_n < n)
+        return refuse(h, nullptr, "no resident public keys for this batch: pk == NULL needs a key generation (or a verifier staging call) of at least n proofs on this context");
     CombineReq r;
     r.kind = call.pk ? CK_VERIFY_PK_GIVEN : CK_VERIFY_PK_RESIDENT;
     if (h->hooks_unmerged && h->c->round_hook) r.kind = CK_ALONE;
@@ -830,41 +840,36 @@ static int combined_verify(kosk_ctx *h, int n, const VerifyCall &call)
     return rc;
 }
 
-static int keygen_resident_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk)
+static int keygen_resident_src(kosk_ctx *ctx, const char *fn, int n, bool seeded, const uint8_t *rand, size_t stride, uint8_t *pk, uint8_t *sk)
 {
-    // stateful callback: seeds are drawn here, on the caller's own thread and in proof order, whatever serves the call afterwards; whole
-    // tapes only where the sub-batches of the call run in parallel (one sub-context draws its own inside its call)
-    src.resolve(ctx, n, !ctx->cohort && ctx->sub.size() > 1);
-    if (ctx->cohort) return combined_keygen(ctx, n, KeygenCall{src.tapes, src.tape_stride, pk, sk, src.seeds, src.seed_stride});
-    const Params &P = ctx->c->P;
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg = src.part(P, first, pk, sk);
-        return prove_at(c, first, count, &kg);
-    });
+    if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, fn);
+    if (ctx->armed && n > ctx->armed) return refuse(ctx, fn, WHY_ARMED);
+    if (seeded && rand && stride < SEED_BYTES) return refuse(ctx, fn, WHY_SEED_STRIDE);
+    return guard(ctx, fn, [&]() -> int { return wiped_call(ctx, [&]() -> int {
+        RandSrc src = RandSrc::of(ctx, seeded, rand, stride);
+        // stateful callback: seeds are drawn here, on the caller's own thread and in proof order, whatever serves the call afterwards; whole
+        // tapes only where the sub-batches of the call run in parallel (one sub-context draws its own inside its call)
+        src.resolve(ctx, n, !ctx->cohort && ctx->sub.size() > 1);
+        if (ctx->cohort) return combined_keygen(ctx, n, KeygenCall{src.tapes, src.tape_stride, pk, sk, src.seeds, src.seed_stride});
+        const Params &P = ctx->c->P;
+        return ctx->run(n, [&](Ctx &c, int first, int count) {
+            const KeygenIn kg = src.part(P, first, pk, sk);
+            return prove_at(c, first, count, &kg);
+        });
+    }); });
 }
 int kosk_verifiable_keygen_resident(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk)
 {
-    if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return keygen_resident_from(ctx, n, src, pk, sk);
-    WGUARD_END
+    return keygen_resident_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk);
 }
 int kosk_verifiable_keygen_seeded_resident(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk)
 {
-    if (!ctx || n < 1 || n > ctx->max_batch || !pk || !sk) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return keygen_resident_from(ctx, n, src, pk, sk);
-    WGUARD_END
+    return keygen_resident_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk);
 }
 int kosk_tape_expand_device(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *d_tapes, size_t tape_stride)
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !seeds || !d_tapes) return bad_args(ctx, __func__);
-    if (seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
+    if (seed_stride < SEED_BYTES) return refuse(ctx, __func__, WHY_SEED_STRIDE);
     WGUARD(ctx)
     ctx->clear_err();
     return tape_expand_device(*ctx->c, n, seeds, seed_stride, d_tapes, tape_stride);
@@ -890,7 +895,7 @@ int kosk_set_round_hook(kosk_ctx *ctx, kosk_round_fn fn, void *user)
 {
     if (!ctx) return -1;
     GUARD(ctx)
-    if (fn && ctx->sub.size() > 1) { ctx->err = "kosk_set_round_hook needs streams = 1 (one digest table per round)"; return -1; }
+    if (fn && ctx->sub.size() > 1) return refuse(ctx, nullptr, "kosk_set_round_hook needs streams = 1 (one digest table per round)");
     for (Ctx *c : ctx->sub) { c->round_hook = fn; c->round_user = user; }
     return 0;
     GUARD_END
@@ -899,164 +904,93 @@ int kosk_resident_digests(kosk_ctx *ctx, int round, void **d_digests, size_t *st
 {
     if (!ctx || round < 0 || round > 1) return bad_args(ctx, __func__);
     GUARD(ctx)
-    if (ctx->sub.size() > 1) { ctx->err = "kosk_resident_digests needs streams = 1 (sub-batches keep separate tables)"; return -1; }
+    if (ctx->sub.size() > 1) return refuse(ctx, nullptr, "kosk_resident_digests needs streams = 1 (sub-batches keep separate tables)");
     if (d_digests) *d_digests = round ? ctx->c->d_dig2 : ctx->c->d_dig1;
     if (stride) *stride = (size_t)NPARTY * 32;
     return 0;
     GUARD_END
 }
 
-static int keygen_batch_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *pi)
+// ---- the host-buffer calls, proofs in wire format `fmt` ----
+// image: the raw struct image.  compact: packed / unpacked on the GPU, so PCIe carries 78 % of the image bytes in each
+// direction.  dense, kosk-dense-v1 (kosk_dense.hip): packed by the same kernel on the dense field plan; unpacked and
+// refilled (rows 407..1303 of the seven low-degree fields) on the GPU behind the H2D copy.  Same chunking and lanes for all three
+static int keygen_batch_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *out, int fmt)
 {
     const Params &P = ctx->c->P;
+    const size_t rb = format_bytes(P, fmt);
     src.resolve(ctx, n); // stateful callback: everything sequentially, in proof order, then the chunks in parallel
-    // images go straight into a buffer the CALLER page-locked (KOSK_REGISTER=0: never), else through the pinned staging buffer
-    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
+    const bool direct = copy_direct(ctx, out, (size_t)n * rb);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         const KeygenIn kg = src.part(P, first, pk, sk);
         if (prove_at(c, first, count, &kg)) return -1;
-        return fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned);
+        return fetch_proofs(c, count, fmt, out + (size_t)first * rb, direct);
     });
 }
-int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
-                                 uint8_t *pk, uint8_t *sk, uint8_t *pi)
+static int keygen_batch_src(kosk_ctx *ctx, const char *fn, int n, bool seeded, const uint8_t *rand, size_t stride, uint8_t *pk, uint8_t *sk, uint8_t *out, int fmt)
 {
-    if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
+    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, fn);
+    if (ctx->armed && n > ctx->armed) return refuse(ctx, fn, WHY_ARMED);
+    if (seeded && rand && stride < SEED_BYTES) return refuse(ctx, fn, WHY_SEED_STRIDE);
     if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return keygen_batch_from(ctx, n, src, pk, sk, pi);
-    WGUARD_END
+    return guard(ctx, fn, [&]() -> int { return wiped_call(ctx, [&]() -> int {
+        RandSrc src = RandSrc::of(ctx, seeded, rand, stride);
+        return keygen_batch_from(ctx, n, src, pk, sk, out, fmt);
+    }); });
+}
+static int verify_batch_fmt(kosk_ctx *ctx, const char *fn, int n, int fmt, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
+{
+    if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, fn);
+    if (ctx->armed && n > ctx->armed) return refuse(ctx, fn, WHY_ARMED);
+    if (n == 0) { ctx->masks_n = 0; return 0; }
+    return guard(ctx, fn, [&]() -> int {
+        const Params &P = ctx->c->P;
+        const size_t rb = format_bytes(P, fmt);
+        reset_masks(ctx, n);
+        const bool direct = copy_direct(ctx, in, (size_t)n * rb);
+        const int rc = run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            const uint8_t *src = in + (size_t)first * rb;
+            c.host_img = nullptr;
+            if (stage_verifier_inputs(c, count, fmt, src, pk + (size_t)first * P.pk_bytes, direct)) return -1;
+            if (fmt == FMT_IMAGE) {
+                // the verifier's host reads the unopened parties' digests straight from the caller's images: nothing to copy back for them
+                // (verify_resident takes the pointer and clears it first thing)
+                c.host_img = src;
+                c.host_img_stride = P.proof_bytes;
+            }
+            return verify_into(ctx, c, first, count, ok, 0, nullptr);
+        });
+        if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
+        return rc;
+    });
+}
+int kosk_verifiable_keygen_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi)
+{
+    return keygen_batch_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk, pi, FMT_IMAGE);
 }
 int kosk_verifiable_keygen_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi)
 {
-    if (!ctx || n < 0 || !pk || !sk || !pi) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return keygen_batch_from(ctx, n, src, pk, sk, pi);
-    WGUARD_END
+    return keygen_batch_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk, pi, FMT_IMAGE);
 }
-
-int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk, uint8_t *ok)
+int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
-    if (!ctx || n < 0 || !pi || !pk || !ok) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (n == 0) { ctx->masks_n = 0; return 0; }
-    GUARD(ctx)
-    const Params &P = ctx->c->P;
-    reset_masks(ctx, n);
-    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
-    const int rc = run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        const uint8_t *src = pi + (size_t)first * P.proof_bytes;
-        c.host_img = nullptr;
-        if (stage_verifier_inputs(c, count, src, pk + (size_t)first * P.pk_bytes, pinned)) return -1;
-        // the verifier's host reads the unopened parties' digests straight from the caller's images: nothing to copy back for them
-        // (verify_resident takes the pointer and clears it first thing)
-        c.host_img = src;
-        c.host_img_stride = P.proof_bytes;
-        return verify_into(ctx, c, first, count, ok, 0, nullptr);
-    });
-    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
-    return rc;
-    GUARD_END
+    return keygen_batch_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk, out, FMT_COMPACT);
 }
-
-// The two host-buffer calls with the proofs in the compact wire format: packed / unpacked on the GPU, so PCIe
-// carries 78 % of the image bytes in each direction.  Same chunking and lanes as the calls above.
-static int keygen_batch_compact_from(kosk_ctx *ctx, int n, RandSrc &src, uint8_t *pk, uint8_t *sk, uint8_t *out, bool dense = false)
+int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
-    const Params &P = ctx->c->P;
-    const size_t cb = dense ? make_dense_plan(P).bytes : make_compact_plan(P).bytes;
-    src.resolve(ctx, n);
-    const bool pinned = ctx->c->host_register && span_is_pinned(out, (size_t)n * cb);
-    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        const KeygenIn kg = src.part(P, first, pk, sk);
-        if (prove_at(c, first, count, &kg)) return -1;
-        return fetch_proofs_compact(c, count, out + (size_t)first * cb, pinned, dense);
-    });
+    return keygen_batch_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk, out, FMT_COMPACT);
 }
-int kosk_verifiable_keygen_batch_compact(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
-                                         uint8_t *pk, uint8_t *sk, uint8_t *out)
-{
-    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
-    WGUARD_END
-}
-int kosk_verifiable_keygen_seeded_batch_compact(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
-                                                uint8_t *out)
-{
-    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return keygen_batch_compact_from(ctx, n, src, pk, sk, out);
-    WGUARD_END
-}
-static int verify_batch_packed(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok, bool dense)
-{
-    const Params &P = ctx->c->P;
-    const size_t cb = dense ? make_dense_plan(P).bytes : make_compact_plan(P).bytes;
-    reset_masks(ctx, n);
-    const bool pinned = ctx->c->host_register && span_is_pinned(in, (size_t)n * cb);
-    const int rc = run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        if (stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, pinned, dense)) return -1;
-        return verify_into(ctx, c, first, count, ok, 0, nullptr);
-    });
-    if (!rc) { ctx->masks_n = n; note_verified_keys(ctx, n > ctx->c->own_batch ? 2 : 1); }
-    return rc;
-}
-int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
-{
-    if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (n == 0) { ctx->masks_n = 0; return 0; }
-    GUARD(ctx)
-    return verify_batch_packed(ctx, n, in, pk, ok, false);
-    GUARD_END
-}
-
-// The same three calls in the dense wire format kosk-dense-v1 (kosk_dense.hip): packed by the compact pack kernel on
-// the dense field plan; unpacked and refilled (rows 407..1303 of the seven low-degree fields) on the GPU behind the H2D copy
 int kosk_verifiable_keygen_batch_dense(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
-    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
-    WGUARD_END
+    return keygen_batch_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk, out, FMT_DENSE);
 }
 int kosk_verifiable_keygen_seeded_batch_dense(kosk_ctx *ctx, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
 {
-    if (!ctx || n < 0 || !pk || !sk || !out) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    if (n == 0) return 0;
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return keygen_batch_compact_from(ctx, n, src, pk, sk, out, true);
-    WGUARD_END
+    return keygen_batch_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk, out, FMT_DENSE);
 }
-int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
-{
-    if (!ctx || n < 0 || !in || !pk || !ok) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (n == 0) { ctx->masks_n = 0; return 0; }
-    GUARD(ctx)
-    return verify_batch_packed(ctx, n, in, pk, ok, true);
-    GUARD_END
-}
+int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk, uint8_t *ok) { return verify_batch_fmt(ctx, __func__, n, FMT_IMAGE, pi, pk, ok); }
+int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok) { return verify_batch_fmt(ctx, __func__, n, FMT_COMPACT, in, pk, ok); }
+int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok) { return verify_batch_fmt(ctx, __func__, n, FMT_DENSE, in, pk, ok); }
 
 // ---- second-level entry points (kosk_split.cpp) -----------------------------------------------------------
 size_t kosk_randomness_bytes(int k) { Params p; return make_params(k, p) ? randomness_bytes(p) : 0; }
@@ -1067,65 +1001,44 @@ int kosk_prepare_randomness(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t t
 {
     if (!ctx || n < 0 || !rand_out) return bad_args(ctx, __func__);
     WGUARD(ctx)
-    Ctx &c = *ctx->c;
-    ctx->clear_err();
-    for (int done = 0; done < n;) {
-        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
-        if (prepare_randomness(c, m, tapes ? tapes + (size_t)done * tape_stride : nullptr, tape_stride,
-                               rand_out + (size_t)done * randomness_bytes(c.P))) return -1;
-        done += m;
-    }
-    return 0;
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return prepare_randomness(c, count, tapes ? tapes + (size_t)first * tape_stride : nullptr, tape_stride, rand_out + (size_t)first * randomness_bytes(c.P));
+    });
     WGUARD_END
 }
 int kosk_prepare_range_proof(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *range_out)
 {
     if (!ctx || n < 0 || !range_out) return bad_args(ctx, __func__);
     WGUARD(ctx)
-    Ctx &c = *ctx->c;
-    ctx->clear_err();
-    for (int done = 0; done < n;) {
-        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
-        if (prepare_range_proof(c, m, tapes ? tapes + (size_t)done * tape_stride : nullptr, tape_stride,
-                                range_out + (size_t)done * range_proof_bytes(c.P))) return -1;
-        done += m;
-    }
-    return 0;
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return prepare_range_proof(c, count, tapes ? tapes + (size_t)first * tape_stride : nullptr, tape_stride, range_out + (size_t)first * range_proof_bytes(c.P));
+    });
     WGUARD_END
 }
 int kosk_prove_prepared(kosk_ctx *ctx, int n, const uint8_t *inst, const uint8_t *rand_in, const uint8_t *range_in,
                         const uint8_t *tapes, size_t tape_stride, uint8_t *pi)
 {
     if (!ctx || n < 0 || !inst || !rand_in || !range_in || !pi) return bad_args(ctx, __func__);
-    if (ctx->armed) return armed_refuse(ctx, __func__, "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind");
+    if (ctx->armed) return refuse(ctx, __func__, WHY_NO_PK_TO_BIND);
     WGUARD(ctx)
-    Ctx &c = *ctx->c;
-    ctx->clear_err();
-    for (int done = 0; done < n;) {
-        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
-        c.bind_first = done; // (forced candidate lists are indexed by the position in the call)
-        if (prove_prepared(c, m, inst + (size_t)done * mlwe_inst_bytes(c.P), rand_in + (size_t)done * randomness_bytes(c.P),
-                           range_in + (size_t)done * range_proof_bytes(c.P), tapes ? tapes + (size_t)done * tape_stride : nullptr,
-                           tape_stride, pi + (size_t)done * c.P.proof_bytes)) return -1;
-        done += m;
-    }
-    return 0;
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        c.bind_first = first; // (forced candidate lists are indexed by the position in the call)
+        return prove_prepared(c, count, inst + (size_t)first * mlwe_inst_bytes(c.P), rand_in + (size_t)first * randomness_bytes(c.P),
+                              range_in + (size_t)first * range_proof_bytes(c.P), tapes ? tapes + (size_t)first * tape_stride : nullptr,
+                              tape_stride, pi + (size_t)first * c.P.proof_bytes);
+    });
     WGUARD_END
 }
 int kosk_verify_inst(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *inst, uint8_t *ok)
 {
     if (!ctx || n < 0 || !pi || !inst || !ok) return bad_args(ctx, __func__);
-    if (ctx->armed) return armed_refuse(ctx, __func__, "not on an armed handle (kosk_set_contexts): instances carry no public key bytes to bind");
+    if (ctx->armed) return refuse(ctx, __func__, WHY_NO_PK_TO_BIND);
     GUARD(ctx)
-    Ctx &c = *ctx->c;
-    ctx->clear_err();
     reset_masks(ctx, n);
-    for (int done = 0; done < n;) {
-        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
-        if (stage_verifier_inst(c, m, pi + (size_t)done * c.P.proof_bytes, inst + (size_t)done * mlwe_inst_bytes(c.P))) return -1;
-        if (verify_into(ctx, c, done, m, ok, 0, nullptr)) return -1;
-        done += m;
-    }
+    if (serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            if (stage_verifier_inst(c, count, pi + (size_t)first * c.P.proof_bytes, inst + (size_t)first * mlwe_inst_bytes(c.P))) return -1;
+            return verify_into(ctx, c, first, count, ok, 0, nullptr);
+        })) return -1;
     ctx->masks_n = n;
     note_verified_keys(ctx, 3);
     return 0;
@@ -1151,25 +1064,6 @@ int kosk_proof_decompress(int k, const uint8_t *in, uint8_t *pi)
     return 0;
     GUARD_END
 }
-int kosk_fetch_proofs_compact(kosk_ctx *ctx, int n, uint8_t *out)
-{
-    if (!ctx || n < 0 || n > ctx->max_batch || !out) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const size_t cb = make_compact_plan(ctx->c->P).bytes;
-    return ctx->run(n, [&](Ctx &c, int first, int count) { return fetch_proofs_compact(c, count, out + (size_t)first * cb); });
-    GUARD_END
-}
-int kosk_stage_verifier_inputs_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk)
-{
-    if (!ctx || n < 0 || n > ctx->max_batch || !in || !pk) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const Params &P = ctx->c->P;
-    const size_t cb = make_compact_plan(P).bytes;
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        return stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes);
-    });
-    GUARD_END
-}
 
 // ---- dense wire format kosk-dense-v1 (kosk_dense.hip) --------------------------------------------------------------
 size_t kosk_dense_proof_bytes(int k) { Params p; return make_params(k, p) ? make_dense_plan(p).bytes : 0; }
@@ -1187,25 +1081,6 @@ int kosk_proof_dense_unpack(int k, const uint8_t *in, uint8_t *pi)
     if (!make_params(k, p) || !pi || !in) return -1;
     return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
     return dense_decode(p, in, pi);
-    GUARD_END
-}
-int kosk_fetch_proofs_dense(kosk_ctx *ctx, int n, uint8_t *out)
-{
-    if (!ctx || n < 0 || n > ctx->max_batch || !out) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const size_t cb = make_dense_plan(ctx->c->P).bytes;
-    return ctx->run(n, [&](Ctx &c, int first, int count) { return fetch_proofs_compact(c, count, out + (size_t)first * cb, false, true); });
-    GUARD_END
-}
-int kosk_stage_verifier_inputs_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk)
-{
-    if (!ctx || n < 0 || n > ctx->max_batch || !in || !pk) return bad_args(ctx, __func__);
-    GUARD(ctx)
-    const Params &P = ctx->c->P;
-    const size_t cb = make_dense_plan(P).bytes;
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        return stage_verifier_inputs_compact(c, count, in + (size_t)first * cb, pk + (size_t)first * P.pk_bytes, false, true);
-    });
     GUARD_END
 }
 int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
@@ -1227,31 +1102,22 @@ int kosk_dense_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_
 
 // ---- transcoding between the wire formats (kosk_compact.hip: transcode) -----------------------------------------------------------
 static_assert((int)KOSK_FMT_IMAGE == (int)FMT_IMAGE && (int)KOSK_FMT_COMPACT == (int)FMT_COMPACT && (int)KOSK_FMT_DENSE == (int)FMT_DENSE, "kosk_mi355x.h and kosk_ctx.hpp");
-size_t kosk_format_bytes(int k, int fmt)
-{
-    return fmt == KOSK_FMT_IMAGE ? kosk_proof_bytes(k) : fmt == KOSK_FMT_COMPACT ? kosk_compact_proof_bytes(k) : fmt == KOSK_FMT_DENSE ? kosk_dense_proof_bytes(k) : 0;
-}
+size_t kosk_format_bytes(int k, int fmt) { Params p; return make_params(k, p) ? format_bytes(p, fmt) : 0; }
 // unmerged, on sub-context 0 (the handle's own stream), chunks of its batch size; brings no secret onto the handle (no wipe under KOSK_WIPE_CALL)
 int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status)
 {
     if (!ctx) return -1;
-    auto refuse = [&](const char *why) { ctx->clear_err(); ctx->err = std::string("kosk_transcode_batch: ") + why; ctx->c->err = ctx->err; return -1; };
-    if (!in || !out || !status) return refuse("null pointer");
-    if (n < 1) return refuse("n must be at least 1");
-    const size_t ib = kosk_format_bytes(ctx->c->P.K, from), ob = kosk_format_bytes(ctx->c->P.K, to);
-    if (!ib || !ob) return refuse("unknown format (KOSK_FMT_IMAGE, KOSK_FMT_COMPACT, KOSK_FMT_DENSE)");
-    if (from == to) return refuse("from and to are the same format");
+    if (!in || !out || !status) return refuse(ctx, __func__, "null pointer");
+    if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
+    const size_t ib = format_bytes(ctx->c->P, from), ob = format_bytes(ctx->c->P, to);
+    if (!ib || !ob) return refuse(ctx, __func__, "unknown format (KOSK_FMT_IMAGE, KOSK_FMT_COMPACT, KOSK_FMT_DENSE)");
+    if (from == to) return refuse(ctx, __func__, "from and to are the same format");
     const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
-    if (i0 < o0 + (size_t)n * ob && o0 < i0 + (size_t)n * ib) return refuse("in and out overlap");
+    if (i0 < o0 + (size_t)n * ob && o0 < i0 + (size_t)n * ib) return refuse(ctx, __func__, "in and out overlap");
     GUARD(ctx)
-    ctx->clear_err();
-    Ctx &c = *ctx->c;
-    for (int done = 0; done < n;) {
-        const int m = (n - done) < c.own_batch ? (n - done) : c.own_batch;
-        if (transcode(c, m, from, in + (size_t)done * ib, to, out + (size_t)done * ob, status + done)) { ctx->err = c.err; return -1; }
-        done += m;
-    }
-    return 0;
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return transcode(c, count, from, in + (size_t)first * ib, to, out + (size_t)first * ob, status + first);
+    });
     GUARD_END
 }
 
@@ -1467,85 +1333,75 @@ static void resolve_for_keys(const kosk_ctx *ctx, int n, RandSrc &src)
         src.resolve(ctx, n);
     }
 }
-static int bad_tape_stride(kosk_ctx *ctx, const char *fn)
+static int stage_keys_at(Ctx &c, const Params &P, const RandSrc &src, int first, int count, const uint8_t *sk, uint8_t *ok)
 {
-    ctx->clear_err();
-    ctx->err = std::string(fn) + ": tape_stride is smaller than one tape (kosk_tape_bytes)";
-    ctx->c->err = ctx->err;
-    return -1;
+    return stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
+                             src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first);
 }
-static int stage_prover_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src, uint8_t *ok)
+// The shared tail of the host-buffer calls on existing keys, chunk by chunk: the caller's staging step stage(c, first, count), which fills
+// ok[first ...], then prove, fetch the images, and zero those of the rejected keys
+static int prove_keys_chunks(kosk_ctx *ctx, int n, uint8_t *pi, const uint8_t *ok, const std::function<int(Ctx &, int, int)> &stage)
 {
     const Params &P = ctx->c->P;
-    resolve_for_keys(ctx, n, src); // stateful callback: everything sequentially, in proof order
-    return ctx->run(n, [&](Ctx &c, int first, int count) {
-        return stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
-                                 src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first);
-    });
-}
-int kosk_stage_prover_keys(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *ok)
-{
-    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
-    if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
-    GUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return stage_prover_keys_from(ctx, n, sk, src, ok);
-    GUARD_END
-}
-int kosk_stage_prover_keys_seeded(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *ok)
-{
-    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    GUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return stage_prover_keys_from(ctx, n, sk, src, ok);
-    GUARD_END
-}
-static int prove_keys_from(kosk_ctx *ctx, int n, const uint8_t *sk, RandSrc &src, uint8_t *pi, uint8_t *ok)
-{
-    const Params &P = ctx->c->P;
-    resolve_for_keys(ctx, n, src);
-    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
+    const bool direct = copy_direct(ctx, pi, (size_t)n * P.proof_bytes);
     return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        if (stage_prover_keys(c, count, sk + (size_t)first * P.sk_bytes, src.seeded ? nullptr : src.tapes + (size_t)first * src.tape_stride, src.tape_stride,
-                              src.seeded ? src.seeds + (size_t)first * src.seed_stride : nullptr, src.seed_stride, ok + first)) return -1;
+        if (stage(c, first, count)) return -1;
         if (prove_at(c, first, count)) return -1;
-        if (fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned)) return -1;
+        if (fetch_proofs_image(c, count, pi + (size_t)first * P.proof_bytes, direct)) return -1;
         for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
             if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
         return 0;
     });
 }
+// the stride check of both twins: a tape call's against one tape, a seeded call's against one seed
+static const char *key_stride_why(const kosk_ctx *ctx, bool seeded, const uint8_t *rand, size_t stride)
+{
+    if (!rand) return nullptr;
+    if (seeded) return stride < SEED_BYTES ? WHY_SEED_STRIDE : nullptr;
+    return stride < ctx->c->P.tape_bytes ? WHY_TAPE_STRIDE : nullptr;
+}
+static int stage_prover_keys_src(kosk_ctx *ctx, const char *fn, int n, const uint8_t *sk, bool seeded, const uint8_t *rand, size_t stride, uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, fn);
+    if (const char *why = key_stride_why(ctx, seeded, rand, stride)) return refuse(ctx, fn, why);
+    return guard(ctx, fn, [&]() -> int {
+        const Params &P = ctx->c->P;
+        RandSrc src = RandSrc::of(ctx, seeded, rand, stride);
+        resolve_for_keys(ctx, n, src); // stateful callback: everything sequentially, in proof order
+        return ctx->run(n, [&](Ctx &c, int first, int count) { return stage_keys_at(c, P, src, first, count, sk, ok); });
+    });
+}
+static int prove_keys_src(kosk_ctx *ctx, const char *fn, int n, const uint8_t *sk, bool seeded, const uint8_t *rand, size_t stride, uint8_t *pi, uint8_t *ok)
+{
+    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, fn);
+    if (ctx->armed && n > ctx->armed) return refuse(ctx, fn, WHY_ARMED);
+    if (const char *why = key_stride_why(ctx, seeded, rand, stride)) return refuse(ctx, fn, why);
+    return guard(ctx, fn, [&]() -> int { return wiped_call(ctx, [&]() -> int {
+        const Params &P = ctx->c->P;
+        RandSrc src = RandSrc::of(ctx, seeded, rand, stride);
+        resolve_for_keys(ctx, n, src);
+        return prove_keys_chunks(ctx, n, pi, ok, [&](Ctx &c, int first, int count) { return stage_keys_at(c, P, src, first, count, sk, ok); });
+    }); });
+}
+int kosk_stage_prover_keys(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *ok)
+{
+    return stage_prover_keys_src(ctx, __func__, n, sk, false, tapes, tape_stride, ok);
+}
+int kosk_stage_prover_keys_seeded(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *ok)
+{
+    return stage_prover_keys_src(ctx, __func__, n, sk, true, seeds, seed_stride, ok);
+}
 int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *pi, uint8_t *ok)
 {
-    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (tapes && tape_stride < ctx->c->P.tape_bytes) return bad_tape_stride(ctx, __func__);
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_tapes(ctx, tapes, tape_stride);
-    return prove_keys_from(ctx, n, sk, src, pi, ok);
-    WGUARD_END
+    return prove_keys_src(ctx, __func__, n, sk, false, tapes, tape_stride, pi, ok);
 }
 int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok)
 {
-    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
-    ARMED_CHECK(ctx, n);
-    if (seeds && seed_stride < SEED_BYTES) return bad_seed_stride(ctx, __func__);
-    WGUARD(ctx)
-    RandSrc src = RandSrc::from_seeds(seeds, seed_stride);
-    return prove_keys_from(ctx, n, sk, src, pi, ok);
-    WGUARD_END
+    return prove_keys_src(ctx, __func__, n, sk, true, seeds, seed_stride, pi, ok);
 }
 
 // ---- kosk-keyseed-v1: the randomness derived from the key itself.  Position b of the call hashes armed context b (the
 // handle's device copy; chunks and sub-batches pass their offset on as for binding) and salt b
-static int bad_salt_stride(kosk_ctx *ctx, const char *fn)
-{
-    ctx->clear_err();
-    ctx->err = std::string(fn) + ": salt_stride is smaller than one salt (32 bytes)";
-    ctx->c->err = ctx->err;
-    return -1;
-}
 static int stage_derived_at(Ctx &c, const Params &P, int first, int count, const uint8_t *sk, const uint8_t *salts, size_t salt_stride, uint8_t *ok)
 {
     const DerivedSrc src{salts ? salts + (size_t)first * salt_stride : nullptr, salt_stride};
@@ -1556,7 +1412,7 @@ int kosk_stage_prover_keys_derived(kosk_ctx *ctx, int n, const uint8_t *sk, cons
 {
     if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
-    if (salts && salt_stride < 32) return bad_salt_stride(ctx, __func__);
+    if (salts && salt_stride < 32) return refuse(ctx, __func__, WHY_SALT_STRIDE);
     GUARD(ctx)
     const Params &P = ctx->c->P;
     return ctx->run(n, [&](Ctx &c, int first, int count) { return stage_derived_at(c, P, first, count, sk, salts, salt_stride, ok); });
@@ -1566,18 +1422,10 @@ int kosk_prove_keys_derived_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const
 {
     if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
     ARMED_CHECK(ctx, n);
-    if (salts && salt_stride < 32) return bad_salt_stride(ctx, __func__);
+    if (salts && salt_stride < 32) return refuse(ctx, __func__, WHY_SALT_STRIDE);
     WGUARD(ctx)
     const Params &P = ctx->c->P;
-    const bool pinned = ctx->c->host_register && span_is_pinned(pi, (size_t)n * P.proof_bytes);
-    return run_chunks(ctx, n, [&](Ctx &c, int first, int count) {
-        if (stage_derived_at(c, P, first, count, sk, salts, salt_stride, ok)) return -1;
-        if (prove_at(c, first, count)) return -1;
-        if (fetch_proofs(c, count, pi + (size_t)first * P.proof_bytes, pinned)) return -1;
-        for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
-            if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
-        return 0;
-    });
+    return prove_keys_chunks(ctx, n, pi, ok, [&](Ctx &c, int first, int count) { return stage_derived_at(c, P, first, count, sk, salts, salt_stride, ok); });
     WGUARD_END
 }
 int kosk_keyseed_device(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride,
@@ -1826,7 +1674,7 @@ int kosk_resident_proofs(kosk_ctx *ctx, void **d_proofs, size_t *stride)
 {
     if (!ctx) return -1;
     GUARD(ctx)
-    if (ctx->sub.size() > 1) { ctx->err = "kosk_resident_proofs needs streams = 1 (sub-batches keep separate images)"; return -1; }
+    if (ctx->sub.size() > 1) return refuse(ctx, nullptr, "kosk_resident_proofs needs streams = 1 (sub-batches keep separate images)");
     if (d_proofs) *d_proofs = ctx->c->d_proof;
     if (stride) *stride = ctx->c->image_stride;
     return 0;

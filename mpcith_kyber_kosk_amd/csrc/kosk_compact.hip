@@ -148,13 +148,24 @@ __global__ __launch_bounds__(256) void k_unpack_proofs(const uint8_t *__restrict
     }
 }
 
-static int ensure_compact(Ctx &c)
+size_t format_bytes(const Params &P, int fmt)
 {
-    if (c.d_compact) return 0;
+    return fmt == FMT_IMAGE ? P.proof_bytes : fmt == FMT_COMPACT ? make_compact_plan(P).bytes : fmt == FMT_DENSE ? make_dense_plan(P).bytes : 0;
+}
+
+void ensure_plans(Ctx &c)
+{
+    if (c.cplan.bytes) return;
     c.cplan = make_compact_plan(c.P);
     c.compact_stride = (c.cplan.bytes + 63) / 64 * 64;
     c.dplan = make_dense_plan(c.P); // dense records are shorter and go through the same staging buffers
     c.dense_stride = (c.dplan.bytes + 63) / 64 * 64;
+}
+
+static int ensure_compact(Ctx &c)
+{
+    if (c.d_compact) return 0;
+    ensure_plans(c);
     // a view keeps its own staging, sized for its own callers' batches (the compact calls are never merged)
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact), (size_t)c.own_batch * c.compact_stride));
     HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact_bad), sizeof(uint32_t) * c.own_batch));
@@ -168,59 +179,74 @@ static int ensure_compact(Ctx &c)
     return 0;
 }
 
-// dense: the same kernel on the dense plan.  It packs rows 0..406 of the seven low-degree fields and does not look at the rows it drops:
+// The two stream-level halves of every packed call, on explicit device pointers (the resident buffers and the transcode workspace alike):
+// queued on c.stream, not synchronised; images are c.image_stride apart, records w.stride.
+// images -> records: padding bytes are zero; d_bad[b] (zeroed by the caller) is set where image b holds a value >= 4096.  dense: the same
+// kernel on the dense plan.  It packs rows 0..406 of the seven low-degree fields and does not look at the rows it drops
+static int pack_launch(Ctx &c, int n, const WireFmt &w, const uint8_t *d_img, uint8_t *d_rec, uint32_t *d_bad)
+{
+    HIPCHK(hipMemsetAsync(d_rec, 0, (size_t)n * w.stride, c.stream));
+    hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, d_img, c.image_stride, d_rec, w.stride, *w.plan, d_bad);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+// records -> images.  dense: the dropped rows start as zero and stay so where the opened list is malformed (d_status 1; the verifier
+// rejects such an image), and the refill of kosk_dense.hip follows the unpack kernel (needs ensure_dense_ws)
+static int unpack_launch(Ctx &c, int n, const WireFmt &w, const uint8_t *d_rec, uint8_t *d_img, uint32_t *d_status)
+{
+    const Params &P = c.P;
+    const CompactPlan &plan = *w.plan;
+    if (w.id == FMT_DENSE)
+        for (int f = 0; f < NFIELDS; f++)
+            if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
+                HIPCHK(hipMemset2DAsync(d_img + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
+    hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, d_rec, w.stride, d_img, c.image_stride, plan);
+    HIPCHK(hipGetLastError());
+    if (w.id == FMT_DENSE && dense_fill_launch(c, n, d_img, c.image_stride, d_status)) return -1;
+    return 0;
+}
+
 // what the library's own prover left in HBM is a codeword by construction (kosk_dense.hip; the host codec checks, this call does not)
-int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct, bool dense)
+int fetch_proofs_packed(Ctx &c, int n, int fmt, uint8_t *out, bool direct)
 {
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (ensure_compact(c)) return -1;
-    const CompactPlan &plan = dense ? c.dplan : c.cplan;
-    const size_t stride = dense ? c.dense_stride : c.compact_stride;
-    HIPCHK(hipMemsetAsync(c.d_compact, 0, (size_t)n * stride, c.stream)); // padding bytes are zero
+    const WireFmt w = wire_fmt(c, fmt);
     HIPCHK(hipMemsetAsync(c.d_compact_bad, 0, sizeof(uint32_t) * n, c.stream));
-    hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_proof, c.image_stride, c.d_compact, stride,
-                       plan, c.d_compact_bad);
-    HIPCHK(hipGetLastError());
+    if (pack_launch(c, n, w, c.d_proof, c.d_compact, c.d_compact_bad)) return -1;
     // direct: `out` is page-locked host memory (the caller's own, or locked for this call by kosk_capi.cpp): no staging copy
-    if (direct) HIPCHK(hipMemcpy2DAsync(out, plan.bytes, c.d_compact, stride, plan.bytes, n, hipMemcpyDeviceToHost, c.stream));
-    else HIPCHK(hipMemcpyAsync(c.h_compact, c.d_compact, (size_t)n * stride, hipMemcpyDeviceToHost, c.stream));
+    if (direct) HIPCHK(hipMemcpy2DAsync(out, w.bytes, c.d_compact, w.stride, w.bytes, n, hipMemcpyDeviceToHost, c.stream));
+    else HIPCHK(hipMemcpyAsync(c.h_compact, c.d_compact, (size_t)n * w.stride, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(c.h_compact_bad, c.d_compact_bad, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c.stream));
     HIPCHK(stream_sync(c));
     c.path_n[direct ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     for (int b = 0; b < n; b++)
         if (c.h_compact_bad[b]) { c.err = "a resident proof holds a value >= 4096: not representable in the compact format"; return -1; }
     if (!direct)
-        parallel_for(c.pool, n, c.nthreads, [&](int b) { memcpy(out + (size_t)b * plan.bytes, c.h_compact + (size_t)b * stride, plan.bytes); });
+        parallel_for(c.pool, n, c.nthreads, [&](int b) { memcpy(out + (size_t)b * w.bytes, c.h_compact + (size_t)b * w.stride, w.bytes); });
     return 0;
 }
 
-int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct, bool dense)
+int stage_verifier_inputs_packed(Ctx &c, int n, int fmt, const uint8_t *in, const uint8_t *pk, bool direct)
 {
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (ensure_verify_workspace(c)) return -1;
     if (ensure_compact(c)) return -1;
-    if (dense && ensure_dense_ws(c)) return -1;
+    if (fmt == FMT_DENSE && ensure_dense_ws(c)) return -1;
     const Params &P = c.P;
-    const CompactPlan &plan = dense ? c.dplan : c.cplan;
-    const size_t stride = dense ? c.dense_stride : c.compact_stride;
+    const WireFmt w = wire_fmt(c, fmt);
     parallel_for(c.pool, n, c.nthreads, [&](int b) {
         memcpy(c.h_pk + (size_t)b * c.pk_stride, pk + (size_t)b * P.pk_bytes, P.pk_bytes);
-        if (!direct) memcpy(c.h_compact + (size_t)b * stride, in + (size_t)b * plan.bytes, plan.bytes);
+        if (!direct) memcpy(c.h_compact + (size_t)b * w.stride, in + (size_t)b * w.bytes, w.bytes);
     });
     c.path_n[direct ? PATH_COPY_DIRECT : PATH_COPY_STAGED]++;
     HIPCHK(hipMemcpyAsync(c.d_pk, c.h_pk, (size_t)n * c.pk_stride, hipMemcpyHostToDevice, c.stream));
     c.note_pk_written(n);
-    if (direct) HIPCHK(hipMemcpy2DAsync(c.d_compact, stride, in, plan.bytes, plan.bytes, n, hipMemcpyHostToDevice, c.stream));
-    else HIPCHK(hipMemcpyAsync(c.d_compact, c.h_compact, (size_t)n * stride, hipMemcpyHostToDevice, c.stream));
-    if (dense) // the dropped rows start as zero: they stay so where the opened list is malformed (status 1; the verifier rejects such an image)
-        for (int f = 0; f < NFIELDS; f++)
-            if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
-                HIPCHK(hipMemset2DAsync(c.d_proof + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
-    hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, c.d_compact, stride, c.d_proof, c.image_stride, plan);
-    HIPCHK(hipGetLastError());
-    if (dense && dense_fill_launch(c, n, c.d_proof, c.image_stride, c.d_dense_status)) return -1;
+    if (direct) HIPCHK(hipMemcpy2DAsync(c.d_compact, w.stride, in, w.bytes, w.bytes, n, hipMemcpyHostToDevice, c.stream));
+    else HIPCHK(hipMemcpyAsync(c.d_compact, c.h_compact, (size_t)n * w.stride, hipMemcpyHostToDevice, c.stream));
+    if (unpack_launch(c, n, w, c.d_compact, c.d_proof, c.d_dense_status)) return -1;
     HIPCHK(launch_decode_pk(c.d_pk, c.pk_stride, c.d_t, c.d_A, c.key_stride, P.K, n, c.stream, c.xof_guard()));
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;
@@ -250,12 +276,7 @@ void transcode_release(Ctx &c)
 static int transcode_ensure(Ctx &c)
 {
     if (c.tc) return 0;
-    if (!c.cplan.bytes) { // the plans and strides of ensure_compact, without its buffers
-        c.cplan = make_compact_plan(c.P);
-        c.compact_stride = (c.cplan.bytes + 63) / 64 * 64;
-        c.dplan = make_dense_plan(c.P);
-        c.dense_stride = (c.dplan.bytes + 63) / 64 * 64;
-    }
+    ensure_plans(c);
     TcWs *w = new TcWs();
     c.tc = w;
     const size_t N = (size_t)c.own_batch;
@@ -295,38 +316,24 @@ int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, 
     HIPCHK(hipSetDevice(c.device));
     if (transcode_ensure(c)) return -1;
     if ((from == FMT_DENSE || to == FMT_DENSE) && ensure_dense_ws(c)) return -1;
-    const Params &P = c.P;
     TcWs &w = *c.tc;
     uint32_t *d_st = w.d_words, *d_bad = w.d_words + c.own_batch;
-    auto plan_of = [&](int fmt) -> const CompactPlan & { return fmt == FMT_DENSE ? c.dplan : c.cplan; };
-    auto stride_of = [&](int fmt) { return fmt == FMT_IMAGE ? c.image_stride : fmt == FMT_DENSE ? c.dense_stride : c.compact_stride; };
-    auto bytes_of = [&](int fmt) { return fmt == FMT_IMAGE ? P.proof_bytes : plan_of(fmt).bytes; };
+    const WireFmt wf = wire_fmt(c, from), wt = wire_fmt(c, to);
     HIPCHK(hipMemsetAsync(w.d_words, 0, 2 * (size_t)c.own_batch * sizeof(uint32_t), c.stream));
     // in
     uint8_t *d_src = from == FMT_IMAGE ? w.d_img : w.d_in;
-    HIPCHK(hipMemcpy2DAsync(d_src, stride_of(from), in, bytes_of(from), bytes_of(from), n, is_device_pointer(in) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
-    if (from != FMT_IMAGE) {
-        const CompactPlan &plan = plan_of(from);
-        if (from == FMT_DENSE) // the dropped rows start as zero and stay so under a malformed I (status 1)
-            for (int f = 0; f < NFIELDS; f++)
-                if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
-                    HIPCHK(hipMemset2DAsync(w.d_img + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
-        hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, w.d_in, stride_of(from), w.d_img, c.image_stride, plan);
-        HIPCHK(hipGetLastError());
-        if (from == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st)) return -1;
-    }
+    HIPCHK(hipMemcpy2DAsync(d_src, wf.stride, in, wf.bytes, wf.bytes, n, is_device_pointer(in) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    if (from != FMT_IMAGE && unpack_launch(c, n, wf, w.d_in, w.d_img, d_st)) return -1;
     // out
     const uint8_t *d_dst = w.d_img;
     if (to != FMT_IMAGE) {
-        if (to == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st, true)) return -1;
-        HIPCHK(hipMemsetAsync(w.d_out, 0, (size_t)n * stride_of(to), c.stream)); // padding bytes are zero
-        hipLaunchKernelGGL(k_pack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, w.d_img, c.image_stride, w.d_out, stride_of(to), plan_of(to), d_bad);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_zero_failed, dim3(8, n), dim3(256), 0, c.stream, w.d_out, stride_of(to), d_st, d_bad, to == FMT_DENSE ? 1 : 0);
+        if (to == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st, true)) return -1; // the codeword check
+        if (pack_launch(c, n, wt, w.d_img, w.d_out, d_bad)) return -1;
+        hipLaunchKernelGGL(k_zero_failed, dim3(8, n), dim3(256), 0, c.stream, w.d_out, wt.stride, d_st, d_bad, to == FMT_DENSE ? 1 : 0);
         HIPCHK(hipGetLastError());
         d_dst = w.d_out;
     }
-    HIPCHK(hipMemcpy2DAsync(out, bytes_of(to), d_dst, stride_of(to), bytes_of(to), n, is_device_pointer(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpy2DAsync(out, wt.bytes, d_dst, wt.stride, wt.bytes, n, is_device_pointer(out) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
     HIPCHK(hipMemcpyAsync(w.h_words, w.d_words, 2 * (size_t)c.own_batch * sizeof(uint32_t), hipMemcpyDeviceToHost, c.stream));
     HIPCHK(stream_sync(c));
     if (device_error_check(c)) return -1;

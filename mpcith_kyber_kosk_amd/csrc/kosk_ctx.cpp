@@ -1345,7 +1345,7 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     return 0;
 }
 
-int fetch_proofs(Ctx &c, int n, uint8_t *pi, bool registered)
+int fetch_proofs_image(Ctx &c, int n, uint8_t *pi, bool registered)
 {
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));

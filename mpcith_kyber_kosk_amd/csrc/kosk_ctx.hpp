@@ -312,7 +312,7 @@ struct Ctx {
     };
     WaitHist wait_hist[WAIT_SITES][WAIT_SIZES];
     unsigned long wait_stamp = 0;
-    hipEvent_t ev_sync = nullptr; // KOSK_BLOCKING_SYNC=1: every host wait sleeps on an event instead of spinning (few host cores per GPU)
+    hipEvent_t ev_sync = nullptr; // kosk_options::blocking_sync: every host wait sleeps on an event instead of spinning (few host cores per GPU)
     bool blocking_sync = false;
     int n_simd = 1024;      // SIMDs of the device (4 per CU)
     hipEvent_t timer_ev[2] = {nullptr, nullptr}; // kosk_stream_timer_start / _stop
@@ -352,13 +352,13 @@ struct Ctx {
     SegGraph seg[SEG_COUNT];
     bool use_graphs = false; // KOSK_GRAPHS=1 turns them on (measured on ROCm 7.2: no gain over plain launches)
     bool capturing = false;
-    // strict_encoding (kosk_options::strict_encoding, KOSK_STRICT_ENCODING; DEFAULT 1 since round 6): the verifier marks a proof malformed
+    // strict_encoding (kosk_options::strict_encoding; DEFAULT 1 since round 6): the verifier marks a proof malformed
     // (fail bit 0) when ANY u16 element of a record the reference reads is >= q -- no honest prover emits one, and accepting them makes
     // proofs malleable (v and v + q verify alike).  0 = the reference-following mode of round 5: such elements are treated exactly as
     // the reference treats them, record by record: folded where it only multiplies / converts to ZZ_p, raw in its
     // non-reducing add / sub and comparisons; pinned against the oracle by two differential suites, opt-in for parity work
     bool strict_encoding = true;
-    // Fiat-Shamir aggregation on the device (kosk_options::fs_mode = KOSK_FS_DEVICE, or KOSK_FS_DEVICE=1 for kosk_create): the four
+    // Fiat-Shamir aggregation on the device (kosk_options::fs_mode = KOSK_FS_DEVICE): the four
     // sha3_256 chains of a prove + verify over the 46.5 KB digest tables run as one wave per proof where the tables are, the challenge
     // vectors / opened lists / the verifier's I' == I never leave HBM, and the resident calls have NO host round trip left: no digest
     // table crosses PCIe, the host neither hashes nor waits between segments (kosk_fs_kernels.hip).  Host mode (default)
@@ -452,12 +452,12 @@ int run_segment(Ctx &c, int seg, int n, F &&body, const void *key_ptr = nullptr,
     return 0;
 }
 
-// what kosk_create_ex's options struct decides per context (-1 / 0 = not given: the environment variable of the same name, then the default)
+// what kosk_create_ex's options struct decides per context (-1 / 0 = not given: the default; no environment variable is consulted)
 struct CtxOpts {
-    int host_threads = 0;    // KOSK_HOST_THREADS
-    int blocking_sync = -1;  // KOSK_BLOCKING_SYNC
-    int strict_encoding = -1; // KOSK_STRICT_ENCODING
-    int fs_device = -1;      // KOSK_FS_DEVICE
+    int host_threads = 0;    // kosk_options::host_threads
+    int blocking_sync = -1;  // kosk_options::blocking_sync
+    int strict_encoding = -1; // kosk_options::strict_encoding
+    int fs_device = -1;      // kosk_options::fs_mode == KOSK_FS_DEVICE
 };
 // host_share: sub-contexts of the same handle that share this process's CPUs (divides the host thread budget)
 int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &err, int host_share = 1, const CtxOpts &opts = CtxOpts());
@@ -467,7 +467,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
 
 // p is device memory (hipMalloc); plain, page-locked and unknown pointers are host memory
 bool is_device_pointer(const void *p);
-// host wait for everything queued on the context's stream (spinning, or sleeping with KOSK_BLOCKING_SYNC=1)
+// host wait for everything queued on the context's stream (spinning, or sleeping with kosk_options::blocking_sync)
 hipError_t stream_sync(Ctx &c);
 // wait for `ev` (recorded on the context's stream); site = which of the pipeline's long waits this is (0..WAIT_SITES-1: napped with
 // KOSK_WAIT_NAP=1), n = the batch size the wait belongs to; site < 0: a plain wait
@@ -535,10 +535,37 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
                    size_t tape_stride, uint8_t *pi);
 int stage_verifier_inst(Ctx &c, int n, const uint8_t *pi, const uint8_t *inst);
 int ensure_verify_workspace(Ctx &c);
-// direct: the host buffer is page-locked (copied to / from straight, no staging)
-// dense = true: the same two calls in the dense wire format (stage: unpack, then the refill of kosk_dense.hip)
-int fetch_proofs_compact(Ctx &c, int n, uint8_t *out, bool direct = false, bool dense = false);
-int stage_verifier_inputs_compact(Ctx &c, int n, const uint8_t *in, const uint8_t *pk, bool direct = false, bool dense = false);
+// ---- wire formats: the image, and the two packed forms of it (kosk_compact.hip, kosk_dense.hip) ----
+enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality)
+// what one format is on a context: its field plan (nullptr: the image), the bytes of a record on the wire and its stride in HBM / staging
+struct WireFmt {
+    int id;
+    const CompactPlan *plan;
+    size_t bytes, stride;
+};
+void ensure_plans(Ctx &c); // cplan, dplan and their strides (no buffer); wire_fmt() of a packed format needs it
+inline WireFmt wire_fmt(const Ctx &c, int fmt)
+{
+    if (fmt == FMT_IMAGE) return WireFmt{fmt, nullptr, c.P.proof_bytes, c.image_stride};
+    return fmt == FMT_DENSE ? WireFmt{fmt, &c.dplan, c.dplan.bytes, c.dense_stride} : WireFmt{fmt, &c.cplan, c.cplan.bytes, c.compact_stride};
+}
+size_t format_bytes(const Params &P, int fmt); // of one record; 0 for an unknown format
+// n resident images <-> n records of format `fmt` in host memory; direct: the host buffer is page-locked (copied to / from straight, no
+// staging).  The image bodies (kosk_ctx.cpp, kosk_verify.cpp) and the packed ones (kosk_compact.hip: pack in front of the D2H copy, unpack
+// and for dense the refill behind the H2D copy) differ on purpose: call_cap against own_batch (packed calls are never merged), the staging
+// buffers, the PH_D2H clock
+int fetch_proofs_image(Ctx &c, int n, uint8_t *pi, bool direct = false);
+int fetch_proofs_packed(Ctx &c, int n, int fmt, uint8_t *out, bool direct = false);
+int stage_verifier_inputs_image(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, bool direct = false);
+int stage_verifier_inputs_packed(Ctx &c, int n, int fmt, const uint8_t *in, const uint8_t *pk, bool direct = false);
+inline int fetch_proofs(Ctx &c, int n, int fmt, uint8_t *out, bool direct = false)
+{
+    return fmt == FMT_IMAGE ? fetch_proofs_image(c, n, out, direct) : fetch_proofs_packed(c, n, fmt, out, direct);
+}
+inline int stage_verifier_inputs(Ctx &c, int n, int fmt, const uint8_t *in, const uint8_t *pk, bool direct = false)
+{
+    return fmt == FMT_IMAGE ? stage_verifier_inputs_image(c, n, in, pk, direct) : stage_verifier_inputs_packed(c, n, fmt, in, pk, direct);
+}
 int ensure_dense_ws(Ctx &c);
 // check = true: the codeword check (k_dense_check): the refill compared with the images' own rows 407..1303 instead of stored, the images only read
 // (the pointer is not const because the fill shares the signature); d_status 0, 1 malformed I, 2 a dropped row that is not the refill
@@ -546,13 +573,8 @@ int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uin
 int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false);
 // transcoding between the wire formats (kosk_compact.hip): n <= own_batch records, `in` / `out` host or device memory of any alignment,
 // status[b] (host) the host codecs' composition (kosk_mi355x.h); touches nothing but its own workspace and the refill's scratch.  Synchronised
-enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality)
 int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status);
 void transcode_release(Ctx &c);
-// registered: `pi` is page-locked host memory (hipHostRegister): copied to directly, no staging
-int fetch_proofs(Ctx &c, int n, uint8_t *pi, bool registered = false);
-
-int stage_verifier_inputs(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, bool registered = false);
 // pk_mode 0: A and t are already resident (stage_verifier_inputs / stage_verifier_inst); 1: decode `pk` (host or
 // device memory, n records of pk_bytes) at the head of the first segment (kosk.cpp:94-99: polyvec_frombytes + gen_matrix);
 // 2: decode the pk bytes the key generation left resident in HBM

@@ -2022,12 +2022,13 @@ hipError_t launch_post_relation(uint16_t *P, size_t proof_stride, const RowMap &
     return hipGetLastError();
 }
 
-hipError_t launch_assemble(const AssembleArgs &a, size_t off_tcomm, size_t off_comm, size_t off_I, int nproofs, hipStream_t st)
+hipError_t launch_assemble(const AssembleArgs &args, size_t off_tcomm, size_t off_comm, size_t off_I, int nproofs, hipStream_t st)
 {
-    if (!a.groups || a.ngroups <= 0) return hipErrorInvalidValue;
+    if (!args.groups || args.ngroups <= 0) return hipErrorInvalidValue;
+    AssembleArgs a = args; // the kernel's copy: img_align is decided here, the caller's struct stays as it is
     // widest store the image's digest fields allow (field offsets, image stride and base all multiples of it)
     auto ok = [&](size_t m) { return off_tcomm % m == 0 && off_comm % m == 0 && a.image_stride % m == 0 && (reinterpret_cast<uintptr_t>(a.proof) % m) == 0; };
-    const_cast<AssembleArgs &>(a).img_align = ok(16) ? 16 : ok(8) ? 8 : ok(4) ? 4 : 2;
+    a.img_align = ok(16) ? 16 : ok(8) ? 8 : ok(4) ? 4 : 2;
     const int bpp = a.ngroups * NWIN + (NREST * 4 + 63) / 64;
     const long nwg = ((long)bpp * nproofs + 7) / 8 * 8;
     hipLaunchKernelGGL(k_assemble_groups, dim3((unsigned)nwg), dim3(64), 0, st, a, (uint32_t)off_tcomm, (uint32_t)off_comm, (uint32_t)off_I, bpp, nproofs);

@@ -200,7 +200,7 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
     }
     if (fill_tape_part(c, n, false, 2 * M + 2 * KE, P.nfresh, tapes, tape_stride)) return -1;
     if (prove_resident(c, n, true)) return -1;
-    return fetch_proofs(c, n, pi);
+    return fetch_proofs_image(c, n, pi);
 }
 
 int stage_verifier_inst(Ctx &c, int n, const uint8_t *pi, const uint8_t *inst)

@@ -164,7 +164,7 @@ int ensure_verify_workspace(Ctx &c)
     return 0;
 }
 
-int stage_verifier_inputs(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, bool registered)
+int stage_verifier_inputs_image(Ctx &c, int n, const uint8_t *pi, const uint8_t *pk, bool registered)
 {
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
