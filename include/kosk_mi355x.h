@@ -296,7 +296,7 @@ int kosk_dense_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image
  * handle and is not one of the entry points that wipe under KOSK_WIPE_CALL.  It runs unmerged on a cohort member, and with streams > 1
  * on sub-batch 0's stream. */
 enum { KOSK_FMT_IMAGE = 0, KOSK_FMT_COMPACT = 1, KOSK_FMT_DENSE = 2 };
-size_t kosk_format_bytes(int kyber_k, int fmt);      /* kosk_proof_bytes / kosk_compact_proof_bytes / kosk_dense_proof_bytes; 0 for a bad k or fmt */
+size_t kosk_format_bytes(int kyber_k, int fmt);      /* kosk_proof_bytes / kosk_compact_proof_bytes / kosk_dense_proof_bytes / (fmt 4, below) kosk_dense2_proof_bytes; 0 for a bad k or fmt */
 int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status);
 /* kernel level: the codeword check alone on n >= 1 images in the caller's HBM (alignment rules of kosk_dense_fill_device; -1 and a text
  * otherwise).  Strictly read-only on the images.  d_status[b] (device memory, n x uint32): 0; 1 a malformed I; 2 some u16 in rows
@@ -304,6 +304,39 @@ int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int 
  * row is a difference.  It says nothing about values >= 4096 in kept rows (the pack kernel's overflow word does).  Runs on the handle's
  * own stream, synchronised on return. */
 int kosk_dense_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+
+/* ---- Dense wire format kosk-dense-v2 (INTEGRATION.md 11.2 is the normative text).  Everything of kosk-dense-v1 holds except the stored
+ * rows of four fields whose sharing polynomials have PUBLIC values at the 256 packed positions x = 0..255:
+ *   fields 15, 16 (s_eta, e_eta shares) store rows 0..150: column c shares the constant kappa_c = (c mod (2 eta1 + 1)) - eta1 mod q at
+ *     all 256 positions (the verifier's fail bit 7 insists on it), so a polynomial of degree <= 406 has 151 free values;
+ *   fields 21, 22 (u_s, u_e shares of degree <= 812) store rows 0..556: u is zero at all 256 positions (fail bit 9).
+ * With Z(x) = prod_{a < 256} (x - a) every such column is p = kappa + Z v, and the dropped rows are rebuilt from v's interpolation
+ * through the nodes 256 + rest[j], j < 151 / 557.  Fields 2, 3, 8, 13, 14 stay at rows 0..406 with v1's refill.
+ * 247 552 / 252 512 / 269 600 bytes for kyber_k 2 / 3 / 4: 37 % of the image.  A v2 record verifies exactly as the image it unpacks to;
+ * every image the verifier accepts is representable; an image whose eta rows lie on a degree-406 polynomial with OTHER values at the
+ * packed positions packs to v1 and gives -2 here.  v1 records stay valid and byte-identical.
+ * Host codec: the return codes of the v1 codec, on v2's stored and dropped rows (pack 0 / -1 a stored value >= 4096, it wins / -2;
+ * unpack 0 / 1 a malformed I, rows 407.. of the five v1 fields, 151.. of fields 15 / 16 and 557.. of fields 21 / 22 then zero). */
+enum { KOSK_FMT_DENSE2 = 4 }; /* a separate enum: 0..2 above are pinned.  3 is not a format and will not become one */
+size_t kosk_dense2_proof_bytes(int kyber_k); /* = kosk_format_bytes(kyber_k, KOSK_FMT_DENSE2) */
+int kosk_proof_dense2_pack(int kyber_k, const uint8_t *pi, uint8_t *out);
+int kosk_proof_dense2_unpack(int kyber_k, const uint8_t *in, uint8_t *pi);
+/* kernel level, the contracts of kosk_dense_fill_device / kosk_dense_check_device on v2's dropped rows: status 0 / 1 / 2, nothing outside
+ * the refilled rows is written, the check is strictly read-only. */
+int kosk_dense2_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+int kosk_dense2_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_t image_stride, uint32_t *d_status);
+/* kosk_transcode_batch takes KOSK_FMT_DENSE2 on either side (12 ordered pairs; the composition rule above with the v2 codec).
+ * The five host-buffer calls with the packed format as an argument, so that a further format needs no further names: fmt =
+ * KOSK_FMT_COMPACT / KOSK_FMT_DENSE run the bodies of the _compact / _dense calls (same bytes, return codes, argument-check order,
+ * counters and resident-state effects); KOSK_FMT_DENSE2 behaves the same way in the new format (chunked by max_batch, streams, pageable
+ * and page-locked buffers, armed handles, never merged; a verifier staging call counts as "replaced the resident keys" for
+ * kosk_kem_enc_verified).  Any other fmt, the image included, is refused with a text that names the format. */
+int kosk_verifiable_keygen_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out);
+int kosk_verifiable_keygen_seeded_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk,
+                                            uint8_t *out);
+int kosk_verify_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok);
+int kosk_fetch_proofs_fmt(kosk_ctx *ctx, int fmt, int n, uint8_t *out);
+int kosk_stage_verifier_inputs_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *in, const uint8_t *pk);
 
 /* ---- Kyber KEM on the keys this library makes and vouches for: crypto_kem_enc_derand / crypto_kem_enc / crypto_kem_dec
  * (kyber/kem.c:76-96, :113-121, :140-169; indcpa_enc / indcpa_dec, kyber/indcpa.c:264-336), bit-exact, for kyber_k 2 / 3 / 4, n items
@@ -429,7 +462,9 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * 18 launches of k_wipe (kosk_wipe_secrets, the wipe at the end of a call under KOSK_WIPE_CALL, kosk_wipe_device),
  * 19 launches of k_kem_key_setup (one per kosk_kem_key_set), 20 kem_enc_key / 21 kem_dec_key: launch groups of kosk_kem_enc_key /
  * kosk_kem_dec_key (ids 12 / 13 do not move for them),
- * 22 launches of k_dense_check (the codeword check: one per chunk of kosk_transcode_batch to dense or kosk_dense_check_device sub-batch). */
+ * 22 launches of k_dense_check (the codeword check: one per chunk of kosk_transcode_batch to dense or kosk_dense_check_device sub-batch),
+ * 23 refills of kosk-dense-v2 (k_dense2_setup + k_dense2_fill) / 24 launches of k_dense2_check, counted like 14 / 22, which do not move
+ * for v2 work. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

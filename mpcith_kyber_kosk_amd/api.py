@@ -202,6 +202,21 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_transcode_batch")):
         sig.update(transcode)
+    # dense wire format kosk-dense-v2 and the calls that take the packed format as an argument; optional under the same rule (and only then)
+    dense2 = {
+        "kosk_dense2_proof_bytes": (sz, [C.c_int]),
+        "kosk_proof_dense2_pack": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_proof_dense2_unpack": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_dense2_fill_device": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+        "kosk_dense2_check_device": (C.c_int, [vp, C.c_int, vp, sz, vp]),
+        "kosk_verifiable_keygen_batch_fmt": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verifiable_keygen_seeded_batch_fmt": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, vp]),
+        "kosk_verify_batch_fmt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+        "kosk_fetch_proofs_fmt": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "kosk_stage_verifier_inputs_fmt": (C.c_int, [vp, C.c_int, C.c_int, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_dense2_proof_bytes")):
+        sig.update(dense2)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -236,7 +251,10 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_wipe_secrets", "kosk_set_wipe", "kosk_secret_scan", "kosk_wipe_device", "kosk_wipe_timing",
            "kosk_kem_key_set", "kosk_kem_key_state", "kosk_kem_key_clear", "kosk_kem_enc_key", "kosk_kem_dec_key",
            "kosk_force_opened_candidates", "kosk_opened_tables",
-           "kosk_format_bytes", "kosk_transcode_batch", "kosk_dense_check_device"]
+           "kosk_format_bytes", "kosk_transcode_batch", "kosk_dense_check_device",
+           "kosk_dense2_proof_bytes", "kosk_proof_dense2_pack", "kosk_proof_dense2_unpack", "kosk_dense2_fill_device", "kosk_dense2_check_device",
+           "kosk_verifiable_keygen_batch_fmt", "kosk_verifiable_keygen_seeded_batch_fmt", "kosk_verify_batch_fmt", "kosk_fetch_proofs_fmt",
+           "kosk_stage_verifier_inputs_fmt"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -256,6 +274,7 @@ KEYPAIR_COIN_BYTES = 64  # d || z of crypto_kem_keypair_derand
 KEYCHK_HASH, KEYCHK_PK_RANGE, KEYCHK_S_RANGE = 1, 2, 4  # KOSK_KEYCHK_*
 KEM_KEY_NONE, KEM_KEY_PK, KEM_KEY_SK = 0, 1, 2  # KOSK_KEM_KEY_*
 FMT_IMAGE, FMT_COMPACT, FMT_DENSE = 0, 1, 2  # KOSK_FMT_*
+FMT_DENSE2 = 4  # KOSK_FMT_DENSE2 (kosk-dense-v2); 3 is not a format
 
 
 def options(**fields):
@@ -274,7 +293,27 @@ def proof_bytes(k): return lib.kosk_proof_bytes(k)
 def tape_bytes(k): return lib.kosk_tape_bytes(k)
 def ct_bytes(k): return lib.kosk_ct_bytes(k)
 def dense_proof_bytes(k): return lib.kosk_dense_proof_bytes(k)
+def dense2_proof_bytes(k): return lib.kosk_dense2_proof_bytes(k)
 def format_bytes(k, fmt): return lib.kosk_format_bytes(k, fmt)
+
+
+def proof_dense2_pack(k, pi):
+    """host codec of kosk-dense-v2 (kosk_proof_dense2_pack) -> (return code, record): 0, -1 a stored value >= 4096, -2 a malformed I or
+    a dropped row that is not the refill; the record is only meaningful for 0"""
+    if len(pi) != proof_bytes(k):
+        raise KoskError("proof_dense2_pack: an image of kosk_proof_bytes")
+    out = C.create_string_buffer(dense2_proof_bytes(k))
+    rc = lib.kosk_proof_dense2_pack(k, C.c_char_p(bytes(pi)), out)
+    return rc, out.raw
+
+
+def proof_dense2_unpack(k, rec):
+    """kosk_proof_dense2_unpack -> (status, image): status 1 = malformed opened list (the dropped rows are zero)"""
+    if len(rec) != dense2_proof_bytes(k):
+        raise KoskError("proof_dense2_unpack: a record of kosk_dense2_proof_bytes")
+    out = C.create_string_buffer(proof_bytes(k))
+    rc = lib.kosk_proof_dense2_unpack(k, C.c_char_p(bytes(rec)), out)
+    return rc, out.raw
 
 
 def dense_pack(k, pi):
@@ -599,18 +638,24 @@ class Kosk:
         sp, ss, n, _keep = self._seed_arg(seeds, n, seed_stride)
         self._chk(lib.kosk_tape_expand_device(self._h, n, sp, ss, d_tapes, tape_stride), "tape_expand_device")
 
-    # ---- the three wire formats (FMT_IMAGE / FMT_COMPACT / FMT_DENSE): one body per operation, the library's functions by format ----
+    # ---- the wire formats (FMT_IMAGE / FMT_COMPACT / FMT_DENSE / FMT_DENSE2): one body per operation, the library's functions by format ----
     # format -> (suffix of the public names, size function, then the library's keygen, seeded keygen, verify, fetch and stage functions)
     _FMT = {fmt: (sfx, size) + tuple(name + sfx for name in ("kosk_verifiable_keygen_batch", "kosk_verifiable_keygen_seeded_batch", "kosk_verify_batch",
                                                               "kosk_fetch_proofs", "kosk_stage_verifier_inputs"))
             for fmt, sfx, size in ((FMT_IMAGE, "", "kosk_proof_bytes"), (FMT_COMPACT, "_compact", "kosk_compact_proof_bytes"),
                                    (FMT_DENSE, "_dense", "kosk_dense_proof_bytes"))}
+    # kosk-dense-v2 has no names of its own in the library: the _fmt calls, with the format right behind the handle
+    _FMT[FMT_DENSE2] = ("_dense2", "kosk_dense2_proof_bytes") + tuple(name + "_fmt" for name in _FMT[FMT_IMAGE][2:])
     _KEYGEN, _KEYGEN_SEEDED, _VERIFY, _FETCH, _STAGE = 2, 3, 4, 5, 6
 
     def _fmt(self, fmt, op):
         """(suffix, record size, the library's function for `op`) of a format"""
         row = self._FMT[fmt]
-        return row[0], getattr(lib, row[1])(self.k), getattr(lib, row[op])
+        fn = getattr(lib, row[op])
+        if row[op].endswith("_fmt"):
+            by_fmt = fn
+            fn = lambda h, *args: by_fmt(h, fmt, *args)
+        return row[0], getattr(lib, row[1])(self.k), fn
 
     def _keygen(self, fmt, tapes, n, seeds, seed_stride):
         if seeds is not None:
@@ -658,8 +703,15 @@ class Kosk:
         """verifiable_keygen with the proofs in the dense wire format kosk-dense-v1 (kosk_verifiable_keygen_[seeded_]batch_dense)"""
         return self._keygen(FMT_DENSE, tapes, n, seeds, seed_stride)
 
+    def verifiable_keygen_dense2(self, tapes=None, n=None, seeds=None, seed_stride=None):
+        """verifiable_keygen with the proofs in the dense wire format kosk-dense-v2 (kosk_verifiable_keygen_[seeded_]batch_fmt)"""
+        return self._keygen(FMT_DENSE2, tapes, n, seeds, seed_stride)
+
     def verify(self, pis, pks): return self._verify(FMT_IMAGE, pis, pks)
     def verify_dense(self, recs, pks): return self._verify(FMT_DENSE, recs, pks)
+    def verify_dense2(self, recs, pks): return self._verify(FMT_DENSE2, recs, pks)
+    def fetch_proofs_dense2(self, n): return self._fetch(FMT_DENSE2, n)
+    def stage_verifier_inputs_dense2(self, recs, pks): self._stage(FMT_DENSE2, recs, pks)
     def fetch_proofs(self, n): return self._fetch(FMT_IMAGE, n)
     def fetch_proofs_compact(self, n): return self._fetch(FMT_COMPACT, n)
     def fetch_proofs_dense(self, n): return self._fetch(FMT_DENSE, n)
@@ -684,6 +736,15 @@ class Kosk:
         """kernel level: the codeword check on n images in HBM, read only (int device pointers); d_status[b] 0, 1 malformed I, 2 a row
         407..1303 of a listed field that is not the refill of rows 0..406"""
         self._chk(lib.kosk_dense_check_device(self._h, n, d_images, image_stride, d_status), "dense_check_device")
+
+    def dense2_fill_device(self, n, d_images, image_stride, d_status):
+        """kernel level: refill the dropped rows of kosk-dense-v2 (407.. of five fields, 151.. of the eta fields, 557.. of the u fields) of n
+        images in HBM, in place (int device pointers)"""
+        self._chk(lib.kosk_dense2_fill_device(self._h, n, d_images, image_stride, d_status), "dense2_fill_device")
+
+    def dense2_check_device(self, n, d_images, image_stride, d_status):
+        """kernel level: the codeword check of kosk-dense-v2 on n images in HBM, read only (int device pointers); d_status[b] 0, 1, 2"""
+        self._chk(lib.kosk_dense2_check_device(self._h, n, d_images, image_stride, d_status), "dense2_check_device")
 
     def transcode(self, records, from_fmt, to_fmt, n=None, out=None):
         """kosk_transcode_batch: records of format from_fmt into format to_fmt (FMT_IMAGE / FMT_COMPACT / FMT_DENSE) -> (statuses, records).
@@ -1064,6 +1125,8 @@ class Kosk:
     PATH_KEM_ENC_KEY = 20
     PATH_KEM_DEC_KEY = 21
     PATH_DENSE_CHECK = 22
+    PATH_DENSE2_FILL = 23
+    PATH_DENSE2_CHECK = 24
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

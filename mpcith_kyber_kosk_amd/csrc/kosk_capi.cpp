@@ -992,6 +992,41 @@ int kosk_verify_batch(kosk_ctx *ctx, int n, const uint8_t *pi, const uint8_t *pk
 int kosk_verify_batch_compact(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok) { return verify_batch_fmt(ctx, __func__, n, FMT_COMPACT, in, pk, ok); }
 int kosk_verify_batch_dense(kosk_ctx *ctx, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok) { return verify_batch_fmt(ctx, __func__, n, FMT_DENSE, in, pk, ok); }
 
+// ---- the same five calls with the packed format as an argument (KOSK_FMT_COMPACT, KOSK_FMT_DENSE, KOSK_FMT_DENSE2): the bodies above, so
+// a further format needs no further names.  Anything else, the image included (it has the unsuffixed calls), is refused
+static const char WHY_FMT[] = "unknown format: a _fmt call takes KOSK_FMT_COMPACT, KOSK_FMT_DENSE or KOSK_FMT_DENSE2";
+static bool packed_fmt(int fmt) { return fmt == FMT_COMPACT || fmt == FMT_DENSE || fmt == FMT_DENSE2; }
+int kosk_verifiable_keygen_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *tapes, size_t tape_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
+{
+    if (!ctx) return -1;
+    if (!packed_fmt(fmt)) return refuse(ctx, __func__, WHY_FMT);
+    return keygen_batch_src(ctx, __func__, n, false, tapes, tape_stride, pk, sk, out, fmt);
+}
+int kosk_verifiable_keygen_seeded_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *out)
+{
+    if (!ctx) return -1;
+    if (!packed_fmt(fmt)) return refuse(ctx, __func__, WHY_FMT);
+    return keygen_batch_src(ctx, __func__, n, true, seeds, seed_stride, pk, sk, out, fmt);
+}
+int kosk_verify_batch_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *in, const uint8_t *pk, uint8_t *ok)
+{
+    if (!ctx) return -1;
+    if (!packed_fmt(fmt)) return refuse(ctx, __func__, WHY_FMT);
+    return verify_batch_fmt(ctx, __func__, n, fmt, in, pk, ok);
+}
+int kosk_fetch_proofs_fmt(kosk_ctx *ctx, int fmt, int n, uint8_t *out)
+{
+    if (!ctx) return -1;
+    if (!packed_fmt(fmt)) return refuse(ctx, __func__, WHY_FMT);
+    return fetch_fmt(ctx, __func__, n, fmt, out);
+}
+int kosk_stage_verifier_inputs_fmt(kosk_ctx *ctx, int fmt, int n, const uint8_t *in, const uint8_t *pk)
+{
+    if (!ctx) return -1;
+    if (!packed_fmt(fmt)) return refuse(ctx, __func__, WHY_FMT);
+    return stage_fmt(ctx, __func__, n, fmt, in, pk);
+}
+
 // ---- second-level entry points (kosk_split.cpp) -----------------------------------------------------------
 size_t kosk_randomness_bytes(int k) { Params p; return make_params(k, p) ? randomness_bytes(p) : 0; }
 size_t kosk_range_proof_bytes(int k) { Params p; return make_params(k, p) ? range_proof_bytes(p) : 0; }
@@ -1100,8 +1135,43 @@ int kosk_dense_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_
     GUARD_END
 }
 
+// ---- dense wire format kosk-dense-v2 (kosk_dense.hip): the same codec and kernels on the second field plan ----
+size_t kosk_dense2_proof_bytes(int k) { Params p; return make_params(k, p) ? make_dense_plan(p, FMT_DENSE2).bytes : 0; }
+int kosk_proof_dense2_pack(int k, const uint8_t *pi, uint8_t *out)
+{
+    Params p;
+    if (!make_params(k, p) || !pi || !out) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    return dense_encode(p, pi, out, FMT_DENSE2);
+    GUARD_END
+}
+int kosk_proof_dense2_unpack(int k, const uint8_t *in, uint8_t *pi)
+{
+    Params p;
+    if (!make_params(k, p) || !pi || !in) return -1;
+    return guard(static_cast<const kosk_ctx *>(nullptr), __func__, [&]() -> int {
+    return dense_decode(p, in, pi, FMT_DENSE2);
+    GUARD_END
+}
+int kosk_dense2_fill_device(kosk_ctx *ctx, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    if (!ctx || n < 1 || !d_images || !d_status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return dense_fill_device(*ctx->c, n, d_images, image_stride, d_status, false, FMT_DENSE2);
+    GUARD_END
+}
+int kosk_dense2_check_device(kosk_ctx *ctx, int n, const uint8_t *d_images, size_t image_stride, uint32_t *d_status)
+{
+    if (!ctx || n < 1 || !d_images || !d_status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return dense_fill_device(*ctx->c, n, const_cast<uint8_t *>(d_images), image_stride, d_status, true, FMT_DENSE2); // the check kernel takes them const
+    GUARD_END
+}
+
 // ---- transcoding between the wire formats (kosk_compact.hip: transcode) -----------------------------------------------------------
-static_assert((int)KOSK_FMT_IMAGE == (int)FMT_IMAGE && (int)KOSK_FMT_COMPACT == (int)FMT_COMPACT && (int)KOSK_FMT_DENSE == (int)FMT_DENSE, "kosk_mi355x.h and kosk_ctx.hpp");
+static_assert((int)KOSK_FMT_IMAGE == (int)FMT_IMAGE && (int)KOSK_FMT_COMPACT == (int)FMT_COMPACT && (int)KOSK_FMT_DENSE == (int)FMT_DENSE && (int)KOSK_FMT_DENSE2 == (int)FMT_DENSE2, "kosk_mi355x.h and kosk_ctx.hpp");
 size_t kosk_format_bytes(int k, int fmt) { Params p; return make_params(k, p) ? format_bytes(p, fmt) : 0; }
 // unmerged, on sub-context 0 (the handle's own stream), chunks of its batch size; brings no secret onto the handle (no wipe under KOSK_WIPE_CALL)
 int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status)
@@ -1110,7 +1180,7 @@ int kosk_transcode_batch(kosk_ctx *ctx, int n, int from, const uint8_t *in, int 
     if (!in || !out || !status) return refuse(ctx, __func__, "null pointer");
     if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
     const size_t ib = format_bytes(ctx->c->P, from), ob = format_bytes(ctx->c->P, to);
-    if (!ib || !ob) return refuse(ctx, __func__, "unknown format (KOSK_FMT_IMAGE, KOSK_FMT_COMPACT, KOSK_FMT_DENSE)");
+    if (!ib || !ob) return refuse(ctx, __func__, "unknown format (KOSK_FMT_IMAGE, KOSK_FMT_COMPACT, KOSK_FMT_DENSE, KOSK_FMT_DENSE2)");
     if (from == to) return refuse(ctx, __func__, "from and to are the same format");
     const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), o0 = reinterpret_cast<uintptr_t>(out);
     if (i0 < o0 + (size_t)n * ob && o0 < i0 + (size_t)n * ib) return refuse(ctx, __func__, "in and out overlap");

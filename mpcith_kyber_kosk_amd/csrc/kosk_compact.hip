@@ -150,7 +150,7 @@ __global__ __launch_bounds__(256) void k_unpack_proofs(const uint8_t *__restrict
 
 size_t format_bytes(const Params &P, int fmt)
 {
-    return fmt == FMT_IMAGE ? P.proof_bytes : fmt == FMT_COMPACT ? make_compact_plan(P).bytes : fmt == FMT_DENSE ? make_dense_plan(P).bytes : 0;
+    return fmt == FMT_IMAGE ? P.proof_bytes : fmt == FMT_COMPACT ? make_compact_plan(P).bytes : fmt_dense(fmt) ? make_dense_plan(P, fmt).bytes : 0;
 }
 
 void ensure_plans(Ctx &c)
@@ -160,6 +160,8 @@ void ensure_plans(Ctx &c)
     c.compact_stride = (c.cplan.bytes + 63) / 64 * 64;
     c.dplan = make_dense_plan(c.P); // dense records are shorter and go through the same staging buffers
     c.dense_stride = (c.dplan.bytes + 63) / 64 * 64;
+    c.d2plan = make_dense_plan(c.P, FMT_DENSE2);
+    c.dense2_stride = (c.d2plan.bytes + 63) / 64 * 64;
 }
 
 static int ensure_compact(Ctx &c)
@@ -196,13 +198,13 @@ static int unpack_launch(Ctx &c, int n, const WireFmt &w, const uint8_t *d_rec, 
 {
     const Params &P = c.P;
     const CompactPlan &plan = *w.plan;
-    if (w.id == FMT_DENSE)
+    if (fmt_dense(w.id))
         for (int f = 0; f < NFIELDS; f++)
             if (!plan.f[f].raw && (size_t)plan.f[f].n * 2 < P.size[f])
                 HIPCHK(hipMemset2DAsync(d_img + P.off[f] + (size_t)plan.f[f].n * 2, c.image_stride, 0, P.size[f] - (size_t)plan.f[f].n * 2, n, c.stream));
     hipLaunchKernelGGL(k_unpack_proofs, dim3(16, NFIELDS, n), dim3(256), 0, c.stream, d_rec, w.stride, d_img, c.image_stride, plan);
     HIPCHK(hipGetLastError());
-    if (w.id == FMT_DENSE && dense_fill_launch(c, n, d_img, c.image_stride, d_status)) return -1;
+    if (fmt_dense(w.id) && dense_fill_launch(c, n, d_img, c.image_stride, d_status, false, w.id)) return -1;
     return 0;
 }
 
@@ -234,7 +236,7 @@ int stage_verifier_inputs_packed(Ctx &c, int n, int fmt, const uint8_t *in, cons
     HIPCHK(hipSetDevice(c.device));
     if (ensure_verify_workspace(c)) return -1;
     if (ensure_compact(c)) return -1;
-    if (fmt == FMT_DENSE && ensure_dense_ws(c)) return -1;
+    if (fmt_dense(fmt) && ensure_dense_ws(c)) return -1;
     const Params &P = c.P;
     const WireFmt w = wire_fmt(c, fmt);
     parallel_for(c.pool, n, c.nthreads, [&](int b) {
@@ -253,7 +255,7 @@ int stage_verifier_inputs_packed(Ctx &c, int n, int fmt, const uint8_t *in, cons
     return 0;
 }
 
-// ---- transcoding between the three wire formats (kosk_transcode_batch) ----------------------------------------
+// ---- transcoding between the four wire formats (kosk_transcode_batch) ----------------------------------------
 // Its own workspace, so that nothing resident moves: own_batch 16-byte-aligned images, the records of either side, two status words per
 // proof (the refill's / check's, the pack kernel's overflow flag) and their page-locked mirror.  All public: proofs are
 struct TcWs {
@@ -315,7 +317,7 @@ int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, 
     if (n < 1 || n > c.own_batch) { c.err = "batch size out of range"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (transcode_ensure(c)) return -1;
-    if ((from == FMT_DENSE || to == FMT_DENSE) && ensure_dense_ws(c)) return -1;
+    if ((fmt_dense(from) || fmt_dense(to)) && ensure_dense_ws(c)) return -1;
     TcWs &w = *c.tc;
     uint32_t *d_st = w.d_words, *d_bad = w.d_words + c.own_batch;
     const WireFmt wf = wire_fmt(c, from), wt = wire_fmt(c, to);
@@ -327,9 +329,9 @@ int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, 
     // out
     const uint8_t *d_dst = w.d_img;
     if (to != FMT_IMAGE) {
-        if (to == FMT_DENSE && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st, true)) return -1; // the codeword check
+        if (fmt_dense(to) && dense_fill_launch(c, n, w.d_img, c.image_stride, d_st, true, to)) return -1; // the codeword check
         if (pack_launch(c, n, wt, w.d_img, w.d_out, d_bad)) return -1;
-        hipLaunchKernelGGL(k_zero_failed, dim3(8, n), dim3(256), 0, c.stream, w.d_out, wt.stride, d_st, d_bad, to == FMT_DENSE ? 1 : 0);
+        hipLaunchKernelGGL(k_zero_failed, dim3(8, n), dim3(256), 0, c.stream, w.d_out, wt.stride, d_st, d_bad, fmt_dense(to) ? 1 : 0);
         HIPCHK(hipGetLastError());
         d_dst = w.d_out;
     }
@@ -339,8 +341,8 @@ int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, 
     if (device_error_check(c)) return -1;
     const uint32_t *st = w.h_words, *bad = w.h_words + c.own_batch;
     for (int b = 0; b < n; b++) {
-        const int32_t dec = from == FMT_DENSE ? (int32_t)st[b] : 0; // the decoder's: 1 a malformed I
-        const int32_t enc = to == FMT_IMAGE ? 0 : bad[b] ? -1 : (to == FMT_DENSE && st[b]) ? -2 : 0;
+        const int32_t dec = fmt_dense(from) ? (int32_t)st[b] : 0; // the decoder's: 1 a malformed I
+        const int32_t enc = to == FMT_IMAGE ? 0 : bad[b] ? -1 : (fmt_dense(to) && st[b]) ? -2 : 0;
         status[b] = enc ? enc : dec;
     }
     return 0;

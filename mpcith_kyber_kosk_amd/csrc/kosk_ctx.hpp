@@ -73,7 +73,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
-              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_COUNT };
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -111,9 +111,10 @@ CompactPlan make_compact_plan(const Params &P);
 int compact_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a value >= 4096
 void compact_decode(const Params &P, const uint8_t *in, uint8_t *img);
 // dense wire format kosk-dense-v1 (kosk_dense.hip): the compact layout with rows 0..406 only of the seven low-degree fields
-CompactPlan make_dense_plan(const Params &P);
-int dense_encode(const Params &P, const uint8_t *img, uint8_t *out); // -1: a stored value >= 4096; -2: malformed I, or a dropped row that is not the refill
-int dense_decode(const Params &P, const uint8_t *in, uint8_t *img);  // 0, or 1: malformed I (rows 407..1303 of the seven fields left zero)
+// kosk-dense-v2 (fmt = 4, FMT_DENSE2 below): the eta-gate fields keep rows 0..150 and the two u fields rows 0..556
+CompactPlan make_dense_plan(const Params &P, int fmt = 2);
+int dense_encode(const Params &P, const uint8_t *img, uint8_t *out, int fmt = 2); // -1: a stored value >= 4096; -2: malformed I, or a dropped row that is not the refill
+int dense_decode(const Params &P, const uint8_t *in, uint8_t *img, int fmt = 2);  // 0, or 1: malformed I (the dropped rows of the format's fields left zero)
 
 struct TcWs;  // HBM workspace of kosk_transcode_batch (kosk_compact.hip)
 struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
@@ -324,6 +325,8 @@ struct Ctx {
     // dense wire format: its field plan and record stride in the compact staging buffers; the refill's workspace (allocated on first use)
     CompactPlan dplan{};
     size_t dense_stride = 0;
+    CompactPlan d2plan{}; // kosk-dense-v2
+    size_t dense2_stride = 0;
     uint16_t *d_dense_ws = nullptr;
     uint32_t *d_dense_status = nullptr;
     TcWs *tc = nullptr; // kosk_transcode_batch: allocated at this context's first such call, owned by it like `kem`
@@ -535,18 +538,20 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
                    size_t tape_stride, uint8_t *pi);
 int stage_verifier_inst(Ctx &c, int n, const uint8_t *pi, const uint8_t *inst);
 int ensure_verify_workspace(Ctx &c);
-// ---- wire formats: the image, and the two packed forms of it (kosk_compact.hip, kosk_dense.hip) ----
-enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality)
+// ---- wire formats: the image, and the three packed forms of it (kosk_compact.hip; kosk_dense.hip: v1 and v2) ----
+enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2, FMT_DENSE2 = 4 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality); 3 is no format
+inline bool fmt_dense(int fmt) { return fmt == FMT_DENSE || fmt == FMT_DENSE2; } // a format with dropped rows: refill behind unpack, codeword check before pack
 // what one format is on a context: its field plan (nullptr: the image), the bytes of a record on the wire and its stride in HBM / staging
 struct WireFmt {
     int id;
     const CompactPlan *plan;
     size_t bytes, stride;
 };
-void ensure_plans(Ctx &c); // cplan, dplan and their strides (no buffer); wire_fmt() of a packed format needs it
+void ensure_plans(Ctx &c); // cplan, dplan, d2plan and their strides (no buffer); wire_fmt() of a packed format needs it
 inline WireFmt wire_fmt(const Ctx &c, int fmt)
 {
     if (fmt == FMT_IMAGE) return WireFmt{fmt, nullptr, c.P.proof_bytes, c.image_stride};
+    if (fmt == FMT_DENSE2) return WireFmt{fmt, &c.d2plan, c.d2plan.bytes, c.dense2_stride};
     return fmt == FMT_DENSE ? WireFmt{fmt, &c.dplan, c.dplan.bytes, c.dense_stride} : WireFmt{fmt, &c.cplan, c.cplan.bytes, c.compact_stride};
 }
 size_t format_bytes(const Params &P, int fmt); // of one record; 0 for an unknown format
@@ -569,8 +574,9 @@ inline int stage_verifier_inputs(Ctx &c, int n, int fmt, const uint8_t *in, cons
 int ensure_dense_ws(Ctx &c);
 // check = true: the codeword check (k_dense_check): the refill compared with the images' own rows 407..1303 instead of stored, the images only read
 // (the pointer is not const because the fill shares the signature); d_status 0, 1 malformed I, 2 a dropped row that is not the refill
-int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false); // n <= own_batch, on c.stream, not synchronised
-int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false);
+// fmt: FMT_DENSE or FMT_DENSE2 (its own kernels, dropped rows and counters)
+int dense_fill_launch(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false, int fmt = FMT_DENSE); // n <= own_batch, on c.stream, not synchronised
+int dense_fill_device(Ctx &c, int n, uint8_t *d_images, size_t image_stride, uint32_t *d_status, bool check = false, int fmt = FMT_DENSE);
 // transcoding between the wire formats (kosk_compact.hip): n <= own_batch records, `in` / `out` host or device memory of any alignment,
 // status[b] (host) the host codecs' composition (kosk_mi355x.h); touches nothing but its own workspace and the refill's scratch.  Synchronised
 int transcode(Ctx &c, int n, int from, const uint8_t *in, int to, uint8_t *out, int32_t *status);
