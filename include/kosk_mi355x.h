@@ -91,7 +91,7 @@ int kosk_set_entropy(kosk_ctx *ctx, int mode);
 
 /* ---- Erasing secrets.  The handle keeps an inventory of every buffer it owns, in HBM and in page-locked host
  * memory, and of which of them can hold secret-derived bytes: the row matrix, tapes and seeds, s / e and their NTTs, the NTT(s) bytes
- * and sha3_512 output of the key records, the sk copies and salts of the calls on existing keys, and the KEM workspace except its
+ * and sha3_512 output of the key records, the sk copies and salts of the calls on existing keys, the offline bank, and the KEM workspace except its
  * public keys, ciphertexts, A, H(pk) and flags.
  * kosk_wipe_secrets zeroes all of those now (one launch of k_wipe for the HBM regions, the host for the page-locked staging) and returns
  * when that is done.  It must not be called while another thread is inside a call on the handle.  Afterwards the handle is as usable
@@ -102,9 +102,11 @@ int kosk_set_entropy(kosk_ctx *ctx, int mode);
  * kosk_set_wipe(KOSK_WIPE_CALL): every entry point that brings secrets onto the handle ends with that wipe, on success and on every
  * error return: the key generations in every form, kosk_prove_resident, kosk_prove_prepared, kosk_prepare_*, kosk_kem_enc_batch /
  * _dec_batch / _enc_verified / _keypair_batch, kosk_kem_check_sk, kosk_keyseed_device, kosk_tape_expand_device and kosk_prove_keys_*;
+ * kosk_bank_fill, kosk_prove_keys_banked_batch and kosk_verifiable_keygen_banked_batch (everything but the unconsumed entries of the
+ * offline bank, a long-lived secret like the resident key; only kosk_wipe_secrets, kosk_bank_reserve(0) and kosk_destroy erase those);
  * kosk_kem_enc_key / _dec_key (their per-call scratch; the resident key of kosk_kem_key_set is a long-lived secret and stays);
  * chunked calls and streams > 1 wipe every sub-context.  Not the staging calls (kosk_stage_prover_inputs*, kosk_stage_prover_keys*,
- * kosk_witness_from_sk): their secrets are the input of the kosk_prove_resident that follows, which wipes when it ends.  A member of
+ * kosk_stage_prover_keys_banked, kosk_witness_from_sk): their secrets are the input of the kosk_prove_resident that follows, which wipes when it ends.  A member of
  * a cohort (combine >= 2) in this mode keeps its calls out of merged runs, exactly as an armed handle does, and wipes its own block of
  * the shared workspace.  One difference: kosk_combine_stats counts an armed member's solo runs (calls == members) and leaves the solo
  * runs of a member in this mode out (0, 0).  KOSK_WIPE_OFF is the default; any other mode: -1, nothing changed.  With the mode off every call returns
@@ -448,6 +450,60 @@ int kosk_stage_prover_keys_seeded(kosk_ctx *ctx, int n, const uint8_t *sk, const
 int kosk_prove_keys_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, uint8_t *pi, uint8_t *ok);
 int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok);
 
+/* ---- The offline bank (INTEGRATION.md 14 is the normative text; the reference's offline / online split, mlwe_prover.cpp:4-59 against
+ * :81-).  prepare_randomness and prepare_range_proof need no key: their output -- the 2M sharings of f / NTT f and the
+ * 2K(2 eta1 + 1) range sharings of a proof -- can be made ahead of time and wait in HBM, and a proof then costs only the part that depends
+ * on the key.  With M = 71 + 2K, E = 2 eta1 + 1 and T = kosk_tape_bytes(k) = 64 + 32M + 302 (2M + 2KE + 3K + 4K eta1) a tape has three
+ * SECTIONS: 0 the key seed [0, 64), 1 offline [64, O) with O = 64 + 32M + 302 (2M + 2KE), 2 online [O, T).
+ * A bank ENTRY is the offline rows of one proof as the offline pass leaves them in the row matrix (whole rows, packed secrets included),
+ * kosk_bank_entry_bytes(k) bytes of HBM.  The bank is a FIFO ring of `capacity` entries owned by the handle: kosk_bank_fill appends,
+ * and proof b of a consuming call takes the b-th oldest entry, also across max_batch chunks.
+ * THE CONTRACT of every consuming call: for entry e and proof b it returns byte for byte (ok[], zero images, return codes and resident
+ * state included) what the non-banked call returns on the SPLICED tape: key seed || offline section of the tape e was filled from ||
+ * online section of the tape given to the consuming call.  For seeds "the tape" is kosk_tape_from_seed(seed).  The same tape on both
+ * sides gives the proof of the existing call on that tape.  ONE EXCEPTION in the resident state: a banked proof leaves no staged prover
+ * inputs.  After kosk_verifiable_keygen_banked_batch, after kosk_prove_keys_banked_batch, and after the ONE kosk_prove_resident behind
+ * kosk_stage_prover_keys_banked, kosk_prove_resident returns -1 ("no resident prover inputs") until a staging call has run: the handle
+ * never held these proofs' offline sections as a tape, and the rows of a consumed entry serve one proof.  The proofs, pk bytes, A and t
+ * stay resident as after the non-banked call.
+ * EXACTLY ONCE: two proofs on one entry open s + r and s' + r with the same r and so leak s - s'.  An entry is consumed exactly once:
+ * the kernel that copies it out zeroes it in the same pass, taken entries never come back whatever happens afterwards (a later HIP error
+ * included), and a position with ok[b] = 0 consumes its entry like any other.
+ * Randomness arguments of the four calls that take them: at most one of tapes / seeds non-NULL (both: -1).  tapes are in the full format
+ * of every other call, tape_stride >= T, host or device memory; only the section the call consumes is read (fill: 1; prove: 2; key
+ * generation: 0 and 2), and from host memory only that section crosses PCIe.  seeds follow the seeded calls.  Both NULL: the handle's
+ * entropy mode -- KOSK_ENTROPY_TAPE the reference's draws for that section in its order (fill: M x 32 then (2M + 2KE) x 302; consume:
+ * (3K + 4K eta1) x 302, the key generation form with its 64-byte draw in front), KOSK_ENTROPY_SEED one 32-byte draw per entry / proof.
+ * Every refusal (-1 with a kosk_last_error text) consumes nothing and writes nothing: argument errors, n larger than the level ("bank is
+ * empty" at level 0), a full bank.  The bank needs streams = 1; on a member of a cohort (combine >= 2) the calls run unmerged on the
+ * member's own block, as kosk_prove_keys_batch does.  An armed handle (kosk_set_contexts) makes bound proofs as the non-banked calls do.
+ * ERASURE: the bank is a secret buffer of the inventory.  kosk_wipe_secrets zeroes it and sets the level to 0;
+ * the wipe at the end of a call under KOSK_WIPE_CALL leaves unconsumed entries alone (a long-lived secret, like the key slot of 8.2) and
+ * clears everything else; kosk_destroy and kosk_bank_reserve(0) wipe before they free; kosk_secret_scan sees the bank. */
+size_t kosk_bank_entry_bytes(int kyber_k);                                            /* 0 for a bad k */
+int kosk_tape_section(int kyber_k, int section, size_t *offset, size_t *size);        /* -1: bad k, bad section, NULL pointer */
+/* HBM for exactly `capacity` entries: the handle's own allocation, made here and nowhere else.  Again only while the bank is empty (the
+ * old allocation is wiped and freed first); 0 wipes and frees.  -1: capacity < 0, a non-empty bank, streams > 1 */
+int kosk_bank_reserve(kosk_ctx *ctx, int capacity);
+int kosk_bank_level(const kosk_ctx *ctx, int *ready, int *capacity);
+/* n >= 1 entries appended in order, chunked by max_batch: the offline pass, then k_bank_put.  ready + n > capacity: -1, nothing changes.
+ * Staged prover inputs (kosk_stage_prover_*) do not survive a fill */
+int kosk_bank_fill(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride);
+/* kosk_stage_prover_keys on n <= max_batch bank entries; then kosk_prove_resident(n), ONCE, which runs the online part only, and
+ * kosk_fetch_proofs*.  After kosk_wipe_secrets kosk_prove_resident fails as after any staging call */
+int kosk_stage_prover_keys_banked(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride,
+                                  const uint8_t *seeds, size_t seed_stride, uint8_t *ok);
+/* kosk_prove_keys_batch on n >= 1 bank entries */
+int kosk_prove_keys_banked_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride,
+                                 const uint8_t *seeds, size_t seed_stride, uint8_t *pi, uint8_t *ok);
+/* kosk_verifiable_keygen_batch on n >= 1 bank entries: the key seed and the online section of the tapes are read */
+int kosk_verifiable_keygen_banked_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride,
+                                        const uint8_t *seeds, size_t seed_stride, uint8_t *pk, uint8_t *sk, uint8_t *pi);
+/* diagnostic (tools/bank_rate.py): on an EMPTY bank of >= n entries, n <= max_batch: `reps` launches each of k_bank_put and k_bank_take
+ * on n slots, of the runtime's own two strided D2D copies of the same bytes, and of those copies plus its fill of the slots; milliseconds
+ * per repetition between two events; bytes = n x kosk_bank_entry_bytes.  The offline rows of the row matrix are overwritten */
+int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *take_ms, double *copy_ms, double *copy_fill_ms, size_t *bytes);
+
 /* Which kernel / copy paths ran on this handle since it was created (the tests of the fallbacks and of the Fiat-Shamir mode assert on
  * these).  ids: 0 commitment hash with LDS-DMA staging, 1 without (a layout the staged kernel cannot take: unaligned rows),
  * 2 shared-table products on k_table_gemm / k_table_gemm_p (every mod-q product), 3 retired, always 0 (the generic limb GEMM, which no call
@@ -464,7 +520,9 @@ int kosk_prove_keys_seeded_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const 
  * kosk_kem_dec_key (ids 12 / 13 do not move for them),
  * 22 launches of k_dense_check (the codeword check: one per chunk of kosk_transcode_batch to dense or kosk_dense_check_device sub-batch),
  * 23 refills of kosk-dense-v2 (k_dense2_setup + k_dense2_fill) / 24 launches of k_dense2_check, counted like 14 / 22, which do not move
- * for v2 work. */
+ * for v2 work,
+ * 25 launches of k_bank_put (one per chunk of kosk_bank_fill) / 26 launches of k_bank_take (one per chunk of a call that consumes bank
+ * entries); the diagnostic kosk_bank_timing moves both by reps + 1. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -217,6 +217,21 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_dense2_proof_bytes")):
         sig.update(dense2)
+    # the offline bank; optional under the same rule (and only then)
+    bank = {
+        "kosk_bank_entry_bytes": (sz, [C.c_int]),
+        "kosk_tape_section": (C.c_int, [C.c_int, C.c_int, C.POINTER(sz), C.POINTER(sz)]),
+        "kosk_bank_reserve": (C.c_int, [vp, C.c_int]),
+        "kosk_bank_level": (C.c_int, [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+        "kosk_bank_fill": (C.c_int, [vp, C.c_int, vp, sz, vp, sz]),
+        "kosk_stage_prover_keys_banked": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, sz, vp]),
+        "kosk_prove_keys_banked_batch": (C.c_int, [vp, C.c_int, vp, vp, sz, vp, sz, vp, vp]),
+        "kosk_verifiable_keygen_banked_batch": (C.c_int, [vp, C.c_int, vp, sz, vp, sz, vp, vp, vp]),
+        "kosk_bank_timing": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                       C.POINTER(sz)]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_bank_reserve")):
+        sig.update(bank)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -254,7 +269,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_format_bytes", "kosk_transcode_batch", "kosk_dense_check_device",
            "kosk_dense2_proof_bytes", "kosk_proof_dense2_pack", "kosk_proof_dense2_unpack", "kosk_dense2_fill_device", "kosk_dense2_check_device",
            "kosk_verifiable_keygen_batch_fmt", "kosk_verifiable_keygen_seeded_batch_fmt", "kosk_verify_batch_fmt", "kosk_fetch_proofs_fmt",
-           "kosk_stage_verifier_inputs_fmt"]
+           "kosk_stage_verifier_inputs_fmt",
+           "kosk_bank_entry_bytes", "kosk_tape_section", "kosk_bank_reserve", "kosk_bank_level", "kosk_bank_fill", "kosk_stage_prover_keys_banked",
+           "kosk_prove_keys_banked_batch", "kosk_verifiable_keygen_banked_batch", "kosk_bank_timing"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -295,6 +312,26 @@ def ct_bytes(k): return lib.kosk_ct_bytes(k)
 def dense_proof_bytes(k): return lib.kosk_dense_proof_bytes(k)
 def dense2_proof_bytes(k): return lib.kosk_dense2_proof_bytes(k)
 def format_bytes(k, fmt): return lib.kosk_format_bytes(k, fmt)
+def bank_entry_bytes(k): return lib.kosk_bank_entry_bytes(k)
+
+
+TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
+
+
+def tape_section(k, section):
+    """kosk_tape_section -> (offset, size) of section 0 key seed / 1 offline / 2 online of a tape"""
+    off, size = C.c_size_t(), C.c_size_t()
+    if lib.kosk_tape_section(k, section, C.byref(off), C.byref(size)):
+        raise KoskError("tape_section: bad kyber_k or section")
+    return off.value, size.value
+
+
+def tape_splice(k, offline_tape, online_tape, seed_tape=None):
+    """the spliced tape of INTEGRATION.md 14: key seed (of seed_tape, default online_tape) || offline section of offline_tape || online
+    section of online_tape"""
+    (o0, s0), (o1, s1), (o2, s2) = (tape_section(k, i) for i in range(3))
+    head = online_tape if seed_tape is None else seed_tape
+    return bytes(head[o0:o0 + s0]) + bytes(offline_tape[o1:o1 + s1]) + bytes(online_tape[o2:o2 + s2])
 
 
 def proof_dense2_pack(k, pi):
@@ -1112,6 +1149,64 @@ class Kosk:
         self._chk(fn(self._h, n, sp, rp, stride, pi, ok), "prove_keys")
         return _cut(pi, self.proof_bytes, n), [b == 1 for b in ok.raw[:n]]
 
+    # the offline bank
+    def bank_reserve(self, capacity):
+        self._chk(lib.kosk_bank_reserve(self._h, int(capacity)), "bank_reserve")
+
+    def bank_level(self):
+        """kosk_bank_level -> (ready, capacity)"""
+        r, c_ = C.c_int(), C.c_int()
+        self._chk(lib.kosk_bank_level(self._h, C.byref(r), C.byref(c_)), "bank_level")
+        return r.value, c_.value
+
+    def _bank_rand(self, tapes, seeds, n, seed_stride):
+        """the randomness arguments of the bank calls -> (tapes pointer, tape stride, seeds pointer, seed stride, keepalive)"""
+        seeded, rp, stride, keep = self._key_rand(tapes, seeds, n, seed_stride)
+        return (None, 0, rp, stride, keep) if seeded else (rp, stride, None, 0, keep)
+
+    def bank_fill(self, n=None, tapes=None, seeds=None, seed_stride=None):
+        """kosk_bank_fill: n entries from tapes (list of bytes, or an int DEVICE pointer with n), seeds (see _seed_arg) or, with neither,
+        the handle's entropy mode"""
+        if n is None:
+            n = len(tapes if tapes is not None else seeds)
+        tp, ts, sp, ss, _keep = self._bank_rand(tapes, seeds, n, seed_stride)
+        self._chk(lib.kosk_bank_fill(self._h, n, tp, ts, sp, ss), "bank_fill")
+
+    def stage_prover_keys_banked(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
+        """kosk_stage_prover_keys_banked: as stage_prover_keys, on the n oldest bank entries; then prove_resident(n).  Returns ok"""
+        kp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        tp, ts, sp, ss, _keep = self._bank_rand(tapes, seeds, n, seed_stride)
+        ok = C.create_string_buffer(n)
+        self._chk(lib.kosk_stage_prover_keys_banked(self._h, n, kp, tp, ts, sp, ss, ok), "stage_prover_keys_banked")
+        return [b == 1 for b in ok.raw[:n]]
+
+    def prove_keys_banked(self, sks, tapes=None, seeds=None, n=None, seed_stride=None):
+        """kosk_prove_keys_banked_batch: as prove_keys, on the n oldest bank entries.  Returns (proofs, ok)"""
+        kp, n, _k1 = self._records("sk", sks, n, self.sk_bytes)
+        tp, ts, sp, ss, _keep = self._bank_rand(tapes, seeds, n, seed_stride)
+        ok = C.create_string_buffer(n)
+        pi = C.create_string_buffer(self.proof_bytes * n)
+        self._chk(lib.kosk_prove_keys_banked_batch(self._h, n, kp, tp, ts, sp, ss, pi, ok), "prove_keys_banked")
+        return _cut(pi, self.proof_bytes, n), [b == 1 for b in ok.raw[:n]]
+
+    def verifiable_keygen_banked(self, n=None, tapes=None, seeds=None, seed_stride=None):
+        """kosk_verifiable_keygen_banked_batch: as verifiable_keygen, on the n oldest bank entries.  Returns (pks, sks, proofs)"""
+        if n is None:
+            n = len(tapes if tapes is not None else seeds)
+        tp, ts, sp, ss, _keep = self._bank_rand(tapes, seeds, n, seed_stride)
+        pk = C.create_string_buffer(self.pk_bytes * n)
+        sk = C.create_string_buffer(self.sk_bytes * n)
+        pi = C.create_string_buffer(self.proof_bytes * n)
+        self._chk(lib.kosk_verifiable_keygen_banked_batch(self._h, n, tp, ts, sp, ss, pk, sk, pi), "verifiable_keygen_banked")
+        return _cut(pk, self.pk_bytes, n), _cut(sk, self.sk_bytes, n), _cut(pi, self.proof_bytes, n)
+
+    def bank_timing(self, n, reps=20):
+        """kosk_bank_timing -> dict(put_ms, take_ms, copy_ms, copy_fill_ms, bytes)"""
+        v = [C.c_double() for _ in range(4)]
+        nb = C.c_size_t()
+        self._chk(lib.kosk_bank_timing(self._h, n, reps, *[C.byref(x) for x in v], C.byref(nb)), "bank_timing")
+        return dict(put_ms=v[0].value, take_ms=v[1].value, copy_ms=v[2].value, copy_fill_ms=v[3].value, bytes=nb.value)
+
     PATH_IDS = ["hash_dma", "hash_plain", "table_gemm", "limb_gemm", "copy_direct", "copy_staged", "graph_replay", "digest_copy", "small_copy_kernel",
                 "fs_device", "fs_host", "tape_expand", "kem_enc", "kem_dec"]
 
@@ -1127,6 +1222,8 @@ class Kosk:
     PATH_DENSE_CHECK = 22
     PATH_DENSE2_FILL = 23
     PATH_DENSE2_CHECK = 24
+    PATH_BANK_PUT = 25
+    PATH_BANK_TAKE = 26
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

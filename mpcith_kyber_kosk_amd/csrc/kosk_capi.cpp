@@ -1508,6 +1508,179 @@ int kosk_keyseed_device(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *
     WGUARD_END
 }
 
+// ---- the offline bank (kosk_bank.hip): offline material banked ahead of the key, consumed exactly once ----
+size_t kosk_bank_entry_bytes(int k) { Params p; return make_params(k, p) ? bank_entry_bytes(p) : 0; }
+int kosk_tape_section(int k, int section, size_t *offset, size_t *size)
+{
+    Params p;
+    if (!make_params(k, p) || !offset || !size) return -1;
+    return tape_section(p, section, offset, size) ? 0 : -1;
+}
+static const char *const WHY_BANK_STREAMS = "needs streams = 1 (the bank belongs to one sub-context)";
+static const char *const WHY_BANK_BOTH = "at most one of tapes / seeds";
+// The randomness of a bank call: the caller's tapes (full format) or seeds, or, with neither, draws by the handle's entropy mode -- one seed
+// per item, or the reference's draws for the sections `mask` of a tape in its order, into records that hold those sections only
+struct BankRand {
+    const uint8_t *tapes = nullptr, *seeds = nullptr;
+    size_t tape_stride = 0, seed_stride = 0;
+    bool compact = false; // drawn in tape mode: a record holds only the sections the call consumes
+    std::vector<uint8_t> drawn;
+    ~BankRand() { host_wipe_vec(drawn); }
+    void resolve(const kosk_ctx *ctx, int n, unsigned mask)
+    {
+        if (tapes || seeds) return;
+        const Ctx &c0 = *ctx->c;
+        const Params &P = c0.P;
+        if (c0.entropy_seed) {
+            drawn.resize((size_t)n * SEED_BYTES);
+            draw_seeds(c0, n, drawn.data());
+            seeds = drawn.data();
+            seed_stride = SEED_BYTES;
+            return;
+        }
+        // compact records: exactly the sections of the mask back to back, every byte of them drawn (stage_tape_sections, compact)
+        size_t rec = 0, off = 0, len = 0;
+        for (int sec = 0; sec < 3; sec++)
+            if ((mask >> sec & 1) && tape_section(P, sec, &off, &len)) rec += len;
+        drawn.resize((size_t)n * rec);
+        uint8_t *tp = drawn.data();
+        auto draw = [&](size_t bytes) { if (c0.rb) c0.rb(c0.rb_user, tp, bytes); else os_randombytes(tp, bytes); tp += bytes; };
+        for (int b = 0; b < n; b++) {
+            if (mask >> TAPE_SEC_KEYSEED & 1) draw(64); // kosk.cpp:12
+            if (mask >> TAPE_SEC_OFFLINE & 1) {
+                for (int i = 0; i < P.M; i++) draw(32);                            // mlwe_prover.cpp:9
+                for (int i = 0; i < 2 * P.M + 2 * P.K * P.E; i++) draw(302);       // ss.cpp:5
+            }
+            if (mask >> TAPE_SEC_ONLINE & 1) {
+                tape_section(P, TAPE_SEC_ONLINE, &off, &len);
+                for (size_t i = 0; i < len / 302; i++) draw(302);
+            }
+        }
+        tapes = drawn.data();
+        tape_stride = rec;
+        compact = true;
+    }
+    const uint8_t *tapes_at(int first) const { return tapes ? tapes + (size_t)first * tape_stride : nullptr; }
+    const uint8_t *seeds_at(int first) const { return seeds ? seeds + (size_t)first * seed_stride : nullptr; }
+};
+// the checks the four calls with randomness arguments share, behind bad_args: nullptr, or why the call is refused
+static const char *bank_rand_why(const kosk_ctx *ctx, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride)
+{
+    if (ctx->sub.size() > 1) return WHY_BANK_STREAMS;
+    if (tapes && seeds) return WHY_BANK_BOTH;
+    if (tapes && tape_stride < ctx->c->P.tape_bytes) return WHY_TAPE_STRIDE;
+    if (seeds && seed_stride < SEED_BYTES) return WHY_SEED_STRIDE;
+    return nullptr;
+}
+static const char *bank_level_why(const kosk_ctx *ctx, int n)
+{
+    if (ctx->c->bank_ready == 0) return "bank is empty (kosk_bank_fill makes entries)";
+    return n > ctx->c->bank_ready ? "the bank holds fewer entries than this call has proofs (kosk_bank_level)" : nullptr;
+}
+int kosk_bank_reserve(kosk_ctx *ctx, int capacity)
+{
+    if (!ctx) return -1;
+    if (capacity < 0) return refuse(ctx, __func__, "the capacity cannot be negative");
+    if (ctx->sub.size() > 1) return refuse(ctx, __func__, WHY_BANK_STREAMS);
+    if (ctx->c->bank_ready) return refuse(ctx, __func__, "the bank is not empty: its entries are consumed, or wiped by kosk_wipe_secrets, before it is reserved again");
+    GUARD(ctx)
+    ctx->clear_err();
+    return bank_reserve(*ctx->c, capacity);
+    GUARD_END
+}
+int kosk_bank_level(const kosk_ctx *ctx, int *ready, int *capacity)
+{
+    if (!ctx || !ready || !capacity) return -1;
+    *ready = ctx->c->bank_ready;
+    *capacity = ctx->c->bank_cap;
+    return 0;
+}
+int kosk_bank_fill(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride)
+{
+    if (!ctx || n < 1) return bad_args(ctx, __func__);
+    if (const char *why = bank_rand_why(ctx, tapes, tape_stride, seeds, seed_stride)) return refuse(ctx, __func__, why);
+    if (n > ctx->c->bank_cap - ctx->c->bank_ready) return refuse(ctx, __func__, "the bank has no room for this many entries (kosk_bank_reserve, kosk_bank_level)");
+    WGUARD(ctx)
+    BankRand r;
+    r.tapes = tapes; r.tape_stride = tape_stride; r.seeds = seeds; r.seed_stride = seed_stride;
+    r.resolve(ctx, n, 1u << TAPE_SEC_OFFLINE); // stateful callback: everything sequentially, in entry order
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) { return bank_fill(c, count, r.tapes_at(first), r.tape_stride, r.seeds_at(first), r.seed_stride, r.compact); });
+    WGUARD_END
+}
+int kosk_stage_prover_keys_banked(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride,
+                                  uint8_t *ok)
+{
+    if (!ctx || n < 1 || n > ctx->max_batch || !sk || !ok) return bad_args(ctx, __func__);
+    if (const char *why = bank_rand_why(ctx, tapes, tape_stride, seeds, seed_stride)) return refuse(ctx, __func__, why);
+    if (const char *why = bank_level_why(ctx, n)) return refuse(ctx, __func__, why);
+    GUARD(ctx)
+    ctx->clear_err();
+    BankRand r;
+    r.tapes = tapes; r.tape_stride = tape_stride; r.seeds = seeds; r.seed_stride = seed_stride;
+    r.resolve(ctx, n, 1u << TAPE_SEC_ONLINE);
+    return stage_prover_keys_banked(*ctx->c, n, sk, r.tapes, r.tape_stride, r.seeds, r.seed_stride, ok, r.compact);
+    GUARD_END
+}
+int kosk_prove_keys_banked_batch(kosk_ctx *ctx, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride,
+                                 uint8_t *pi, uint8_t *ok)
+{
+    if (!ctx || n < 1 || !sk || !pi || !ok) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (const char *why = bank_rand_why(ctx, tapes, tape_stride, seeds, seed_stride)) return refuse(ctx, __func__, why);
+    if (const char *why = bank_level_why(ctx, n)) return refuse(ctx, __func__, why);
+    WGUARD(ctx)
+    const Params &P = ctx->c->P;
+    BankRand r;
+    r.tapes = tapes; r.tape_stride = tape_stride; r.seeds = seeds; r.seed_stride = seed_stride;
+    r.resolve(ctx, n, 1u << TAPE_SEC_ONLINE);
+    const bool direct = copy_direct(ctx, pi, (size_t)n * P.proof_bytes);
+    // proof b of the call takes the b-th oldest entry: the chunks run one after the other on the bank's sub-context
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        if (stage_prover_keys_banked(c, count, sk + (size_t)first * P.sk_bytes, r.tapes_at(first), r.tape_stride, r.seeds_at(first), r.seed_stride, ok + first, r.compact)) return -1;
+        if (prove_at(c, first, count)) return -1;
+        if (fetch_proofs_image(c, count, pi + (size_t)first * P.proof_bytes, direct)) return -1;
+        for (int b = first; b < first + count; b++) // a rejected key's image (made from the zero witness) is not handed out
+            if (!ok[b]) memset(pi + (size_t)b * P.proof_bytes, 0, P.proof_bytes);
+        return 0;
+    });
+    WGUARD_END
+}
+int kosk_verifiable_keygen_banked_batch(kosk_ctx *ctx, int n, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *pk,
+                                        uint8_t *sk, uint8_t *pi)
+{
+    if (!ctx || n < 1 || !pk || !sk || !pi) return bad_args(ctx, __func__);
+    ARMED_CHECK(ctx, n);
+    if (const char *why = bank_rand_why(ctx, tapes, tape_stride, seeds, seed_stride)) return refuse(ctx, __func__, why);
+    if (const char *why = bank_level_why(ctx, n)) return refuse(ctx, __func__, why);
+    WGUARD(ctx)
+    const Params &P = ctx->c->P;
+    BankRand r;
+    r.tapes = tapes; r.tape_stride = tape_stride; r.seeds = seeds; r.seed_stride = seed_stride;
+    const unsigned mask = 1u << TAPE_SEC_KEYSEED | 1u << TAPE_SEC_ONLINE;
+    r.resolve(ctx, n, mask); // the key generation's 64 bytes first, then the online draws
+    const bool direct = copy_direct(ctx, pi, (size_t)n * P.proof_bytes);
+    return serial_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        KeygenIn kg{r.tapes_at(first), r.tape_stride, pk + (size_t)first * P.pk_bytes, sk + (size_t)first * P.sk_bytes};
+        if (r.seeds) { kg.seeds = r.seeds_at(first); kg.seed_stride = r.seed_stride; }
+        kg.sections = mask;
+        kg.sections_compact = r.compact;
+        if (bank_take(c, count)) return -1;
+        c.bind_first = first;
+        if (prove_resident(c, count, true, &kg)) return -1;
+        return fetch_proofs_image(c, count, pi + (size_t)first * P.proof_bytes, direct);
+    });
+    WGUARD_END
+}
+// diagnostic (tools/bank_rate.py): k_bank_put / k_bank_take of n entries on an empty bank against the runtime's own D2D copies and fill
+int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *take_ms, double *copy_ms, double *copy_fill_ms, size_t *bytes)
+{
+    if (!ctx || n < 1 || reps < 1 || !put_ms || !take_ms || !copy_ms || !copy_fill_ms) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    return bank_timing(*ctx->c, n, reps, put_ms, take_ms, copy_ms, copy_fill_ms, bytes);
+    GUARD_END
+}
+
 void *kosk_host_alloc(size_t bytes)
 {
     void *p = nullptr;

@@ -65,6 +65,7 @@ Ctx::~Ctx()
     transcode_release(*this);
     kem_key_release(*this);
     witness_release(*this);
+    bank_release(*this);
     if (is_view) {
         if (h_err) (void)hipHostFree(h_err);
         // a view owns its events, host workers and compact staging; tables, workspace and the stream belong to the arena
@@ -592,6 +593,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.tc = nullptr;
     c.kem_key = nullptr;
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
+    c.d_bank = nullptr; c.bank_cap = 0; c.bank_ready = 0; c.bank_head = 0; c.staged_online = false; // a bank is per handle
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
     c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
     c.force_d = nullptr; c.force_h = nullptr; c.force_n = 0;
@@ -646,6 +648,7 @@ static int upload_tapes_part(Ctx &c, int first, int n, const uint8_t *tapes, siz
 {
     const Params &P = c.P;
     if (tapes && tape_stride < P.tape_bytes) { c.err = "tape_stride smaller than kosk_tape_bytes"; return -1; }
+    c.staged_online = false;
     uint8_t *d_dst = c.d_tape + (size_t)first * c.tape_stride, *h_dst = c.h_tape + (size_t)first * c.tape_stride;
     if (tapes && is_device_pointer(tapes)) {
         // the caller keeps its randomness in HBM: use it in place when the kernels' 8-byte loads are aligned, else one D2D copy
@@ -735,6 +738,7 @@ static int seed_tapes(Ctx &c, int n, const uint8_t *seeds, size_t seed_stride)
 {
     SeedRun run;
     c.tape_segs.count = 0;
+    c.staged_online = false;
     if (seed_tapes_part(c, 0, n, seeds, seed_stride, run) || flush_seed_run(c, run)) return -1;
     c.tape_cur = c.d_tape;
     c.tape_cur_stride = c.tape_stride;
@@ -772,10 +776,57 @@ int upload_tapes(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride)
     return upload_tapes_part(c, 0, n, tapes, tape_stride, true);
 }
 
+int stage_tape_sections(Ctx &c, int n, unsigned mask, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, bool compact)
+{
+    const Params &P = c.P;
+    if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    if ((tapes != nullptr) + (seeds != nullptr) != 1) { c.err = "internal: exactly one of tapes / seeds"; return -1; }
+    size_t compact_bytes = 0;
+    for (int sec = 0; sec < 3; sec++) {
+        size_t off = 0, len = 0;
+        if ((mask >> sec & 1) && tape_section(P, sec, &off, &len)) compact_bytes += len;
+    }
+    if (tapes && tape_stride < (compact ? compact_bytes : P.tape_bytes)) { c.err = "tape_stride smaller than kosk_tape_bytes"; return -1; }
+    if (seeds) return seed_tapes(c, n, seeds, seed_stride); // whole tapes: the blocks of the other sections are expanded and never read
+    c.tape_segs.count = 0;
+    c.staged_online = false;
+    const bool dev = is_device_pointer(tapes);
+    if (dev && compact) { c.err = "internal: compact tape records are host memory"; return -1; }
+    size_t at = 0; // compact records: where the next section of the mask starts in a record
+    if (dev && tape_stride % 8 == 0 && (reinterpret_cast<uintptr_t>(tapes) & 7) == 0) { // read where they lie, as upload_tapes() does
+        c.tape_cur = tapes;
+        c.tape_cur_stride = tape_stride;
+        return 0;
+    }
+    for (int sec = 0; sec < 3; sec++) {
+        size_t off = 0, len = 0;
+        if (!(mask >> sec & 1) || !tape_section(P, sec, &off, &len)) continue;
+        const size_t from = compact ? at : off;
+        at += len;
+        const uint8_t *src = tapes + off;
+        size_t src_stride = tape_stride;
+        if (!dev) { // through the page-locked staging buffer, each section at its place in the tape
+            parallel_for(c.pool, n, c.nthreads, [&](int b) { memcpy(c.h_tape + (size_t)b * c.tape_stride + off, tapes + (size_t)b * tape_stride + from, len); });
+            src = c.h_tape + off;
+            src_stride = c.tape_stride;
+        }
+        HIPCHK(hipMemcpy2DAsync(c.d_tape + off, c.tape_stride, src, src_stride, len, (size_t)n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    }
+    c.tape_cur = c.d_tape;
+    c.tape_cur_stride = c.tape_stride;
+    return 0;
+}
+
 // the tapes of every caller of a (possibly merged) call, segment after segment
 static int upload_tapes_segs(Ctx &c, int n, const KeygenIn &kg)
 {
     c.tape_segs.count = 0;
+    c.staged_online = false;
+    if (kg.sections) {
+        if (kg.next || (kg.count && kg.count != n)) { c.err = "internal: tape sections in a merged run"; return -1; }
+        if (!kg.tapes && !kg.seeds) { c.err = "internal: tape sections need explicit tapes or seeds"; return -1; }
+        return stage_tape_sections(c, n, kg.sections, kg.seeds ? nullptr : kg.tapes, kg.tape_stride, kg.seeds, kg.seed_stride, kg.sections_compact);
+    }
     if (!kg.next && (kg.count == 0 || kg.count == n))
         return kg.seeds ? seed_tapes(c, n, kg.seeds, kg.seed_stride) : upload_tapes(c, n, kg.tapes, kg.tape_stride);
     { // every caller keeps aligned tapes in HBM, equal strides, full blocks except the last: read them where they are
@@ -991,6 +1042,7 @@ static int stage_prover_keys_derived(Ctx &c, int n, const uint8_t *sk, const Der
     if (src.salts && src.salt_stride < 32) { c.err = "salt_stride smaller than one salt (32 bytes)"; return -1; }
     if (bind_check(c, n)) return -1;
     if (witness_ensure(c, n)) return -1;
+    c.staged_online = false;
     HIPCHK(copy_sk_records(c, n, sk));
     if (src.salts) HIPCHK(hipMemcpy2DAsync(c.d_wsalt, 32, src.salts, src.salt_stride, 32, (size_t)n, is_device_pointer(src.salts) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
     KeyseedArgs ka{};
@@ -1073,7 +1125,8 @@ int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, si
 
 // The sharing front of the prover for the fresh sharings [s0, s1) of the tape order: tape / witness expansion, NTTs,
 // A*NTT(s), and the Lagrange expansion of exactly those rows.  FRONT_FULL is what kyber_verifiable_keygen needs;
-// the other three are the reference's separate entry points (mlwe_prover.cpp:4-39, :41-59, and the sharing part of :81-).
+// the next three are the reference's separate entry points (mlwe_prover.cpp:4-39, :41-59, and the sharing part of :81-); FRONT_OFFLINE is
+// the first two in one pass (kosk_bank.hip).
 int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen)
 {
     const Params &P = c.P;
@@ -1085,6 +1138,7 @@ int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen)
     if (part == FRONT_RANDOMNESS) { s1 = noff_f; witness = 0; ntt_count = P.M; matvec = false; }
     else if (part == FRONT_RANGE) { s0 = noff_f; s1 = noff; witness = 2; ntt_count = 0; expand = false; matvec = false; }
     else if (part == FRONT_ONLINE) { s0 = noff; expand = false; ntt_first = P.M; ntt_count = K; }
+    else if (part == FRONT_OFFLINE) { s1 = noff; witness = 2; ntt_count = P.M; matvec = false; } // f-PRF, both tape ranges and the range constants: one launch
     const KeygenFront kgf{c.d_seeds, c.kg_rec, c.d_A, c.key_stride, c.d_se, c.se_stride, c.xof_guard()};
     HIPCHK(launch_prover_pre(c.tape_cur, c.tape_cur_stride, c.d_P, c.proof_stride, rm.f, P.M, 64 + 32 * P.M, c.d_fresh_rows, s0, s1, expand,
                              witness, c.d_se, c.se_stride, rm, P.eta1, n, st, with_keygen ? &kgf : nullptr, c.tape_segs.count ? &c.tape_segs : nullptr));
@@ -1124,8 +1178,8 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
         return -1;
     }
     if (!keygen) c.tape_segs.count = 0;
+    if (!keygen && c.staged_online) online_only = true; // the staging call took the offline rows from the bank
     const bool bound = c.bind_n > 0; // kosk-bind-v1: B of every proof follows both digest tables into their hashes
-    if (bound && online_only) { c.err = "an armed handle (kosk_set_contexts) cannot prove from prepared inputs: there are no public key bytes to bind"; return -1; }
     if (bound && keygen && (keygen->next || (keygen->count && keygen->count != n))) { c.err = "internal: an armed handle's call in a merged run"; return -1; }
     if (bind_check(c, n)) return -1;
     const bool forced = c.force_n > 0; // tests: round 2 takes its candidates from the handle's lists (kosk_force_opened_candidates)
@@ -1135,6 +1189,12 @@ int prove_resident(Ctx &c, int n, bool online_only, const KeygenIn *keygen)
     }
     if (forced && (c.use_graphs || (keygen && keygen->next))) { c.err = "internal: forced candidate lists under graph replay or in a merged run"; return -1; }
     if (bound && !keygen && c.resident_pk_n < n) { c.err = "no resident public keys to bind the proofs to"; return -1; }
+    // A proof on bank entries leaves no staged inputs behind, however it ends: the tape buffer never held the offline sections of these
+    // proofs (a later full front would share out whatever other entries' bytes lie there), and the rows of a consumed entry serve ONE proof
+    struct Unstage {
+        Ctx &c; bool on;
+        ~Unstage() { if (on) { c.tape_cur = nullptr; c.tape_cur_stride = 0; c.tape_segs.count = 0; c.staged_online = false; } }
+    } unstage{c, (!keygen && c.staged_online) || (keygen && keygen->sections)};
     HIPCHK(hipSetDevice(c.device));
     const Params &P = c.P;
     const RowMap &rm = c.rm;

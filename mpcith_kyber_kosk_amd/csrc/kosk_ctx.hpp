@@ -50,6 +50,10 @@ struct KeygenIn {
     // expanded from its 32-byte seeds into the context's own tape buffer (kosk-seedtape-v1, k_tape_expand)
     const uint8_t *seeds = nullptr;
     size_t seed_stride = 0;
+    // a banked key generation (unmerged only): bit s set = section s of the tapes is made resident and nothing else of them is read
+    // (stage_tape_sections); 0: whole tapes
+    unsigned sections = 0;
+    bool sections_compact = false; // the records hold exactly those sections back to back (drawn randomness), not whole tapes
 };
 // the verifier's per-caller parts of a merged call: `count` proofs each, own key source and own result bytes
 struct VerifySeg {
@@ -73,7 +77,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
-              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_COUNT };
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -145,7 +149,7 @@ struct Ctx {
     // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
     // buffers that come and go (inv_drop)
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK };
     struct InvBuf {
         const char *name;
         size_t field_off; // (size_t)-1: `abs`
@@ -406,6 +410,16 @@ struct Ctx {
     uint8_t *d_wsk = nullptr, *d_wok = nullptr, *h_wok = nullptr;
     uint8_t *d_wsalt = nullptr; // kosk-keyseed-v1: the call's salts, 32 bytes per key (allocated with d_wsk)
 
+    // the offline bank (kosk_bank.hip): bank_cap entries of bank_entry_bytes(P) each in one allocation of this context's
+    // own, made by bank_reserve() and nowhere else.  A FIFO ring: the oldest of the bank_ready entries lies in slot bank_head, a fill appends
+    // behind the youngest.  A free slot is all zero (k_bank_take zeroes what it reads; a fill that fails behind its put zeroes the slots it wrote)
+    uint8_t *d_bank = nullptr;
+    int bank_cap = 0, bank_ready = 0, bank_head = 0;
+    // the last staging call took the offline rows from the bank (stage_prover_keys_banked): the next prove_resident runs the online front
+    // only, and is the only one -- it ends with no staged inputs, as a banked key generation does, because the tape buffer never held the
+    // offline sections of these proofs and the rows of a consumed entry serve one proof.  Every call that makes other tapes current clears it
+    bool staged_online = false;
+
     ~Ctx();
 };
 
@@ -522,9 +536,12 @@ int stage_prover_keys(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, si
 // kernel level: n seeds of format kosk-keyseed-v1 into DEVICE memory (8-byte aligned), every input host or device memory; synchronised
 int keyseed_device(Ctx &c, int n, const uint8_t *sk, const uint8_t *contexts, size_t context_stride, const uint8_t *salts, size_t salt_stride, uint8_t *d_seeds);
 // everything from resident inputs to resident proof images (two host Fiat-Shamir round trips)
-enum FrontPart { FRONT_FULL = 0, FRONT_RANDOMNESS, FRONT_RANGE, FRONT_ONLINE };
+// FRONT_OFFLINE: FRONT_RANDOMNESS and FRONT_RANGE in one pass (one launch of each kernel), what a bank entry is made by
+enum FrontPart { FRONT_FULL = 0, FRONT_RANDOMNESS, FRONT_RANGE, FRONT_ONLINE, FRONT_OFFLINE };
 int issue_sharing_front(Ctx &c, int n, FrontPart part, bool with_keygen = false);
-// online_only: the offline material (f, NTT f, eta sharings) is already in the row matrix (prove_prepared)
+// online_only: the offline material (f, NTT f, eta sharings) is already in the row matrix (prove_prepared, the banked calls; implied
+// after stage_prover_keys_banked, which the call uses up: a second prove_resident needs a new staging call; so does one after a banked key
+// generation).  An armed context binds as usual: the pk bytes must be resident (prove_prepared has none and refuses)
 // keygen != nullptr: key generation runs at the head of the first segment (no extra synchronisation) and pk / sk are
 // written before the call returns -- the whole kyber_verifiable_keygen, proofs left resident
 int prove_resident(Ctx &c, int n, bool online_only = false, const KeygenIn *keygen = nullptr);
@@ -537,6 +554,41 @@ int prepare_range_proof(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride,
 int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, const uint8_t *range_in, const uint8_t *tapes,
                    size_t tape_stride, uint8_t *pi);
 int stage_verifier_inst(Ctx &c, int n, const uint8_t *pi, const uint8_t *inst);
+// ---- the offline bank (kosk_bank.hip) ----
+// the three sections of a tape: 0 key seed [0, 64), 1 offline [64, O), 2 online [O, T)
+enum { TAPE_SEC_KEYSEED = 0, TAPE_SEC_OFFLINE = 1, TAPE_SEC_ONLINE = 2 };
+inline bool tape_section(const Params &P, int section, size_t *offset, size_t *size)
+{
+    const size_t O = 64 + (size_t)32 * P.M + (size_t)302 * (2 * P.M + 2 * P.K * P.E);
+    const size_t lo[4] = {0, 64, O, P.tape_bytes};
+    if (section < 0 || section > 2) return false;
+    *offset = lo[section];
+    *size = lo[section + 1] - lo[section];
+    return true;
+}
+// sections `mask` (bit s = section s) of n tapes made current for the fronts that read exactly those: explicit tapes (host memory: only
+// the sections cross PCIe; device memory: read in place when aligned, else the sections are copied) or seeds (kosk-seedtape-v1, expanded
+// on the device).  Exactly one of tapes / seeds.  compact (host memory only): a record holds exactly the sections of `mask` back to back
+// instead of a whole tape (what the entry points draw when they are given neither).  Queued on the stream, not synchronised
+int stage_tape_sections(Ctx &c, int n, unsigned mask, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, bool compact = false);
+inline size_t bank_entry_bytes(const Params &P) { return (size_t)(2 * P.M + 2 * P.K * P.E) * RS * sizeof(uint16_t); } // whole rows, RS columns each
+// capacity 0 wipes and frees; a non-empty bank is refused.  The old allocation is wiped before it is freed
+int bank_reserve(Ctx &c, int capacity);
+void bank_release(Ctx &c); // frees without wiping (the destructor: kosk_destroy has wiped)
+void bank_note_wiped(Ctx &c); // wipe_secrets() zeroed the bank: it is empty
+// n <= call_cap entries appended in proof order: the offline front on the given tapes / seeds, then k_bank_put; bank_ready + n <= bank_cap
+// is the caller's check.  Synchronised; staged prover inputs are gone afterwards (the tape buffer was reused)
+int bank_fill(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, bool compact = false);
+// the n oldest entries into the row matrix of proofs 0..n-1 (k_bank_take: the slots are zero afterwards); n <= bank_ready is the caller's
+// check.  The entries are gone once this has been called, whatever it returns.  Queued on the stream, not synchronised
+int bank_take(Ctx &c, int n);
+// stage_prover_keys for a banked proof: the online section of the tapes / seeds, the witness of the records, the n oldest entries of the
+// bank; prove_resident(c, n) then runs online-only.  Ends with the stream synchronised up to the witness
+int stage_prover_keys_banked(Ctx &c, int n, const uint8_t *sk, const uint8_t *tapes, size_t tape_stride, const uint8_t *seeds, size_t seed_stride, uint8_t *ok,
+                             bool compact = false);
+// diagnostic (tools/bank_rate.py): `reps` times k_bank_put + k_bank_take of n entries on scratch slots, and the runtime's own copies and
+// fill of the same bytes, each between two events
+int bank_timing(Ctx &c, int n, int reps, double *put_ms, double *take_ms, double *copy_ms, double *copy_fill_ms, size_t *bytes);
 int ensure_verify_workspace(Ctx &c);
 // ---- wire formats: the image, and the three packed forms of it (kosk_compact.hip; kosk_dense.hip: v1 and v2) ----
 enum { FMT_IMAGE = 0, FMT_COMPACT = 1, FMT_DENSE = 2, FMT_DENSE2 = 4 }; // KOSK_FMT_* (kosk_capi.cpp asserts the equality); 3 is no format
@@ -618,10 +670,11 @@ enum : unsigned long long { WIPE_MEMSET_BYTES = 320ull << 20 }; // a single run 
 int launch_wipe(Ctx &c, const WipeRegion *regions, int n);
 // zero every secret buffer of the inventory, HBM by k_wipe and page-locked staging by the host; synchronised.  A view wipes its own block
 // of the per-proof buffers and its private buffers.  Staged prover inputs are gone afterwards (staged_wiped).  keep_key (the wipe at the end
-// of a call under KOSK_WIPE_CALL): the resident KEM key is a long-lived secret, not per-call scratch, and stays
+// of a call under KOSK_WIPE_CALL): the resident KEM key and the unconsumed entries of the offline bank are long-lived secrets, not per-call
+// scratch, and stay
 int wipe_secrets(Ctx &c, bool keep_key = false);
-// the HBM regions wipe_secrets() clears (group >= 0: of that owner only; skip_group >= 0: all but that owner's)
-int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1, int skip_group = -1);
+// the HBM regions wipe_secrets() clears (group >= 0: of that owner only; skip_mask: bit g set = not owner g's)
+int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1, unsigned skip_mask = 0);
 // the secret HBM buffers of one owner (Ctx::INVG_*), synchronised: before they are freed to be allocated larger
 int wipe_group(Ctx &c, int group);
 void host_wipe(void *p, size_t bytes); // explicit_bzero: not removed as a dead store

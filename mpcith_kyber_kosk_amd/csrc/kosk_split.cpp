@@ -32,6 +32,7 @@ static int fill_tape_part(Ctx &c, int n, bool seeds, int s0, int s1, const uint8
 {
     const Params &P = c.P;
     const size_t seed_bytes = seeds ? (size_t)32 * P.M : 0, slice_bytes = (size_t)302 * (s1 - s0);
+    c.staged_online = false;
     if (tapes && tape_stride < seed_bytes + slice_bytes) { c.err = "tape_stride smaller than the randomness this call consumes"; return -1; }
     for (int b = 0; b < n; b++) {
         uint8_t *tp = c.h_tape + (size_t)b * c.tape_stride;
@@ -156,6 +157,8 @@ int prove_prepared(Ctx &c, int n, const uint8_t *inst, const uint8_t *rand_in, c
                    size_t tape_stride, uint8_t *pi)
 {
     if (n < 1 || n > c.call_cap) { c.err = "batch size out of range"; return -1; }
+    // (online-only proving itself binds like any other: the banked calls have the pk bytes resident.  Instances have none)
+    if (c.bind_n > 0) { c.err = "an armed handle (kosk_set_contexts) cannot prove from prepared inputs: there are no public key bytes to bind"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     const Params &P = c.P;
     const RowMap &rm = c.rm;

@@ -206,12 +206,12 @@ static bool inv_secret_span(const Ctx &c, const Ctx::InvBuf &b, uint8_t *&p, siz
     return sb != 0;
 }
 
-int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group, int skip_group)
+int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group, unsigned skip_mask)
 {
     for (const Ctx::InvBuf &b : c.inv) {
         uint8_t *p;
         size_t rec, nrec, so, sb;
-        if ((group >= 0 && b.group != group) || (skip_group >= 0 && b.group == skip_group) || (b.flags & Ctx::INV_HOST) || !inv_secret_span(c, b, p, rec, nrec, so, sb)) continue;
+        if ((group >= 0 && b.group != group) || (skip_mask >> b.group & 1) || (b.flags & Ctx::INV_HOST) || !inv_secret_span(c, b, p, rec, nrec, so, sb)) continue;
         // records without a public part lie back to back: one record of nrec x rec bytes
         if (so == 0 && sb == rec) out.push_back(WipeRegion{p, rec * nrec, 0, 1});
         else out.push_back(WipeRegion{p + so, sb, rec, (uint32_t)nrec});
@@ -237,7 +237,7 @@ int wipe_secrets(Ctx &c, bool keep_key)
 {
     HIPCHK(hipSetDevice(c.device));
     std::vector<WipeRegion> dev;
-    wipe_regions_list(c, dev, -1, keep_key ? (int)Ctx::INVG_KEMKEY : -1);
+    wipe_regions_list(c, dev, -1, keep_key ? 1u << Ctx::INVG_KEMKEY | 1u << Ctx::INVG_BANK : 0u); // long-lived secrets stay
     // the stream may still carry this context's earlier work on these buffers: the wipe is queued behind it
     if (launch_wipe(c, dev.data(), (int)dev.size())) return -1;
     HIPCHK(stream_sync(c));
@@ -254,6 +254,8 @@ int wipe_secrets(Ctx &c, bool keep_key)
     c.tape_cur_stride = 0;
     c.tape_segs.count = 0;
     c.kg_on_host_pending = false;
+    c.staged_online = false;
+    if (!keep_key) bank_note_wiped(c); // every slot is zero: the bank is empty
     if (!keep_key) kem_key_note_wiped(c); // the slot's s-hat and z are zero now: it serves as a public key from here on
     return 0;
 }
