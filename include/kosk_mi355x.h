@@ -399,6 +399,48 @@ int kosk_kem_key_clear(kosk_ctx *ctx);
 int kosk_kem_enc_key(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
 int kosk_kem_dec_key(kosk_ctx *ctx, int n, const uint8_t *ct, uint8_t *ss);
 
+/* ---- The verified-key registry (INTEGRATION.md 8.3 is the normative text): a table of admitted public keys in HBM, for a registrar that
+ * talks to many enrolled peers again and again.  A key enters where a proof verified (kosk_registry_admit_verified) or where the caller
+ * vouches for it (kosk_registry_admit); what depends on the key alone -- the pk bytes, SHA3-256 of them, A^T -- is computed once, at
+ * admission (k_registry_admit); kosk_kem_enc_slots names a slot per item and does the per-item work only.
+ * One registry per handle, on sub-context 0, in HBM allocations of its own (the KEM workspace may grow and move; the registry does not):
+ * kosk_registry_slot_bytes per slot, about 2.9 / 5.8 / 9.8 KB for kyber_k 2 / 3 / 4 (0 for any other k).  A handle that never reserves
+ * allocates nothing.  kosk_registry_reserve allocates exactly `capacity` empty slots; again only while no slot is occupied (the old
+ * allocation is freed first); capacity 0 frees; -1 with a text for capacity < 0, a non-empty registry, or an allocation that fails (nothing is
+ * left allocated then).  kosk_registry_level: occupied slots and capacity (0 / 0 without a registry); used / capacity may be NULL.
+ * slots: n int32 values in HOST memory.  A value outside [0, capacity) makes any of these calls return -1 with a text and nothing started;
+ * so does a value named twice within one kosk_registry_admit* call.  Repeats are fine in kosk_registry_evict, kosk_registry_read and
+ * kosk_kem_enc_slots (many items to one peer is the normal case).
+ * kosk_registry_admit_verified: key b of the LAST COMPLETED verify call of at least n proofs goes into slots[b], only where that call's verify
+ * bit is 1; done[b] (host memory) is that bit; where it is 0 the named slot is not touched and keeps an earlier key.  The preconditions and
+ * refusals are those of kosk_kem_enc_verified, and the keys are decoded from their resident bytes as there.
+ * kosk_registry_admit: the same for n pk records (host or device memory) that THE CALLER VOUCHES FOR -- the library has not seen a proof
+ * for them; accept: n bytes of host memory, 0 = leave the slot alone, or NULL for all.  For verdicts of a cohort member's merged run, of a
+ * chunked kosk_verify_batch, or of another handle; works on a cohort member, unmerged.  No encoding check: 12-bit fields >= q are folded
+ * as in kosk_kem_enc_batch (run kosk_kem_check_pk first for FIPS 203's modulus check).
+ * Admitting into an occupied slot replaces its key.  -1 ("block limit") if gen_matrix reached its block limit inside an admitting call: the
+ * slots that call wrote are left empty, every other slot is untouched.
+ * kosk_registry_evict zeroes the named slots' records and flags; an empty slot stays as it is.  kosk_registry_read (audits, tests):
+ * state[b] (host memory) 0 or 1; pk / h: NULL, or n records of kosk_pk_bytes / 32 bytes, host or device memory, zeros for an empty slot.
+ * kosk_kem_enc_slots: for every b with an occupied slots[b], ct and ss equal byte for byte what kosk_kem_enc_batch returns for the pk
+ * record admitted to that slot with the same coins (fields >= q folded, H(pk) over the bytes as given).  done[b] is the slot's occupancy
+ * (host or device memory); ct and ss of an empty slot are zero-filled; coins are consumed for every position (coins == NULL: one 32-byte
+ * draw per item, in item order, on the caller's thread, whatever done says).  Any n >= 1 in launch groups of 16384 items, buffers host or
+ * device memory, unmerged on the handle's own stream, also on a cohort member.
+ * No registry call touches the prover's or verifier's resident state, the bank, the one-key slot or the fail masks.
+ * Erasure: the registry's buffers are public buffers of the inventory: kosk_secret_scan covers them, kosk_wipe_secrets and
+ * the wipe at the end of a call under KOSK_WIPE_CALL leave them alone; the per-call scratch of kosk_kem_enc_slots (coins, K-bar || coins,
+ * noise, ss) is secret as for kosk_kem_enc_batch.  kosk_destroy and kosk_registry_reserve(0) free the registry.
+ * reserve, admit* and evict must not be called while another thread is inside a call on the handle (the rule of kosk_kem_key_set). */
+size_t kosk_registry_slot_bytes(int kyber_k);
+int kosk_registry_reserve(kosk_ctx *ctx, int capacity);
+int kosk_registry_level(const kosk_ctx *ctx, int *used, int *capacity);
+int kosk_registry_admit_verified(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *done);
+int kosk_registry_admit(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, const int32_t *slots);
+int kosk_registry_evict(kosk_ctx *ctx, int n, const int32_t *slots);
+int kosk_registry_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *pk, uint8_t *h);
+int kosk_kem_enc_slots(kosk_ctx *ctx, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -522,7 +564,9 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 23 refills of kosk-dense-v2 (k_dense2_setup + k_dense2_fill) / 24 launches of k_dense2_check, counted like 14 / 22, which do not move
  * for v2 work,
  * 25 launches of k_bank_put (one per chunk of kosk_bank_fill) / 26 launches of k_bank_take (one per chunk of a call that consumes bank
- * entries); the diagnostic kosk_bank_timing moves both by reps + 1. */
+ * entries); the diagnostic kosk_bank_timing moves both by reps + 1,
+ * 27 launches of k_registry_admit (one per launch group of kosk_registry_admit / kosk_registry_admit_verified), 28 kem_enc_slots: launch
+ * groups of kosk_kem_enc_slots (ids 12 / 20 do not move for it); kosk_registry_evict runs k_wipe (id 18). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

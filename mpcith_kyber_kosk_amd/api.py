@@ -232,6 +232,20 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_bank_reserve")):
         sig.update(bank)
+    # the verified-key registry; optional under the same rule (and only then)
+    ip = C.POINTER(C.c_int)
+    registry = {
+        "kosk_registry_slot_bytes": (sz, [C.c_int]),
+        "kosk_registry_reserve": (C.c_int, [vp, C.c_int]),
+        "kosk_registry_level": (C.c_int, [vp, ip, ip]),
+        "kosk_registry_admit_verified": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_registry_admit": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_registry_evict": (C.c_int, [vp, C.c_int, vp]),
+        "kosk_registry_read": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "kosk_kem_enc_slots": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_reserve")):
+        sig.update(registry)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -271,7 +285,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_verifiable_keygen_batch_fmt", "kosk_verifiable_keygen_seeded_batch_fmt", "kosk_verify_batch_fmt", "kosk_fetch_proofs_fmt",
            "kosk_stage_verifier_inputs_fmt",
            "kosk_bank_entry_bytes", "kosk_tape_section", "kosk_bank_reserve", "kosk_bank_level", "kosk_bank_fill", "kosk_stage_prover_keys_banked",
-           "kosk_prove_keys_banked_batch", "kosk_verifiable_keygen_banked_batch", "kosk_bank_timing"]
+           "kosk_prove_keys_banked_batch", "kosk_verifiable_keygen_banked_batch", "kosk_bank_timing",
+           "kosk_registry_slot_bytes", "kosk_registry_reserve", "kosk_registry_level", "kosk_registry_admit_verified", "kosk_registry_admit",
+           "kosk_registry_evict", "kosk_registry_read", "kosk_kem_enc_slots"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -313,6 +329,7 @@ def dense_proof_bytes(k): return lib.kosk_dense_proof_bytes(k)
 def dense2_proof_bytes(k): return lib.kosk_dense2_proof_bytes(k)
 def format_bytes(k, fmt): return lib.kosk_format_bytes(k, fmt)
 def bank_entry_bytes(k): return lib.kosk_bank_entry_bytes(k)
+def registry_slot_bytes(k): return lib.kosk_registry_slot_bytes(k)
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1081,6 +1098,69 @@ class Kosk:
             return out
         return _cut(bufs[0], SS_BYTES, n)
 
+    # the verified-key registry
+    @staticmethod
+    def _slots(slots):
+        """a list of slot ids -> (int32 array in host memory, n)"""
+        arr = (C.c_int32 * max(len(slots), 1))(*[int(s_) for s_ in slots])
+        return arr, len(slots)
+
+    def registry_reserve(self, capacity):
+        """kosk_registry_reserve: exactly `capacity` empty slots in HBM (0 frees); only while no slot is occupied"""
+        self._chk(lib.kosk_registry_reserve(self._h, capacity), "registry_reserve")
+
+    def registry_level(self):
+        """kosk_registry_level -> (used, capacity)"""
+        u, c_ = C.c_int(), C.c_int()
+        self._chk(lib.kosk_registry_level(self._h, C.byref(u), C.byref(c_)), "registry_level")
+        return u.value, c_.value
+
+    def registry_admit_verified(self, slots):
+        """kosk_registry_admit_verified: key b of the last completed verify call into slots[b] where its verify bit is 1; returns those bits"""
+        sp, n = self._slots(slots)
+        done = C.create_string_buffer(max(n, 1))
+        self._chk(lib.kosk_registry_admit_verified(self._h, n, sp, done), "registry_admit_verified")
+        return [bool(x) for x in done.raw[:n]]
+
+    def registry_admit(self, pks, slots, accept=None, n=None):
+        """kosk_registry_admit: the CALLER vouches for these keys (no proof was seen).  pks: a list of bytes or an int DEVICE pointer (with n);
+        accept: None for all, or one truth value per key (0: the slot is left alone)"""
+        pp, n, _k = self._records("pk", pks, n, self.pk_bytes)
+        sp, ns = self._slots(slots)
+        if ns != n or (accept is not None and len(accept) != n):
+            raise KoskError("registry_admit: %d keys need %d slots and accept bytes" % (n, n))
+        ap = None if accept is None else C.c_char_p(bytes(1 if a_ else 0 for a_ in accept))
+        self._chk(lib.kosk_registry_admit(self._h, n, pp, ap, sp), "registry_admit")
+
+    def registry_evict(self, slots):
+        """kosk_registry_evict: zero the named slots' records and flags"""
+        sp, n = self._slots(slots)
+        self._chk(lib.kosk_registry_evict(self._h, n, sp), "registry_evict")
+
+    def registry_read(self, slots):
+        """kosk_registry_read -> (states, pks, hs): occupancy, the pk bytes and SHA3-256 of them per named slot (zeros for an empty one)"""
+        sp, n = self._slots(slots)
+        state = C.create_string_buffer(max(n, 1))
+        pk = C.create_string_buffer(self.pk_bytes * max(n, 1)); h = C.create_string_buffer(32 * max(n, 1))
+        self._chk(lib.kosk_registry_read(self._h, n, sp, state, pk, h), "registry_read")
+        return list(state.raw[:n]), _cut(pk, self.pk_bytes, n), _cut(h, 32, n)
+
+    def kem_enc_slots(self, slots, coins=None, out=None):
+        """kosk_kem_enc_slots: item b to the key in slots[b]; coins / out as in kem_enc, with out=(d_ct, d_ss, d_done).  Returns (cts, sss,
+        done); ct and ss of an empty slot are zero-filled"""
+        sp, n = self._slots(slots)
+        cp, _k = None, None
+        if coins is not None:
+            cp, nc, _k = self._records("coins", coins, n, 32)
+            if nc != n:
+                raise KoskError("coins for %d items, slots for %d" % (nc, n))
+        ctb = ct_bytes(self.k)
+        bufs, host = self._kem_out(out, n, (ctb, SS_BYTES, 1))
+        self._chk(lib.kosk_kem_enc_slots(self._h, n, sp, cp, bufs[0], bufs[1], bufs[2]), "kem_enc_slots")
+        if host is None:
+            return out
+        return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1224,6 +1304,8 @@ class Kosk:
     PATH_DENSE2_CHECK = 24
     PATH_BANK_PUT = 25
     PATH_BANK_TAKE = 26
+    PATH_REGISTRY_ADMIT = 27
+    PATH_KEM_ENC_SLOTS = 28
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

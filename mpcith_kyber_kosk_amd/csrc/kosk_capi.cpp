@@ -1288,19 +1288,25 @@ int kosk_kem_check_sk(kosk_ctx *ctx, int n, const uint8_t *sk, uint8_t *flags)
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) { return kem_check(c, count, sk + (size_t)first * P.sk_bytes, 1, flags + first); });
     WGUARD_END
 }
+// why the keys of the last verify call cannot serve a call on its first n keys (kosk_kem_enc_verified, kosk_registry_admit_verified); nullptr: they can
+static const char *verified_keys_refusal(const kosk_ctx *ctx, int n)
+{
+    if (ctx->cohort) return "not available with call combining (the handle is a member of a cohort)";
+    if (ctx->sub.size() > 1) return "needs streams = 1 (sub-batches keep separate public keys)";
+    if (ctx->verify_keys == 0 || ctx->masks_n < 1) return "no verify call has completed on this handle";
+    if (ctx->verify_keys == 2) return "the last verify call was a chunked kosk_verify_batch call (n > max_batch): its public keys are not resident as one batch";
+    if (ctx->masks_n < n) return "the last verify call covered fewer than n proofs";
+    if (ctx->verify_keys == 3) return "the last verify call left no public key bytes in HBM (its A and t came from instances)";
+    if (ctx->verify_epoch != ctx->c->pk_epoch || ctx->c->resident_pk_n < n) return "the resident public keys were replaced after the last verify call";
+    return nullptr;
+}
 int kosk_kem_enc_verified(kosk_ctx *ctx, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
 {
     if (!ctx || n < 1 || !ct || !ss || !done) return bad_args(ctx, __func__);
     WGUARD(ctx)
     ctx->clear_err();
     auto refuse = [&](const char *why) { ctx->err = std::string("kosk_kem_enc_verified: ") + why; ctx->c->err = ctx->err; return -1; };
-    if (ctx->cohort) return refuse("not available with call combining (the handle is a member of a cohort)");
-    if (ctx->sub.size() > 1) return refuse("needs streams = 1 (sub-batches keep separate public keys)");
-    if (ctx->verify_keys == 0 || ctx->masks_n < 1) return refuse("no verify call has completed on this handle");
-    if (ctx->verify_keys == 2) return refuse("the last verify call was a chunked kosk_verify_batch call (n > max_batch): its public keys are not resident as one batch");
-    if (ctx->masks_n < n) return refuse("the last verify call covered fewer than n proofs");
-    if (ctx->verify_keys == 3) return refuse("the last verify call left no public key bytes in HBM (its A and t came from instances)");
-    if (ctx->verify_epoch != ctx->c->pk_epoch || ctx->c->resident_pk_n < n) return refuse("the resident public keys were replaced after the last verify call");
+    if (const char *why = verified_keys_refusal(ctx, n)) return refuse(why);
     // coins are drawn for every position, accepted or not: the draw order does not depend on the outcome
     std::vector<uint8_t> drawn, bits((size_t)n);
     VecWiper<uint8_t> drawn_gone(drawn);
@@ -1363,6 +1369,144 @@ int kosk_kem_dec_key(kosk_ctx *ctx, int n, const uint8_t *ct, uint8_t *ss)
     return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
         return kem_dec_key(c, count, ct + (size_t)first * ctb, ss + (size_t)first * 32);
     });
+    WGUARD_END
+}
+
+// ---- the verified-key registry (kosk_registry.hip) ----
+size_t kosk_registry_slot_bytes(int k) { return k >= 2 && k <= 4 ? registry_slot_bytes(k) : 0; }
+
+// why a call that names `slots` is refused before anything starts; nullptr: the handle has a registry and every value is one of its slots
+// (distinct: and none is named twice -- the admissions, where the later writer would be undefined)
+static const char *registry_slots_refusal(const kosk_ctx *ctx, int n, const int32_t *slots, bool distinct)
+{
+    const KemRegistry *r = ctx->c->registry;
+    if (!r) return "no registry is reserved (kosk_registry_reserve)";
+    for (int b = 0; b < n; b++)
+        if (slots[b] < 0 || slots[b] >= r->capacity) return "a slot id outside [0, capacity)";
+    if (distinct) {
+        std::vector<uint8_t> seen((size_t)r->capacity, 0);
+        for (int b = 0; b < n; b++) {
+            if (seen[(size_t)slots[b]]) return "a slot id is named twice in one admission";
+            seen[(size_t)slots[b]] = 1;
+        }
+    }
+    return nullptr;
+}
+
+int kosk_registry_reserve(kosk_ctx *ctx, int capacity)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (registry_reserve(*ctx->c, capacity)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_level(const kosk_ctx *ctx, int *used, int *capacity)
+{
+    if (!ctx) return -1;
+    const KemRegistry *r = ctx->c->registry;
+    if (used) *used = r ? r->used : 0;
+    if (capacity) *capacity = r ? r->capacity : 0;
+    return 0;
+}
+
+// key b of the call (pk records, or pk == nullptr: the resident keys) into slots[b] where accept[b] != 0 (nullptr: everywhere), in launch groups;
+// the mirror follows what the launches wrote.  A launch group that fails (gen_matrix at its block limit) leaves the slots this call wrote empty
+static int registry_admit_run(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, const int32_t *slots)
+{
+    std::vector<int32_t> dst((size_t)n);
+    for (int b = 0; b < n; b++) dst[(size_t)b] = !accept || accept[b] ? slots[b] : -1;
+    const size_t pkb = ctx->c->P.pk_bytes;
+    int done = 0; // keys of completed or started launch groups
+    const int rc = kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        done = first + count;
+        return kem_registry_admit(c, count, pk ? pk + (size_t)first * pkb : nullptr, first, dst.data() + first);
+    });
+    KemRegistry &r = *ctx->c->registry;
+    for (int b = 0; b < done; b++) {
+        if (dst[(size_t)b] < 0 || r.occ[(size_t)dst[(size_t)b]]) continue; // masked, or a replacement: `used` does not change
+        r.occ[(size_t)dst[(size_t)b]] = 1;
+        r.used++;
+    }
+    if (!rc) return 0;
+    const std::string why = ctx->err;
+    std::vector<int32_t> named;
+    for (int b = 0; b < done; b++)
+        if (dst[(size_t)b] >= 0) named.push_back(dst[(size_t)b]);
+    (void)hipGetLastError();
+    (void)registry_evict(*ctx->c, (int)named.size(), named.data());
+    ctx->err = why;
+    ctx->c->err = why;
+    return -1;
+}
+
+int kosk_registry_admit_verified(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *done)
+{
+    if (!ctx || n < 1 || !slots || !done) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, true)) return refuse(ctx, "kosk_registry_admit_verified", why);
+    if (const char *why = verified_keys_refusal(ctx, n)) return refuse(ctx, "kosk_registry_admit_verified", why);
+    std::vector<uint8_t> bits((size_t)n);
+    for (int b = 0; b < n; b++) bits[(size_t)b] = ctx->masks[(size_t)b] == 0;
+    if (registry_admit_run(ctx, n, nullptr, bits.data(), slots)) return -1;
+    memcpy(done, bits.data(), (size_t)n);
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_admit(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, const int32_t *slots)
+{
+    if (!ctx || n < 1 || !pk || !slots) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, true)) return refuse(ctx, "kosk_registry_admit", why);
+    return registry_admit_run(ctx, n, pk, accept, slots);
+    GUARD_END
+}
+
+int kosk_registry_evict(kosk_ctx *ctx, int n, const int32_t *slots)
+{
+    if (!ctx || n < 1 || !slots) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, false)) return refuse(ctx, "kosk_registry_evict", why);
+    if (registry_evict(*ctx->c, n, slots)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *pk, uint8_t *h)
+{
+    if (!ctx || n < 1 || !slots || !state) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, false)) return refuse(ctx, "kosk_registry_read", why);
+    if (registry_read(*ctx->c, n, slots, state, pk, h)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_kem_enc_slots(kosk_ctx *ctx, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (!ctx || n < 1 || !slots || !ct || !ss || !done) return bad_args(ctx, __func__);
+    WGUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, false)) return refuse(ctx, "kosk_kem_enc_slots", why); // before any coin is drawn
+    // coins are drawn for every position, occupied or not: the draw order does not depend on the registry
+    std::vector<uint8_t> drawn, bits((size_t)n);
+    VecWiper<uint8_t> drawn_gone(drawn);
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    const KemRegistry &r = *ctx->c->registry;
+    for (int b = 0; b < n; b++) bits[(size_t)b] = r.occ[(size_t)slots[b]];
+    const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return kem_enc_slots(c, count, slots + first, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32);
+        })) return -1;
+    if (hipMemcpy(done, bits.data(), (size_t)n, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return refuse(ctx, "kosk_kem_enc_slots", "copying the occupancy bits to `done` failed"); }
+    return 0;
     WGUARD_END
 }
 

@@ -64,6 +64,7 @@ Ctx::~Ctx()
     kem_release(*this);
     transcode_release(*this);
     kem_key_release(*this);
+    registry_release(*this);
     witness_release(*this);
     bank_release(*this);
     if (is_view) {
@@ -592,6 +593,7 @@ int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx
     c.kem = nullptr;
     c.tc = nullptr;
     c.kem_key = nullptr;
+    c.registry = nullptr;
     c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
     c.d_bank = nullptr; c.bank_cap = 0; c.bank_ready = 0; c.bank_head = 0; c.staged_online = false; // a bank is per handle
     c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;

@@ -77,7 +77,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
-              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_COUNT };
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -123,6 +123,7 @@ int dense_decode(const Params &P, const uint8_t *in, uint8_t *img, int fmt = 2);
 struct TcWs;  // HBM workspace of kosk_transcode_batch (kosk_compact.hip)
 struct KemWs; // HBM workspace of the KEM calls (kosk_kem_kernels.hip)
 struct KemKey; // the resident key of the one-key KEM calls (kosk_kem_kernels.hip)
+struct KemRegistry; // the table of admitted keys (kosk_registry.hip)
 enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
        KEM_WAVE_MAX = 1024 }; // launch groups of up to this many items (one wave per SIMD) run their long one-lane-per-item chains on a wave sponge, one wave per item
 
@@ -149,7 +150,7 @@ struct Ctx {
     // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
     // buffers that come and go (inv_drop)
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK, INVG_REGISTRY };
     struct InvBuf {
         const char *name;
         size_t field_off; // (size_t)-1: `abs`
@@ -391,6 +392,7 @@ struct Ctx {
     long path_n[PATH_COUNT] = {0};
     KemWs *kem = nullptr; // allocated at this context's first KEM call, owned by it (a view's is its own, never the arena's)
     KemKey *kem_key = nullptr; // the key slot: allocated at the first kem_key_set, its own allocation (kem_ensure never moves it), owned like `kem`
+    KemRegistry *registry = nullptr; // the verified-key registry: allocated by registry_reserve, its own allocations, owned like `kem`
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -660,6 +662,46 @@ void kem_key_release(Ctx &c); // frees without wiping (the destructor: kosk_dest
 void kem_key_note_wiped(Ctx &c); // wipe_secrets() zeroed the slot's secret part: SK -> PK
 int kem_enc_key(Ctx &c, int n, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
 int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss);
+
+// The verified-key registry (kosk_registry.hip): `capacity` slots in HBM, structure of arrays -- what depends on a key alone, decoded
+// once at admission (k_registry_admit) and read by kem_enc_slots through KemKeySide, slot s at base + s * stride.  Four allocations of its
+// own (kem_ensure frees and reallocates the KEM workspace; the registry must not move), public buffers of the inventory under INVG_REGISTRY.
+// `occ` mirrors d_flag on the host: every mutation goes through a host call.
+struct KemRegistry {
+    int capacity = 0, used = 0;
+    uint8_t *d_pk = nullptr;   // [capacity][384 K + 32] the pk bytes as admitted
+    uint8_t *d_h = nullptr;    // [capacity][32]         SHA3-256 of those bytes
+    int16_t *d_A = nullptr;    // [capacity][K K][256]   A^T, the layout encrypt_block reads
+    uint8_t *d_flag = nullptr; // [capacity]             1 = occupied
+    std::vector<uint8_t> occ;
+};
+inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
+// One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
+// memory; < 0: masked, nothing is written).  wave: K^2 + 1 one-wave blocks per key; else one sponge per lane.  Queued, not synchronised
+struct RegAdmitJob {
+    int n, K, pk_bytes, wave;
+    const uint8_t *src;
+    size_t src_stride;
+    const int32_t *slot;
+    uint8_t *pk, *h, *flag;
+    int16_t *A;
+    uint32_t *err;
+    int max_blocks;
+};
+hipError_t launch_registry_admit(const RegAdmitJob &j, hipStream_t st);
+// capacity 0 frees; a non-empty registry is refused; -1 leaves nothing allocated
+int registry_reserve(Ctx &c, int capacity);
+void registry_release(Ctx &c);
+// the named slots' records and flags zeroed (k_wipe), the mirror updated; slots are valid ids, repeats allowed; synchronised
+int registry_evict(Ctx &c, int n, const int32_t *slots);
+// state (host), pk / h (host or device memory, or nullptr) of the named slots; an empty slot reads as zeros; synchronised
+int registry_read(Ctx &c, int n, const int32_t *slots, uint8_t *state, uint8_t *pk, uint8_t *h);
+// n <= KEM_CHUNK keys into slots[b] (host; valid and distinct ids, or < 0: masked): pk records in host or device memory, or pk == nullptr: the
+// keys resident in c.d_pk from record resident_first on.  Synchronised; -1 ("block limit") with the mirror untouched -- the caller evicts
+int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, const int32_t *slots);
+// crypto_kem_enc_derand for n <= KEM_CHUNK items, item b to the key in slots[b] (host; valid ids): per-item work only; an empty slot's ct and ss
+// are zero-filled
+int kem_enc_slots(Ctx &c, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
 
 // ---- erasure (kosk_wipe.hip) ----
 // `count` records of `bytes` bytes, `stride` apart, in HBM (count 1: one run of bytes)

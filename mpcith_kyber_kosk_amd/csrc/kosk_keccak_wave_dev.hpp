@@ -192,4 +192,19 @@ struct WaveSponge {
     }
 };
 
+// The whole-word message of a wave sponge at rate 136 (17 words a block): absorbs words fetch(0 .. nwords - 1) and the padding behind them,
+// domain byte `dom` (0x06 SHA3, 0x1F SHAKE), through the last permutation.  Which word a lane fetches is a function of the lane and the block.
+template <class Fetch>
+__device__ __forceinline__ void wave_absorb_words(const WaveSponge &sp, uint32_t &a, Fetch fetch, int nwords, uint32_t dom)
+{
+    const int word = sp.word(), nfull = nwords / 17, rem = nwords - 17 * nfull;
+    for (int blk = 0; blk < nfull; blk++) {
+        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
+        sp.permute(a);
+    }
+    // rem <= 16 whole words, then the padding: the domain byte opens the first free word
+    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, dom, 136));
+    sp.permute(a);
+}
+
 } // namespace kosk

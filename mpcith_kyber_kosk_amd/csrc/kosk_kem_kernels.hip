@@ -53,6 +53,7 @@ struct KemWs {
     uint8_t *d_pk = nullptr, *d_sk = nullptr, *d_ct = nullptr, *d_m = nullptr, *d_kr = nullptr, *d_rk = nullptr, *d_ss = nullptr, *d_mask = nullptr;
     uint8_t *d_h = nullptr; // [n][32] H(pk) from the wave sponge
     int16_t *d_A = nullptr, *d_noise = nullptr;
+    int32_t *d_key = nullptr; // [n] the slot of item b (kem_enc_slots), or the slot key b goes to (kem_registry_admit)
 };
 
 struct KemHashJob {
@@ -64,6 +65,7 @@ struct KemHashJob {
     const uint8_t *m;                 // [n][32]     seed role: the message
     const uint8_t *h;                 // seed role: H(pk) of item b at h + b * h_stride (wave sponge, or the slot's); nullptr: it hashes pk itself
     size_t h_stride;
+    const int32_t *key;               // seed role, with h: item b's H(pk) is that of key key[b]; nullptr: of key b
     uint8_t *kr;                      // [n][64]     seed role writes, noise role reads (coins = kr + 32)
     int16_t *A, *noise;               // [n][K K][256], [n][2 K + 1][256]
     const uint8_t *z;                 // rkprf role: z of item b at z + b * z_stride
@@ -97,7 +99,7 @@ __global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
         for (int l = 0; l < 4; l++) m[l] = ld64(j.m, 4 * b + l);
         if (j.h) {
 #pragma unroll
-            for (int l = 0; l < 4; l++) h[l] = ld64(j.h + (size_t)b * j.h_stride, l);
+            for (int l = 0; l < 4; l++) h[l] = ld64(j.h + (size_t)(j.key ? j.key[b] : b) * j.h_stride, l);
         } else {
             sha3_256_words(pk, j.pk_bytes, h);
         }
@@ -123,21 +125,6 @@ __global__ __launch_bounds__(64) void k_kem_hash(KemHashJob j)
     noise_poly(coins, t, t < j.K ? j.eta1 : 2, j.noise + ((size_t)b * j.n_noise + t) * 256);
 }
 
-// The whole-word message of a wave sponge at rate 136 (17 words a block): absorbs words fetch(0 .. nwords - 1) and the padding behind them,
-// domain byte `dom` (0x06 SHA3, 0x1F SHAKE), through the last permutation.  Which word a lane fetches is a function of the lane and the block.
-template <class Fetch>
-__device__ __forceinline__ void wave_absorb_words(const WaveSponge &sp, uint32_t &a, Fetch fetch, int nwords, uint32_t dom)
-{
-    const int word = sp.word(), nfull = nwords / 17, rem = nwords - 17 * nfull;
-    for (int blk = 0; blk < nfull; blk++) {
-        sp.absorb(a, word < 17 ? fetch(17 * blk + word) : make_uint2(0, 0));
-        sp.permute(a);
-    }
-    // rem <= 16 whole words, then the padding: the domain byte opens the first free word
-    sp.absorb(a, word < rem ? fetch(17 * nfull + word) : WaveSponge::pad(word, 8 * rem, dom, 136));
-    sp.permute(a);
-}
-
 // rkprf = SHAKE256(z[32] || ct) (symmetric-shake.c: kyber_shake256_rkprf), one WAVE per item on the wave sponge: a 32-bit half of a state
 // word per lane, bit-interleaved (kosk_keccak_wave_dev.hpp, WaveSponge).  z and ct are 8-byte aligned and 32 + ct_bytes is a multiple of 8, so
 // every block is whole words.  z is secret: it is data only; the addresses are functions of the lane and the block.
@@ -156,13 +143,15 @@ __global__ __launch_bounds__(64) void k_kem_rkprf_wave(const uint8_t *z, size_t 
     if (lane < 4) *reinterpret_cast<uint2 *>(rk + b * 32 + 8 * lane) = w;
 }
 
-// pk and A^T of item b at pk + b * pk_stride and A + b * A_stride (int16_t elements): one of each per item, or the slot's at stride 0
+// pk and A^T of item b at pk + kb * pk_stride and A + kb * A_stride (int16_t elements), kb = key[b], or b where key is nullptr: one of each
+// per item, the one-key slot's at stride 0, or the registry's by slot
 struct KemEncJob {
     int K, dec;
     const uint8_t *pk;
     size_t pk_stride;
     const int16_t *A, *noise;
     size_t A_stride;
+    const int32_t *key;
     const uint8_t *m, *kr, *rk; // [n][32], [n][64], [n][32] (dec)
     uint8_t *ct;                // [n][ct_bytes]: written (enc) or compared with (dec)
     uint8_t *ss;                // [n][32]
@@ -184,7 +173,8 @@ __global__ __launch_bounds__(256) void k_kem_encrypt(KemEncJob j)
     }
     if (tid == 0) fail = 0;
     __syncthreads();
-    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk + b * j.pk_stride, j.A + b * j.A_stride,
+    const size_t kb = j.key ? (size_t)j.key[b] : b; // block-uniform: one load
+    const uint32_t diff = encrypt_block(D, L, tid, 256, j.pk + kb * j.pk_stride, j.A + kb * j.A_stride,
                                         j.noise + b * (size_t)((2 * D.K + 1) * 256), j.m + b * 32, j.dec ? nullptr : ct, ct);
     if (!j.dec) {
         if (tid < 32) j.ss[b * 32 + tid] = j.kr[b * 64 + tid];
@@ -382,7 +372,7 @@ void kem_release(Ctx &c)
 {
     KemWs *w = c.kem;
     if (!w) return;
-    void *dev[] = {w->d_pk, w->d_sk, w->d_ct, w->d_m, w->d_kr, w->d_rk, w->d_ss, w->d_mask, w->d_h, w->d_A, w->d_noise};
+    void *dev[] = {w->d_pk, w->d_sk, w->d_ct, w->d_m, w->d_kr, w->d_rk, w->d_ss, w->d_mask, w->d_h, w->d_A, w->d_noise, w->d_key};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     delete w;
@@ -416,6 +406,7 @@ static int kem_ensure(Ctx &c, int n)
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_h), N * 32));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_A), N * D.K * D.K * 512));
         HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_noise), N * (2 * D.K + 1) * 512));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_key), N * sizeof(int32_t)));
         return 0;
     };
     if (body()) { kem_release(c); return -1; }
@@ -433,6 +424,7 @@ static int kem_ensure(Ctx &c, int n)
     c.reg_buf("kem.d_mask", &w->d_mask, N, 0, G);
     c.reg_buf("kem.d_h", &w->d_h, N * 32, 0, G);
     c.reg_buf("kem.d_A", &w->d_A, N * D.K * D.K * 512, 0, G);
+    c.reg_buf("kem.d_key", &w->d_key, N * sizeof(int32_t), 0, G);
     return 0;
 }
 
@@ -470,11 +462,14 @@ static int kem_hpk_wave(Ctx &c, int n, const uint8_t *in, size_t in_stride, int 
 }
 
 // The key side of a KEM call: item b's piece of the key lies at base + b * stride.  The per-item calls point it into the workspace (or at
-// the resident verified keys), where A^T and H(pk) are still to be computed; a one-key call points it at the slot, every stride 0.
+// the resident verified keys), where A^T and H(pk) are still to be computed; a one-key call points it at the slot, every stride 0; a call by
+// slot points it at the registry with the index `key` (device memory): item b's pieces then lie at base + key[b] * stride.  Only the seed role of
+// k_kem_hash (h_enc) and k_kem_encrypt (pk, A) read the index.
 struct KemKeySide {
     const uint8_t *pk, *h_enc, *shat, *h_dec, *z; // h_enc: H(pk) for G of an encapsulation; h_dec: the H(pk) stored in the sk
     const int16_t *A;
     size_t pk_stride, h_enc_stride, shat_stride, h_dec_stride, z_stride, A_stride; // A_stride in int16_t elements
+    const int32_t *key;                           // nullptr: item b uses key b
     bool derive;                                  // A^T (matrix role, into A) and H(pk) (kem_wave_max() rule, into h_enc) belong to the call
 };
 
@@ -516,7 +511,7 @@ static hipError_t kem_launch_encrypt(Ctx &c, int n, const KemKeySide &k, int dec
 {
     KemWs &w = *c.kem;
     KemEncJob e{};
-    e.K = c.P.K; e.dec = dec; e.pk = k.pk; e.pk_stride = k.pk_stride; e.A = k.A; e.A_stride = k.A_stride; e.noise = w.d_noise;
+    e.K = c.P.K; e.dec = dec; e.pk = k.pk; e.pk_stride = k.pk_stride; e.A = k.A; e.A_stride = k.A_stride; e.key = k.key; e.noise = w.d_noise;
     e.m = w.d_m; e.kr = w.d_kr; e.rk = dec ? w.d_rk : nullptr; e.ct = w.d_ct; e.ss = w.d_ss; e.mask = d_mask;
     k_kem_encrypt<<<dim3((unsigned)n), dim3(256), 0, c.stream>>>(e);
     return hipGetLastError();
@@ -530,7 +525,7 @@ static int kem_enc_body(Ctx &c, int n, const KemKeySide &k, const uint8_t *coins
     HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
     if (mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
     KemHashJob h = kem_hash_job(c, n, k);
-    h.m = w.d_m; h.h = k.h_enc; h.h_stride = k.h_enc_stride;
+    h.m = w.d_m; h.h = k.h_enc; h.h_stride = k.h_enc_stride; h.key = k.key;
     if (k.derive) {
         bool wave = false; // H(pk): one wave per key on the wave sponge, or the seed role hashes pk itself
         if (kem_hpk_wave(c, n, k.pk, k.pk_stride, D.pk, wave)) return -1;
@@ -772,6 +767,54 @@ int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss)
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(kem_copy_in(c, c.kem->d_ct, ct, (size_t)n * dims(c.P.K).ct));
     return kem_dec_body(c, n, kem_side_slot(*c.kem_key), ss, PATH_KEM_DEC_KEY);
+}
+
+// ---- the verified-key registry (kosk_registry.hip) ----------------------------------------------------------
+int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, const int32_t *slots)
+{
+    if (n < 1 || n > KEM_CHUNK || !slots || !c.registry) { c.err = "kem_registry_admit: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    KemRegistry &r = *c.registry;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    RegAdmitJob j{};
+    j.n = n; j.K = D.K; j.pk_bytes = D.pk; j.wave = n <= kem_wave_max();
+    if (pk) { // the records through the workspace: 16-byte aligned whatever the caller's pointer is
+        HIPCHK(kem_copy_in(c, w.d_pk, pk, (size_t)n * D.pk));
+        j.src = w.d_pk; j.src_stride = (size_t)D.pk;
+    } else {  // the keys the last verify call left resident (kosk_registry_admit_verified)
+        j.src = c.d_pk + (size_t)resident_first * c.pk_stride; j.src_stride = c.pk_stride;
+    }
+    HIPCHK(hipMemcpyAsync(w.d_key, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+    j.slot = w.d_key; j.pk = r.d_pk; j.h = r.d_h; j.flag = r.d_flag; j.A = r.d_A;
+    j.err = c.h_err; j.max_blocks = c.xof_max_blocks;
+    HIPCHK(launch_registry_admit(j, c.stream));
+    c.path_n[PATH_REGISTRY_ADMIT]++;
+    // the staged copy goes: after an eviction no byte of the key is left in the handle's HBM
+    if (pk) HIPCHK(hipMemsetAsync(w.d_pk, 0, (size_t)n * D.pk, c.stream));
+    HIPCHK(stream_sync(c));
+    return device_error_check(c); // gen_matrix block limit: the caller empties the slots
+}
+
+int kem_enc_slots(Ctx &c, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss)
+{
+    if (n < 1 || n > KEM_CHUNK || !slots || !coins || !ct || !ss || !c.registry) { c.err = "kem_enc_slots: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const KemRegistry &r = *c.registry;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    std::vector<uint8_t> mask((size_t)n); // the occupancy mirror: an empty slot's ct and ss are zero-filled
+    bool all = true;
+    for (int b = 0; b < n; b++) all &= (mask[(size_t)b] = r.occ[(size_t)slots[b]]) != 0;
+    HIPCHK(hipMemcpyAsync(w.d_key, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+    KemKeySide k{};
+    k.pk = r.d_pk; k.pk_stride = (size_t)D.pk;
+    k.h_enc = r.d_h; k.h_enc_stride = 32;
+    k.A = r.d_A; k.A_stride = (size_t)D.K * D.K * 256;
+    k.key = w.d_key;
+    return kem_enc_body(c, n, k, coins, ct, ss, all ? nullptr : mask.data(), PATH_KEM_ENC_SLOTS);
 }
 
 } // namespace kosk

@@ -1,0 +1,187 @@
+// The verified-key registry: a table of admitted Kyber public keys in HBM.  What depends on a key alone --
+// the pk bytes, H(pk), A^T: 36 of the 37 Keccak permutations of a Kyber-768 encapsulation -- is computed once, at admission, by
+// k_registry_admit; kem_enc_slots (kosk_kem_kernels.hip) then runs the per-item kernels with the registry as their key side, item b's key
+// pieces at base + slot[b] * stride.
+//
+//   admission   k_registry_admit   per accepted key: the K^2 entries of A^T straight into the slot, H(pk), the pk bytes in 16-byte stores, the flag
+//     up to KEM_WAVE_MAX keys      K^2 + 1 one-wave blocks per key (the shape of k_kem_key_setup for n keys): one matrix entry on lane 0 of a
+//                                  block, the entries side by side; H(pk) on the wave sponge, whose block then copies the bytes
+//     above                        one sponge per lane in task-major lane ranges, longest role first (as k_kem_hash): H(pk), then the K^2
+//                                  entries; the copy is a flat range behind them, consecutive lanes on consecutive 16-byte lines of one key
+//   eviction    k_wipe             the slots' four pieces are regions of a wipe
+// slot[b] and the accept bit (slot[b] < 0: masked, nothing is written) are public; the admission reads nothing secret.
+#include <hip/hip_runtime.h>
+
+#include "kosk_ctx.hpp"
+#include "kosk_keccak_wave_dev.hpp"
+#include "kosk_kem_dev.hpp"
+
+namespace kosk {
+
+using namespace kem;
+
+#define HIPCHK(x) KOSK_HIPCHK(x)
+
+// A^T[i][j] = XOF(rho, i, j) (indcpa.c:177-178) of entry t = i K + j, as the matrix role of k_kem_hash
+__device__ __forceinline__ void registry_entry(const RegAdmitJob &j, const uint8_t *src, size_t s, int t)
+{
+    uint64_t rho[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++) rho[l] = ld64(src + j.pk_bytes - 32, l);
+    if (!matrix_entry(rho, t / j.K, t % j.K, j.max_blocks, j.A + (s * (size_t)(j.K * j.K) + t) * 256))
+        if (j.err) *reinterpret_cast<volatile uint32_t *>(j.err) = DEVERR_XOF_BLOCKS;
+}
+
+__global__ __launch_bounds__(64) void k_registry_admit(RegAdmitJob j)
+{
+    __shared__ __align__(16) uint32_t st[64];
+    const int lane = threadIdx.x, KK = j.K * j.K, lines = j.pk_bytes / 16;
+    if (j.wave) { // block t n + b: task t of key b (block-uniform)
+        const int t = (int)(blockIdx.x / (unsigned)j.n), b = (int)(blockIdx.x - (unsigned)t * (unsigned)j.n);
+        const int slot = j.slot[b];
+        if (slot < 0) return;
+        const uint8_t *src = j.src + (size_t)b * j.src_stride;
+        if (t < KK) {
+            if (lane == 0) registry_entry(j, src, (size_t)slot, t);
+            return;
+        }
+        __builtin_amdgcn_s_setprio(3); // a chain is latency, not throughput
+        WaveSponge sp;
+        sp.setup(lane);
+        uint32_t a = 0;
+        wave_absorb_words(sp, a, [&](int i) { return *reinterpret_cast<const uint2 *>(src + 8 * i); }, j.pk_bytes / 8, 0x06u);
+        const uint2 w = sp.words(a, st, 4);
+        if (lane < 4) *reinterpret_cast<uint2 *>(j.h + (size_t)slot * 32 + 8 * lane) = w;
+        const U128 *in = reinterpret_cast<const U128 *>(src);
+        U128 *out = reinterpret_cast<U128 *>(j.pk + (size_t)slot * j.pk_bytes);
+        for (int i = lane; i < lines; i += 64) out[i] = in[i];
+        if (lane == 0) j.flag[slot] = 1;
+        return;
+    }
+    const long gid = (long)blockIdx.x * 64 + lane, sponges = (long)(1 + KK) * j.n;
+    if (gid < sponges) { // lane t n + b: H(pk) (t = 0: 6 / 9 / 12 permutations), then entry t - 1 (three or four)
+        const int t = (int)(gid / j.n), b = (int)(gid - (long)t * j.n);
+        const int slot = j.slot[b];
+        if (slot < 0) return;
+        const uint8_t *src = j.src + (size_t)b * j.src_stride;
+        if (t) { registry_entry(j, src, (size_t)slot, t - 1); return; }
+        uint64_t d[4];
+        sha3_256_words(src, j.pk_bytes, d);
+        U128 *o = reinterpret_cast<U128 *>(j.h + (size_t)slot * 32);
+        o[0] = U128{(uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32)};
+        o[1] = U128{(uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32)};
+        j.flag[slot] = 1;
+        return;
+    }
+    const long c = gid - sponges; // line c % lines of key c / lines
+    if (c >= (long)lines * j.n) return;
+    const int b = (int)(c / lines), i = (int)(c - (long)b * lines);
+    const int slot = j.slot[b];
+    if (slot < 0) return;
+    reinterpret_cast<U128 *>(j.pk + (size_t)slot * j.pk_bytes)[i] = reinterpret_cast<const U128 *>(j.src + (size_t)b * j.src_stride)[i];
+}
+
+hipError_t launch_registry_admit(const RegAdmitJob &j, hipStream_t st)
+{
+    const long KK = (long)j.K * j.K;
+    const long blocks = j.wave ? (KK + 1) * j.n : (((KK + 1) + j.pk_bytes / 16) * j.n + 63) / 64;
+    k_registry_admit<<<dim3((unsigned)blocks), dim3(64), 0, st>>>(j);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host --
+void registry_release(Ctx &c)
+{
+    KemRegistry *r = c.registry;
+    if (!r) return;
+    void *dev[] = {r->d_pk, r->d_h, r->d_A, r->d_flag};
+    for (void *p : dev)
+        if (p) (void)hipFree(p);
+    delete r;
+    c.registry = nullptr;
+    c.inv_drop(Ctx::INVG_REGISTRY);
+}
+
+int registry_reserve(Ctx &c, int capacity)
+{
+    if (capacity < 0) { c.err = "kosk_registry_reserve: capacity < 0"; return -1; }
+    if (c.registry && c.registry->used) { c.err = "kosk_registry_reserve: the registry is not empty (kosk_registry_evict)"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    if (c.registry) {
+        HIPCHK(stream_sync(c));
+        registry_release(c); // every slot is empty, and an empty slot is zeros
+    }
+    if (!capacity) return 0;
+    const Dims D = dims(c.P.K);
+    KemRegistry *r = new KemRegistry();
+    c.registry = r;
+    const size_t N = (size_t)capacity, a_bytes = N * D.K * D.K * 512;
+    auto body = [&]() -> int {
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_pk), N * D.pk));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_h), N * 32));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_A), a_bytes));
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_flag), N));
+        HIPCHK(hipMemsetAsync(r->d_pk, 0, N * D.pk, c.stream));
+        HIPCHK(hipMemsetAsync(r->d_h, 0, N * 32, c.stream));
+        HIPCHK(hipMemsetAsync(r->d_A, 0, a_bytes, c.stream));
+        HIPCHK(hipMemsetAsync(r->d_flag, 0, N, c.stream));
+        HIPCHK(stream_sync(c));
+        return 0;
+    };
+    if (body()) {
+        const std::string why = c.err;
+        (void)hipGetLastError();
+        registry_release(c); // nothing is left allocated
+        c.err = "kosk_registry_reserve: " + why;
+        return -1;
+    }
+    r->capacity = capacity;
+    r->occ.assign(N, 0);
+    const int G = Ctx::INVG_REGISTRY; // public, all four: the wipes leave them alone, the scan covers them
+    c.reg_buf("registry.d_pk", &r->d_pk, N * D.pk, 0, G);
+    c.reg_buf("registry.d_h", &r->d_h, N * 32, 0, G);
+    c.reg_buf("registry.d_A", &r->d_A, a_bytes, 0, G);
+    c.reg_buf("registry.d_flag", &r->d_flag, N, 0, G);
+    return 0;
+}
+
+int registry_evict(Ctx &c, int n, const int32_t *slots)
+{
+    KemRegistry &r = *c.registry;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    const size_t a_bytes = (size_t)D.K * D.K * 512;
+    std::vector<WipeRegion> dev;
+    for (int b = 0; b < n; b++) {
+        const size_t s = (size_t)slots[b];
+        if (!r.occ[s]) continue; // empty already (or named twice)
+        r.occ[s] = 0;
+        r.used--;
+        dev.push_back(WipeRegion{r.d_pk + s * D.pk, (size_t)D.pk, 0, 1});
+        dev.push_back(WipeRegion{r.d_h + s * 32, 32, 0, 1});
+        dev.push_back(WipeRegion{reinterpret_cast<uint8_t *>(r.d_A) + s * a_bytes, a_bytes, 0, 1});
+        dev.push_back(WipeRegion{r.d_flag + s, 1, 0, 1});
+    }
+    if (launch_wipe(c, dev.data(), (int)dev.size())) return -1;
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+int registry_read(Ctx &c, int n, const int32_t *slots, uint8_t *state, uint8_t *pk, uint8_t *h)
+{
+    const KemRegistry &r = *c.registry;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    const hipMemcpyKind kp = pk && is_device_pointer(pk) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind kh = h && is_device_pointer(h) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    for (int b = 0; b < n; b++) {
+        const size_t s = (size_t)slots[b];
+        state[b] = r.occ[s];
+        if (pk) HIPCHK(hipMemcpyAsync(pk + (size_t)b * D.pk, r.d_pk + s * D.pk, (size_t)D.pk, kp, c.stream));
+        if (h) HIPCHK(hipMemcpyAsync(h + (size_t)b * 32, r.d_h + s * 32, 32, kh, c.stream));
+    }
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
+} // namespace kosk
