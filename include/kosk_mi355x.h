@@ -441,6 +441,42 @@ int kosk_registry_evict(kosk_ctx *ctx, int n, const int32_t *slots);
 int kosk_registry_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *pk, uint8_t *h);
 int kosk_kem_enc_slots(kosk_ctx *ctx, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* ---- The registry by fingerprint (INTEGRATION.md 8.4 is the normative text): the index beside the keys.  A peer is known by
+ * SHA3-256(pk), which every slot stores as h; an open-addressing table over those fingerprints in HBM lets the library look keys up, refuse
+ * keys that are enrolled already, and pick the slots.
+ * The index: T = kosk_registry_index_entries(capacity) = the smallest power of two >= 2 x capacity int32 entries (0 for capacity < 1), one more
+ * allocation of the registry (a public buffer, slot numbers only), made at the first of the calls below and freed with the registry; a
+ * registry that never uses them allocates what it allocated before.  kosk_registry_index_home(capacity, h) = LE32(h[0..4)) & (T - 1) is a
+ * fingerprint's home entry (-1 for capacity < 1 or NULL); probing is linear.  One entry per distinct fingerprint among the occupied slots,
+ * holding the LOWEST such slot (the admit calls above may put equal keys into several slots).  Every reserve / admit / evict / enrol
+ * invalidates the index and the next call below rebuilds it on the GPU (k_registry_index); no unsalted-hash attack applies beyond a probe
+ * chain as long as the keys the attacker itself enrolled (8.4).
+ * kosk_registry_find: h = n x 32 bytes, slots = n int32, each host or device memory of any alignment; slots[b] = the lowest occupied slot
+ * whose stored H(pk) equals h[b], or -1.  Any n >= 1 in launch groups of 16384; works on a cohort member, unmerged.
+ * kosk_registry_enrol_verified / kosk_registry_enrol: the candidates and preconditions of kosk_registry_admit_verified /
+ * kosk_registry_admit, but the library picks the slots: slots (n int32) and status (n bytes) are OUTPUTS in host memory.  Positions are
+ * taken in ascending b.  A position whose verify bit / accept byte is 0 is KOSK_ENROL_REJECTED, slot -1, and does not count as an occurrence
+ * of its key.  A position whose fingerprint is in the registry already, or was admitted at a lower position of this call, is
+ * KOSK_ENROL_DUPLICATE; slots[b] is the slot that holds the key; nothing is written for it.  Every other position is KOSK_ENROL_ADMITTED
+ * into the lowest-numbered empty slot not yet given out in this call.  More new keys than empty slots: -1 ("registry is full"), nothing
+ * changed.  Equality is equality of the pk BYTES: two encodings of one key (12-bit fields >= q) are two fingerprints; the strict verifier
+ * refuses proofs over such a pk anyway, and a caller of kosk_registry_enrol who cares runs kosk_kem_check_pk first.  -1 ("block limit")
+ * as for kosk_registry_admit: the slots this call wrote are emptied.
+ * kosk_kem_enc_peers: kosk_kem_enc_slots with the lookup on the GPU in front of the per-item kernels; no slot number crosses to the host.
+ * h: n x 32 bytes, host or device memory.  For every b whose fingerprint is found, ct and ss are byte for byte those of kosk_kem_enc_slots
+ * on kosk_registry_find's slot with the same coins; done[b] = found (host or device memory); ct and ss of a miss are zero-filled; coins are
+ * consumed for every position (coins == NULL: one 32-byte draw per item, in item order, on the caller's thread; a refused call draws none).
+ * Refusals (-1, a text that begins with the call's name, nothing started): NULL arguments, n < 1, no registry reserved.
+ * Erasure: the index holds slot numbers only; the staged query fingerprints and candidate records are zeroed before each of these calls
+ * returns; kosk_wipe_secrets and KOSK_WIPE_CALL leave the index alone, as they leave the registry. */
+size_t kosk_registry_index_entries(int capacity);
+int kosk_registry_index_home(int capacity, const uint8_t h[32]);
+int kosk_registry_find(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *slots);
+enum { KOSK_ENROL_REJECTED = 0, KOSK_ENROL_ADMITTED = 1, KOSK_ENROL_DUPLICATE = 2 };
+int kosk_registry_enrol_verified(kosk_ctx *ctx, int n, int32_t *slots, uint8_t *status);
+int kosk_registry_enrol(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, int32_t *slots, uint8_t *status);
+int kosk_kem_enc_peers(kosk_ctx *ctx, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -566,7 +602,10 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 25 launches of k_bank_put (one per chunk of kosk_bank_fill) / 26 launches of k_bank_take (one per chunk of a call that consumes bank
  * entries); the diagnostic kosk_bank_timing moves both by reps + 1,
  * 27 launches of k_registry_admit (one per launch group of kosk_registry_admit / kosk_registry_admit_verified), 28 kem_enc_slots: launch
- * groups of kosk_kem_enc_slots (ids 12 / 20 do not move for it); kosk_registry_evict runs k_wipe (id 18). */
+ * groups of kosk_kem_enc_slots (ids 12 / 20 do not move for it); kosk_registry_evict runs k_wipe (id 18),
+ * 29 launches of k_registry_index (one per rebuild of the fingerprint index: the first lookup after a mutation of the registry),
+ * 30 launches of k_registry_find (one per launch group of kosk_registry_find, kosk_registry_enrol* and kosk_kem_enc_peers),
+ * 31 kem_enc_peers: launch groups of kosk_kem_enc_peers (ids 12 / 20 / 28 do not move for it). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

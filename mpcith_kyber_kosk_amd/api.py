@@ -246,6 +246,17 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_reserve")):
         sig.update(registry)
+    # the registry by fingerprint; optional under the same rule (and only then)
+    peers = {
+        "kosk_registry_index_entries": (sz, [C.c_int]),
+        "kosk_registry_index_home": (C.c_int, [C.c_int, vp]),
+        "kosk_registry_find": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_registry_enrol_verified": (C.c_int, [vp, C.c_int, vp, vp]),
+        "kosk_registry_enrol": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "kosk_kem_enc_peers": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_find")):
+        sig.update(peers)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -287,7 +298,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_bank_entry_bytes", "kosk_tape_section", "kosk_bank_reserve", "kosk_bank_level", "kosk_bank_fill", "kosk_stage_prover_keys_banked",
            "kosk_prove_keys_banked_batch", "kosk_verifiable_keygen_banked_batch", "kosk_bank_timing",
            "kosk_registry_slot_bytes", "kosk_registry_reserve", "kosk_registry_level", "kosk_registry_admit_verified", "kosk_registry_admit",
-           "kosk_registry_evict", "kosk_registry_read", "kosk_kem_enc_slots"]
+           "kosk_registry_evict", "kosk_registry_read", "kosk_kem_enc_slots",
+           "kosk_registry_index_entries", "kosk_registry_index_home", "kosk_registry_find", "kosk_registry_enrol_verified",
+           "kosk_registry_enrol", "kosk_kem_enc_peers"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -330,6 +343,18 @@ def dense2_proof_bytes(k): return lib.kosk_dense2_proof_bytes(k)
 def format_bytes(k, fmt): return lib.kosk_format_bytes(k, fmt)
 def bank_entry_bytes(k): return lib.kosk_bank_entry_bytes(k)
 def registry_slot_bytes(k): return lib.kosk_registry_slot_bytes(k)
+def registry_index_entries(capacity): return lib.kosk_registry_index_entries(capacity)
+
+
+ENROL_REJECTED, ENROL_ADMITTED, ENROL_DUPLICATE = 0, 1, 2  # KOSK_ENROL_*
+
+
+def registry_index_home(capacity, h):
+    """kosk_registry_index_home: the home entry of fingerprint h (32 bytes) in the index of a registry of `capacity` slots; -1 for capacity < 1"""
+    h = bytes(h)
+    if len(h) != 32:
+        raise KoskError("a fingerprint has 32 bytes")
+    return lib.kosk_registry_index_home(capacity, C.c_char_p(h))
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1161,6 +1186,51 @@ class Kosk:
             return out
         return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
 
+    # the registry by fingerprint
+    def registry_find(self, hs, n=None, out=None):
+        """kosk_registry_find: per fingerprint SHA3-256(pk) the lowest occupied slot that holds the key, or -1.  hs: a list of 32-byte
+        strings or an int DEVICE pointer (with n); out: None (a list of ints is returned) or an int DEVICE pointer to n int32"""
+        hp, n, _k = self._records("fingerprint", hs, n, 32)
+        if out is not None:
+            self._chk(lib.kosk_registry_find(self._h, n, hp, C.c_void_p(int(out))), "registry_find")
+            return out
+        slots = (C.c_int32 * max(n, 1))()
+        self._chk(lib.kosk_registry_find(self._h, n, hp, slots), "registry_find")
+        return list(slots[:n])
+
+    def registry_enrol(self, pks, accept=None, n=None):
+        """kosk_registry_enrol: kosk_registry_admit with the slots picked by the library and duplicates refused -> (slots, status), status
+        ENROL_REJECTED / ENROL_ADMITTED / ENROL_DUPLICATE per key.  pks / accept as in registry_admit"""
+        pp, n, _k = self._records("pk", pks, n, self.pk_bytes)
+        if accept is not None and len(accept) != n:
+            raise KoskError("registry_enrol: %d keys need %d accept bytes" % (n, n))
+        ap = None if accept is None else C.c_char_p(bytes(1 if a_ else 0 for a_ in accept))
+        slots = (C.c_int32 * max(n, 1))(); status = C.create_string_buffer(max(n, 1))
+        self._chk(lib.kosk_registry_enrol(self._h, n, pp, ap, slots, status), "registry_enrol")
+        return list(slots[:n]), list(status.raw[:n])
+
+    def registry_enrol_verified(self, n):
+        """kosk_registry_enrol_verified: the first n keys of the last completed verify call, where its verify bit is 1 -> (slots, status)"""
+        slots = (C.c_int32 * max(n, 1))(); status = C.create_string_buffer(max(n, 1))
+        self._chk(lib.kosk_registry_enrol_verified(self._h, n, slots, status), "registry_enrol_verified")
+        return list(slots[:n]), list(status.raw[:n])
+
+    def kem_enc_peers(self, hs, coins=None, out=None, n=None):
+        """kosk_kem_enc_peers: item b to the registry's key with fingerprint hs[b] (a list of 32-byte strings, or an int DEVICE pointer
+        with n); coins / out as in kem_enc_slots.  Returns (cts, sss, done); ct and ss of a fingerprint that is not found are zero-filled"""
+        hp, n, _k1 = self._records("fingerprint", hs, n, 32)
+        cp, _k2 = None, None
+        if coins is not None:
+            cp, nc, _k2 = self._records("coins", coins, n, 32)
+            if nc != n:
+                raise KoskError("coins for %d items, fingerprints for %d" % (nc, n))
+        ctb = ct_bytes(self.k)
+        bufs, host = self._kem_out(out, n, (ctb, SS_BYTES, 1))
+        self._chk(lib.kosk_kem_enc_peers(self._h, n, hp, cp, bufs[0], bufs[1], bufs[2]), "kem_enc_peers")
+        if host is None:
+            return out
+        return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1306,6 +1376,9 @@ class Kosk:
     PATH_BANK_TAKE = 26
     PATH_REGISTRY_ADMIT = 27
     PATH_KEM_ENC_SLOTS = 28
+    PATH_REGISTRY_INDEX = 29
+    PATH_REGISTRY_FIND = 30
+    PATH_KEM_ENC_PEERS = 31
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -29,6 +29,7 @@
 #include "kosk_combine.hpp"
 #include "kosk_ctx.hpp"
 #include "kosk_lanes.hpp"
+#include "kosk_registry_resolve.hpp"
 
 using namespace kosk;
 
@@ -1507,6 +1508,89 @@ int kosk_kem_enc_slots(kosk_ctx *ctx, int n, const int32_t *slots, const uint8_t
         })) return -1;
     if (hipMemcpy(done, bits.data(), (size_t)n, hipMemcpyDefault) != hipSuccess) { (void)hipGetLastError(); return refuse(ctx, "kosk_kem_enc_slots", "copying the occupancy bits to `done` failed"); }
     return 0;
+    WGUARD_END
+}
+
+// ---- the registry by fingerprint (kosk_registry.hip) ----
+static_assert((int)KOSK_ENROL_REJECTED == (int)ENROL_REJECTED && (int)KOSK_ENROL_ADMITTED == (int)ENROL_ADMITTED && (int)KOSK_ENROL_DUPLICATE == (int)ENROL_DUPLICATE,
+              "kosk_mi355x.h and kosk_registry_resolve.hpp");
+static const char *const WHY_NO_REGISTRY = "no registry is reserved (kosk_registry_reserve)";
+size_t kosk_registry_index_entries(int capacity) { return registry_index_entries(capacity); }
+int kosk_registry_index_home(int capacity, const uint8_t *h) { return capacity < 1 || !h ? -1 : (int)registry_index_home(capacity, h); }
+
+int kosk_registry_find(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *slots)
+{
+    if (!ctx || n < 1 || !h || !slots) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_find", WHY_NO_REGISTRY);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) { return kem_registry_find(c, count, h + (size_t)first * 32, slots + first); });
+    GUARD_END
+}
+
+// candidates b of the call (pk records, or pk == nullptr: the resident keys) where accept[b] != 0: fingerprints and hits to the host, the
+// resolver, then the admission of the ADMITTED positions through registry_admit_run
+static int registry_enrol_run(kosk_ctx *ctx, const char *fn, int n, const uint8_t *pk, const uint8_t *accept, int32_t *slots, uint8_t *status)
+{
+    const size_t pkb = ctx->c->P.pk_bytes;
+    std::vector<uint8_t> fp((size_t)n * 32), all;
+    std::vector<int32_t> hit((size_t)n);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return kem_registry_probe(c, count, pk ? pk + (size_t)first * pkb : nullptr, first, fp.data() + (size_t)first * 32, hit.data() + first);
+        })) return -1;
+    if (!accept) { all.assign((size_t)n, 1); accept = all.data(); }
+    std::vector<int32_t> dst;
+    std::vector<uint8_t> st;
+    const int admitted = registry_enrol_resolve(n, accept, fp.data(), hit.data(), ctx->c->registry->occ, dst, st);
+    if (admitted < 0) return refuse(ctx, fn, "registry is full (more new keys than empty slots): nothing was changed");
+    if (admitted) {
+        std::vector<uint8_t> take((size_t)n);
+        std::vector<int32_t> named(dst); // a position that is not admitted names no slot: registry_admit_run masks it
+        for (int b = 0; b < n; b++) take[(size_t)b] = st[(size_t)b] == ENROL_ADMITTED;
+        if (registry_admit_run(ctx, n, pk, take.data(), named.data())) return -1;
+    }
+    memcpy(slots, dst.data(), sizeof(int32_t) * (size_t)n);
+    memcpy(status, st.data(), (size_t)n);
+    return 0;
+}
+
+int kosk_registry_enrol_verified(kosk_ctx *ctx, int n, int32_t *slots, uint8_t *status)
+{
+    if (!ctx || n < 1 || !slots || !status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_enrol_verified", WHY_NO_REGISTRY);
+    if (const char *why = verified_keys_refusal(ctx, n)) return refuse(ctx, "kosk_registry_enrol_verified", why);
+    std::vector<uint8_t> bits((size_t)n);
+    for (int b = 0; b < n; b++) bits[(size_t)b] = ctx->masks[(size_t)b] == 0;
+    return registry_enrol_run(ctx, "kosk_registry_enrol_verified", n, nullptr, bits.data(), slots, status);
+    GUARD_END
+}
+
+int kosk_registry_enrol(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, int32_t *slots, uint8_t *status)
+{
+    if (!ctx || n < 1 || !pk || !slots || !status) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_enrol", WHY_NO_REGISTRY);
+    return registry_enrol_run(ctx, "kosk_registry_enrol", n, pk, accept, slots, status);
+    GUARD_END
+}
+
+int kosk_kem_enc_peers(kosk_ctx *ctx, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (!ctx || n < 1 || !h || !ct || !ss || !done) return bad_args(ctx, __func__);
+    WGUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_kem_enc_peers", WHY_NO_REGISTRY); // before any coin is drawn
+    // coins are drawn for every position, found or not: the draw order does not depend on the registry
+    std::vector<uint8_t> drawn;
+    VecWiper<uint8_t> drawn_gone(drawn);
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    const size_t ctb = kosk_ct_bytes(ctx->c->P.K);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_enc_peers(c, count, h + (size_t)first * 32, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32, done + first);
+    });
     WGUARD_END
 }
 

@@ -154,7 +154,8 @@ int device_error_check(Ctx &c)
     *reinterpret_cast<volatile uint32_t *>(c.h_err) = 0;
     c.err = (e & DEVERR_XOF_BLOCKS) ? "gen_matrix: SHAKE128 block limit reached before 256 coefficients were accepted (indcpa.c:124-145 would squeeze on; "
                                       "probability < 2^-300 with the default limit of 32 blocks): no result was produced"
-                                    : "a kernel reported an internal error";
+            : (e & DEVERR_INDEX_FULL) ? "registry index overflow: a probe walk passed every entry of the table without meeting an empty one (impossible at load <= 1/2)"
+                                      : "a kernel reported an internal error";
     return -1;
 }
 

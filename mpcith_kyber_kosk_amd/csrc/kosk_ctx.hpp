@@ -77,7 +77,8 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
-              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS, PATH_COUNT };
+              PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS,
+              PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -665,7 +666,8 @@ int kem_dec_key(Ctx &c, int n, const uint8_t *ct, uint8_t *ss);
 
 // The verified-key registry (kosk_registry.hip): `capacity` slots in HBM, structure of arrays -- what depends on a key alone, decoded
 // once at admission (k_registry_admit) and read by kem_enc_slots through KemKeySide, slot s at base + s * stride.  Four allocations of its
-// own (kem_ensure frees and reallocates the KEM workspace; the registry must not move), public buffers of the inventory under INVG_REGISTRY.
+// own (kem_ensure frees and reallocates the KEM workspace; the registry must not move) and a fifth, the fingerprint index, from the first
+// lookup on: public buffers of the inventory under INVG_REGISTRY.
 // `occ` mirrors d_flag on the host: every mutation goes through a host call.
 struct KemRegistry {
     int capacity = 0, used = 0;
@@ -674,6 +676,10 @@ struct KemRegistry {
     int16_t *d_A = nullptr;    // [capacity][K K][256]   A^T, the layout encrypt_block reads
     uint8_t *d_flag = nullptr; // [capacity]             1 = occupied
     std::vector<uint8_t> occ;
+    // the fingerprint index: allocated at the first call that looks a key up, rebuilt by that call when a mutation cleared
+    // index_valid
+    int32_t *d_index = nullptr; // [registry_index_entries(capacity)] -1 = empty, else the lowest occupied slot of one fingerprint
+    bool index_valid = false;
 };
 inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
 // One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
@@ -702,6 +708,55 @@ int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, con
 // crypto_kem_enc_derand for n <= KEM_CHUNK items, item b to the key in slots[b] (host; valid ids): per-item work only; an empty slot's ct and ss
 // are zero-filled
 int kem_enc_slots(Ctx &c, int n, const int32_t *slots, const uint8_t *coins, uint8_t *ct, uint8_t *ss);
+
+// The fingerprint index (kosk_registry.hip): open addressing over the slots' H(pk), T = the smallest power of two >= 2 x capacity
+// int32 entries, linear probing from LE32(h[0..4)) & (T - 1); one entry per distinct fingerprint among the occupied slots, holding the
+// lowest such slot.
+inline size_t registry_index_entries(int capacity)
+{
+    if (capacity < 1) return 0;
+    size_t t = 2;
+    while (t < 2 * (size_t)capacity) t <<= 1;
+    return t;
+}
+inline uint32_t registry_index_home(int capacity, const uint8_t *h)
+{
+    const uint32_t w = (uint32_t)h[0] | (uint32_t)h[1] << 8 | (uint32_t)h[2] << 16 | (uint32_t)h[3] << 24;
+    return w & (uint32_t)(registry_index_entries(capacity) - 1);
+}
+// k_registry_index: one lane per slot, the table memset to -1 in front of it
+struct RegIndexJob {
+    int capacity;
+    uint32_t mask;       // T - 1
+    const uint8_t *h;    // [capacity][32]
+    const uint8_t *flag; // [capacity]
+    int32_t *index;      // [T]
+    uint32_t *err;
+};
+// k_registry_find: one lane per query (q: [n][32], 16-byte aligned).  slot (may be nullptr): the slot or -1; key / mask (both or neither):
+// what the KEM kernels read, the slot or 0 on a miss, and 1 / 0
+struct RegFindJob {
+    int n, capacity;
+    uint32_t mask;
+    const uint8_t *q, *h;
+    const int32_t *index;
+    int32_t *slot, *key;
+    uint8_t *found;
+    uint32_t *err;
+};
+hipError_t launch_registry_index(const RegIndexJob &j, hipStream_t st);
+hipError_t launch_registry_find(const RegFindJob &j, hipStream_t st);
+// the index allocated and current: a no-op while index_valid; else memset + k_registry_index, synchronised; -1 ("index overflow")
+int registry_index_ensure(Ctx &c);
+// n <= KEM_CHUNK fingerprints (n x 32 bytes, host or device memory of any alignment) -> slots (n int32, host or device memory): the lowest
+// occupied slot with that H(pk), or -1.  Synchronised; the staged fingerprints are zeroed
+int kem_registry_find(Ctx &c, int n, const uint8_t *h, int32_t *slots);
+// the first half of an enrolment: H(pk) of n <= KEM_CHUNK candidates (as kem_registry_admit names them) into h (host, n x 32) and what
+// k_registry_find says of them into hit (host).  Synchronised; the staged records and fingerprints are zeroed
+int kem_registry_probe(Ctx &c, int n, const uint8_t *pk, int resident_first, uint8_t *h, int32_t *hit);
+// crypto_kem_enc_derand for n <= KEM_CHUNK items, item b to the key whose H(pk) is h[b] (host or device memory): k_registry_find writes the
+// slot index and the mask in HBM, the per-item kernels follow; done (host or device memory) = found, ct and ss of a miss zero-filled
+int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
 // ---- erasure (kosk_wipe.hip) ----
 // `count` records of `bytes` bytes, `stride` apart, in HBM (count 1: one run of bytes)

@@ -15,7 +15,8 @@ struct XofGuard {
     uint32_t *err = nullptr;
     int max_blocks = 32;
 };
-enum : uint32_t { DEVERR_XOF_BLOCKS = 1u };
+// DEVERR_INDEX_FULL: a probe walk of the registry's fingerprint index (kosk_registry.hip) reached its bound of one pass over the table
+enum : uint32_t { DEVERR_XOF_BLOCKS = 1u, DEVERR_INDEX_FULL = 2u };
 
 
 // K4: lane `l` of group `g` hashes  [prefix(32 B)] || rows[g][r][col_off + col(l)], r = 0..NROWS-1

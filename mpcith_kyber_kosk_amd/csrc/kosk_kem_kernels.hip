@@ -517,13 +517,14 @@ static hipError_t kem_launch_encrypt(Ctx &c, int n, const KemKeySide &k, int dec
     return hipGetLastError();
 }
 
-// Encapsulation under either key side (the workspace holds n items): `path` is the caller's path_n[] counter
+// Encapsulation under either key side (the workspace holds n items): `path` is the caller's path_n[] counter.  mask: host memory, or
+// w.d_mask itself where a kernel queued on the stream has written it already (kem_enc_peers): nothing is copied then
 static int kem_enc_body(Ctx &c, int n, const KemKeySide &k, const uint8_t *coins, uint8_t *ct, uint8_t *ss, const uint8_t *mask, int path)
 {
     KemWs &w = *c.kem;
     const Dims D = dims(c.P.K);
     HIPCHK(kem_copy_in(c, w.d_m, coins, (size_t)n * 32));
-    if (mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
+    if (mask && mask != w.d_mask) HIPCHK(hipMemcpyAsync(w.d_mask, mask, (size_t)n, hipMemcpyHostToDevice, c.stream));
     KemHashJob h = kem_hash_job(c, n, k);
     h.m = w.d_m; h.h = k.h_enc; h.h_stride = k.h_enc_stride; h.key = k.key;
     if (k.derive) {
@@ -778,6 +779,7 @@ int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, con
     KemRegistry &r = *c.registry;
     const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
+    r.index_valid = false; // the next lookup rebuilds the fingerprint index
     RegAdmitJob j{};
     j.n = n; j.K = D.K; j.pk_bytes = D.pk; j.wave = n <= kem_wave_max();
     if (pk) { // the records through the workspace: 16-byte aligned whatever the caller's pointer is
@@ -815,6 +817,87 @@ int kem_enc_slots(Ctx &c, int n, const int32_t *slots, const uint8_t *coins, uin
     k.A = r.d_A; k.A_stride = (size_t)D.K * D.K * 256;
     k.key = w.d_key;
     return kem_enc_body(c, n, k, coins, ct, ss, all ? nullptr : mask.data(), PATH_KEM_ENC_SLOTS);
+}
+
+// ---- the registry by fingerprint (kosk_registry.hip) --------------------------------------------------------
+// k_registry_find on the n fingerprints staged in w.d_h, queued: the slots into `slot` (or nullptr), and with enc the pair the KEM kernels
+// read into w.d_key / w.d_mask
+static int kem_launch_find(Ctx &c, int n, int32_t *slot, bool enc)
+{
+    KemWs &w = *c.kem;
+    const KemRegistry &r = *c.registry;
+    RegFindJob f{};
+    f.n = n; f.capacity = r.capacity; f.mask = (uint32_t)(registry_index_entries(r.capacity) - 1);
+    f.q = w.d_h; f.h = r.d_h; f.index = r.d_index; f.slot = slot; f.err = c.h_err;
+    if (enc) { f.key = w.d_key; f.found = w.d_mask; }
+    HIPCHK(launch_registry_find(f, c.stream));
+    c.path_n[PATH_REGISTRY_FIND]++;
+    return 0;
+}
+
+int kem_registry_find(Ctx &c, int n, const uint8_t *h, int32_t *slots)
+{
+    if (n < 1 || n > KEM_CHUNK || !h || !slots || !c.registry) { c.err = "kem_registry_find: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    if (registry_index_ensure(c)) return -1;
+    KemWs &w = *c.kem;
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_h, h, (size_t)n * 32)); // through the workspace: 16-byte aligned whatever the caller's pointer is
+    if (kem_launch_find(c, n, w.d_key, false)) return -1;
+    HIPCHK(hipMemsetAsync(w.d_h, 0, (size_t)n * 32, c.stream)); // the staged fingerprints go: an evicted key leaves no hash behind
+    HIPCHK(kem_copy_out(c, slots, w.d_key, (size_t)n * sizeof(int32_t)));
+    HIPCHK(stream_sync(c));
+    return device_error_check(c); // index overflow
+}
+
+int kem_registry_probe(Ctx &c, int n, const uint8_t *pk, int resident_first, uint8_t *h, int32_t *hit)
+{
+    if (n < 1 || n > KEM_CHUNK || !h || !hit || !c.registry) { c.err = "kem_registry_probe: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    if (registry_index_ensure(c)) return -1;
+    KemWs &w = *c.kem;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    const uint8_t *src = w.d_pk;
+    size_t stride = (size_t)D.pk;
+    if (pk) HIPCHK(kem_copy_in(c, w.d_pk, pk, (size_t)n * D.pk));
+    else { src = c.d_pk + (size_t)resident_first * c.pk_stride; stride = c.pk_stride; } // the keys the last verify call left resident
+    bool wave = false; // H(pk) under the two-layout rule, into w.d_h either way
+    if (kem_hpk_wave(c, n, src, stride, D.pk, wave)) return -1;
+    if (!wave) {
+        k_kem_hpk<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c.stream>>>(n, src, stride, D.pk, nullptr, w.d_h, 32);
+        HIPCHK(hipGetLastError());
+    }
+    if (kem_launch_find(c, n, w.d_key, false)) return -1;
+    HIPCHK(hipMemcpyAsync(h, w.d_h, (size_t)n * 32, hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(hipMemcpyAsync(hit, w.d_key, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, c.stream));
+    // the staged copies go, as in kem_registry_admit
+    if (pk) HIPCHK(hipMemsetAsync(w.d_pk, 0, (size_t)n * D.pk, c.stream));
+    HIPCHK(hipMemsetAsync(w.d_h, 0, (size_t)n * 32, c.stream));
+    HIPCHK(stream_sync(c));
+    return device_error_check(c);
+}
+
+int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (n < 1 || n > KEM_CHUNK || !h || !coins || !ct || !ss || !done || !c.registry) { c.err = "kem_enc_peers: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    if (registry_index_ensure(c)) return -1;
+    KemWs &w = *c.kem;
+    const KemRegistry &r = *c.registry;
+    const Dims D = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_h, h, (size_t)n * 32));
+    if (kem_launch_find(c, n, nullptr, true)) return -1; // the slot index and the mask stay in HBM
+    HIPCHK(hipMemsetAsync(w.d_h, 0, (size_t)n * 32, c.stream));
+    HIPCHK(kem_copy_out(c, done, w.d_mask, (size_t)n)); // queued here: the body's last synchronisation covers it
+    KemKeySide k{};
+    k.pk = r.d_pk; k.pk_stride = (size_t)D.pk;
+    k.h_enc = r.d_h; k.h_enc_stride = 32;
+    k.A = r.d_A; k.A_stride = (size_t)D.K * D.K * 256;
+    k.key = w.d_key;
+    if (kem_enc_body(c, n, k, coins, ct, ss, w.d_mask, PATH_KEM_ENC_PEERS)) return -1;
+    return device_error_check(c); // index overflow
 }
 
 } // namespace kosk

@@ -9,6 +9,8 @@
 //     above                        one sponge per lane in task-major lane ranges, longest role first (as k_kem_hash): H(pk), then the K^2
 //                                  entries; the copy is a flat range behind them, consecutive lanes on consecutive 16-byte lines of one key
 //   eviction    k_wipe             the slots' four pieces are regions of a wipe
+//   index       k_registry_index   one lane per slot: open addressing over the slots' H(pk), rebuilt whole by the first lookup after a mutation
+//   lookup      k_registry_find    one lane per query: the slot (or -1), or the slot index and mask the per-item KEM kernels read
 // slot[b] and the accept bit (slot[b] < 0: masked, nothing is written) are public; the admission reads nothing secret.
 #include <hip/hip_runtime.h>
 
@@ -89,12 +91,99 @@ hipError_t launch_registry_admit(const RegAdmitJob &j, hipStream_t st)
     return hipGetLastError();
 }
 
+// ---- the fingerprint index ------------------------------------------------------------------------------
+// T int32 entries, -1 = empty; the home of a fingerprint is LE32(h[0..4)) & (T - 1), probing is linear.  Fingerprints and slots are public:
+// branches and addresses may depend on them.
+__device__ __forceinline__ bool same_fingerprint(const U128 &a0, const U128 &a1, const uint8_t *p)
+{
+    const U128 b0 = reinterpret_cast<const U128 *>(p)[0], b1 = reinterpret_cast<const U128 *>(p)[1];
+    return ((a0.x ^ b0.x) | (a0.y ^ b0.y) | (a0.z ^ b0.z) | (a0.w ^ b0.w) | (a1.x ^ b1.x) | (a1.y ^ b1.y) | (a1.z ^ b1.z) | (a1.w ^ b1.w)) == 0;
+}
+
+// One lane per slot.  An occupied slot s claims the first empty entry of its walk, or joins the entry that already belongs to its fingerprint
+// (atomicMin: the lowest slot stays).  An entry never changes its fingerprint class once claimed, so what a lookup returns does not depend on
+// the order of arrival, though entry positions may.  Every access to an entry is an atomic at agent scope (the table is shared across XCDs)
+// and the atomics' return values are the only reads of entries.  The walk ends after T steps at the latest.
+__global__ __launch_bounds__(256) void k_registry_index(RegIndexJob j)
+{
+    const long s = (long)blockIdx.x * 256 + threadIdx.x;
+    if (s >= j.capacity || !j.flag[s]) return;
+    const U128 h0 = reinterpret_cast<const U128 *>(j.h + (size_t)s * 32)[0], h1 = reinterpret_cast<const U128 *>(j.h + (size_t)s * 32)[1];
+    uint32_t e = h0.x & j.mask;
+    for (uint64_t step = 0; step <= j.mask; step++, e = (e + 1) & j.mask) {
+        int32_t o = -1; // expected; the value found on failure
+        if (__hip_atomic_compare_exchange_strong(j.index + e, &o, (int32_t)s, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+        if (o < 0 || o >= j.capacity) break; // no slot number: never written by this kernel
+        if (same_fingerprint(h0, h1, j.h + (size_t)o * 32)) {
+            (void)__hip_atomic_fetch_min(j.index + e, (int32_t)s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            return;
+        }
+    }
+    if (j.err) *reinterpret_cast<volatile uint32_t *>(j.err) = DEVERR_INDEX_FULL;
+}
+
+// One lane per query: from the home to the first empty entry (a miss) or the first entry whose slot holds the query's fingerprint (a hit),
+// T steps at the latest.  A miss writes key 0, not -1: the seed role of k_kem_hash reads h at key[b] before it looks at the mask
+__global__ __launch_bounds__(64) void k_registry_find(RegFindJob j)
+{
+    const long b = (long)blockIdx.x * 64 + threadIdx.x;
+    if (b >= j.n) return;
+    const U128 q0 = reinterpret_cast<const U128 *>(j.q + (size_t)b * 32)[0], q1 = reinterpret_cast<const U128 *>(j.q + (size_t)b * 32)[1];
+    uint32_t e = q0.x & j.mask;
+    int32_t hit = -1;
+    bool ended = false;
+    for (uint64_t step = 0; step <= j.mask; step++, e = (e + 1) & j.mask) {
+        const int32_t o = j.index[e];
+        if (o < 0 || o >= j.capacity) { ended = true; break; } // empty (k_registry_index writes nothing but -1 and slot numbers)
+        if (same_fingerprint(q0, q1, j.h + (size_t)o * 32)) { hit = o; ended = true; break; }
+    }
+    if (!ended && j.err) *reinterpret_cast<volatile uint32_t *>(j.err) = DEVERR_INDEX_FULL;
+    if (j.slot) j.slot[b] = hit;
+    if (j.key) {
+        j.key[b] = hit < 0 ? 0 : hit;
+        j.found[b] = hit >= 0;
+    }
+}
+
+hipError_t launch_registry_index(const RegIndexJob &j, hipStream_t st)
+{
+    k_registry_index<<<dim3((unsigned)((j.capacity + 255) / 256)), dim3(256), 0, st>>>(j);
+    return hipGetLastError();
+}
+
+hipError_t launch_registry_find(const RegFindJob &j, hipStream_t st)
+{
+    k_registry_find<<<dim3((unsigned)((j.n + 63) / 64)), dim3(64), 0, st>>>(j);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host --
+int registry_index_ensure(Ctx &c)
+{
+    KemRegistry &r = *c.registry;
+    if (r.index_valid) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    const size_t T = registry_index_entries(r.capacity);
+    if (!r.d_index) {
+        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r.d_index), T * sizeof(int32_t)));
+        c.reg_buf("registry.d_index", &r.d_index, T * sizeof(int32_t), 0, Ctx::INVG_REGISTRY); // public: slot numbers only
+    }
+    HIPCHK(hipMemsetAsync(r.d_index, 0xFF, T * sizeof(int32_t), c.stream));
+    RegIndexJob j{};
+    j.capacity = r.capacity; j.mask = (uint32_t)(T - 1); j.h = r.d_h; j.flag = r.d_flag; j.index = r.d_index; j.err = c.h_err;
+    HIPCHK(launch_registry_index(j, c.stream));
+    c.path_n[PATH_REGISTRY_INDEX]++;
+    HIPCHK(stream_sync(c));
+    if (device_error_check(c)) return -1; // index overflow
+    r.index_valid = true;
+    return 0;
+}
+
 void registry_release(Ctx &c)
 {
     KemRegistry *r = c.registry;
     if (!r) return;
-    void *dev[] = {r->d_pk, r->d_h, r->d_A, r->d_flag};
+    void *dev[] = {r->d_pk, r->d_h, r->d_A, r->d_flag, r->d_index};
     for (void *p : dev)
         if (p) (void)hipFree(p);
     delete r;
@@ -150,6 +239,7 @@ int registry_evict(Ctx &c, int n, const int32_t *slots)
     KemRegistry &r = *c.registry;
     const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
+    r.index_valid = false;
     const size_t a_bytes = (size_t)D.K * D.K * 512;
     std::vector<WipeRegion> dev;
     for (int b = 0; b < n; b++) {
