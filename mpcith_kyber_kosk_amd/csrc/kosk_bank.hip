@@ -145,10 +145,8 @@ static void bank_zero_slots(Ctx &c, int first, int n)
 
 void bank_release(Ctx &c)
 {
-    if (c.d_bank) (void)hipFree(c.d_bank);
-    c.d_bank = nullptr;
+    c.inv.release(Inventory::INVG_BANK);
     c.bank_cap = c.bank_ready = c.bank_head = 0;
-    c.inv_drop(Ctx::INVG_BANK);
 }
 
 void bank_note_wiped(Ctx &c)
@@ -163,14 +161,13 @@ int bank_reserve(Ctx &c, int capacity)
     if (c.bank_ready) { c.err = "the bank is not empty: its entries are consumed or wiped before it is reserved again"; return -1; }
     HIPCHK(hipSetDevice(c.device));
     if (c.d_bank) { // nothing secret goes back to the allocator readable (free slots are zero already: this is the belt to those braces)
-        if (wipe_group(c, Ctx::INVG_BANK)) return -1;
+        if (wipe_group(c, Inventory::INVG_BANK)) return -1;
         bank_release(c);
     }
     if (!capacity) return 0;
     const size_t bytes = bank_entry_bytes(c.P) * (size_t)capacity;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_bank), bytes));
+    HIPCHK(c.own("d_bank", &c.d_bank, bytes, Inventory::INV_SECRET, Inventory::INVG_BANK));
     c.bank_cap = capacity;
-    c.reg_buf("d_bank", &c.d_bank, bytes, Ctx::INV_SECRET, Ctx::INVG_BANK);
     // a free slot is all zero, from the first one on
     if (hipMemsetAsync(c.d_bank, 0, bytes, c.stream) != hipSuccess || stream_sync(c) != hipSuccess) {
         (void)hipGetLastError();

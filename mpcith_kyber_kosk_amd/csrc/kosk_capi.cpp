@@ -73,9 +73,7 @@ struct kosk_ctx {
     void disarm()
     {
         for (Ctx *x : sub) { x->bind_ctx = nullptr; x->bind_n = 0; x->bind_first = 0; }
-        if (c) c->inv_drop(Ctx::INVG_BIND);
-        if (d_contexts) (void)hipFree(d_contexts);
-        d_contexts = nullptr;
+        if (c) c->inv.release(Inventory::INVG_BIND); // frees d_contexts, which sub[0]'s inventory owns
         armed = 0;
     }
     // kosk_force_opened_candidates (tests): the handle's lists, 150 candidates each, in HBM for the chain kernel and on the host for the
@@ -85,9 +83,7 @@ struct kosk_ctx {
     void unforce()
     {
         for (Ctx *x : sub) { x->force_d = nullptr; x->force_h = nullptr; x->force_n = 0; }
-        if (c) c->inv_drop(Ctx::INVG_FORCE);
-        if (d_force) (void)hipFree(d_force);
-        d_force = nullptr;
+        if (c) c->inv.release(Inventory::INVG_FORCE); // frees d_force likewise
         h_force.clear();
     }
 
@@ -532,13 +528,13 @@ int kosk_set_contexts(kosk_ctx *ctx, int n, const uint8_t *contexts, size_t cont
     Ctx &c = *ctx->c;
     HIPCHK_C(hipSetDevice(c.device));
     uint8_t *d = nullptr;
-    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&d), (size_t)n * 32));
+    // allocated and filled before the old state goes: a failure leaves the handle armed as it was
+    HIPCHK_C((hipError_t)c.inv.raw_alloc(reinterpret_cast<void **>(&d), (size_t)n * 32, 0));
     const hipError_t e = hipMemcpy2D(d, 32, contexts, context_stride, 32, (size_t)n, is_device_pointer(contexts) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); HIPCHK_C(e); }
+    if (e != hipSuccess) { c.inv.raw_free(d, 0); HIPCHK_C(e); }
     ctx->disarm();
-    ctx->d_contexts = d;
+    c.inv.adopt("d_contexts", &ctx->d_contexts, d, (size_t)n * 32, 0, Inventory::INVG_BIND); // public: the caller's contexts
     ctx->armed = n;
-    c.reg_buf("d_contexts", &ctx->d_contexts, (size_t)n * 32, 0, Ctx::INVG_BIND); // public: the caller's contexts
     for (Ctx *x : ctx->sub) { x->bind_ctx = d; x->bind_n = n; x->bind_first = 0; }
     return 0;
     GUARD_END
@@ -560,13 +556,12 @@ int kosk_force_opened_candidates(kosk_ctx *ctx, int n, const uint16_t *cand)
     HIPCHK_C(hipSetDevice(c.device));
     std::vector<uint16_t> h(cand, cand + (size_t)n * NOPEN);
     uint16_t *d = nullptr;
-    HIPCHK_C(hipMalloc(reinterpret_cast<void **>(&d), h.size() * sizeof(uint16_t)));
+    HIPCHK_C((hipError_t)c.inv.raw_alloc(reinterpret_cast<void **>(&d), h.size() * sizeof(uint16_t), 0));
     const hipError_t e = hipMemcpy(d, h.data(), h.size() * sizeof(uint16_t), hipMemcpyHostToDevice);
-    if (e != hipSuccess) { (void)hipFree(d); HIPCHK_C(e); }
+    if (e != hipSuccess) { c.inv.raw_free(d, 0); HIPCHK_C(e); }
     ctx->unforce();
-    ctx->d_force = d;
     ctx->h_force.swap(h);
-    c.reg_buf("d_force", &ctx->d_force, ctx->h_force.size() * sizeof(uint16_t), 0, Ctx::INVG_FORCE); // public: the test's candidate lists
+    c.inv.adopt("d_force", &ctx->d_force, d, ctx->h_force.size() * sizeof(uint16_t), 0, Inventory::INVG_FORCE); // public: the test's candidate lists
     for (Ctx *x : ctx->sub) { x->force_d = d; x->force_h = ctx->h_force.data(); x->force_n = n; }
     return 0;
     GUARD_END

@@ -168,16 +168,17 @@ static int ensure_compact(Ctx &c)
 {
     if (c.d_compact) return 0;
     ensure_plans(c);
-    // a view keeps its own staging, sized for its own callers' batches (the compact calls are never merged)
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact), (size_t)c.own_batch * c.compact_stride));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_compact_bad), sizeof(uint32_t) * c.own_batch));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_compact), (size_t)c.own_batch * c.compact_stride, hipHostMallocDefault));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_compact_bad), sizeof(uint32_t) * c.own_batch, hipHostMallocDefault));
-    // the inventory: packed proofs and their flags, public
-    c.reg_buf("d_compact", &c.d_compact, (size_t)c.own_batch * c.compact_stride, 0, Ctx::INVG_COMPACT);
-    c.reg_buf("d_compact_bad", &c.d_compact_bad, sizeof(uint32_t) * c.own_batch, 0, Ctx::INVG_COMPACT);
-    c.reg_buf("h_compact", &c.h_compact, (size_t)c.own_batch * c.compact_stride, Ctx::INV_HOST, Ctx::INVG_COMPACT);
-    c.reg_buf("h_compact_bad", &c.h_compact_bad, sizeof(uint32_t) * c.own_batch, Ctx::INV_HOST, Ctx::INVG_COMPACT);
+    // a view keeps its own staging, sized for its own callers' batches (the compact calls are never merged).  Packed proofs and their
+    // flags, public
+    const int G = Inventory::INVG_COMPACT, HOST = Inventory::INV_HOST;
+    auto body = [&]() -> int {
+        HIPCHK(c.own("d_compact", &c.d_compact, (size_t)c.own_batch * c.compact_stride, 0, G));
+        HIPCHK(c.own("d_compact_bad", &c.d_compact_bad, sizeof(uint32_t) * c.own_batch, 0, G));
+        HIPCHK(c.own("h_compact", &c.h_compact, (size_t)c.own_batch * c.compact_stride, HOST, G));
+        HIPCHK(c.own("h_compact_bad", &c.h_compact_bad, sizeof(uint32_t) * c.own_batch, HOST, G));
+        return 0;
+    };
+    if (body()) { c.inv.release(G); return -1; } // d_compact is null again: a retry starts from nothing
     return 0;
 }
 
@@ -267,12 +268,9 @@ void transcode_release(Ctx &c)
 {
     TcWs *w = c.tc;
     if (!w) return;
-    for (void *p : {(void *)w->d_img, (void *)w->d_in, (void *)w->d_out, (void *)w->d_words})
-        if (p) (void)hipFree(p);
-    if (w->h_words) (void)hipHostFree(w->h_words);
+    c.inv.release(Inventory::INVG_TRANSCODE);
     delete w;
     c.tc = nullptr;
-    c.inv_drop(Ctx::INVG_TRANSCODE);
 }
 
 static int transcode_ensure(Ctx &c)
@@ -282,21 +280,16 @@ static int transcode_ensure(Ctx &c)
     TcWs *w = new TcWs();
     c.tc = w;
     const size_t N = (size_t)c.own_batch;
+    const int G = Inventory::INVG_TRANSCODE;
     auto body = [&]() -> int {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_img), N * c.image_stride));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_in), N * c.compact_stride));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_out), N * c.compact_stride));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_words), 2 * N * sizeof(uint32_t)));
-        HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&w->h_words), 2 * N * sizeof(uint32_t), hipHostMallocDefault));
+        HIPCHK(c.own("tc.d_img", &w->d_img, N * c.image_stride, 0, G));
+        HIPCHK(c.own("tc.d_in", &w->d_in, N * c.compact_stride, 0, G));
+        HIPCHK(c.own("tc.d_out", &w->d_out, N * c.compact_stride, 0, G));
+        HIPCHK(c.own("tc.d_words", &w->d_words, 2 * N * sizeof(uint32_t), 0, G));
+        HIPCHK(c.own("tc.h_words", &w->h_words, 2 * N * sizeof(uint32_t), Inventory::INV_HOST, G));
         return 0;
     };
     if (body()) { transcode_release(c); return -1; }
-    const int G = Ctx::INVG_TRANSCODE;
-    c.reg_buf("tc.d_img", &w->d_img, N * c.image_stride, 0, G);
-    c.reg_buf("tc.d_in", &w->d_in, N * c.compact_stride, 0, G);
-    c.reg_buf("tc.d_out", &w->d_out, N * c.compact_stride, 0, G);
-    c.reg_buf("tc.d_words", &w->d_words, 2 * N * sizeof(uint32_t), 0, G);
-    c.reg_buf("tc.h_words", &w->h_words, 2 * N * sizeof(uint32_t), Ctx::INV_HOST, G);
     return 0;
 }
 

@@ -31,17 +31,6 @@ static double now_sec()
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-template <typename T>
-static hipError_t dalloc(T **p, size_t n)
-{
-    return hipMalloc(reinterpret_cast<void **>(p), n * sizeof(T));
-}
-template <typename T>
-static hipError_t halloc(T **p, size_t n)
-{
-    return hipHostMalloc(reinterpret_cast<void **>(p), n * sizeof(T), hipHostMallocDefault);
-}
-
 void Ctx::prof_collect()
 {
     if (!prof_on) return;
@@ -53,6 +42,14 @@ void Ctx::prof_collect()
         }
 }
 
+Ctx::Ctx()
+{
+    inv.mem.dev_alloc = [](void **p, size_t bytes) -> int { return (int)hipMalloc(p, bytes); };
+    inv.mem.dev_free = [](void *p) -> int { return (int)hipFree(p); };
+    inv.mem.host_alloc = [](void **p, size_t bytes) -> int { return (int)hipHostMalloc(p, bytes, hipHostMallocDefault); };
+    inv.mem.host_free = [](void *p) -> int { return (int)hipHostFree(p); };
+}
+
 Ctx::~Ctx()
 {
     for (auto &g : seg)
@@ -60,50 +57,35 @@ Ctx::~Ctx()
     for (auto &pe : prof_ev)
         for (auto e : pe)
             if (e) (void)hipEventDestroy(e);
-    if (ev_sync) (void)hipEventDestroy(ev_sync);
+    for (hipEvent_t e : {ev_sync, ev, ev_kg, timer_ev[0], timer_ev[1]})
+        if (e) (void)hipEventDestroy(e);
+    // the owners whose pointers live in a struct of their own go while that struct is there; the inventory frees the rest
     kem_release(*this);
     transcode_release(*this);
     kem_key_release(*this);
     registry_release(*this);
-    witness_release(*this);
-    bank_release(*this);
-    if (is_view) {
-        if (h_err) (void)hipHostFree(h_err);
-        // a view owns its events, host workers and compact staging; tables, workspace and the stream belong to the arena
-        if (d_compact) (void)hipFree(d_compact);
-        if (d_compact_bad) (void)hipFree(d_compact_bad);
-        if (h_compact) (void)hipHostFree(h_compact);
-        if (h_compact_bad) (void)hipHostFree(h_compact_bad);
-        if (d_dense_ws) (void)hipFree(d_dense_ws);
-        if (d_dense_status) (void)hipFree(d_dense_status);
-        if (pool) pool_destroy(pool);
-        if (ev) (void)hipEventDestroy(ev);
-        if (ev_kg) (void)hipEventDestroy(ev_kg);
-        for (auto e : timer_ev)
-            if (e) (void)hipEventDestroy(e);
-        return; // the stream is the arena's
-    }
-    void *dev[] = {t_expand.dfrag, t_recon_d.dfrag, t_recon_2d.dfrag, d_fresh_rows, d_gemm1_rows, d_gemm2_rows, d_off, d_fields, d_asm_groups, d_asm_elems,
-                   d_rowtab, d_P, d_tape, d_seedbuf, d_dig1, d_dig2, d_proof, d_A, d_se, d_kg, d_sehat, d_t, d_alpha, d_I, d_pwT, d_coef, d_lin_rows,
-                   d_gather, d_gather2, d_O, d_w, d_ell, d_sec, d_sec_u1, d_sec_u2, d_fail, d_inv, d_invlimb, d_vfields,
-                   d_vrowtab, d_rows_bg, d_rows_isrc, d_rows_idst, d_rows_u, d_fact, d_invfact, d_node_of, d_isort, d_hrange, d_odig, d_bind};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
-    void *host[] = {h_err, h_tape, h_seedbuf, h_dig, h_dig2, h_proof, h_alpha, h_I, h_fail, h_Iimg, h_kg, h_odig, h_bind};
-    for (void *p : host)
-        if (p) (void)hipHostFree(p);
-    if (d_compact) (void)hipFree(d_compact);
-    if (d_compact_bad) (void)hipFree(d_compact_bad);
-    if (h_compact) (void)hipHostFree(h_compact);
-    if (h_compact_bad) (void)hipHostFree(h_compact_bad);
-    if (d_dense_ws) (void)hipFree(d_dense_ws);
-    if (d_dense_status) (void)hipFree(d_dense_status);
+    inv.release_all();
     if (pool) pool_destroy(pool);
-    if (ev) (void)hipEventDestroy(ev);
-    if (ev_kg) (void)hipEventDestroy(ev_kg);
-    for (auto e : timer_ev)
-        if (e) (void)hipEventDestroy(e);
-    if (stream) (void)hipStreamDestroy(stream);
+    if (stream && !is_view) (void)hipStreamDestroy(stream); // a view's stream is its arena's
+}
+
+// what every context, owner or view, has of its own: events, and the word its kernels report errors to
+static int create_events(Ctx &c)
+{
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(hipEventCreateWithFlags(&c.ev,hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
+    HIPCHK(hipEventCreateWithFlags(&c.ev_kg, hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
+    if (c.blocking_sync) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming | hipEventBlockingSync));
+    else if (c.wait_nap) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming));
+    for (auto &pe : c.prof_ev)
+        for (auto &e : pe) HIPCHK(hipEventCreate(&e));
+    return 0;
+}
+static int alloc_err_word(Ctx &c)
+{
+    HIPCHK(c.own("h_err", &c.h_err, 16 * sizeof(uint32_t), Inventory::INV_HOST));
+    memset(c.h_err, 0, 16 * sizeof(uint32_t));
+    return 0;
 }
 
 // A[m][k] (canonical) as a limb matrix in fragment-linear tile order (kosk_device.hpp: frag_offset): the table products load it
@@ -128,8 +110,7 @@ static int upload_table(Ctx &c, GemmTable &t, const std::vector<uint16_t> &A, in
     t.KS = (Kdim + 63) / 64;
     std::vector<uint8_t> pk;
     pack_frag_table(A, M, Kdim, t.Mpad, t.KS, pk);
-    HIPCHK(dalloc(&t.dfrag, pk.size()));
-    c.reg_buf("table", &t.dfrag, pk.size(), 0);
+    HIPCHK(c.own("table", &t.dfrag, pk.size(), 0));
     HIPCHK(hipMemcpyAsync(t.dfrag, pk.data(), pk.size(), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
     HIPCHK(hipStreamSynchronize(c.stream));
     return 0;
@@ -278,8 +259,7 @@ int gemm_modq(Ctx &c, const GemmTable &t, const GemmSrc &s, const GemmDst &d, in
 template <typename T>
 static int upload_vec(Ctx &c, T **d, const std::vector<T> &v)
 {
-    HIPCHK(dalloc(d, v.size() ? v.size() : 1));
-    c.reg_buf("table", d, v.size() * sizeof(T), 0);
+    HIPCHK(c.own("table", d, v.size() * sizeof(T), 0, Inventory::INVG_CORE, 0, (size_t)-1, v.empty() ? sizeof(T) : 0)); // an empty table still gets a pointer
     if (!v.empty()) {
         HIPCHK(hipMemcpyAsync(*d, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice, c.stream)); // c.stream, not the legacy null stream
         HIPCHK(hipStreamSynchronize(c.stream));
@@ -472,13 +452,7 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
             if (cus > 0) c.n_simd = 4 * cus;
         }
         HIPCHK(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c.ev, hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
-        HIPCHK(hipEventCreateWithFlags(&c.ev_kg, hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
-        if (c.blocking_sync) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming | hipEventBlockingSync));
-        else if (c.wait_nap) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming));
-        for (auto &pe : c.prof_ev)
-            for (auto &e : pe) HIPCHK(hipEventCreate(&e));
-        if (build_tables(c)) return -1;
+        if (create_events(c) || build_tables(c)) return -1;
         const Params &P = c.P;
         const size_t B = (size_t)max_batch;
         c.proof_stride = (size_t)c.rm.nrows * RS;
@@ -487,71 +461,59 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
         c.key_stride = (size_t)P.K * P.K * 256;
         c.se_stride = (size_t)2 * P.K * 256;
         c.sel_stride = 1312;
-        // per-proof buffers: allocated for B proofs and registered with their bytes per proof (views, kosk_combine.hpp)
-        auto dev = [&](auto **p, size_t per) -> hipError_t {
-            const hipError_t e = dalloc(p, B * per);
-            if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("workspace", p, per * sizeof(**p), Ctx::INV_PER_PROOF); }
-            return e;
+        // per-proof buffers: B records each, owned by the inventory with their bytes per proof (views, kosk_combine.hpp).  `secret`: the
+        // buffer can hold secret-derived bytes (DESIGN.md 26 has the reason for every buffer).  Nothing in them is written once and assumed
+        // later: d_P starts as zeros (below) and a wipe leaves zeros
+        c.inv.records = B;
+        const int PP = Inventory::INV_PER_PROOF, HOST = Inventory::INV_HOST, SEC = Inventory::INV_SECRET;
+        auto dev = [&](auto **p, size_t per, const char *secret = nullptr) -> hipError_t {
+            return c.own(secret ? secret : "workspace", p, per * sizeof(**p), PP | (secret ? SEC : 0));
         };
-        auto host = [&](auto **p, size_t per) -> hipError_t {
-            const hipError_t e = halloc(p, B * per);
-            if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("staging", p, per * sizeof(**p), Ctx::INV_PER_PROOF | Ctx::INV_HOST); }
-            return e;
+        auto host = [&](auto **p, size_t per, const char *secret = nullptr) -> hipError_t {
+            return c.own(secret ? secret : "staging", p, per * sizeof(**p), PP | HOST | (secret ? SEC : 0));
         };
-        HIPCHK(dev(&c.d_P, c.proof_stride));
+        HIPCHK(dev(&c.d_P, c.proof_stride, "d_P"));
         HIPCHK(hipMemsetAsync(c.d_P, 0, B * c.proof_stride * 2, c.stream));
-        HIPCHK(dev(&c.d_tape, c.tape_stride));
-        HIPCHK(dev(&c.d_seedbuf, SEED_BYTES));
+        HIPCHK(dev(&c.d_tape, c.tape_stride, "d_tape"));
+        HIPCHK(dev(&c.d_seedbuf, SEED_BYTES, "d_seedbuf"));
         HIPCHK(dev(&c.d_dig1, (size_t)NPARTY * 32));
         HIPCHK(dev(&c.d_dig2, (size_t)NPARTY * 32));
         HIPCHK(dev(&c.d_proof, c.image_stride));
         HIPCHK(dev(&c.d_A, c.key_stride));
-        HIPCHK(dev(&c.d_se, c.se_stride));
+        HIPCHK(dev(&c.d_se, c.se_stride, "d_se"));
         HIPCHK(dev(&c.d_t, (size_t)P.K * 256));
+        // the key records: the public head (the pk bytes the resident verifier and kosk_kem_enc_verified read) is not part of the secret
+        // span; the six pointers into the records list no bytes of their own
         const size_t pkpad = (P.pk_bytes + 15) / 16 * 16;
         c.sb_bytes = (size_t)384 * P.K;
         c.kg_rec = pkpad + c.sb_bytes + 64;
         c.pk_stride = c.sb_stride = c.kg_rec;
-        HIPCHK(dev(&c.d_kg, c.kg_rec));
-        HIPCHK(host(&c.h_kg, c.kg_rec));
-        c.d_pk = c.d_kg; c.d_sb = c.d_kg + pkpad; c.d_seeds = c.d_kg + pkpad + c.sb_bytes;
-        c.h_pk = c.h_kg; c.h_sb = c.h_kg + pkpad; c.h_seeds = c.h_kg + pkpad + c.sb_bytes;
-        c.reg_pp(&c.d_pk, c.kg_rec); c.reg_pp(&c.d_sb, c.kg_rec); c.reg_pp(&c.d_seeds, c.kg_rec);
-        c.reg_pp(&c.h_pk, c.kg_rec); c.reg_pp(&c.h_sb, c.kg_rec); c.reg_pp(&c.h_seeds, c.kg_rec);
-        HIPCHK(dev(&c.d_sehat, c.se_stride));
+        HIPCHK(c.own("d_kg", &c.d_kg, c.kg_rec, PP | SEC, Inventory::INVG_CORE, pkpad, c.kg_rec - pkpad));
+        HIPCHK(c.own("h_kg", &c.h_kg, c.kg_rec, PP | HOST | SEC, Inventory::INVG_CORE, pkpad, c.kg_rec - pkpad));
+        c.inv.alias("d_pk", &c.d_pk, c.d_kg, 0, c.kg_rec, PP); c.inv.alias("d_sb", &c.d_sb, c.d_kg + pkpad, 0, c.kg_rec, PP);
+        c.inv.alias("d_seeds", &c.d_seeds, c.d_kg + pkpad + c.sb_bytes, 0, c.kg_rec, PP);
+        c.inv.alias("h_pk", &c.h_pk, c.h_kg, 0, c.kg_rec, PP | HOST); c.inv.alias("h_sb", &c.h_sb, c.h_kg + pkpad, 0, c.kg_rec, PP | HOST);
+        c.inv.alias("h_seeds", &c.h_seeds, c.h_kg + pkpad + c.sb_bytes, 0, c.kg_rec, PP | HOST);
+        HIPCHK(dev(&c.d_sehat, c.se_stride, "d_sehat"));
         HIPCHK(dev(&c.d_alpha, 80));
-        HIPCHK(dalloc(&c.d_I, 2 * B * c.sel_stride)); // I rows then complement rows: one upload
-        c.d_rest = c.d_I + B * c.sel_stride;
-        c.reg_pp(&c.d_I, (size_t)c.sel_stride * 2); c.reg_pp(&c.d_rest, (size_t)c.sel_stride * 2);
-        c.reg_buf("d_I", &c.d_I, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF); c.reg_buf("d_rest", &c.d_rest, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF);
+        const size_t sel_bytes = (size_t)c.sel_stride * 2;
+        HIPCHK(c.own("d_I", &c.d_I, sel_bytes, PP, Inventory::INVG_CORE, 0, (size_t)-1, 2 * B * sel_bytes)); // I rows then complement rows: one upload
+        c.inv.alias("d_rest", &c.d_rest, c.d_I + B * c.sel_stride, sel_bytes, sel_bytes, PP);
         HIPCHK(dev(&c.d_pwT, (size_t)MAXM * 80));
         HIPCHK(dev(&c.d_coef, 2 * (size_t)8 * 2 * 2048));
         HIPCHK(dev(&c.d_fail, 1));
         HIPCHK(dev(&c.d_bind, 32));
         HIPCHK(host(&c.h_bind, 32));
-        HIPCHK(host(&c.h_tape, c.tape_stride));
-        HIPCHK(host(&c.h_seedbuf, SEED_BYTES));
+        HIPCHK(host(&c.h_tape, c.tape_stride, "h_tape"));
+        HIPCHK(host(&c.h_seedbuf, SEED_BYTES, "h_seedbuf"));
         HIPCHK(host(&c.h_dig, (size_t)NPARTY * 32));
         HIPCHK(host(&c.h_dig2, (size_t)NPARTY * 32));
         HIPCHK(host(&c.h_proof, c.image_stride));
         HIPCHK(host(&c.h_alpha, 80));
-        HIPCHK(halloc(&c.h_I, 2 * B * c.sel_stride));
-        c.h_rest = c.h_I + B * c.sel_stride;
-        c.reg_pp(&c.h_I, (size_t)c.sel_stride * 2); c.reg_pp(&c.h_rest, (size_t)c.sel_stride * 2);
-        c.reg_buf("h_I", &c.h_I, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF | Ctx::INV_HOST);
-        c.reg_buf("h_rest", &c.h_rest, (size_t)c.sel_stride * 2, Ctx::INV_PER_PROOF | Ctx::INV_HOST);
+        HIPCHK(c.own("h_I", &c.h_I, sel_bytes, PP | HOST, Inventory::INVG_CORE, 0, (size_t)-1, 2 * B * sel_bytes));
+        c.inv.alias("h_rest", &c.h_rest, c.h_I + B * c.sel_stride, sel_bytes, sel_bytes, PP | HOST);
         HIPCHK(host(&c.h_fail, 1));
-        HIPCHK(halloc(&c.h_err, 16));
-        c.reg_buf("h_err", &c.h_err, 16 * sizeof(uint32_t), Ctx::INV_HOST);
-        // which of the buffers registered above can hold secret-derived bytes (DESIGN.md 26 has the reason for every buffer).  Nothing in
-        // them is written once and assumed later: d_P starts as zeros (above) and a wipe leaves zeros; the public head of a key record
-        // (the pk bytes the resident verifier and kosk_kem_enc_verified read) is not part of the secret span
-        c.inv_secret("d_P", &c.d_P);
-        c.inv_secret("d_tape", &c.d_tape); c.inv_secret("h_tape", &c.h_tape);
-        c.inv_secret("d_seedbuf", &c.d_seedbuf); c.inv_secret("h_seedbuf", &c.h_seedbuf);
-        c.inv_secret("d_se", &c.d_se); c.inv_secret("d_sehat", &c.d_sehat);
-        c.inv_secret("d_kg", &c.d_kg, pkpad, c.kg_rec - pkpad); c.inv_secret("h_kg", &c.h_kg, pkpad, c.kg_rec - pkpad);
-        memset(c.h_err, 0, 16 * sizeof(uint32_t));
+        if (alloc_err_word(c)) return -1;
         memset(c.h_alpha, 0, B * 80 * sizeof(uint16_t));
         HIPCHK(stream_sync(c));
         return 0;
@@ -561,73 +523,22 @@ int ctx_create(Ctx **out, int device, int kyber_k, int max_batch, std::string &e
     return 0;
 }
 
-// A view of `arena` (kosk_ctx.hpp): same tables, same workspace, proofs [first, first + reach) of it, own stream / events / workers.
+// A view of `arena`, built by the rule above struct CtxShared (kosk_ctx.hpp): proofs [first, first + own_batch) are its own
 int ctx_make_view(Ctx &arena, int first, int own_batch, int reserve_threads, Ctx **out, std::string &err)
 {
     if (arena.is_view || first < 0 || own_batch < 1 || first + own_batch > arena.max_batch) { err = "internal: bad view range"; return -1; }
-    Ctx *vp = new Ctx(arena); // memberwise copy: constants, strides, table pointers, knobs
+    Ctx *vp = new Ctx();
     Ctx &c = *vp;
+    static_cast<CtxShared &>(c) = arena;
     c.is_view = true;
     c.view_first = first;
     c.max_batch = arena.max_batch - first;
-    c.own_batch = own_batch;
-    c.call_cap = own_batch;
-    c.err.clear();
-    // what the copy must not share with the arena.  The STREAM is shared on purpose: one HIP stream per cohort.  In steady state
-    // a cohort has one merged run in flight, so nothing is lost -- and the number of streams that carry work stays at the
-    // number of cohorts: ROCm deals streams to its (four) hardware queues in creation order, and with a stream per member the
-    // streams of the run leaders of three cohorts of three all landed on the SAME hardware queue (measured: 138-proof runs
-    // took 2.8 ms instead of 1.6).  Calls end with a stream synchronisation, so members never leave work behind for each other.
+    c.own_batch = c.call_cap = own_batch;
     c.use_graphs = false; // stream capture is per stream: not with several callers on one
-    c.ev = nullptr; c.ev_kg = nullptr; c.ev_sync = nullptr; c.pool = nullptr;
-    c.host_img = nullptr;
-    c.h_err = nullptr;
-    for (auto &e : c.timer_ev) e = nullptr;
-    for (auto &pe : c.prof_ev) for (auto &e : pe) e = nullptr;
-    for (auto &g : c.seg) g = Ctx::SegGraph{};
-    c.d_compact = nullptr; c.h_compact = nullptr; c.d_compact_bad = nullptr; c.h_compact_bad = nullptr; c.d_dense_ws = nullptr; c.d_dense_status = nullptr;
-    for (auto &x : c.path_n) x = 0;
-    for (int i = 0; i < PR_COUNT; i++) { c.prof_ms[i] = 0; c.prof_n[i] = 0; c.prof_units[i] = 0; c.prof_used[i] = false; }
-    c.tape_cur = nullptr;
-    c.resident_pk_n = 0;
-    c.keys_from_pk_n = 0;
-    c.kem = nullptr;
-    c.tc = nullptr;
-    c.kem_key = nullptr;
-    c.registry = nullptr;
-    c.wit_cap = 0; c.d_wsk = nullptr; c.d_wok = nullptr; c.h_wok = nullptr; c.d_wsalt = nullptr;
-    c.d_bank = nullptr; c.bank_cap = 0; c.bank_ready = 0; c.bank_head = 0; c.staged_online = false; // a bank is per handle
-    c.rb = nullptr; c.rb_user = nullptr; c.round_hook = nullptr; c.round_user = nullptr;
-    c.bind_ctx = nullptr; c.bind_n = 0; c.bind_first = 0; // arming is per handle
-    c.force_d = nullptr; c.force_h = nullptr; c.force_n = 0;
-    c.staged_wiped = false;
-    { // the inventory: a view owns its block of every per-proof buffer; tables and whole buffers are the arena's, private ones come later
-        size_t k = 0;
-        for (size_t i = 0; i < c.inv.size(); i++)
-            if (c.inv[i].flags & Ctx::INV_PER_PROOF) c.inv[k++] = c.inv[i];
-        c.inv.resize(k);
-    }
-    for (const Ctx::PerProof &pp : arena.per_proof) {
-        char *base = *reinterpret_cast<char *const *>(reinterpret_cast<const char *>(&arena) + pp.field_off);
-        *reinterpret_cast<char **>(reinterpret_cast<char *>(&c) + pp.field_off) = base ? base + (size_t)first * pp.stride_bytes : nullptr;
-    }
-    auto fail = [&]() { err = c.err; delete vp; return -1; };
-    auto body = [&]() -> int {
-        HIPCHK(hipSetDevice(c.device));
-        HIPCHK(hipEventCreateWithFlags(&c.ev, hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
-        HIPCHK(hipEventCreateWithFlags(&c.ev_kg, hipEventDisableTiming | (c.blocking_sync ? hipEventBlockingSync : 0)));
-        if (c.blocking_sync) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming | hipEventBlockingSync));
-        else if (c.wait_nap) HIPCHK(hipEventCreateWithFlags(&c.ev_sync, hipEventDisableTiming));
-        for (auto &pe : c.prof_ev)
-            for (auto &e : pe) HIPCHK(hipEventCreate(&e));
-        HIPCHK(halloc(&c.h_err, 16)); // a view's kernels report to the view's own word
-        c.reg_buf("h_err", &c.h_err, 16 * sizeof(uint32_t), Ctx::INV_HOST);
-        memset(c.h_err, 0, 16 * sizeof(uint32_t));
-        return 0;
-    };
-    if (body()) return fail();
+    const bool stray = c.inv.view_of(arena.inv, static_cast<const CtxBlock &>(arena), static_cast<CtxBlock &>(c), (size_t)first, (size_t)own_batch) != 0;
+    if (stray) c.err = "internal: a per-proof buffer's pointer is not a field of CtxBlock";
+    if (stray || create_events(c) || alloc_err_word(c)) { err = c.err; delete vp; return -1; }
     c.pool = pool_create();
-    c.base_threads = arena.base_threads;
     const int got = pool_reserve(c.pool, reserve_threads > c.base_threads ? reserve_threads : c.base_threads);
     c.reserved_threads = got;
     c.nthreads = got < c.base_threads ? got : c.base_threads;
@@ -963,13 +874,8 @@ int stage_prover_inputs(Ctx &c, int n, const uint8_t *tapes, size_t tape_stride,
 // ---- existing keys: the witness from the secret key (kosk_witness_kernels.hip) ----
 void witness_release(Ctx &c)
 {
-    if (c.d_wsk) (void)hipFree(c.d_wsk);
-    if (c.d_wok) (void)hipFree(c.d_wok);
-    if (c.h_wok) (void)hipHostFree(c.h_wok);
-    if (c.d_wsalt) (void)hipFree(c.d_wsalt);
-    c.d_wsk = c.d_wok = c.h_wok = c.d_wsalt = nullptr;
+    c.inv.release(Inventory::INVG_WITNESS);
     c.wit_cap = 0;
-    c.inv_drop(Ctx::INVG_WITNESS);
 }
 
 static int witness_ensure(Ctx &c, int n)
@@ -977,22 +883,19 @@ static int witness_ensure(Ctx &c, int n)
     if (c.wit_cap >= n) return 0;
     if (c.wit_cap) {
         HIPCHK(stream_sync(c));
-        if (wipe_group(c, Ctx::INVG_WITNESS)) return -1; // the records of the last call do not go back to the allocator readable
+        if (wipe_group(c, Inventory::INVG_WITNESS)) return -1; // the records of the last call do not go back to the allocator readable
         witness_release(c);
     }
+    const int SEC = Inventory::INV_SECRET, G = Inventory::INVG_WITNESS;
     auto body = [&]() -> int {
-        HIPCHK(dalloc(&c.d_wsk, (size_t)n * c.P.sk_bytes));
-        HIPCHK(dalloc(&c.d_wok, (size_t)n));
-        HIPCHK(halloc(&c.h_wok, (size_t)n));
-        HIPCHK(dalloc(&c.d_wsalt, (size_t)n * 32));
+        HIPCHK(c.own("d_wsk", &c.d_wsk, (size_t)n * c.P.sk_bytes, SEC, G));
+        HIPCHK(c.own("d_wsalt", &c.d_wsalt, (size_t)n * 32, SEC, G));
+        HIPCHK(c.own("d_wok", &c.d_wok, (size_t)n, 0, G));
+        HIPCHK(c.own("h_wok", &c.h_wok, (size_t)n, Inventory::INV_HOST, G));
         return 0;
     };
     if (body()) { witness_release(c); return -1; }
     c.wit_cap = n;
-    c.reg_buf("d_wsk", &c.d_wsk, (size_t)n * c.P.sk_bytes, Ctx::INV_SECRET, Ctx::INVG_WITNESS);
-    c.reg_buf("d_wsalt", &c.d_wsalt, (size_t)n * 32, Ctx::INV_SECRET, Ctx::INVG_WITNESS);
-    c.reg_buf("d_wok", &c.d_wok, (size_t)n, 0, Ctx::INVG_WITNESS);
-    c.reg_buf("h_wok", &c.h_wok, (size_t)n, Ctx::INV_HOST, Ctx::INVG_WITNESS);
     return 0;
 }
 

@@ -9,6 +9,7 @@
 
 #include "kosk_device.hpp"
 #include "kosk_host.hpp"
+#include "kosk_inventory.hpp"
 #include "kosk_params.hpp"
 
 // Every HIP call of the host code goes through this (needs a `Ctx &c` in scope, returns -1 from the enclosing function).
@@ -128,85 +129,30 @@ struct KemRegistry; // the table of admitted keys (kosk_registry.hip, DESIGN.md 
 enum { KEM_CHUNK = 16384,    // items per launch group of the KEM calls; larger calls are chunked
        KEM_WAVE_MAX = 1024 }; // launch groups of up to this many items (one wave per SIMD) run their long one-lane-per-item chains on a wave sponge, one wave per item
 
-struct Ctx {
+// ---- the context, in three parts by what a VIEW does with a field ----
+// A view of a context (kosk_combine.hpp) runs the pipeline on proofs [view_first, view_first + max_batch) of the context it was made from
+// (the arena) while other views work on other proofs of it.  ctx_make_view builds one by rule, part by part:
+//   CtxShared  : taken from the arena as it is -- what depends only on (device, kyber_k, options): constants, strides, the constant tables
+//                and the verifier's, the knobs, the stream.  The arena owns the tables; a view only points at them.
+//   CtxBlock   : the per-proof buffers' pointers and nothing else.  A view gets each one `view_first` records further
+//                (Inventory::view_of), as windows it does not own.
+//   CtxPrivate : every context, owner or view, starts these from their defaults: errors, events, workers, counters, the state of the
+//                calls in flight, and every buffer a context allocates for itself on first use (through its own inventory).
+// A NEW FIELD goes where its answer to "what must a cohort member see?" puts it: the arena's value (Shared), its own block of the arena's
+// buffer (Block; allocate it with INV_PER_PROOF), or a fresh one of its own (Private).  If in doubt, Private: a member that lacks something
+// fails loudly, a member that shares something by accident frees it twice or shows its secrets to a neighbour.
+struct CtxShared {
     int device = 0;
     Params P{};
     RowMap rm{};
-    int max_batch = 0;
-    // ---- views (kosk_combine.hpp) ----
-    // Every per-proof buffer is registered (field, bytes per proof) when it is allocated.  A VIEW of a context is a copy of the
-    // struct whose per-proof pointers start `view_first` proofs further: it shares the constant tables and the workspace with
-    // the context it was made from (the arena), has its own stream / events / host workers, and can run the pipeline on proofs
-    // [view_first, view_first + max_batch) of the arena while other views work on other proofs of it.
-    struct PerProof { size_t field_off, stride_bytes; };
-    std::vector<PerProof> per_proof;
-    template <class T> void reg_pp(T **field, size_t stride_bytes)
-    {
-        per_proof.push_back({(size_t)(reinterpret_cast<char *>(field) - reinterpret_cast<char *>(this)), stride_bytes});
-    }
-    // ---- the buffer inventory (kosk_wipe.hip) ----
-    // Every buffer the context owns is registered where it is allocated: HBM or page-locked host memory, per proof or whole, and whether
-    // it can hold secret-derived bytes (sec_off / sec_bytes: the secret part of each record; the key records keep a public head).
-    // wipe_secrets() zeroes the secret ones, secret_scan() searches ALL of them.  A pointer field of this struct is kept as its offset,
-    // so that a view resolves it to its own block; a pointer held elsewhere (the KEM workspace) by value.  `group` names the owner of
-    // buffers that come and go (inv_drop)
-    enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK, INVG_REGISTRY };
-    struct InvBuf {
-        const char *name;
-        size_t field_off; // (size_t)-1: `abs`
-        void *abs;
-        size_t bytes;     // per proof (INV_PER_PROOF) or of the whole buffer
-        size_t sec_off, sec_bytes;
-        int flags, group;
-    };
-    std::vector<InvBuf> inv;
-    template <class T> void reg_buf(const char *name, T **field, size_t bytes, int flags, int group = INVG_CORE, size_t sec_off = 0, size_t sec_bytes = (size_t)-1)
-    {
-        const char *f = reinterpret_cast<const char *>(field), *me = reinterpret_cast<const char *>(this);
-        const bool mine = f >= me && f < me + sizeof(*this);
-        inv.push_back(InvBuf{name, mine ? (size_t)(f - me) : (size_t)-1, mine ? nullptr : (void *)*field, bytes, sec_off, sec_bytes, flags, group});
-    }
-    // the registered buffer behind pointer field `field` can hold secrets (in bytes [sec_off, sec_off + sec_bytes) of each record)
-    template <class T> void inv_secret(const char *name, T **field, size_t sec_off = 0, size_t sec_bytes = (size_t)-1)
-    {
-        const size_t off = (size_t)(reinterpret_cast<const char *>(field) - reinterpret_cast<const char *>(this));
-        for (InvBuf &b : inv)
-            if (b.field_off == off) { b.name = name; b.flags |= INV_SECRET; b.sec_off = sec_off; b.sec_bytes = sec_bytes; }
-    }
-    void *inv_ptr(const InvBuf &b) const
-    {
-        return b.field_off == (size_t)-1 ? b.abs : *reinterpret_cast<void *const *>(reinterpret_cast<const char *>(this) + b.field_off);
-    }
-    void inv_drop(int group)
-    {
-        size_t k = 0;
-        for (size_t i = 0; i < inv.size(); i++)
-            if (inv[i].group != group) inv[k++] = inv[i];
-        inv.resize(k);
-    }
-    // kosk_wipe_secrets cleared staged prover inputs: kosk_prove_resident refuses until a staging call has run again
-    bool staged_wiped = false;
-    bool is_view = false;
-    int view_first = 0;
-    int own_batch = 0;   // proofs of this context's own callers (a view: its member's kosk_create size; else max_batch)
-    // the largest batch ONE call may run on this context: own_batch, except while this view leads a merged run of its cohort
-    // (kosk_capi.cpp: RunScope raises it to the run's total).  A view's max_batch is everything behind its first proof in the
-    // arena -- its neighbours' blocks included -- so no entry point may size a chunk by max_batch (ADVICE r4)
-    int call_cap = 0;
-    int base_threads = 1; // host threads of a call of own_batch proofs (a merged run uses base_threads x members)
-    int reserved_threads = 1; // workers the pool was created with (a call never creates threads: nthreads <= this)
-    int nthreads = 1;
-    Pool *pool = nullptr; // this context's host worker threads
+    // one HIP stream per cohort, shared on purpose.  In steady state a cohort has one merged run in flight, so nothing is lost -- and the
+    // number of streams that carry work stays at the number of cohorts: ROCm deals streams to its (four) hardware queues in creation
+    // order, and with a stream per member the streams of the run leaders of three cohorts of three all landed on the SAME hardware queue
+    // (measured: 138-proof runs took 2.8 ms instead of 1.6).  Calls end with a stream synchronisation, so members never leave work behind
+    // for each other.  Destroyed by the context that created it
     hipStream_t stream = nullptr;
-    std::string err;
-    randombytes_fn rb = nullptr;
-    void *rb_user = nullptr;
-    // kosk_set_entropy: what a call with tapes == NULL draws through `rb` -- false (default) the reference's 64 / M x 32 / 302-byte
-    // sequence, a whole tape per proof; true ONE 32-byte seed per proof, expanded on the device
-    bool entropy_seed = false;
-    round_fn round_hook = nullptr;
-    void *round_user = nullptr;
+    int base_threads = 1; // host threads of a call of own_batch proofs (a merged run uses base_threads x members)
+    int n_simd = 1024;    // SIMDs of the device (4 per CU)
 
     // constant tables (HBM, L2-resident while in use)
     GemmTable t_expand, t_recon_d, t_recon_2d;
@@ -223,48 +169,17 @@ struct Ctx {
     int nfields = 0;
     std::vector<FieldDesc> h_fields;
     std::vector<int16_t> h_rowtab;
+    int16_t *d_lin_rows = nullptr; // [2][128] output rows of the lincomb GEMM (beta/r, gamma/NTT_r)
 
-    // per-batch workspace
+    // strides of the per-batch workspace
     size_t proof_stride = 0; // u16 per proof in the row matrix
     size_t tape_stride = 0, image_stride = 0, key_stride = 0, se_stride = 0;
     int sel_stride = 0;
-    uint16_t *d_P = nullptr;
-    uint8_t *d_tape = nullptr, *d_dig1 = nullptr, *d_dig2 = nullptr, *d_proof = nullptr;
-    // the tapes the kernels read: d_tape after an upload, or the caller's own device buffer used in place
-    const uint8_t *tape_cur = nullptr;
-    size_t tape_cur_stride = 0;
-    // seeded proving: the seeds of a call, 32 bytes per proof (page-locked staging and its device copy, which k_tape_expand reads)
-    uint8_t *d_seedbuf = nullptr, *h_seedbuf = nullptr;
-    TapeSegs tape_segs{}; // a merged call whose callers' device tapes are read in place (count > 0; valid for that call only)
-    int16_t *d_A = nullptr, *d_se = nullptr;
-    // key generation on the device (kosk_keygen_kernels.hip)
-    // one record per proof [pk | NTT(s) bytes | sha3_512 output], kg_rec bytes apart, so that the key generation's
-    // outputs cross PCIe in ONE copy; d_pk / d_sb / d_seeds (and the h_ mirrors) point into it, all with stride kg_rec
-    uint8_t *d_kg = nullptr, *h_kg = nullptr;
-    size_t kg_rec = 0, sb_bytes = 0;
-    uint8_t *d_seeds = nullptr, *d_pk = nullptr, *d_sb = nullptr; // sha3_512 output, packed pk, packed NTT(s)
-    int16_t *d_sehat = nullptr;
-    int resident_pk_n = 0; // pk records valid in d_pk (written by the key generation or a verifier staging call): pk_mode 2 needs >= n
+    size_t kg_rec = 0, sb_bytes = 0; // the key record (CtxBlock::d_kg)
     size_t pk_stride = 0, sb_stride = 0;
-    // kosk_kem_enc_verified encapsulates to d_pk with the bits of a verify call that read d_A / d_t: it must know that d_A / d_t were decoded
-    // from d_pk (keys_from_pk_n: how many leading records of d_A / d_t are decodings of the same records of d_pk; 0 once instances were
-    // uploaded, kosk_split.cpp) and that neither changed since (pk_epoch counts every change of either).  EVERY writer of d_pk goes through
-    // note_pk_written(), the instance upload through note_keys_from_inst(), a verify call that decodes the resident d_pk again
-    // (pk_mode 2) through note_pk_decoded()
-    unsigned long pk_epoch = 0;
-    int keys_from_pk_n = 0;
-    void note_pk_written(int n) { resident_pk_n = n; keys_from_pk_n = n; pk_epoch++; }
-    void note_pk_decoded(int n) { if (n > keys_from_pk_n) keys_from_pk_n = n; } // records [0, n) decoded again from d_pk; the others keep their state
-    void note_keys_from_inst() { keys_from_pk_n = 0; pk_epoch++; }
-    uint8_t *h_seeds = nullptr, *h_pk = nullptr, *h_sb = nullptr;
-    uint16_t *d_t = nullptr; // pk's t, canonical (verifier)
-    uint16_t *d_alpha = nullptr, *d_I = nullptr, *d_rest = nullptr;
-    int32_t *d_pwT = nullptr;
-    uint8_t *d_coef = nullptr; // K3 operand: alpha-power coefficients as a limb matrix
-    int16_t *d_lin_rows = nullptr; // [2][128] output rows of the lincomb GEMM (beta/r, gamma/NTT_r)
-    // verifier workspace (allocated on first use, kosk_verify.cpp)
+
+    // the verifier's tables and plans (allocated with the workspace on first use, kosk_verify.cpp; verify_ready is set last)
     bool verify_ready = false;
-    uint16_t *d_O = nullptr;         // opened matrix [proof][nrows][OS] (kosk_params.hpp)
     size_t o_stride = 0;
     uint16_t *d_inv = nullptr;       // [Q] field inverses
     FieldDesc *d_vfields = nullptr;  // proof image -> rows (verifier row assignment)
@@ -275,13 +190,69 @@ struct Ctx {
     int16_t *d_rows_isrc = nullptr, *d_rows_idst = nullptr; // degree-d interpolations: given rows -> recomputed rows
     int16_t *d_rows_u = nullptr;     // us / ue rows (degree 2d)
     int n_interp_d = 0, n_interp_2d = 0;
-    uint16_t *d_w = nullptr, *d_ell = nullptr, *d_fact = nullptr, *d_invfact = nullptr;
+    uint16_t *d_fact = nullptr, *d_invfact = nullptr;
+    uint16_t *d_invlimb = nullptr;
+
+    // ---- knobs ----
+    // KOSK_WAIT_NAP (default 1 since round 5; 0: spin throughout): the long host waits of the resident calls (six per step: the GPU
+    // phases between the host's rounds) sleep through most of their expected duration -- the SHORTEST of the site's last eight waits
+    // at this batch size (a phase has a floor and outliers are always longer: one 10 ms hiccup must not make the next waits
+    // oversleep), only phases above 250 us -- and spin only for the last 30 %: a spinning wait keeps a core busy for the whole GPU phase,
+    // and an 8-GPU node has few cores per rank (wait_event, kosk_ctx.cpp).  Measured with nine callers in three cohorts: the same
+    // throughput (148-151 k proofs/s either way) at 3.5 busy cores fewer together with KOSK_POOL_SPIN_US=0 (profiles/r05_sweep_host.txt)
+    bool wait_nap = true;
+    bool blocking_sync = false; // kosk_options::blocking_sync: every host wait sleeps on an event instead of spinning (few host cores per GPU)
+    int xof_max_blocks = 32;    // KOSK_DEBUG_XOF_BLOCKS=n lowers gen_matrix's block limit (tests force the error path with 1)
+    // strict_encoding (kosk_options::strict_encoding; DEFAULT 1 since round 6): the verifier marks a proof malformed
+    // (fail bit 0) when ANY u16 element of a record the reference reads is >= q -- no honest prover emits one, and accepting them makes
+    // proofs malleable (v and v + q verify alike).  0 = the reference-following mode of round 5: such elements are treated exactly as
+    // the reference treats them, record by record (INTEGRATION.md 6): folded where it only multiplies / converts to ZZ_p, raw in its
+    // non-reducing add / sub and comparisons; pinned against the oracle by two differential suites, opt-in for parity work
+    bool strict_encoding = true;
+    // Fiat-Shamir aggregation on the device (kosk_options::fs_mode = KOSK_FS_DEVICE): the four
+    // sha3_256 chains of a prove + verify over the 46.5 KB digest tables run as one wave per proof where the tables are, the challenge
+    // vectors / opened lists / the verifier's I' == I never leave HBM, and the resident calls have NO host round trip left: no digest
+    // table crosses PCIe, the host neither hashes nor waits between segments (kosk_fs_kernels.hip, DESIGN.md 16).  Host mode (default)
+    // is the path of rounds 1-5
+    bool fs_device = false;
+    bool host_register = true;       // KOSK_REGISTER=0: staging copies only, even for buffers the caller page-locked itself.  (KOSK_REGISTER=2 of
+                                     // rounds 2-4 -- the library page-locking PAGEABLE caller memory for a call -- is gone: both process aborts on
+                                     // record happened inside calls that had just done that, and neither was ever reproduced or explained)
+};
+
+// Per-proof buffers: B records each, allocated by ctx_create and ensure_verify_workspace with INV_PER_PROOF.  Pointers only
+struct CtxBlock {
+    uint16_t *d_P = nullptr;
+    uint8_t *d_tape = nullptr, *d_dig1 = nullptr, *d_dig2 = nullptr, *d_proof = nullptr;
+    // seeded proving: the seeds of a call, 32 bytes per proof (page-locked staging and its device copy, which k_tape_expand reads)
+    uint8_t *d_seedbuf = nullptr, *h_seedbuf = nullptr;
+    int16_t *d_A = nullptr, *d_se = nullptr;
+    // key generation on the device (kosk_keygen_kernels.hip)
+    // one record per proof [pk | NTT(s) bytes | sha3_512 output], kg_rec bytes apart, so that the key generation's
+    // outputs cross PCIe in ONE copy; d_pk / d_sb / d_seeds (and the h_ mirrors) point into it, all with stride kg_rec
+    uint8_t *d_kg = nullptr, *h_kg = nullptr;
+    uint8_t *d_seeds = nullptr, *d_pk = nullptr, *d_sb = nullptr; // sha3_512 output, packed pk, packed NTT(s)
+    uint8_t *h_seeds = nullptr, *h_pk = nullptr, *h_sb = nullptr;
+    int16_t *d_sehat = nullptr;
+    uint16_t *d_t = nullptr; // pk's t, canonical (verifier)
+    uint16_t *d_alpha = nullptr, *d_I = nullptr, *d_rest = nullptr; // d_rest / h_rest: the second half of d_I's / h_I's allocation (one upload)
+    int32_t *d_pwT = nullptr;
+    uint8_t *d_coef = nullptr; // K3 operand: alpha-power coefficients as a limb matrix
+    uint32_t *d_fail = nullptr;      // [proof] bit mask of failed checks (FailBit)
+    // d_bind / h_bind: the call's binding values (kosk-bind-v1, CtxPrivate::bind_ctx), written by k_bind_values in BOTH Fiat-Shamir modes;
+    // in host mode they cross PCIe with the first digest table
+    uint8_t *d_bind = nullptr, *h_bind = nullptr;
+    // pinned host staging
+    uint8_t *h_tape = nullptr, *h_dig = nullptr, *h_dig2 = nullptr, *h_proof = nullptr; // h_dig / h_dig2: the host's copies of the two digest tables
+    uint16_t *h_alpha = nullptr, *h_I = nullptr, *h_rest = nullptr;
+    uint32_t *h_fail = nullptr;
+    // verifier workspace (allocated on first use, kosk_verify.cpp)
+    uint16_t *d_O = nullptr;         // opened matrix [proof][nrows][OS] (kosk_params.hpp)
+    uint16_t *d_w = nullptr, *d_ell = nullptr;
     int16_t *d_node_of = nullptr;
     uint16_t *d_isort = nullptr, *d_hrange = nullptr;
     uint8_t *d_gather = nullptr, *d_gather2 = nullptr; // weighted shares as MFMA fragment tiles (k_gather_frags)
-    uint16_t *d_invlimb = nullptr;
     uint16_t *d_sec = nullptr, *d_sec_u1 = nullptr, *d_sec_u2 = nullptr;
-    uint32_t *d_fail = nullptr;      // [proof] bit mask of failed checks (FailBit)
     uint16_t *h_Iimg = nullptr;      // I fields as read from the proof images
     // The verifier's host needs both digest tables whole (mlwe_verifier.cpp:40-44, :648-652), but only 150 entries per proof and
     // round are NEW -- the rest are fields of the proof image.  When the caller handed the proofs over in host memory (host_img:
@@ -290,7 +261,56 @@ struct Ctx {
     // (assemble_digest_table).  For resident proofs the whole tables are copied behind each hash (the split with early copies on a
     // side stream measured slower and is gone since round 6: profiles/r04_digest_paths.txt).
     uint8_t *d_odig = nullptr, *h_odig = nullptr; // [proof][NOPEN][32] recomputed digests of the opened parties (one round at a time)
-    const uint8_t *host_img = nullptr;            // the caller's host copy of the proof images of THIS call (kosk_verify_batch)
+};
+
+struct CtxPrivate {
+    // the buffer inventory: owns every buffer this context allocated, lists a view's windows (kosk_inventory.hpp)
+    Inventory inv;
+    int max_batch = 0;
+    // Inventory::add through the HIP error check (KOSK_HIPCHK(c.own(...))): allocate, record and own in one line
+    template <class T>
+    hipError_t own(const char *name, T **at, size_t bytes, int flags, int group = Inventory::INVG_CORE, size_t sec_off = 0, size_t sec_bytes = (size_t)-1,
+                   size_t alloc_bytes = 0)
+    {
+        return (hipError_t)inv.add(name, at, bytes, flags, group, sec_off, sec_bytes, alloc_bytes);
+    }
+    // kosk_wipe_secrets cleared staged prover inputs: kosk_prove_resident refuses until a staging call has run again
+    bool staged_wiped = false;
+    bool is_view = false;
+    int view_first = 0;
+    int own_batch = 0;   // proofs of this context's own callers (a view: its member's kosk_create size; else max_batch)
+    // the largest batch ONE call may run on this context: own_batch, except while this view leads a merged run of its cohort
+    // (kosk_capi.cpp: RunScope raises it to the run's total).  A view's max_batch is everything behind its first proof in the
+    // arena -- its neighbours' blocks included -- so no entry point may size a chunk by max_batch (ADVICE r4)
+    int call_cap = 0;
+    int reserved_threads = 1; // workers the pool was created with (a call never creates threads: nthreads <= this)
+    int nthreads = 1;
+    Pool *pool = nullptr; // this context's host worker threads
+    std::string err;
+    randombytes_fn rb = nullptr;
+    void *rb_user = nullptr;
+    // kosk_set_entropy: what a call with tapes == NULL draws through `rb` -- false (default) the reference's 64 / M x 32 / 302-byte
+    // sequence, a whole tape per proof; true ONE 32-byte seed per proof, expanded on the device
+    bool entropy_seed = false;
+    round_fn round_hook = nullptr;
+    void *round_user = nullptr;
+
+    // the tapes the kernels read: d_tape after an upload, or the caller's own device buffer used in place
+    const uint8_t *tape_cur = nullptr;
+    size_t tape_cur_stride = 0;
+    TapeSegs tape_segs{}; // a merged call whose callers' device tapes are read in place (count > 0; valid for that call only)
+    int resident_pk_n = 0; // pk records valid in d_pk (written by the key generation or a verifier staging call): pk_mode 2 needs >= n
+    // kosk_kem_enc_verified encapsulates to d_pk with the bits of a verify call that read d_A / d_t: it must know that d_A / d_t were decoded
+    // from d_pk (keys_from_pk_n: how many leading records of d_A / d_t are decodings of the same records of d_pk; 0 once instances were
+    // uploaded, kosk_split.cpp) and that neither changed since (pk_epoch counts every change of either).  EVERY writer of d_pk goes through
+    // note_pk_written(), the instance upload through note_keys_from_inst(), a verify call that decodes the resident d_pk again
+    // (pk_mode 2) through note_pk_decoded()
+    unsigned long pk_epoch = 0;
+    int keys_from_pk_n = 0;
+    void note_pk_written(int n) { resident_pk_n = n; keys_from_pk_n = n; pk_epoch++; }
+    void note_pk_decoded(int n) { if (n > keys_from_pk_n) keys_from_pk_n = n; } // records [0, n) decoded again from d_pk; the others keep their state
+    void note_keys_from_inst() { keys_from_pk_n = 0; pk_epoch++; }
+    const uint8_t *host_img = nullptr;            // the caller's host copy of the proof images of THIS call (kosk_verify_batch; CtxBlock::d_odig)
     size_t host_img_stride = 0;
     hipEvent_t ev = nullptr;
     std::vector<uint16_t> v_I2, v_rest2; // the verifier's recomputed opened lists (kept across calls: two fresh 0.4 MB vectors per call were
@@ -298,13 +318,7 @@ struct Ctx {
     std::function<void()> near_end_hook; // set by a merged run's executor: called once when only the call's tail is left (kosk_combine.hpp: near_end)
     bool kg_on_host_pending = false; // ev_kg was recorded by this call's key generation
     hipEvent_t ev_kg = nullptr; // the key records (pk, NTT(s) bytes, seeds) of a keygen-in-front call are on the host once it has passed
-    // KOSK_WAIT_NAP (default 1 since round 5; 0: spin throughout): the long host waits of the resident calls (six per step: the GPU
-    // phases between the host's rounds) sleep through most of their expected duration -- the SHORTEST of the site's last eight waits
-    // at this batch size (a phase has a floor and outliers are always longer: one 10 ms hiccup must not make the next waits
-    // oversleep), only phases above 250 us -- and spin only for the last 30 %: a spinning wait keeps a core busy for the whole GPU phase,
-    // and an 8-GPU node has few cores per rank (wait_event, kosk_ctx.cpp).  Measured with nine callers in three cohorts: the same
-    // throughput (148-151 k proofs/s either way) at 3.5 busy cores fewer together with KOSK_POOL_SPIN_US=0 (profiles/r05_sweep_host.txt)
-    bool wait_nap = true;
+    // the histories behind CtxShared::wait_nap
     enum { WAIT_SITES = 8 };
     enum { WAIT_HIST = 8 };
     // (round 6) a site keeps WAIT_SIZES histories, one per batch size it has recently seen (a cohort whose merged runs alternate
@@ -319,9 +333,7 @@ struct Ctx {
     };
     WaitHist wait_hist[WAIT_SITES][WAIT_SIZES];
     unsigned long wait_stamp = 0;
-    hipEvent_t ev_sync = nullptr; // kosk_options::blocking_sync: every host wait sleeps on an event instead of spinning (few host cores per GPU)
-    bool blocking_sync = false;
-    int n_simd = 1024;      // SIMDs of the device (4 per CU)
+    hipEvent_t ev_sync = nullptr; // what a blocking_sync / napping wait sleeps on
     hipEvent_t timer_ev[2] = {nullptr, nullptr}; // kosk_stream_timer_start / _stop
     // compact wire format staging (allocated on first use)
     CompactPlan cplan{};
@@ -337,16 +349,9 @@ struct Ctx {
     uint32_t *d_dense_status = nullptr;
     TcWs *tc = nullptr; // kosk_transcode_batch: allocated at this context's first such call, owned by it like `kem`
 
-    // pinned host staging
-    uint8_t *h_tape = nullptr, *h_dig = nullptr, *h_dig2 = nullptr, *h_proof = nullptr; // h_dig / h_dig2: the host's copies of the two digest tables
-    uint16_t *h_alpha = nullptr, *h_I = nullptr, *h_rest = nullptr;
-    uint32_t *h_fail = nullptr;
     // device-raised errors (XofGuard): one word of page-locked host memory the kernels store to; checked and cleared by
-    // device_error_check() after a call's last synchronisation.  KOSK_DEBUG_XOF_BLOCKS=n lowers gen_matrix's block limit
-    // (tests force the error path with 1)
+    // device_error_check() after a call's last synchronisation (a view's kernels report to the view's own word)
     uint32_t *h_err = nullptr;
-    int xof_max_blocks = 32;
-    XofGuard xof_guard() const { XofGuard g; g.err = h_err; g.max_blocks = xof_max_blocks; return g; }
 
     // hipGraph per pipeline segment (the launches between two host Fiat-Shamir rounds), captured once per
     // batch size and replayed: one API call instead of ~15 launches of kernels that run 3-6 us each.
@@ -361,35 +366,18 @@ struct Ctx {
     SegGraph seg[SEG_COUNT];
     bool use_graphs = false; // KOSK_GRAPHS=1 turns them on (measured on ROCm 7.2: no gain over plain launches)
     bool capturing = false;
-    // strict_encoding (kosk_options::strict_encoding; DEFAULT 1 since round 6): the verifier marks a proof malformed
-    // (fail bit 0) when ANY u16 element of a record the reference reads is >= q -- no honest prover emits one, and accepting them makes
-    // proofs malleable (v and v + q verify alike).  0 = the reference-following mode of round 5: such elements are treated exactly as
-    // the reference treats them, record by record (INTEGRATION.md 6): folded where it only multiplies / converts to ZZ_p, raw in its
-    // non-reducing add / sub and comparisons; pinned against the oracle by two differential suites, opt-in for parity work
-    bool strict_encoding = true;
-    // Fiat-Shamir aggregation on the device (kosk_options::fs_mode = KOSK_FS_DEVICE): the four
-    // sha3_256 chains of a prove + verify over the 46.5 KB digest tables run as one wave per proof where the tables are, the challenge
-    // vectors / opened lists / the verifier's I' == I never leave HBM, and the resident calls have NO host round trip left: no digest
-    // table crosses PCIe, the host neither hashes nor waits between segments (kosk_fs_kernels.hip, DESIGN.md 16).  Host mode (default)
-    // is the path of rounds 1-5
-    bool fs_device = false;
     // kosk-bind-v1 (kosk_set_contexts): while bind_n > 0 the context is ARMED -- prove_resident and verify_resident hash
     // B_b = k_bind_values(pk_b, context_b) behind both digest tables of proof b.  bind_ctx: the handle's device copy of the armed contexts,
     // 32 bytes each (owned by the handle, kosk_capi.cpp); bind_first: the position in the caller's whole call of this call's proof 0
-    // (set by the entry point for every chunk / sub-batch).  d_bind / h_bind: the call's binding values, written by k_bind_values in BOTH
-    // Fiat-Shamir modes; in host mode they cross PCIe with the first digest table
+    // (set by the entry point for every chunk / sub-batch).  The call's binding values: CtxBlock::d_bind / h_bind
     const uint8_t *bind_ctx = nullptr;
     int bind_n = 0, bind_first = 0;
-    uint8_t *d_bind = nullptr, *h_bind = nullptr;
     // tests (kosk_force_opened_candidates): while force_n > 0 round 2 of prove_resident takes the candidates of proof b from list
     // bind_first + b -- force_d in HBM for the chain kernel, force_h for the host's round; both owned by the handle (kosk_capi.cpp).  The
     // verifier never looks at them
     const uint16_t *force_d = nullptr, *force_h = nullptr;
     int force_n = 0;
-    bool host_register = true;       // KOSK_REGISTER=0: staging copies only, even for buffers the caller page-locked itself.  (KOSK_REGISTER=2 of
-                                     // rounds 2-4 -- the library page-locking PAGEABLE caller memory for a call -- is gone: both process aborts on
-                                     // record happened inside calls that had just done that, and neither was ever reproduced or explained)
-    // which of those paths really ran on this context (kosk_path_count): the tests of the knobs assert on these
+    // which of the library's paths really ran on this context (kosk_path_count): the tests of the knobs assert on these
     long path_n[PATH_COUNT] = {0};
     KemWs *kem = nullptr; // allocated at this context's first KEM call, owned by it (a view's is its own, never the arena's)
     KemKey *kem_key = nullptr; // the key slot: allocated at the first kem_key_set, its own allocation (kem_ensure never moves it), owned like `kem`
@@ -403,9 +391,6 @@ struct Ctx {
     long prof_n[PR_COUNT] = {0};
     long prof_units[PR_COUNT] = {0}; // proofs served by the timed launches (a merged run serves several callers' batches per launch)
     int prof_cur_units[PR_COUNT] = {0};
-    void prof_begin(int id, int units = 0) { if (prof_on && !capturing) { (void)hipEventRecord(prof_ev[id][0], stream); prof_cur_units[id] = units; } }
-    void prof_end(int id) { if (prof_on && !capturing) { (void)hipEventRecord(prof_ev[id][1], stream); prof_used[id] = true; } }
-    void prof_collect(); // call after the stream has been synchronised
 
     // witness recovery (witness_from_sk): the secret-key records of the largest call so far and their verdicts; allocated at the first
     // such call and owned by this context like `kem`
@@ -422,8 +407,15 @@ struct Ctx {
     // only, and is the only one -- it ends with no staged inputs, as a banked key generation does, because the tape buffer never held the
     // offline sections of these proofs and the rows of a consumed entry serve one proof.  Every call that makes other tapes current clears it
     bool staged_online = false;
+};
 
-    ~Ctx();
+struct Ctx : CtxShared, CtxBlock, CtxPrivate {
+    Ctx();
+    ~Ctx(); // graph execs, events, the workers; every buffer through the inventory; the stream unless this is a view
+    XofGuard xof_guard() const { XofGuard g; g.err = h_err; g.max_blocks = xof_max_blocks; return g; }
+    void prof_begin(int id, int units = 0) { if (prof_on && !capturing) { (void)hipEventRecord(prof_ev[id][0], stream); prof_cur_units[id] = units; } }
+    void prof_end(int id) { if (prof_on && !capturing) { (void)hipEventRecord(prof_ev[id][1], stream); prof_used[id] = true; } }
+    void prof_collect(); // call after the stream has been synchronised
 };
 
 // Run `body` (stream launches on c.stream only: kernels, pinned-memory copies, memsets) as segment `seg`:
@@ -759,8 +751,6 @@ int kem_registry_probe(Ctx &c, int n, const uint8_t *pk, int resident_first, uin
 int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
 // ---- erasure (kosk_wipe.hip) ----
-// `count` records of `bytes` bytes, `stride` apart, in HBM (count 1: one run of bytes)
-struct WipeRegion { uint8_t *p; size_t bytes, stride; uint32_t count; };
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches
 enum : unsigned long long { WIPE_MEMSET_BYTES = 320ull << 20 }; // a single run of this many bytes or more is cleared by hipMemsetAsync (kosk_wipe.hip)
 // zero the regions: queued on the context's stream (never while it is capturing), not synchronised; empty regions are skipped
@@ -772,7 +762,7 @@ int launch_wipe(Ctx &c, const WipeRegion *regions, int n);
 int wipe_secrets(Ctx &c, bool keep_key = false);
 // the HBM regions wipe_secrets() clears (group >= 0: of that owner only; skip_mask: bit g set = not owner g's)
 int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group = -1, unsigned skip_mask = 0);
-// the secret HBM buffers of one owner (Ctx::INVG_*), synchronised: before they are freed to be allocated larger
+// the secret HBM buffers of one owner (Inventory::INVG_*), synchronised: before they are freed to be allocated larger
 int wipe_group(Ctx &c, int group);
 void host_wipe(void *p, size_t bytes); // explicit_bzero: not removed as a dead store
 template <class T> void host_wipe_vec(std::vector<T> &v) { if (!v.empty()) host_wipe(v.data(), v.size() * sizeof(T)); }

@@ -559,11 +559,13 @@ static DenseFill2Args make_fill_args(const Params &P, int fmt)
 int ensure_dense_ws(Ctx &c)
 {
     if (c.d_dense_ws) return 0;
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_ws), (size_t)c.own_batch * DN_WS * sizeof(uint16_t)));
-    HIPCHK(hipMalloc(reinterpret_cast<void **>(&c.d_dense_status), sizeof(uint32_t) * c.own_batch));
-    // the inventory: rows of proof images and a status word per proof, public
-    c.reg_buf("d_dense_ws", &c.d_dense_ws, (size_t)c.own_batch * DN_WS * sizeof(uint16_t), 0, Ctx::INVG_DENSE);
-    c.reg_buf("d_dense_status", &c.d_dense_status, sizeof(uint32_t) * c.own_batch, 0, Ctx::INVG_DENSE);
+    // rows of proof images and a status word per proof, public
+    auto body = [&]() -> int {
+        HIPCHK(c.own("d_dense_ws", &c.d_dense_ws, (size_t)c.own_batch * DN_WS * sizeof(uint16_t), 0, Inventory::INVG_DENSE));
+        HIPCHK(c.own("d_dense_status", &c.d_dense_status, sizeof(uint32_t) * c.own_batch, 0, Inventory::INVG_DENSE));
+        return 0;
+    };
+    if (body()) { c.inv.release(Inventory::INVG_DENSE); return -1; }
     return 0;
 }
 

@@ -372,12 +372,9 @@ void kem_release(Ctx &c)
 {
     KemWs *w = c.kem;
     if (!w) return;
-    void *dev[] = {w->d_pk, w->d_sk, w->d_ct, w->d_m, w->d_kr, w->d_rk, w->d_ss, w->d_mask, w->d_h, w->d_A, w->d_noise, w->d_key};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
+    c.inv.release(Inventory::INVG_KEM);
     delete w;
     c.kem = nullptr;
-    c.inv_drop(Ctx::INVG_KEM);
 }
 
 // the workspace holds the largest launch group the context has seen (rounded up to 1 024 items, at most KEM_CHUNK)
@@ -386,45 +383,33 @@ static int kem_ensure(Ctx &c, int n)
     if (c.kem && c.kem->cap >= n) return 0;
     if (c.kem) {
         KOSK_HIPCHK(stream_sync(c));
-        if (wipe_group(c, Ctx::INVG_KEM)) return -1; // the workspace of the earlier calls does not go back to the allocator readable
+        if (wipe_group(c, Inventory::INVG_KEM)) return -1; // the workspace of the earlier calls does not go back to the allocator readable
         kem_release(c);
     }
     const Dims D = dims(c.P.K);
     KemWs *w = new KemWs();
     c.kem = w;
     const size_t N = (size_t)((n + 1023) / 1024 * 1024 < KEM_CHUNK ? (n + 1023) / 1024 * 1024 : KEM_CHUNK);
+    // secret are the records, messages, hashes of them and the noise; public the keys, ciphertexts, A, H(pk), flags
+    const int S = Inventory::INV_SECRET, G = Inventory::INVG_KEM;
     auto body = [&]() -> int {
         HIPCHK(hipSetDevice(c.device));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_pk), N * D.pk));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_sk), N * D.sk));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_ct), N * D.ct));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_m), N * 32));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_kr), N * 64));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_rk), N * 32));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_ss), N * 32));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_mask), N));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_h), N * 32));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_A), N * D.K * D.K * 512));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_noise), N * (2 * D.K + 1) * 512));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&w->d_key), N * sizeof(int32_t)));
+        HIPCHK(c.own("kem.d_sk", &w->d_sk, N * D.sk, S, G));
+        HIPCHK(c.own("kem.d_m", &w->d_m, N * 32, S, G));
+        HIPCHK(c.own("kem.d_kr", &w->d_kr, N * 64, S, G));
+        HIPCHK(c.own("kem.d_rk", &w->d_rk, N * 32, S, G));
+        HIPCHK(c.own("kem.d_ss", &w->d_ss, N * 32, S, G));
+        HIPCHK(c.own("kem.d_noise", &w->d_noise, N * (2 * D.K + 1) * 512, S, G));
+        HIPCHK(c.own("kem.d_pk", &w->d_pk, N * D.pk, 0, G));
+        HIPCHK(c.own("kem.d_ct", &w->d_ct, N * D.ct, 0, G));
+        HIPCHK(c.own("kem.d_mask", &w->d_mask, N, 0, G));
+        HIPCHK(c.own("kem.d_h", &w->d_h, N * 32, 0, G));
+        HIPCHK(c.own("kem.d_A", &w->d_A, N * D.K * D.K * 512, 0, G));
+        HIPCHK(c.own("kem.d_key", &w->d_key, N * sizeof(int32_t), 0, G));
         return 0;
     };
     if (body()) { kem_release(c); return -1; }
     w->cap = (int)N;
-    // the inventory: secret are the records, messages, hashes of them and the noise; public the keys, ciphertexts, A, H(pk), flags
-    const int S = Ctx::INV_SECRET, G = Ctx::INVG_KEM;
-    c.reg_buf("kem.d_sk", &w->d_sk, N * D.sk, S, G);
-    c.reg_buf("kem.d_m", &w->d_m, N * 32, S, G);
-    c.reg_buf("kem.d_kr", &w->d_kr, N * 64, S, G);
-    c.reg_buf("kem.d_rk", &w->d_rk, N * 32, S, G);
-    c.reg_buf("kem.d_ss", &w->d_ss, N * 32, S, G);
-    c.reg_buf("kem.d_noise", &w->d_noise, N * (2 * D.K + 1) * 512, S, G);
-    c.reg_buf("kem.d_pk", &w->d_pk, N * D.pk, 0, G);
-    c.reg_buf("kem.d_ct", &w->d_ct, N * D.ct, 0, G);
-    c.reg_buf("kem.d_mask", &w->d_mask, N, 0, G);
-    c.reg_buf("kem.d_h", &w->d_h, N * 32, 0, G);
-    c.reg_buf("kem.d_A", &w->d_A, N * D.K * D.K * 512, 0, G);
-    c.reg_buf("kem.d_key", &w->d_key, N * sizeof(int32_t), 0, G);
     return 0;
 }
 
@@ -678,11 +663,9 @@ void kem_key_release(Ctx &c)
 {
     KemKey *k = c.kem_key;
     if (!k) return;
-    if (k->d_pub) (void)hipFree(k->d_pub);
-    if (k->d_sec) (void)hipFree(k->d_sec);
+    c.inv.release(Inventory::INVG_KEMKEY);
     delete k;
     c.kem_key = nullptr;
-    c.inv_drop(Ctx::INVG_KEMKEY);
 }
 
 int kem_key_state(const Ctx &c) { return c.kem_key ? c.kem_key->state : (int)KEM_KEY_NONE; }
@@ -698,7 +681,7 @@ int kem_key_clear(Ctx &c)
     if (!c.kem_key) return 0;
     HIPCHK(hipSetDevice(c.device));
     HIPCHK(stream_sync(c));
-    const int rc = wipe_group(c, Ctx::INVG_KEMKEY); // s-hat and z do not go back to the allocator readable
+    const int rc = wipe_group(c, Inventory::INVG_KEMKEY); // s-hat and z do not go back to the allocator readable
     kem_key_release(c);
     return rc;
 }
@@ -713,13 +696,11 @@ int kem_key_set(Ctx &c, const uint8_t *pk, const uint8_t *sk)
     c.kem_key = k;
     const size_t pub_bytes = (size_t)D.pk + 64 + (size_t)D.K * D.K * 512, sec_bytes = (size_t)D.pvb + 32;
     auto body = [&]() -> int {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&k->d_pub), pub_bytes));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&k->d_sec), sec_bytes));
+        HIPCHK(c.own("kemkey.pub", &k->d_pub, pub_bytes, 0, Inventory::INVG_KEMKEY));
+        HIPCHK(c.own("kemkey.sec", &k->d_sec, sec_bytes, Inventory::INV_SECRET, Inventory::INVG_KEMKEY));
         k->pk = k->d_pub; k->h_enc = k->d_pub + D.pk; k->h_dec = k->h_enc + 32; // D.pk is a multiple of 16: A^T stays 16-byte aligned
         k->A = reinterpret_cast<int16_t *>(k->h_dec + 32);
         k->shat = k->d_sec; k->z = k->d_sec + D.pvb;
-        c.reg_buf("kemkey.pub", &k->d_pub, pub_bytes, 0, Ctx::INVG_KEMKEY);
-        c.reg_buf("kemkey.sec", &k->d_sec, sec_bytes, Ctx::INV_SECRET, Ctx::INVG_KEMKEY);
         HIPCHK(hipMemsetAsync(k->d_pub, 0, pub_bytes, c.stream));
         HIPCHK(hipMemsetAsync(k->d_sec, 0, sec_bytes, c.stream));
         if (sk) { // sk = s-hat || pk || H(pk) || z: the pieces go straight to their places, no copy of the record in between

@@ -164,10 +164,7 @@ int registry_index_ensure(Ctx &c)
     if (r.index_valid) return 0;
     HIPCHK(hipSetDevice(c.device));
     const size_t T = registry_index_entries(r.capacity);
-    if (!r.d_index) {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r.d_index), T * sizeof(int32_t)));
-        c.reg_buf("registry.d_index", &r.d_index, T * sizeof(int32_t), 0, Ctx::INVG_REGISTRY); // public: slot numbers only
-    }
+    if (!r.d_index) HIPCHK(c.own("registry.d_index", &r.d_index, T * sizeof(int32_t), 0, Inventory::INVG_REGISTRY)); // public: slot numbers only
     HIPCHK(hipMemsetAsync(r.d_index, 0xFF, T * sizeof(int32_t), c.stream));
     RegIndexJob j{};
     j.capacity = r.capacity; j.mask = (uint32_t)(T - 1); j.h = r.d_h; j.flag = r.d_flag; j.index = r.d_index; j.err = c.h_err;
@@ -183,12 +180,9 @@ void registry_release(Ctx &c)
 {
     KemRegistry *r = c.registry;
     if (!r) return;
-    void *dev[] = {r->d_pk, r->d_h, r->d_A, r->d_flag, r->d_index};
-    for (void *p : dev)
-        if (p) (void)hipFree(p);
+    c.inv.release(Inventory::INVG_REGISTRY);
     delete r;
     c.registry = nullptr;
-    c.inv_drop(Ctx::INVG_REGISTRY);
 }
 
 int registry_reserve(Ctx &c, int capacity)
@@ -205,11 +199,12 @@ int registry_reserve(Ctx &c, int capacity)
     KemRegistry *r = new KemRegistry();
     c.registry = r;
     const size_t N = (size_t)capacity, a_bytes = N * D.K * D.K * 512;
+    const int G = Inventory::INVG_REGISTRY; // public, all four: the wipes leave them alone, the scan covers them
     auto body = [&]() -> int {
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_pk), N * D.pk));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_h), N * 32));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_A), a_bytes));
-        HIPCHK(hipMalloc(reinterpret_cast<void **>(&r->d_flag), N));
+        HIPCHK(c.own("registry.d_pk", &r->d_pk, N * D.pk, 0, G));
+        HIPCHK(c.own("registry.d_h", &r->d_h, N * 32, 0, G));
+        HIPCHK(c.own("registry.d_A", &r->d_A, a_bytes, 0, G));
+        HIPCHK(c.own("registry.d_flag", &r->d_flag, N, 0, G));
         HIPCHK(hipMemsetAsync(r->d_pk, 0, N * D.pk, c.stream));
         HIPCHK(hipMemsetAsync(r->d_h, 0, N * 32, c.stream));
         HIPCHK(hipMemsetAsync(r->d_A, 0, a_bytes, c.stream));
@@ -226,11 +221,6 @@ int registry_reserve(Ctx &c, int capacity)
     }
     r->capacity = capacity;
     r->occ.assign(N, 0);
-    const int G = Ctx::INVG_REGISTRY; // public, all four: the wipes leave them alone, the scan covers them
-    c.reg_buf("registry.d_pk", &r->d_pk, N * D.pk, 0, G);
-    c.reg_buf("registry.d_h", &r->d_h, N * 32, 0, G);
-    c.reg_buf("registry.d_A", &r->d_A, a_bytes, 0, G);
-    c.reg_buf("registry.d_flag", &r->d_flag, N, 0, G);
     return 0;
 }
 

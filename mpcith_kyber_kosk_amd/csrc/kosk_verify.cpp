@@ -35,12 +35,9 @@ static double now_sec()
 #define HIPCHK(x) KOSK_HIPCHK(x)
 
 template <typename T>
-static hipError_t dalloc(T **p, size_t n) { return hipMalloc(reinterpret_cast<void **>(p), (n ? n : 1) * sizeof(T)); }
-template <typename T>
 static int upload_vec(Ctx &c, T **d, const std::vector<T> &v)
 {
-    HIPCHK(dalloc(d, v.size()));
-    c.reg_buf("verifier table", d, v.size() * sizeof(T), 0, Ctx::INVG_VERIFY);
+    HIPCHK(c.own("verifier table", d, v.size() * sizeof(T), 0, Inventory::INVG_VERIFY, 0, (size_t)-1, v.empty() ? sizeof(T) : 0)); // an empty table still gets a pointer
     // on the context's own stream (a non-blocking stream is NOT ordered against the legacy null stream that a plain hipMemcpy /
     // hipMemset uses), and complete before `v` goes away: the caller synchronises the stream before it returns
     if (!v.empty()) {
@@ -50,10 +47,19 @@ static int upload_vec(Ctx &c, T **d, const std::vector<T> &v)
     return 0;
 }
 
+static int build_verify_workspace(Ctx &c);
+// tables and workspace in one group: a failure half-way releases all of it, so that a retry starts from nothing
 int ensure_verify_workspace(Ctx &c)
 {
     if (c.verify_ready) return 0;
     if (c.is_view) { c.err = "internal: a view's verifier workspace is allocated with its arena"; return -1; }
+    if (build_verify_workspace(c)) { c.inv.release(Inventory::INVG_VERIFY); return -1; }
+    c.verify_ready = true;
+    return 0;
+}
+
+static int build_verify_workspace(Ctx &c)
+{
     const Params &P = c.P;
     const RowMap &rm = c.rm;
     const int K = P.K, M = P.M, E = P.E, Z = P.Z;
@@ -134,12 +140,9 @@ int ensure_verify_workspace(Ctx &c)
         return -1;
 
     c.o_stride = (size_t)rm.nrows * OS;
-    // per-proof buffers, registered for views like the ones of ctx_create
-    auto dev = [&](auto **p, size_t per) -> hipError_t {
-        const hipError_t e = dalloc(p, B * per);
-        if (e == hipSuccess) { c.reg_pp(p, per * sizeof(**p)); c.reg_buf("verifier workspace", p, per * sizeof(**p), Ctx::INV_PER_PROOF, Ctx::INVG_VERIFY); }
-        return e;
-    };
+    // per-proof buffers, B records each for views like the ones of ctx_create
+    const int PP = Inventory::INV_PER_PROOF, G = Inventory::INVG_VERIFY;
+    auto dev = [&](auto **p, size_t per) -> hipError_t { return c.own("verifier workspace", p, per * sizeof(**p), PP, G); };
     HIPCHK(dev(&c.d_O, c.o_stride));
     HIPCHK(hipMemsetAsync(c.d_O, 0, B * c.o_stride * sizeof(uint16_t), c.stream));
     HIPCHK(dev(&c.d_w, (size_t)2 * 832));
@@ -152,15 +155,10 @@ int ensure_verify_workspace(Ctx &c)
     HIPCHK(dev(&c.d_sec, (size_t)2 * NCHK * 256));
     HIPCHK(dev(&c.d_sec_u1, (size_t)c.n_interp_2d * 256));
     HIPCHK(dev(&c.d_sec_u2, (size_t)c.n_interp_2d * 256));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_Iimg), B * 2 * NOPEN, hipHostMallocDefault));
-    c.reg_pp(&c.h_Iimg, (size_t)2 * NOPEN);
-    c.reg_buf("h_Iimg", &c.h_Iimg, (size_t)2 * NOPEN, Ctx::INV_PER_PROOF | Ctx::INV_HOST, Ctx::INVG_VERIFY);
+    HIPCHK(c.own("h_Iimg", &c.h_Iimg, (size_t)2 * NOPEN, PP | Inventory::INV_HOST, G));
     HIPCHK(dev(&c.d_odig, (size_t)NOPEN * 32));
-    HIPCHK(hipHostMalloc(reinterpret_cast<void **>(&c.h_odig), B * NOPEN * 32, hipHostMallocDefault));
-    c.reg_pp(&c.h_odig, (size_t)NOPEN * 32);
-    c.reg_buf("h_odig", &c.h_odig, (size_t)NOPEN * 32, Ctx::INV_PER_PROOF | Ctx::INV_HOST, Ctx::INVG_VERIFY);
+    HIPCHK(c.own("h_odig", &c.h_odig, (size_t)NOPEN * 32, PP | Inventory::INV_HOST, G));
     HIPCHK(hipStreamSynchronize(c.stream)); // every table and the zeroed opened matrix are in HBM before the first verifier kernel is queued
-    c.verify_ready = true;
     return 0;
 }
 

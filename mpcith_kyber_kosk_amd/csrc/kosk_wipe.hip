@@ -187,36 +187,11 @@ int launch_wipe(Ctx &c, const WipeRegion *regions, int n)
 
 // ---- the inventory's two users ----
 
-// the part of buffer b this context owns: a view sees its member's block of a per-proof buffer and its private buffers
-static bool inv_span(const Ctx &c, const Ctx::InvBuf &b, uint8_t *&p, size_t &rec_bytes, size_t &nrec)
-{
-    p = static_cast<uint8_t *>(c.inv_ptr(b));
-    if (!p) return false;
-    rec_bytes = b.bytes;
-    nrec = (b.flags & Ctx::INV_PER_PROOF) ? (size_t)(c.is_view ? c.own_batch : c.max_batch) : 1;
-    return rec_bytes != 0;
-}
-
-// the secret part of buffer b as this context sees it: nrec records, the secret bytes [so, so + sb) of each
-static bool inv_secret_span(const Ctx &c, const Ctx::InvBuf &b, uint8_t *&p, size_t &rec, size_t &nrec, size_t &so, size_t &sb)
-{
-    if (!(b.flags & Ctx::INV_SECRET) || !inv_span(c, b, p, rec, nrec)) return false;
-    so = b.sec_off < rec ? b.sec_off : rec;
-    sb = b.sec_bytes < rec - so ? b.sec_bytes : rec - so;
-    return sb != 0;
-}
-
+// (what a context owns of a buffer -- a view: its member's block of a per-proof buffer and its private buffers -- is the inventory's
+// arithmetic: Inventory::span / secret_span / secret_regions, kosk_inventory.hpp)
 int wipe_regions_list(const Ctx &c, std::vector<WipeRegion> &out, int group, unsigned skip_mask)
 {
-    for (const Ctx::InvBuf &b : c.inv) {
-        uint8_t *p;
-        size_t rec, nrec, so, sb;
-        if ((group >= 0 && b.group != group) || (skip_mask >> b.group & 1) || (b.flags & Ctx::INV_HOST) || !inv_secret_span(c, b, p, rec, nrec, so, sb)) continue;
-        // records without a public part lie back to back: one record of nrec x rec bytes
-        if (so == 0 && sb == rec) out.push_back(WipeRegion{p, rec * nrec, 0, 1});
-        else out.push_back(WipeRegion{p + so, sb, rec, (uint32_t)nrec});
-    }
-    return (int)out.size();
+    return c.inv.secret_regions(out, group, skip_mask);
 }
 
 int wipe_group(Ctx &c, int group)
@@ -237,14 +212,14 @@ int wipe_secrets(Ctx &c, bool keep_key)
 {
     HIPCHK(hipSetDevice(c.device));
     std::vector<WipeRegion> dev;
-    wipe_regions_list(c, dev, -1, keep_key ? 1u << Ctx::INVG_KEMKEY | 1u << Ctx::INVG_BANK : 0u); // long-lived secrets stay
+    wipe_regions_list(c, dev, -1, keep_key ? 1u << Inventory::INVG_KEMKEY | 1u << Inventory::INVG_BANK : 0u); // long-lived secrets stay
     // the stream may still carry this context's earlier work on these buffers: the wipe is queued behind it
     if (launch_wipe(c, dev.data(), (int)dev.size())) return -1;
     HIPCHK(stream_sync(c));
-    for (const Ctx::InvBuf &b : c.inv) { // page-locked staging: by the host, once nothing on the stream can write to it any more
+    for (const InvBuf &b : c.inv.bufs) { // page-locked staging: by the host, once nothing on the stream can write to it any more
         uint8_t *p;
         size_t rec, nrec, so, sb;
-        if (!(b.flags & Ctx::INV_HOST) || !inv_secret_span(c, b, p, rec, nrec, so, sb)) continue;
+        if (!(b.flags & Inventory::INV_HOST) || !c.inv.secret_span(b, p, rec, nrec, so, sb)) continue;
         if (so == 0 && sb == rec) host_wipe(p, rec * nrec);
         else for (size_t i = 0; i < nrec; i++) host_wipe(p + i * rec + so, sb);
     }
@@ -298,12 +273,12 @@ int secret_scan(Ctx &c, const uint8_t *needle, size_t len, const uint8_t *d_need
         j.first[0] = 0;
         return 0;
     };
-    for (const Ctx::InvBuf &b : c.inv) {
+    for (const InvBuf &b : c.inv.bufs) {
         uint8_t *p;
         size_t rec, nrec;
-        if (!inv_span(c, b, p, rec, nrec)) continue;
+        if (!c.inv.span(b, p, rec, nrec)) continue;
         const size_t bytes = rec * nrec;
-        if (b.flags & Ctx::INV_HOST) { total += host_count(p, bytes, needle, len); continue; }
+        if (b.flags & Inventory::INV_HOST) { total += host_count(p, bytes, needle, len); continue; }
         if (bytes < len) continue;
         if (j.n == WIPE_MAX_REGIONS && flush()) return -1;
         j.p[j.n] = p;
