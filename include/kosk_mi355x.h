@@ -477,6 +477,55 @@ int kosk_registry_enrol_verified(kosk_ctx *ctx, int n, int32_t *slots, uint8_t *
 int kosk_registry_enrol(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, int32_t *slots, uint8_t *status);
 int kosk_kem_enc_peers(kosk_ctx *ctx, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* ---- The registry tree, format kosk-regtree-v1 (INTEGRATION.md 8.5 is the normative text): a Merkle tree over the slots' fingerprints, built
+ * and kept current on the GPU beside the registry.  Out of it come a 32-byte root that pins the whole table, and per-key inclusion paths that
+ * anyone checks with kosk_regtree_root_from_path, on the host, without a handle.  A path for an empty slot proves that the slot is empty.
+ * TAG = the 15 ASCII bytes "kosk-regtree-v1"; every hash is SHA3-256 of one rate block:
+ *   leaf of an occupied slot   L(h)   = SHA3-256(TAG || 00 || h[32] || LE32(kyber_k))     h = the slot's stored SHA3-256(pk)
+ *   leaf of an empty slot      E      = SHA3-256(TAG || 01 || LE32(kyber_k))
+ *   inner node                 N(l,r) = SHA3-256(TAG || 02 || l[32] || r[32])
+ * D = kosk_registry_tree_depth(capacity) is the smallest D with 2^D >= capacity (0 for capacity 1, -1 for capacity < 1), P = 2^D.  Level 0
+ * has P leaves: L(h_s) for an occupied slot s < capacity, E for an empty slot and for every padding position s >= capacity; node i of level
+ * l + 1 is N(level_l[2i], level_l[2i + 1]); the root is the one node of level D (for D = 0: leaf 0).  The path of slot s is D records of 32
+ * bytes, level 0 first, record l = node (s >> l) ^ 1 of level l; walking up from the leaf, step l computes N(path[l], cur) if bit l of s is
+ * set, else N(cur, path[l]).  The root binds neither capacity nor the occupied count: kosk_registry_root returns them beside it for a signed
+ * tree head.  Equal keys in several slots (kosk_registry_admit) give equal leaves; lookup by fingerprint names the lowest slot.  Proofs of
+ * ABSENCE of a fingerprint would need a sorted tree and are out of scope.
+ * Host functions: kosk_registry_tree_bytes = (2P - 1) * 32, the HBM the tree takes (0 for capacity < 1).  kosk_regtree_leaf (h == NULL: E)
+ * and kosk_regtree_node: -1 for kyber_k outside 2..4 or a NULL argument.  kosk_regtree_root_from_path: the root that (slot, h or NULL for
+ * "empty", path[depth][32]) implies -- the caller compares it with the published root; -1: bad k, depth outside 0..31, slot outside
+ * [0, 2^depth), NULL root, NULL path with depth > 0.  Pointers of any alignment.
+ * On a handle: the tree is one more allocation of the registry (with a list of subtree numbers and, from the first proving call on, a
+ * staging buffer for paths), made by the first of the calls below and freed with the registry; a registry that never asks allocates and
+ * launches what it did before.  Every admit / evict / enrol marks the leaf subtrees (KOSK_REGTREE_TIER_LEVELS = 10 levels, 1 024 slots)
+ * of the slots it writes, and the first tree call after a mutation rehashes those subtrees and the levels above them (k_registry_tree); a tree
+ * call on a current tree launches nothing but the gather (k_registry_path).
+ * kosk_registry_root: root = 32 bytes of host or device memory; used / capacity may be NULL.
+ * kosk_registry_prove_slots: slots = n int32 in HOST memory, repeats are fine, a value outside [0, capacity) returns -1 and starts nothing;
+ * state[b] (host memory) = occupancy; h: NULL, or n x 32 bytes, the stored fingerprints, zeros for an empty slot; paths: n x D x 32 bytes
+ * (may be NULL when D = 0); root: NULL, or the root the paths belong to, taken from the same tree state.  h, paths and root may be host or
+ * device memory of any alignment.  An empty slot gets a valid path: it checks with h == NULL in kosk_regtree_root_from_path.
+ * kosk_registry_prove_peers: h = n x 32 query fingerprints; the lookup runs on the GPU (k_registry_find) in front of the gather; slots[b] =
+ * the lowest occupied slot that holds the fingerprint, or -1; done[b] = found; a miss gets a zero-filled path.  h, slots, done, paths and root
+ * may be host or device memory.
+ * Both: any n >= 1 in launch groups of 16384, unmerged on the handle's own stream, also on a cohort member.  Refusals (-1, a text that begins
+ * with the call's name, nothing started): NULL required arguments, n < 1, no registry reserved.  No call here touches the prover's or
+ * verifier's resident state, the bank, the one-key slot, the fail masks, the registry's slots, or the validity of the fingerprint index
+ * (kosk_registry_prove_peers builds a stale index as kosk_registry_find does).
+ * Erasure: the tree, the subtree list and the path staging are public buffers of the inventory: kosk_secret_scan covers
+ * them, kosk_wipe_secrets and KOSK_WIPE_CALL leave them alone; the staged query fingerprints are zeroed before kosk_registry_prove_peers
+ * returns.  After an eviction the evicted key's leaf and its ancestors stay in the tree until the next tree call rebuilds them: hashes of a
+ * public fingerprint, not the fingerprint. */
+enum { KOSK_REGTREE_TIER_LEVELS = 10 };
+int kosk_registry_tree_depth(int capacity);
+size_t kosk_registry_tree_bytes(int capacity);
+int kosk_regtree_leaf(int kyber_k, const uint8_t *h, uint8_t out[32]);
+int kosk_regtree_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]);
+int kosk_regtree_root_from_path(int kyber_k, int depth, int32_t slot, const uint8_t *h, const uint8_t *path, uint8_t root[32]);
+int kosk_registry_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *capacity);
+int kosk_registry_prove_slots(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h, uint8_t *paths, uint8_t *root);
+int kosk_registry_prove_peers(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *slots, uint8_t *paths, uint8_t *done, uint8_t *root);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -605,7 +654,9 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * groups of kosk_kem_enc_slots (ids 12 / 20 do not move for it); kosk_registry_evict runs k_wipe (id 18),
  * 29 launches of k_registry_index (one per rebuild of the fingerprint index: the first lookup after a mutation of the registry),
  * 30 launches of k_registry_find (one per launch group of kosk_registry_find, kosk_registry_enrol* and kosk_kem_enc_peers),
- * 31 kem_enc_peers: launch groups of kosk_kem_enc_peers (ids 12 / 20 / 28 do not move for it). */
+ * 31 kem_enc_peers: launch groups of kosk_kem_enc_peers (ids 12 / 20 / 28 do not move for it),
+ * 32 launches of k_registry_tree (one per tier of a rebuild) / 33 leaf subtrees hashed by those launches,
+ * 34 launches of k_registry_path (one per launch group of kosk_registry_prove_slots / kosk_registry_prove_peers). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

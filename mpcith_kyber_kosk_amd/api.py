@@ -257,6 +257,19 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_find")):
         sig.update(peers)
+    # the registry tree, kosk-regtree-v1; optional under the same rule (and only then)
+    tree = {
+        "kosk_registry_tree_depth": (C.c_int, [C.c_int]),
+        "kosk_registry_tree_bytes": (sz, [C.c_int]),
+        "kosk_regtree_leaf": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_regtree_node": (C.c_int, [vp, vp, vp]),
+        "kosk_regtree_root_from_path": (C.c_int, [C.c_int, C.c_int, C.c_int32, vp, vp, vp]),
+        "kosk_registry_root": (C.c_int, [vp, vp, ip, ip]),
+        "kosk_registry_prove_slots": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+        "kosk_registry_prove_peers": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_root")):
+        sig.update(tree)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -300,7 +313,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_registry_slot_bytes", "kosk_registry_reserve", "kosk_registry_level", "kosk_registry_admit_verified", "kosk_registry_admit",
            "kosk_registry_evict", "kosk_registry_read", "kosk_kem_enc_slots",
            "kosk_registry_index_entries", "kosk_registry_index_home", "kosk_registry_find", "kosk_registry_enrol_verified",
-           "kosk_registry_enrol", "kosk_kem_enc_peers"]
+           "kosk_registry_enrol", "kosk_kem_enc_peers",
+           "kosk_registry_tree_depth", "kosk_registry_tree_bytes", "kosk_regtree_leaf", "kosk_regtree_node", "kosk_regtree_root_from_path",
+           "kosk_registry_root", "kosk_registry_prove_slots", "kosk_registry_prove_peers"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -355,6 +370,52 @@ def registry_index_home(capacity, h):
     if len(h) != 32:
         raise KoskError("a fingerprint has 32 bytes")
     return lib.kosk_registry_index_home(capacity, C.c_char_p(h))
+
+
+# the registry tree, kosk-regtree-v1: the host functions, no handle and no GPU
+REGTREE_TIER_LEVELS = 10  # KOSK_REGTREE_TIER_LEVELS
+
+
+def registry_tree_depth(capacity): return lib.kosk_registry_tree_depth(capacity)
+def registry_tree_bytes(capacity): return lib.kosk_registry_tree_bytes(capacity)
+
+
+def _digest(what, b):
+    b = bytes(b)
+    if len(b) != 32:
+        raise KoskError("%s has 32 bytes" % what)
+    return b
+
+
+def regtree_leaf(k, h=None):
+    """kosk_regtree_leaf: the leaf of an occupied slot whose stored fingerprint is h, or (h None) of an empty slot"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_regtree_leaf(k, None if h is None else C.c_char_p(_digest("a fingerprint", h)), out):
+        raise KoskError("regtree_leaf: kyber_k outside 2..4")
+    return out.raw
+
+
+def regtree_node(left, right):
+    """kosk_regtree_node: the inner node over two 32-byte children"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_regtree_node(C.c_char_p(_digest("a node", left)), C.c_char_p(_digest("a node", right)), out):
+        raise KoskError("regtree_node failed")
+    return out.raw
+
+
+def regtree_root_from_path(k, depth, slot, h, path):
+    """kosk_regtree_root_from_path: the root that slot, its fingerprint h (None: the slot is empty) and path (depth x 32 bytes, or a list
+    of depth 32-byte records) imply; compare it with the published root"""
+    if not isinstance(path, (bytes, bytearray)):
+        path = b"".join(path)
+    path = bytes(path)
+    if depth < 0 or len(path) != 32 * depth:
+        raise KoskError("a path of depth %d has %d bytes" % (depth, 32 * max(depth, 0)))
+    out = C.create_string_buffer(32)
+    if lib.kosk_regtree_root_from_path(k, depth, slot, None if h is None else C.c_char_p(_digest("a fingerprint", h)),
+                                       C.c_char_p(path) if depth else None, out):
+        raise KoskError("regtree_root_from_path: bad kyber_k, depth or slot")
+    return out.raw
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1231,6 +1292,44 @@ class Kosk:
             return out
         return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
 
+    # the registry tree, kosk-regtree-v1
+    def registry_root(self, out=None):
+        """kosk_registry_root -> (root, used, capacity); out: an int DEVICE pointer to 32 bytes, returned in place of the root"""
+        u, c_ = C.c_int(), C.c_int()
+        buf = C.create_string_buffer(32) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_registry_root(self._h, buf, C.byref(u), C.byref(c_)), "registry_root")
+        return (buf.raw if out is None else out), u.value, c_.value
+
+    def registry_prove_slots(self, slots, out=None):
+        """kosk_registry_prove_slots -> (states, hs, paths, root): occupancy, the stored fingerprint (zeros for an empty slot) and the
+        inclusion path (a bytes of depth x 32) per named slot, and the root they belong to.  out=(d_h, d_paths, d_root): int DEVICE
+        pointers (any of them None); (states, out) is returned"""
+        sp, n = self._slots(slots)
+        d = registry_tree_depth(self.registry_level()[1])
+        state = C.create_string_buffer(max(n, 1))
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_registry_prove_slots(self._h, n, sp, state, ptr[0], ptr[1], ptr[2]), "registry_prove_slots")
+            return list(state.raw[:n]), out
+        h = C.create_string_buffer(32 * max(n, 1)); paths = C.create_string_buffer(max(32 * max(d, 0) * n, 1)); root = C.create_string_buffer(32)
+        self._chk(lib.kosk_registry_prove_slots(self._h, n, sp, state, h, paths, root), "registry_prove_slots")
+        return list(state.raw[:n]), _cut(h, 32, n), [paths.raw[32 * d * b:32 * d * (b + 1)] for b in range(n)], root.raw
+
+    def registry_prove_peers(self, hs, n=None, out=None):
+        """kosk_registry_prove_peers -> (slots, paths, done, root): per fingerprint the lowest occupied slot that holds it (or -1), its
+        inclusion path (zeros for a miss) and whether it was found.  hs: a list of 32-byte strings or an int DEVICE pointer (with n);
+        out=(d_slots, d_paths, d_done, d_root): int DEVICE pointers (d_root may be None), returned as they are"""
+        hp, n, _k = self._records("fingerprint", hs, n, 32)
+        d = registry_tree_depth(self.registry_level()[1])
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_registry_prove_peers(self._h, n, hp, ptr[0], ptr[1], ptr[2], ptr[3]), "registry_prove_peers")
+            return out
+        slots = (C.c_int32 * max(n, 1))(); done = C.create_string_buffer(max(n, 1))
+        paths = C.create_string_buffer(max(32 * max(d, 0) * n, 1)); root = C.create_string_buffer(32)
+        self._chk(lib.kosk_registry_prove_peers(self._h, n, hp, slots, paths, done, root), "registry_prove_peers")
+        return list(slots[:n]), [paths.raw[32 * d * b:32 * d * (b + 1)] for b in range(n)], [bool(x) for x in done.raw[:n]], root.raw
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1379,6 +1478,9 @@ class Kosk:
     PATH_REGISTRY_INDEX = 29
     PATH_REGISTRY_FIND = 30
     PATH_KEM_ENC_PEERS = 31
+    PATH_REGISTRY_TREE = 32
+    PATH_REGISTRY_SUBTREES = 33
+    PATH_REGISTRY_PATH = 34
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

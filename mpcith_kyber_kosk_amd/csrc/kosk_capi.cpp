@@ -30,6 +30,7 @@
 #include "kosk_ctx.hpp"
 #include "kosk_lanes.hpp"
 #include "kosk_registry_resolve.hpp"
+#include "kosk_regtree.hpp"
 
 using namespace kosk;
 
@@ -1587,6 +1588,64 @@ int kosk_kem_enc_peers(kosk_ctx *ctx, int n, const uint8_t *h, const uint8_t *co
         return kem_enc_peers(c, count, h + (size_t)first * 32, m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32, done + first);
     });
     WGUARD_END
+}
+
+// ---- the registry tree, format kosk-regtree-v1 (kosk_regtree.hpp, kosk_registry.hip) ----
+static_assert((int)KOSK_REGTREE_TIER_LEVELS == (int)regtree::TIER_LEVELS, "kosk_mi355x.h and kosk_regtree.hpp");
+int kosk_registry_tree_depth(int capacity) { return regtree::depth(capacity); }
+size_t kosk_registry_tree_bytes(int capacity) { return regtree::tree_bytes(capacity); }
+int kosk_regtree_leaf(int kyber_k, const uint8_t *h, uint8_t out[32]) { return regtree::leaf(kyber_k, h, out); }
+int kosk_regtree_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]) { return regtree::node(l, r, out); }
+int kosk_regtree_root_from_path(int kyber_k, int depth, int32_t slot, const uint8_t *h, const uint8_t *path, uint8_t root[32])
+{
+    return regtree::root_from_path(kyber_k, depth, slot, h, path, root);
+}
+
+int kosk_registry_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *capacity)
+{
+    if (!ctx || !root) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_root", WHY_NO_REGISTRY);
+    if (registry_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    if (used) *used = ctx->c->registry->used;
+    if (capacity) *capacity = ctx->c->registry->capacity;
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_prove_slots(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h, uint8_t *paths, uint8_t *root)
+{
+    if (!ctx || n < 1 || !slots || !state) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = registry_slots_refusal(ctx, n, slots, false)) return refuse(ctx, "kosk_registry_prove_slots", why);
+    const KemRegistry &r = *ctx->c->registry;
+    const size_t rec = (size_t)regtree::depth(r.capacity) * 32;
+    if (rec && !paths) return bad_args(ctx, __func__);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return kem_registry_prove(c, count, slots + first, nullptr, h ? h + (size_t)first * 32 : nullptr, nullptr, nullptr, paths ? paths + (size_t)first * rec : nullptr);
+        })) return -1;
+    for (int b = 0; b < n; b++) state[b] = r.occ[(size_t)slots[b]];
+    if (root && registry_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_prove_peers(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *slots, uint8_t *paths, uint8_t *done, uint8_t *root)
+{
+    if (!ctx || n < 1 || !h || !slots || !done) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_prove_peers", WHY_NO_REGISTRY);
+    const size_t rec = (size_t)regtree::depth(ctx->c->registry->capacity) * 32;
+    if (rec && !paths) return bad_args(ctx, __func__);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return kem_registry_prove(c, count, nullptr, h + (size_t)first * 32, nullptr, slots + first, done + first, paths ? paths + (size_t)first * rec : nullptr);
+        })) return -1;
+    if (root && registry_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
 }
 
 // ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----

@@ -79,7 +79,7 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
               PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS,
-              PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_COUNT };
+              PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -672,6 +672,20 @@ struct KemRegistry {
     // index_valid
     int32_t *d_index = nullptr; // [registry_index_entries(capacity)] -1 = empty, else the lowest occupied slot of one fingerprint
     bool index_valid = false;
+    // the registry tree (kosk-regtree-v1): allocated at the first tree call, brought up to date by the first tree call after
+    // a mutation -- tier 0 over the leaf subtrees (1 024 slots each) that a mutation marked, every upper tier whole
+    uint8_t *d_tree = nullptr;   // [regtree::tree_bytes(capacity)] every node of every level, level-major
+    int32_t *d_dirty = nullptr;  // [regtree::subtrees(D)] the subtree numbers of one tier-0 launch: block i hashes subtree d_dirty[i]
+    uint8_t *d_paths = nullptr;  // [paths_cap] staging of k_registry_path's sibling records for one launch group
+    size_t paths_cap = 0;
+    bool tree_valid = false;
+    std::vector<uint8_t> dirty;  // [subtrees] 1 = a slot of the leaf subtree changed since the tree was current; empty while there is no tree
+    // a mutation wrote or zeroed `slot`
+    void tree_touch(size_t slot)
+    {
+        tree_valid = false;
+        if (!dirty.empty()) dirty[slot >> 10] = 1;
+    }
 };
 inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
 // One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
@@ -749,6 +763,39 @@ int kem_registry_probe(Ctx &c, int n, const uint8_t *pk, int resident_first, uin
 // crypto_kem_enc_derand for n <= KEM_CHUNK items, item b to the key whose H(pk) is h[b] (host or device memory): k_registry_find writes the
 // slot index and the mask in HBM, the per-item kernels follow; done (host or device memory) = found, ct and ss of a miss zero-filled
 int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
+
+// The registry tree (kosk_registry.hip, kosk_regtree.hpp).
+// k_registry_tree, one tier: block i reduces up to 1 024 inputs through up to 10 levels in LDS and writes every node to the tree.  Tier 0
+// forms the leaves from flag / h (positions >= capacity and empty slots are `empty`) and takes its subtree number from list[i]; an upper
+// tier reads level 10 tier of the tree and block i is subtree i
+enum { REGTREE_WAVE_TAIL = 8 }; // levels of this many nodes or fewer run one wave per node on the wave sponge
+struct RegTreeJob {
+    int tier, D, K, capacity, wave_tail;
+    const uint8_t *h, *flag;
+    const int32_t *list;
+    uint64_t empty[4]; // E as words
+    uint8_t *tree;
+};
+// k_registry_path: per item b the D sibling records of slot[b] (level l: node (slot >> l) ^ 1), zeros where slot[b] < 0, into paths[b][D][32];
+// hout (may be nullptr): the slot's stored fingerprint, zeros for slot < 0; found (may be nullptr): slot >= 0
+struct RegPathJob {
+    int n, D;
+    const int32_t *slot;
+    const uint8_t *tree, *h;
+    uint8_t *paths, *hout, *found;
+};
+hipError_t launch_registry_tree(const RegTreeJob &j, unsigned blocks, hipStream_t st);
+hipError_t launch_registry_path(const RegPathJob &j, hipStream_t st);
+// the tree allocated and current: a no-op while tree_valid; else the tiers, synchronised
+int registry_tree_ensure(Ctx &c);
+// r.d_paths holds n items' paths
+int registry_paths_ensure(Ctx &c, int n);
+// the root of the current tree to `root` (host or device memory); synchronised
+int registry_root(Ctx &c, uint8_t *root);
+// n <= KEM_CHUNK paths.  slots != nullptr (host; valid ids): of those slots, with their stored fingerprints to hout (or nullptr); else of the
+// lowest occupied slots that hold the fingerprints h (k_registry_find in front), with those slots to slots_out and found to done.  paths (may
+// be nullptr when D = 0), hout, slots_out, done: host or device memory.  Synchronised; what was staged in the KEM workspace is zeroed
+int kem_registry_prove(Ctx &c, int n, const int32_t *slots, const uint8_t *h, uint8_t *hout, int32_t *slots_out, uint8_t *done, uint8_t *paths);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches

@@ -42,6 +42,7 @@
 #include "kosk_ctx.hpp"
 #include "kosk_keccak_wave_dev.hpp"
 #include "kosk_kem_dev.hpp"
+#include "kosk_regtree.hpp"
 
 namespace kosk {
 
@@ -761,6 +762,10 @@ int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, con
     const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
     r.index_valid = false; // the next lookup rebuilds the fingerprint index
+    r.tree_valid = false;  // and the next tree call the leaf subtrees of these slots (a registry without a tree has no bitmap: nothing to walk)
+    if (uint8_t *dirty = r.dirty.empty() ? nullptr : r.dirty.data())
+        for (int b = 0; b < n; b++)
+            if (slots[b] >= 0) dirty[slots[b] >> regtree::TIER_LEVELS] = 1;
     RegAdmitJob j{};
     j.n = n; j.K = D.K; j.pk_bytes = D.pk; j.wave = n <= kem_wave_max();
     if (pk) { // the records through the workspace: 16-byte aligned whatever the caller's pointer is
@@ -879,6 +884,47 @@ int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t
     k.key = w.d_key;
     if (kem_enc_body(c, n, k, coins, ct, ss, w.d_mask, PATH_KEM_ENC_PEERS)) return -1;
     return device_error_check(c); // index overflow
+}
+
+// ---- the registry tree (kosk_registry.hip) ------------------------------------------------------------------
+// the slot numbers in w.d_key (copied in, or left there by k_registry_find), k_registry_path into the registry's staging, the copies out
+int kem_registry_prove(Ctx &c, int n, const int32_t *slots, const uint8_t *h, uint8_t *hout, int32_t *slots_out, uint8_t *done, uint8_t *paths)
+{
+    if (n < 1 || n > KEM_CHUNK || (!slots && (!h || !slots_out || !done)) || !c.registry) { c.err = "kem_registry_prove: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    if (!slots && registry_index_ensure(c)) return -1;
+    if (registry_tree_ensure(c)) return -1;
+    if (registry_paths_ensure(c, n)) return -1;
+    KemWs &w = *c.kem;
+    const KemRegistry &r = *c.registry;
+    const int D = regtree::depth(r.capacity);
+    if (D > 0 && !paths) { c.err = "kem_registry_prove: bad arguments"; return -1; }
+    HIPCHK(hipSetDevice(c.device));
+    RegPathJob j{};
+    j.n = n; j.D = D; j.slot = w.d_key; j.tree = r.d_tree; j.h = r.d_h; j.paths = r.d_paths;
+    if (slots) {
+        HIPCHK(hipMemcpyAsync(w.d_key, slots, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+        if (hout) j.hout = w.d_h;
+    } else {
+        HIPCHK(kem_copy_in(c, w.d_h, h, (size_t)n * 32));
+        if (kem_launch_find(c, n, w.d_key, false)) return -1;
+        HIPCHK(hipMemsetAsync(w.d_h, 0, (size_t)n * 32, c.stream)); // the staged fingerprints go, as in kem_registry_find
+        j.found = w.d_mask;
+    }
+    HIPCHK(launch_registry_path(j, c.stream));
+    c.path_n[PATH_REGISTRY_PATH]++;
+    if (D > 0) HIPCHK(kem_copy_out(c, paths, r.d_paths, (size_t)n * D * 32));
+    if (slots) {
+        if (hout) {
+            HIPCHK(kem_copy_out(c, hout, w.d_h, (size_t)n * 32));
+            HIPCHK(hipMemsetAsync(w.d_h, 0, (size_t)n * 32, c.stream));
+        }
+    } else {
+        HIPCHK(kem_copy_out(c, slots_out, w.d_key, (size_t)n * sizeof(int32_t)));
+        HIPCHK(kem_copy_out(c, done, w.d_mask, (size_t)n));
+    }
+    HIPCHK(stream_sync(c));
+    return slots ? 0 : device_error_check(c); // index overflow
 }
 
 } // namespace kosk

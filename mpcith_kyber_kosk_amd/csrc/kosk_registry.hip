@@ -11,12 +11,19 @@
 //   eviction    k_wipe             the slots' four pieces are regions of a wipe
 //   index       k_registry_index   one lane per slot: open addressing over the slots' H(pk), rebuilt whole by the first lookup after a mutation
 //   lookup      k_registry_find    one lane per query: the slot (or -1), or the slot index and mask the per-item KEM kernels read
+//   tree        k_registry_tree    one block per 1 024 inputs of a tier: up to 10 levels of kosk-regtree-v1 through LDS, every node to HBM
+//   paths       k_registry_path    one lane per 16-byte half of a sibling record
 // slot[b] and the accept bit (slot[b] < 0: masked, nothing is written) are public; the admission reads nothing secret.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
 
 #include "kosk_ctx.hpp"
 #include "kosk_keccak_wave_dev.hpp"
 #include "kosk_kem_dev.hpp"
+#include "kosk_regtree.hpp"
 
 namespace kosk {
 
@@ -157,7 +164,221 @@ hipError_t launch_registry_find(const RegFindJob &j, hipStream_t st)
     return hipGetLastError();
 }
 
+// ---- the registry tree (kosk-regtree-v1, kosk_regtree.hpp) -------------------------------------------------
+// Every hash is ONE permutation: the inputs are 20, 52 and 80 bytes of a 136-byte rate block, so a lane builds the padded block in its state
+// and permutes once (the one-state-per-lane Keccak of kosk_keccak_dev.hpp).  Fingerprints, flags and slot numbers are public.
+__device__ __forceinline__ void regtree_store(uint8_t *dst, const uint64_t (&d)[4])
+{
+    U128 *o = reinterpret_cast<U128 *>(dst);
+    o[0] = U128{(uint32_t)d[0], (uint32_t)(d[0] >> 32), (uint32_t)d[1], (uint32_t)(d[1] >> 32)};
+    o[1] = U128{(uint32_t)d[2], (uint32_t)(d[2] >> 32), (uint32_t)d[3], (uint32_t)(d[3] >> 32)};
+}
+__device__ __forceinline__ void regtree_load(const uint8_t *src, uint64_t (&d)[4])
+{
+    const U128 a = reinterpret_cast<const U128 *>(src)[0], b = reinterpret_cast<const U128 *>(src)[1];
+    d[0] = (uint64_t)a.x | (uint64_t)a.y << 32; d[1] = (uint64_t)a.z | (uint64_t)a.w << 32;
+    d[2] = (uint64_t)b.x | (uint64_t)b.y << 32; d[3] = (uint64_t)b.z | (uint64_t)b.w << 32;
+}
+
+// One block, one subtree of a tier: `cnt` <= 1 024 inputs, then `up` <= 10 levels, level by level through LDS (two buffers, 32 KB + 16 KB,
+// a barrier between levels); every node also goes to its place in the level-major tree.  Block q of an upper tier owns nodes
+// [q (1024 >> lv), (q + 1) (1024 >> lv)) of level 10 tier + lv.  All loop bounds are block-uniform.
+__global__ __launch_bounds__(256) void k_registry_tree(RegTreeJob j)
+{
+    __shared__ __align__(16) uint64_t lds[(regtree::TIER_INPUTS + regtree::TIER_INPUTS / 2) * 4];
+    const int tid = threadIdx.x, L0 = j.tier * regtree::TIER_LEVELS;
+    const size_t q = j.tier ? (size_t)blockIdx.x : (size_t)j.list[blockIdx.x];
+    const int cnt = j.D - L0 >= regtree::TIER_LEVELS ? (int)regtree::TIER_INPUTS : 1 << (j.D - L0);
+    const int up = j.D - L0 >= regtree::TIER_LEVELS ? (int)regtree::TIER_LEVELS : j.D - L0;
+    uint8_t *in_lvl = j.tree + regtree::level_offset(j.D, L0) + q * regtree::TIER_INPUTS * 32;
+    for (int i = tid; i < cnt; i += 256) {
+        uint64_t d[4];
+        if (j.tier) {
+            regtree_load(in_lvl + (size_t)i * 32, d);
+        } else {
+            const size_t s = q * regtree::TIER_INPUTS + (size_t)i;
+            if (s < (size_t)j.capacity && j.flag[s]) {
+                uint64_t h[4], st[25];
+                regtree_load(j.h + s * 32, h);
+                regtree::leaf_state(st, j.K, h);
+                perm(st);
+#pragma unroll
+                for (int l = 0; l < 4; l++) d[l] = st[l];
+            } else {
+#pragma unroll
+                for (int l = 0; l < 4; l++) d[l] = j.empty[l];
+            }
+            regtree_store(in_lvl + (size_t)i * 32, d);
+        }
+#pragma unroll
+        for (int l = 0; l < 4; l++) lds[4 * i + l] = d[l];
+    }
+    __syncthreads();
+    int in = 0, out = regtree::TIER_INPUTS * 4; // word offsets of the two buffers
+    int lv = 1;
+    for (; lv <= up && (cnt >> lv) > j.wave_tail; lv++) { // one sponge per lane
+        const int m = cnt >> lv;
+        uint8_t *dst = j.tree + regtree::level_offset(j.D, L0 + lv) + q * (size_t)(regtree::TIER_INPUTS >> lv) * 32;
+        for (int i = tid; i < m; i += 256) {
+            uint64_t l[4], r[4], st[25];
+#pragma unroll
+            for (int w = 0; w < 4; w++) { l[w] = lds[in + 8 * i + w]; r[w] = lds[in + 8 * i + 4 + w]; }
+            regtree::node_state(st, l, r);
+            perm(st);
+#pragma unroll
+            for (int w = 0; w < 4; w++) { l[w] = st[w]; lds[out + 4 * i + w] = st[w]; }
+            regtree_store(dst + (size_t)i * 32, l);
+        }
+        __syncthreads();
+        const int t = in; in = out; out = t;
+    }
+    if (lv > up) return;
+    // the last levels, wave_tail nodes or fewer: a chain of single permutations that would run on a nearly empty wave -- one WAVE per node on
+    // the wave sponge instead, the block's four waves side by side (DESIGN.md 37 has the measurement that chose wave_tail)
+    __shared__ __align__(16) uint32_t wst[4][64];
+    const int wave = tid >> 6, lane = tid & 63;
+    WaveSponge sp;
+    sp.setup(lane);
+    for (; lv <= up; lv++) {
+        const int m = cnt >> lv;
+        uint8_t *dst = j.tree + regtree::level_offset(j.D, L0 + lv) + q * (size_t)(regtree::TIER_INPUTS >> lv) * 32;
+        for (int i = wave; i < m; i += 4) { // wave-uniform
+            const uint64_t *src = lds + in + 8 * i;
+            uint32_t a = 0;
+            wave_absorb_words(sp, a, [&](int w) {
+                const uint64_t v = w == 0 ? regtree::TAG0 : w == 1 ? (regtree::TAG1 | 2ULL << 56) : src[w - 2];
+                return make_uint2((uint32_t)v, (uint32_t)(v >> 32));
+            }, 10, 0x06u);
+            const uint2 d = sp.words(a, wst[wave], 4);
+            if (lane < 4) {
+                lds[out + 4 * i + lane] = (uint64_t)d.x | (uint64_t)d.y << 32;
+                *reinterpret_cast<uint2 *>(dst + (size_t)i * 32 + 8 * lane) = d;
+            }
+        }
+        __syncthreads();
+        const int t = in; in = out; out = t;
+    }
+}
+
+// One lane per 16-byte half of a record; records 0 .. D - 1 of an item are its path, record D carries the slot's fingerprint and the found bit
+__global__ __launch_bounds__(256) void k_registry_path(RegPathJob j)
+{
+    const long gid = (long)blockIdx.x * 256 + threadIdx.x;
+    const int per = 2 * (j.D + 1);
+    if (gid >= (long)per * j.n) return;
+    const long b = gid / per;
+    const int r = (int)(gid - b * per), l = r >> 1, half = r & 1;
+    const int32_t s = j.slot[b];
+    U128 v{0, 0, 0, 0};
+    if (l < j.D) {
+        if (s >= 0) v = reinterpret_cast<const U128 *>(j.tree + regtree::level_offset(j.D, l) + (((size_t)s >> l) ^ 1) * 32)[half];
+        reinterpret_cast<U128 *>(j.paths)[((size_t)b * j.D + l) * 2 + half] = v;
+        return;
+    }
+    if (j.hout) {
+        if (s >= 0) v = reinterpret_cast<const U128 *>(j.h + (size_t)s * 32)[half];
+        reinterpret_cast<U128 *>(j.hout)[(size_t)b * 2 + half] = v;
+    }
+    if (j.found && !half) j.found[b] = s >= 0;
+}
+
+hipError_t launch_registry_tree(const RegTreeJob &j, unsigned blocks, hipStream_t st)
+{
+    k_registry_tree<<<dim3(blocks), dim3(256), 0, st>>>(j);
+    return hipGetLastError();
+}
+
+hipError_t launch_registry_path(const RegPathJob &j, hipStream_t st)
+{
+    const long lanes = 2L * (j.D + 1) * j.n;
+    k_registry_path<<<dim3((unsigned)((lanes + 255) / 256)), dim3(256), 0, st>>>(j);
+    return hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host --
+// KOSK_DEBUG_REGTREE_WAVE_TAIL=m moves the boundary between the two sponge layouts of k_registry_tree: levels of m nodes or fewer run on the
+// wave sponge (0: none); read at every rebuild, so a measurement can alternate the settings in one process
+static int regtree_wave_tail()
+{
+    const char *e = getenv("KOSK_DEBUG_REGTREE_WAVE_TAIL");
+    const int v = e ? atoi(e) : (int)REGTREE_WAVE_TAIL;
+    return v < 0 ? 0 : v > 64 ? 64 : v;
+}
+
+int registry_tree_ensure(Ctx &c)
+{
+    KemRegistry &r = *c.registry;
+    if (r.tree_valid) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    const int D = regtree::depth(r.capacity), S = regtree::subtrees(D), T = regtree::tiers(D);
+    if (!r.d_tree) { // public, both: hashes of public fingerprints, subtree numbers
+        const int G = Inventory::INVG_REGISTRY;
+        HIPCHK(c.own("registry.d_dirty", &r.d_dirty, (size_t)S * sizeof(int32_t), 0, G));
+        if (c.own("registry.d_tree", &r.d_tree, regtree::tree_bytes(r.capacity), 0, G) != hipSuccess) { // both or neither
+            void **at = reinterpret_cast<void **>(&r.d_dirty);
+            c.inv.release_if([at](const InvBuf &b) { return b.at == at; });
+            (void)hipGetLastError();
+            c.err = "registry_tree_ensure: out of memory for the tree";
+            return -1;
+        }
+        r.dirty.assign((size_t)S, 1); // the first build hashes every leaf subtree
+    }
+    std::vector<int32_t> list;
+    for (int q = 0; q < S; q++)
+        if (r.dirty[(size_t)q]) list.push_back(q);
+    RegTreeJob j{};
+    j.D = D; j.K = c.P.K; j.capacity = r.capacity; j.h = r.d_h; j.flag = r.d_flag; j.list = r.d_dirty; j.tree = r.d_tree;
+    j.wave_tail = regtree_wave_tail();
+    uint8_t e[32];
+    (void)regtree::leaf(c.P.K, nullptr, e);
+    memcpy(j.empty, e, 32);
+    if (!list.empty()) {
+        HIPCHK(hipMemcpyAsync(r.d_dirty, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
+        HIPCHK(launch_registry_tree(j, (unsigned)list.size(), c.stream));
+        c.path_n[PATH_REGISTRY_TREE]++;
+        c.path_n[PATH_REGISTRY_SUBTREES] += (long)list.size();
+        for (int t = 1; t < T; t++) { // the upper tiers whole: at most P / 1024 + ... nodes
+            j.tier = t;
+            const int above = D - t * regtree::TIER_LEVELS;
+            HIPCHK(launch_registry_tree(j, above > regtree::TIER_LEVELS ? 1u << (above - regtree::TIER_LEVELS) : 1u, c.stream));
+            c.path_n[PATH_REGISTRY_TREE]++;
+        }
+        // paths staged from the earlier tree state go with it: after an eviction and this rebuild no hash of the evicted key is left
+        if (r.d_paths) HIPCHK(hipMemsetAsync(r.d_paths, 0, r.paths_cap, c.stream));
+        HIPCHK(stream_sync(c));
+        std::fill(r.dirty.begin(), r.dirty.end(), 0);
+    }
+    r.tree_valid = true;
+    return 0;
+}
+
+int registry_paths_ensure(Ctx &c, int n)
+{
+    KemRegistry &r = *c.registry;
+    const size_t need = (size_t)((n + 1023) / 1024 * 1024) * regtree::depth(r.capacity) * 32;
+    if (need <= r.paths_cap) return 0;
+    HIPCHK(hipSetDevice(c.device));
+    if (r.d_paths) {
+        HIPCHK(stream_sync(c));
+        void **at = reinterpret_cast<void **>(&r.d_paths);
+        c.inv.release_if([at](const InvBuf &b) { return b.at == at; });
+        r.paths_cap = 0;
+    }
+    HIPCHK(c.own("registry.d_paths", &r.d_paths, need, 0, Inventory::INVG_REGISTRY)); // public: copies of tree nodes
+    r.paths_cap = need;
+    return 0;
+}
+
+int registry_root(Ctx &c, uint8_t *root)
+{
+    if (registry_tree_ensure(c)) return -1;
+    const KemRegistry &r = *c.registry;
+    const int D = regtree::depth(r.capacity);
+    HIPCHK(hipMemcpyAsync(root, r.d_tree + regtree::level_offset(D, D), 32, is_device_pointer(root) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
+    HIPCHK(stream_sync(c));
+    return 0;
+}
+
 int registry_index_ensure(Ctx &c)
 {
     KemRegistry &r = *c.registry;
@@ -235,6 +456,7 @@ int registry_evict(Ctx &c, int n, const int32_t *slots)
     for (int b = 0; b < n; b++) {
         const size_t s = (size_t)slots[b];
         if (!r.occ[s]) continue; // empty already (or named twice)
+        r.tree_touch(s);
         r.occ[s] = 0;
         r.used--;
         dev.push_back(WipeRegion{r.d_pk + s * D.pk, (size_t)D.pk, 0, 1});
