@@ -490,7 +490,7 @@ int kosk_kem_enc_peers(kosk_ctx *ctx, int n, const uint8_t *h, const uint8_t *co
  * bytes, level 0 first, record l = node (s >> l) ^ 1 of level l; walking up from the leaf, step l computes N(path[l], cur) if bit l of s is
  * set, else N(cur, path[l]).  The root binds neither capacity nor the occupied count: kosk_registry_root returns them beside it for a signed
  * tree head.  Equal keys in several slots (kosk_registry_admit) give equal leaves; lookup by fingerprint names the lowest slot.  Proofs of
- * ABSENCE of a fingerprint would need a sorted tree and are out of scope.
+ * ABSENCE of a fingerprint come from the sorted tree, kosk-regsort-v1, below.
  * Host functions: kosk_registry_tree_bytes = (2P - 1) * 32, the HBM the tree takes (0 for capacity < 1).  kosk_regtree_leaf (h == NULL: E)
  * and kosk_regtree_node: -1 for kyber_k outside 2..4 or a NULL argument.  kosk_regtree_root_from_path: the root that (slot, h or NULL for
  * "empty", path[depth][32]) implies -- the caller compares it with the published root; -1: bad k, depth outside 0..31, slot outside
@@ -525,6 +525,57 @@ int kosk_regtree_root_from_path(int kyber_k, int depth, int32_t slot, const uint
 int kosk_registry_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *capacity);
 int kosk_registry_prove_slots(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h, uint8_t *paths, uint8_t *root);
 int kosk_registry_prove_peers(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *slots, uint8_t *paths, uint8_t *done, uint8_t *root);
+
+/* ---- The sorted tree, format kosk-regsort-v1 (INTEGRATION.md 8.6 is the normative text): a second Merkle tree over the registry, its leaves
+ * the occupied slots' (fingerprint, slot) pairs in ascending order.  Two adjacent leaves that straddle a fingerprint prove that it is NOT
+ * enrolled; anyone checks such a proof with kosk_regsort_check_proof, on the host, without a handle.
+ * TAG = the 15 ASCII bytes "kosk-regsort-v1"; every hash is SHA3-256 of one rate block:
+ *   key leaf       S(h, slot) = SHA3-256(TAG || 00 || h[32] || LE32(slot) || LE32(kyber_k))
+ *   padding leaf   Z          = SHA3-256(TAG || 01 || LE32(kyber_k))
+ *   inner node     N(l, r)    = SHA3-256(TAG || 02 || l[32] || r[32])
+ * One entry (h, slot) per occupied slot, m = used of them (equal keys in several slots give several entries), ascending by h as 32 bytes in
+ * memcmp order, then by slot: the order is total and the sequence unique.  D = kosk_registry_tree_depth(capacity), P = 2^D; position i < m
+ * holds S of the i-th entry, positions m .. P - 1 hold Z; levels, paths (record l of position p = node (p >> l) ^ 1 of level l) and the walk
+ * are those of the slot tree with this section's N.
+ * Rank of a query x: lb = the number of entries with h < x.  x is PRESENT iff lb < m and entry lb has h == x (the lowest slot that holds x,
+ * the rule of kosk_registry_find), else ABSENT.  The left neighbour is position lb - 1 (exists iff lb >= 1), the right neighbour position
+ * lb (exists iff lb < P; a key leaf iff lb < m, else Z).
+ * The proof record, kosk_regsort_proof_bytes(D) = 16 + 64 + 64 D bytes (0 for D outside 0..31), integers LE32:
+ *    0 pos_l (-1: no left record)   4 slot_l   8 slot_r (0 if Z or none)
+ *   12 flags: bit0 left record present, bit1 right record present, bit2 right is a key leaf, bit3 PRESENT
+ *   16 h_l[32]   48 h_r[32]   80 path_l[D][32]   80 + 32 D path_r[D][32]        (unused parts are zero)
+ * PRESENT: bits 0 and 3, h_l == x, pos_l = lb, the right half zero.
+ * kosk_regsort_check_proof: 2 = PRESENT (h_l == x, 0 <= pos_l < P, the left walk gives root); 1 = ABSENT (bit3 clear, at least one record;
+ * with a left record 0 <= pos_l < P, h_l < x and its walk gives root, without one pos_l == -1; with a right record pos_l + 1 < P and at
+ * position pos_l + 1 either bit2, x < h_r and the walk of S(h_r, slot_r) gives root, or no bit2 and the walk of Z gives root, without one
+ * pos_l == P - 1); 0 = the record proves neither (any other flag pattern, bits above bit3); -1 = bad kyber_k, depth outside 0..31, a NULL
+ * argument.  The root binds the sorted sequence of (fingerprint, slot) pairs; an ABSENT verdict is sound against a registrar whose tree is
+ * well formed (sorted, padding at the end), which one record cannot show: an auditor who holds the table recomputes the root (one host sort
+ * and 2P hashes).  A signed head carries both roots, used and capacity.
+ * kosk_regsort_leaf (h == NULL: Z), kosk_regsort_node, kosk_regsort_root_from_path (pos, h or NULL for Z, slot, path[depth][32]): -1 as
+ * their kosk_regtree_* counterparts, and for a key leaf with slot < 0.  Pointers of any alignment.
+ * On a handle: the sorted records, the tree and (from the first proving call on) four staging buffers are public allocations of the
+ * registry, made by the first call below and freed with it; a registry that never asks allocates and launches what it did before.  Every
+ * admit / evict / enrol marks the sorted tree stale, and the first call below after a mutation rebuilds it whole: a bitonic sort of P
+ * 16-byte records (k_regsort_keys, k_regsort_tile: tiles of 2 048 in LDS, k_regsort_step above the tile), then the tiers (k_regsort_tree).
+ * kosk_registry_sorted_root: root = 32 bytes of host or device memory; used / capacity may be NULL.
+ * kosk_registry_prove_absent: h = n x 32 query fingerprints; kind[b] = 1 (ABSENT) or 2 (PRESENT); records = n x proof_bytes(D); root: NULL,
+ * or the root the records belong to.  Every query gets a valid record of one kind or the other.  Every pointer may be host or device memory
+ * of any alignment.  Any n >= 1 in launch groups of 16384, unmerged on the handle's own stream, also on a cohort member.  Refusals, the
+ * thread rule and the erasure rule are those of the slot tree: -1 for NULL required arguments, n < 1, no registry reserved; the buffers are
+ * public entries of the inventory; the staged queries are zeroed before the call returns.  After an eviction the sorted records keep the
+ * evicted key's 8-byte prefix and slot until the next call here rebuilds them.
+ * kosk_regsort_order_device: a kernel-level entry point that needs no registry and runs exactly the sort kernels of the rebuild: n records of
+ * 32 bytes (d_h, 8-byte aligned) and n flag bytes in DEVICE memory give d_order[i] = the index of the i-th entry in order for i < m (the
+ * number of non-zero flags), -1 from m on.  -1: NULL arguments, n < 1, n > 2^24, a misaligned pointer. */
+size_t kosk_regsort_proof_bytes(int depth);
+int kosk_regsort_leaf(int kyber_k, const uint8_t *h, int32_t slot, uint8_t out[32]);
+int kosk_regsort_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]);
+int kosk_regsort_root_from_path(int kyber_k, int depth, int32_t pos, const uint8_t *h, int32_t slot, const uint8_t *path, uint8_t root[32]);
+int kosk_regsort_check_proof(int kyber_k, int depth, const uint8_t x[32], const uint8_t *record, const uint8_t root[32]);
+int kosk_registry_sorted_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *capacity);
+int kosk_registry_prove_absent(kosk_ctx *ctx, int n, const uint8_t *h, uint8_t *kind, uint8_t *records, uint8_t *root);
+int kosk_regsort_order_device(kosk_ctx *ctx, int n, const uint8_t *d_h, const uint8_t *d_flag, int32_t *d_order);
 
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
@@ -656,7 +707,10 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 30 launches of k_registry_find (one per launch group of kosk_registry_find, kosk_registry_enrol* and kosk_kem_enc_peers),
  * 31 kem_enc_peers: launch groups of kosk_kem_enc_peers (ids 12 / 20 / 28 do not move for it),
  * 32 launches of k_registry_tree (one per tier of a rebuild) / 33 leaf subtrees hashed by those launches,
- * 34 launches of k_registry_path (one per launch group of kosk_registry_prove_slots / kosk_registry_prove_peers). */
+ * 34 launches of k_registry_path (one per launch group of kosk_registry_prove_slots / kosk_registry_prove_peers),
+ * 35 launches of the sort kernels k_regsort_keys / k_regsort_tile / k_regsort_step (a rebuild of the sorted tree, or kosk_regsort_order_device),
+ * 36 launches of k_regsort_tree (one per tier of a rebuild of the sorted tree; ids 27..34 do not move for any call of that section),
+ * 37 launches of k_regsort_prove (one per launch group of kosk_registry_prove_absent). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

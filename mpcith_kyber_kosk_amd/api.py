@@ -270,6 +270,19 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_root")):
         sig.update(tree)
+    # the sorted tree, kosk-regsort-v1; optional under the same rule (and only then)
+    sorted_tree = {
+        "kosk_regsort_proof_bytes": (sz, [C.c_int]),
+        "kosk_regsort_leaf": (C.c_int, [C.c_int, vp, C.c_int32, vp]),
+        "kosk_regsort_node": (C.c_int, [vp, vp, vp]),
+        "kosk_regsort_root_from_path": (C.c_int, [C.c_int, C.c_int, C.c_int32, vp, C.c_int32, vp, vp]),
+        "kosk_regsort_check_proof": (C.c_int, [C.c_int, C.c_int, vp, vp, vp]),
+        "kosk_registry_sorted_root": (C.c_int, [vp, vp, ip, ip]),
+        "kosk_registry_prove_absent": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "kosk_regsort_order_device": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_sorted_root")):
+        sig.update(sorted_tree)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -315,7 +328,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_registry_index_entries", "kosk_registry_index_home", "kosk_registry_find", "kosk_registry_enrol_verified",
            "kosk_registry_enrol", "kosk_kem_enc_peers",
            "kosk_registry_tree_depth", "kosk_registry_tree_bytes", "kosk_regtree_leaf", "kosk_regtree_node", "kosk_regtree_root_from_path",
-           "kosk_registry_root", "kosk_registry_prove_slots", "kosk_registry_prove_peers"]
+           "kosk_registry_root", "kosk_registry_prove_slots", "kosk_registry_prove_peers",
+           "kosk_regsort_proof_bytes", "kosk_regsort_leaf", "kosk_regsort_node", "kosk_regsort_root_from_path", "kosk_regsort_check_proof",
+           "kosk_registry_sorted_root", "kosk_registry_prove_absent", "kosk_regsort_order_device"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -416,6 +431,55 @@ def regtree_root_from_path(k, depth, slot, h, path):
                                        C.c_char_p(path) if depth else None, out):
         raise KoskError("regtree_root_from_path: bad kyber_k, depth or slot")
     return out.raw
+
+
+# the sorted tree, kosk-regsort-v1: the host functions, no handle and no GPU
+REGSORT_NEITHER, REGSORT_ABSENT, REGSORT_PRESENT = 0, 1, 2  # kosk_regsort_check_proof
+
+
+def regsort_proof_bytes(depth): return lib.kosk_regsort_proof_bytes(depth)
+
+
+def regsort_leaf(k, h=None, slot=0):
+    """kosk_regsort_leaf: the key leaf S(h, slot), or (h None) the padding leaf Z"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_regsort_leaf(k, None if h is None else C.c_char_p(_digest("a fingerprint", h)), slot, out):
+        raise KoskError("regsort_leaf: kyber_k outside 2..4, or a key leaf with slot < 0")
+    return out.raw
+
+
+def regsort_node(left, right):
+    """kosk_regsort_node: the inner node over two 32-byte children"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_regsort_node(C.c_char_p(_digest("a node", left)), C.c_char_p(_digest("a node", right)), out):
+        raise KoskError("regsort_node failed")
+    return out.raw
+
+
+def regsort_root_from_path(k, depth, pos, h, slot, path):
+    """kosk_regsort_root_from_path: the root that position pos, its entry (h, slot) (h None: padding) and path (depth x 32 bytes, or a list
+    of depth 32-byte records) imply"""
+    if not isinstance(path, (bytes, bytearray)):
+        path = b"".join(path)
+    path = bytes(path)
+    if depth < 0 or len(path) != 32 * depth:
+        raise KoskError("a path of depth %d has %d bytes" % (depth, 32 * max(depth, 0)))
+    out = C.create_string_buffer(32)
+    if lib.kosk_regsort_root_from_path(k, depth, pos, None if h is None else C.c_char_p(_digest("a fingerprint", h)), slot,
+                                       C.c_char_p(path) if depth else None, out):
+        raise KoskError("regsort_root_from_path: bad kyber_k, depth, position or slot")
+    return out.raw
+
+
+def regsort_check_proof(k, depth, x, record, root):
+    """kosk_regsort_check_proof: what record proves about fingerprint x under root -- REGSORT_PRESENT, REGSORT_ABSENT or REGSORT_NEITHER"""
+    record = bytes(record)
+    if depth < 0 or depth > 31 or len(record) != regsort_proof_bytes(depth):
+        raise KoskError("a proof record of depth %d has %d bytes" % (depth, regsort_proof_bytes(depth) if 0 <= depth <= 31 else 0))
+    rc = lib.kosk_regsort_check_proof(k, depth, C.c_char_p(_digest("a fingerprint", x)), C.c_char_p(record), C.c_char_p(_digest("a root", root)))
+    if rc < 0:
+        raise KoskError("regsort_check_proof: bad kyber_k or depth")
+    return rc
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1330,6 +1394,34 @@ class Kosk:
         self._chk(lib.kosk_registry_prove_peers(self._h, n, hp, slots, paths, done, root), "registry_prove_peers")
         return list(slots[:n]), [paths.raw[32 * d * b:32 * d * (b + 1)] for b in range(n)], [bool(x) for x in done.raw[:n]], root.raw
 
+    # the sorted tree, kosk-regsort-v1
+    def registry_sorted_root(self, out=None):
+        """kosk_registry_sorted_root -> (root, used, capacity); out: an int DEVICE pointer to 32 bytes, returned in place of the root"""
+        u, c_ = C.c_int(), C.c_int()
+        buf = C.create_string_buffer(32) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_registry_sorted_root(self._h, buf, C.byref(u), C.byref(c_)), "registry_sorted_root")
+        return (buf.raw if out is None else out), u.value, c_.value
+
+    def registry_prove_absent(self, hs, n=None, out=None):
+        """kosk_registry_prove_absent -> (kinds, records, root): per fingerprint REGSORT_ABSENT or REGSORT_PRESENT and the proof record
+        (kosk_regsort_check_proof reads it).  hs: a list of 32-byte strings or an int DEVICE pointer (with n); out=(d_kind, d_records,
+        d_root): int DEVICE pointers (d_root may be None), returned as they are"""
+        hp, n, _k = self._records("fingerprint", hs, n, 32)
+        rec = regsort_proof_bytes(registry_tree_depth(self.registry_level()[1]))
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_registry_prove_absent(self._h, n, hp, ptr[0], ptr[1], ptr[2]), "registry_prove_absent")
+            return out
+        kind = C.create_string_buffer(max(n, 1)); records = C.create_string_buffer(max(rec * n, 1)); root = C.create_string_buffer(32)
+        self._chk(lib.kosk_registry_prove_absent(self._h, n, hp, kind, records, root), "registry_prove_absent")
+        return list(kind.raw[:n]), [records.raw[rec * b:rec * (b + 1)] for b in range(n)], root.raw
+
+    def regsort_order(self, n, d_h, d_flag, d_order):
+        """kosk_regsort_order_device: the sort kernels alone on n caller-made fingerprints (d_h, n x 32 bytes) and flags (d_flag, n bytes) in
+        DEVICE memory; d_order (n int32, DEVICE memory) = the index of the i-th entry in (fingerprint, index) order, -1 behind the entries"""
+        self._chk(lib.kosk_regsort_order_device(self._h, n, C.c_void_p(int(d_h)), C.c_void_p(int(d_flag)), C.c_void_p(int(d_order))), "regsort_order")
+        return d_order
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1481,6 +1573,9 @@ class Kosk:
     PATH_REGISTRY_TREE = 32
     PATH_REGISTRY_SUBTREES = 33
     PATH_REGISTRY_PATH = 34
+    PATH_REGSORT_SORT = 35
+    PATH_REGSORT_TREE = 36
+    PATH_REGSORT_PROVE = 37
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

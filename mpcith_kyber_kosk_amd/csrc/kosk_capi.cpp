@@ -30,6 +30,7 @@
 #include "kosk_ctx.hpp"
 #include "kosk_lanes.hpp"
 #include "kosk_registry_resolve.hpp"
+#include "kosk_regsort.hpp"
 #include "kosk_regtree.hpp"
 
 using namespace kosk;
@@ -1644,6 +1645,57 @@ int kosk_registry_prove_peers(kosk_ctx *ctx, int n, const uint8_t *h, int32_t *s
             return kem_registry_prove(c, count, nullptr, h + (size_t)first * 32, nullptr, slots + first, done + first, paths ? paths + (size_t)first * rec : nullptr);
         })) return -1;
     if (root && registry_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+// ---- the sorted tree, format kosk-regsort-v1 (kosk_regsort.hpp, kosk_regsort.hip) ----
+size_t kosk_regsort_proof_bytes(int depth) { return regsort::proof_bytes(depth); }
+int kosk_regsort_leaf(int kyber_k, const uint8_t *h, int32_t slot, uint8_t out[32]) { return regsort::leaf(kyber_k, h, slot, out); }
+int kosk_regsort_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]) { return regsort::node(l, r, out); }
+int kosk_regsort_root_from_path(int kyber_k, int depth, int32_t pos, const uint8_t *h, int32_t slot, const uint8_t *path, uint8_t root[32])
+{
+    return regsort::root_from_path(kyber_k, depth, pos, h, slot, path, root);
+}
+int kosk_regsort_check_proof(int kyber_k, int depth, const uint8_t x[32], const uint8_t *record, const uint8_t root[32])
+{
+    return regsort::check_proof(kyber_k, depth, x, record, root);
+}
+
+int kosk_registry_sorted_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *capacity)
+{
+    if (!ctx || !root) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_sorted_root", WHY_NO_REGISTRY);
+    if (registry_sorted_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    if (used) *used = ctx->c->registry->used;
+    if (capacity) *capacity = ctx->c->registry->capacity;
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_prove_absent(kosk_ctx *ctx, int n, const uint8_t *h, uint8_t *kind, uint8_t *records, uint8_t *root)
+{
+    if (!ctx || n < 1 || !h || !kind || !records) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->registry) return refuse(ctx, "kosk_registry_prove_absent", WHY_NO_REGISTRY);
+    const size_t rec = regsort::proof_bytes(regtree::depth(ctx->c->registry->capacity));
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return registry_prove_absent(c, count, h + (size_t)first * 32, kind + first, records + (size_t)first * rec);
+        })) return -1;
+    if (root && registry_sorted_root(*ctx->c, root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_regsort_order_device(kosk_ctx *ctx, int n, const uint8_t *d_h, const uint8_t *d_flag, int32_t *d_order)
+{
+    if (!ctx || n < 1 || n > (1 << 24) || !d_h || !d_flag || !d_order || ((uintptr_t)d_h & 7) || ((uintptr_t)d_order & 3)) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (regsort_order_device(*ctx->c, n, d_h, d_flag, d_order)) { ctx->err = ctx->c->err; return -1; }
     return 0;
     GUARD_END
 }

@@ -79,7 +79,8 @@ enum ProfId { PR_HASH_TCOMM = 0, PR_HASH_VIEW, PR_GEMM_EXPAND1, PR_GEMM_EXPAND2,
 enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEMM, PATH_COPY_DIRECT, PATH_COPY_STAGED,
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
               PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS,
-              PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH, PATH_COUNT };
+              PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH,
+              PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -686,6 +687,18 @@ struct KemRegistry {
         tree_valid = false;
         if (!dirty.empty()) dirty[slot >> 10] = 1;
     }
+    // the sorted tree (kosk-regsort-v1): allocated at the first call of kosk_registry_sorted_root / _prove_absent, rebuilt whole
+    // by the first such call after a mutation cleared sorted_valid (wherever index_valid is cleared)
+    uint8_t *d_srec = nullptr;   // [P][16] the sort records, ascending: the first `used` name the occupied slots in (fingerprint, slot) order
+    uint8_t *d_stree = nullptr;  // [regtree::tree_bytes(capacity)] every node of every level, level-major
+    uint8_t *d_sq = nullptr;     // [sproof_cap][32] the staged queries of one launch group
+    int32_t *d_srank = nullptr;  // [sproof_cap][2] per query: lb, present
+    uint8_t *d_skind = nullptr;  // [sproof_cap] per query: 1 absent, 2 present
+    uint8_t *d_sproof = nullptr; // [sproof_cap][regsort::proof_bytes(D)] the staged proof records
+    int sproof_cap = 0;
+    bool sorted_valid = false;
+    // a mutation changed the set of occupied slots or a fingerprint
+    void lookups_stale() { index_valid = false; sorted_valid = false; }
 };
 inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
 // One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
@@ -796,6 +809,48 @@ int registry_root(Ctx &c, uint8_t *root);
 // lowest occupied slots that hold the fingerprints h (k_registry_find in front), with those slots to slots_out and found to done.  paths (may
 // be nullptr when D = 0), hout, slots_out, done: host or device memory.  Synchronised; what was staged in the KEM workspace is zeroed
 int kem_registry_prove(Ctx &c, int n, const int32_t *slots, const uint8_t *h, uint8_t *hout, int32_t *slots_out, uint8_t *done, uint8_t *paths);
+
+// The sorted tree (kosk_regsort.hip, kosk_regsort.hpp).
+// A sort record is 16 bytes: the first 8 bytes of the fingerprint as a big-endian number (two words, low first), the slot, the class (0: an
+// occupied slot; 1: an empty slot or padding, which sorts last).  The order is (class, prefix, bytes 8..31 of h[slot] where two class-0
+// prefixes tie, slot).  regsort_sort: a bitonic network over 2^lg records -- tiles of 2^REGSORT_TILE_LG records in LDS (k_regsort_tile),
+// compare-exchange steps at a distance of a tile or more in HBM (k_regsort_step).  Queued, not synchronised; every launch counts in
+// PATH_REGSORT_SORT
+// 2 048 records, 32 KB of LDS (the residency of k_registry_tree), one compare-exchange per lane and step: measured against tiles of 2^10
+// and 2^12 records and blocks of 256 and 512 threads
+enum { REGSORT_TILE_LG = 11, REGSORT_TILE_THREADS = 1024 };
+struct RegSortJob {
+    int n, lg;           // records < n come from flag / h, the rest up to 2^lg are padding
+    int phase, jg;       // k_regsort_tile: the merge phase it finishes (0: every phase up to the tile); k_regsort_step: phase and distance, as logarithms
+    const uint8_t *h, *flag;
+    uint8_t *rec;
+    int32_t *order;      // k_regsort_order: record i < n to its slot, or -1 for class 1
+};
+int regsort_sort(Ctx &c, const RegSortJob &j);
+// k_regsort_tree, one tier, the shape of k_registry_tree: tier 0 forms S(h[slot], slot) from record i < used and Z from there on
+struct RegSortTreeJob {
+    int tier, D, K, used;
+    const uint8_t *h, *rec;
+    uint64_t pad[4]; // Z as words
+    uint8_t *tree;
+};
+// k_regsort_rank: one lane per query, lb and present by binary search; k_regsort_prove: one lane per 16-byte piece of a proof record
+struct RegSortProveJob {
+    int n, D, used;
+    const uint8_t *q, *h, *rec, *tree;
+    int32_t *rank;
+    uint8_t *kind, *proof;
+};
+// the sorted tree allocated and current: a no-op while sorted_valid; else keys, sort, tiers, synchronised
+int registry_sorted_ensure(Ctx &c);
+// the root of the current sorted tree to `root` (host or device memory); synchronised
+int registry_sorted_root(Ctx &c, uint8_t *root);
+// n <= KEM_CHUNK queries (host or device memory of any alignment) -> kind[b] and one proof record each.  Synchronised; the staged queries
+// are zeroed
+int registry_prove_absent(Ctx &c, int n, const uint8_t *h, uint8_t *kind, uint8_t *records);
+// the sort alone on caller-made fingerprints and flags in device memory (h 8-byte aligned): d_order[i] = the index of the i-th entry, -1 from
+// the number of flagged records on.  Synchronised; the records live in a buffer that comes and goes with the call
+int regsort_order_device(Ctx &c, int n, const uint8_t *d_h, const uint8_t *d_flag, int32_t *d_order);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches

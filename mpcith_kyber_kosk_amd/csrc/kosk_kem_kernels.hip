@@ -761,7 +761,7 @@ int kem_registry_admit(Ctx &c, int n, const uint8_t *pk, int resident_first, con
     KemRegistry &r = *c.registry;
     const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
-    r.index_valid = false; // the next lookup rebuilds the fingerprint index
+    r.lookups_stale(); // the next lookup rebuilds the fingerprint index, the next proof of absence the sorted tree
     r.tree_valid = false;  // and the next tree call the leaf subtrees of these slots (a registry without a tree has no bitmap: nothing to walk)
     if (uint8_t *dirty = r.dirty.empty() ? nullptr : r.dirty.data())
         for (int b = 0; b < n; b++)

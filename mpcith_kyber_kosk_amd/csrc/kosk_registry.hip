@@ -450,7 +450,7 @@ int registry_evict(Ctx &c, int n, const int32_t *slots)
     KemRegistry &r = *c.registry;
     const Dims D = dims(c.P.K);
     HIPCHK(hipSetDevice(c.device));
-    r.index_valid = false;
+    r.lookups_stale();
     const size_t a_bytes = (size_t)D.K * D.K * 512;
     std::vector<WipeRegion> dev;
     for (int b = 0; b < n; b++) {
