@@ -577,6 +577,79 @@ int kosk_registry_sorted_root(kosk_ctx *ctx, uint8_t root[32], int *used, int *c
 int kosk_registry_prove_absent(kosk_ctx *ctx, int n, const uint8_t *h, uint8_t *kind, uint8_t *records, uint8_t *root);
 int kosk_regsort_order_device(kosk_ctx *ctx, int n, const uint8_t *d_h, const uint8_t *d_flag, int32_t *d_order);
 
+/* ---- The registry history, format kosk-reghist-v1 (INTEGRATION.md 8.7 is the normative text): an append-only Merkle tree over the
+ * registry's mutation events, kept current in HBM by the mutating calls themselves, with checkpoints that bind the two state roots into it,
+ * inclusion proofs for events and consistency proofs between any two sizes.  It is the third leg beside inclusion (8.5) and absence (8.6):
+ * a peer that holds two signed heads checks that the later history extends the earlier one.
+ * TAG = the 15 ASCII bytes "kosk-reghist-v1"; every hash is SHA3-256 of one rate block:
+ *   event leaf       V = SHA3-256(TAG || 00 || h[32] || LE32(op) || LE32(slot) || LE32(kyber_k))
+ *   checkpoint leaf  C = SHA3-256(TAG || 01 || slot_root[32] || sorted_root[32] || LE32(used) || LE32(capacity) || LE32(kyber_k))
+ *   inner node       N(l, r) = SHA3-256(TAG || 02 || l[32] || r[32])
+ *   empty history    O = SHA3-256(TAG || 03 || LE32(kyber_k))
+ * The stored event record, KOSK_REGHIST_EVENT_BYTES = 80 bytes: 0 LE32 op; 4 LE32 a (ops 1 / 2: the slot; op 3: used); 8 LE32 b (0;
+ * capacity); 12 LE32 zero; 16 x[32] (the fingerprint h, of the evicted key for op 2; slot_root); 48 y[32] (zeros; sorted_root).
+ * The tree over the first n leaves has the shape of RFC 6962: H(0) = O, H of one leaf is that leaf's hash, and for n > 1 with s the largest
+ * power of two below n, H(D[0:n]) = N(H(D[0:s]), H(D[s:n])).  Node (l, i) is complete at size n iff (i + 1) 2^l <= n; it covers leaves
+ * [i 2^l, (i + 1) 2^l) and never changes.  R_l is the hash of the trailing leaves [(n >> l) << l, n) where there are any.
+ * Inclusion path of leaf i at size n: l = 0, idx = i; while level l has more than one node (n >> l complete ones and one ragged node iff
+ * n & (2^l - 1) != 0): emit node (l, idx ^ 1) if it is complete, R_l if idx ^ 1 == n >> l and there is a ragged node, nothing otherwise; then
+ * l += 1, idx >>= 1.  At most depth(n) records.  Consistency proof from m to n, 0 < m < n: l = the trailing zero bits of m, idx = (m - 1) >> l;
+ * emit node (l, idx) first if idx != 0, then the records of the walk above from (l, idx).  At most depth(n) + 1 records; empty for m == n
+ * and m == 0.
+ * A proof record: four LE32 (count; index or old_size; size; 0), `count` records of 32 bytes, zero padding to kosk_reghist_path_bytes(size)
+ * = 16 + 32 depth(size) or kosk_reghist_consistency_bytes(size) = 16 + 32 (depth(size) + 1) bytes (both 0 for size < 1).
+ * kosk_reghist_depth: the smallest d with 2^d >= size; 0 for size 0 or 1; -1 for size < 0.
+ * kosk_reghist_leaf: the leaf of a stored record; -1: bad k, NULL, op outside 1..3, a non-zero reserved field (b and y of ops 1 / 2, word 12).
+ * kosk_reghist_root_from_path: fn = index, sn = size - 1, r = leaf; per record v: fail if sn == 0; if fn is odd or fn == sn, r = N(v, r) and,
+ * if fn is even, both shift right until fn is odd or zero; otherwise r = N(r, v); then both shift right by one.  0 with the root written iff
+ * sn == 0 at the end; -1: malformed (also: a header that disagrees with the arguments, a count above depth(size), non-zero padding).
+ * kosk_reghist_check_consistency: 1 consistent / 0 not / -1 bad arguments (NULL, a negative size, old_size > size, size < 1).  m == 0:
+ * consistent iff count == 0 (root_old is not read); m == n: iff count == 0 and the roots are equal.  Otherwise root_m goes in front of the
+ * proof if m is a power of two; fn = m - 1, sn = n - 1, both shifted right while fn is odd; fr = sr = proof[0]; per further record v: fail
+ * if sn == 0; if fn is odd or fn == sn, fr = N(v, fr), sr = N(v, sr) and, if fn is even, both shift right until fn is odd or zero; otherwise
+ * sr = N(sr, v); then both shift right by one.  Consistent iff sn == 0, fr == root_m, sr == root_n.  A header that disagrees with the
+ * arguments, a count above the bound and non-zero padding give 0.  All host functions: no handle, no GPU, pointers of any alignment.
+ * Which events a call appends (decided on the host from the occupancy mirror before anything runs): an admitting call
+ * (kosk_registry_admit, _admit_verified, _enrol, _enrol_verified) appends one EVICT(slot, old fingerprint) per accepted position whose slot
+ * is occupied, in ascending position, then one ADMIT(slot, new fingerprint) per accepted position, in ascending position; masked, REJECTED
+ * and DUPLICATE positions append nothing.  kosk_registry_evict appends one EVICT per occupied slot at its first occurrence in the call.
+ * An admitting call that fails with "block limit" has emptied the slots it wrote: its events are the EVICT events of the positions in the
+ * launch groups that were started.  Replaying events 0 .. size - 1 onto an empty table gives the table's (slot, fingerprint) content.  A
+ * call whose events do not fit is refused with -1 ("history is full"), nothing changed.
+ * On a handle.  kosk_registry_history_reserve: needs a reserved registry with no occupied slot; max_events 1 .. 2^24; allowed again only
+ * while size == 0; 0 frees at any time; kosk_registry_reserve frees the history with the registry.  The events, the complete nodes
+ * (level-major), 33 ragged-node slots, a job list and (from the first proving call on) staging are public allocations of the registry; a
+ * registry without a history allocates and launches what it did before.  kosk_registry_history_head: the root at any size <= the current
+ * one (< 0: current), size 0 gives O; root = host or device memory.  kosk_registry_history_checkpoint: brings both state trees up to date
+ * (their counters move as for kosk_registry_root and kosk_registry_sorted_root) and appends one op-3 event whose roots are read in HBM;
+ * *index = the event's position.  kosk_registry_history_read: n raw records from `first` on to host or device memory.
+ * kosk_registry_history_prove_events / _prove_consistency: index / old_size = n int32 in HOST memory; size < 0: the current size; an index
+ * outside [0, size), an old size outside [0, size] or a size above the current one returns -1 and starts nothing; leaves (n x 32) and root
+ * may be NULL; every output may be host or device memory of any alignment; any n >= 1 in launch groups of 16384, unmerged on the handle's
+ * own stream, also on a cohort member.  Refusals return -1 with a text that begins with the call's name, and nothing is started; calls that
+ * may append follow the thread rule of kosk_registry_reserve, kosk_registry_admit* and kosk_registry_evict.
+ * Erasure: the buffers are public entries of the inventory: kosk_secret_scan covers them, kosk_wipe_secrets and
+ * KOSK_WIPE_CALL leave them alone.  With a history reserved the fingerprint of an evicted key STAYS in HBM on purpose: a public log
+ * remembers.  A registrar who needs "no byte of the key is left" (8.3) does not reserve a history. */
+enum { KOSK_REGHIST_ADMIT = 1, KOSK_REGHIST_EVICT = 2, KOSK_REGHIST_CHECKPOINT = 3 };
+enum { KOSK_REGHIST_TIER_LEVELS = 10 };
+#define KOSK_REGHIST_EVENT_BYTES 80
+int kosk_reghist_depth(int size);
+size_t kosk_reghist_path_bytes(int size);
+size_t kosk_reghist_consistency_bytes(int size);
+int kosk_reghist_leaf(int kyber_k, const uint8_t event[80], uint8_t out[32]);
+int kosk_reghist_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]);
+int kosk_reghist_empty_root(int kyber_k, uint8_t out[32]);
+int kosk_reghist_root_from_path(int index, int size, const uint8_t leaf[32], const uint8_t *record, uint8_t root[32]);
+int kosk_reghist_check_consistency(int old_size, int size, const uint8_t root_old[32], const uint8_t root_new[32], const uint8_t *record);
+int kosk_registry_history_reserve(kosk_ctx *ctx, int max_events);
+int kosk_registry_history_level(const kosk_ctx *ctx, int *size, int *max_events);
+int kosk_registry_history_head(kosk_ctx *ctx, int size, uint8_t root[32], int *size_out);
+int kosk_registry_history_checkpoint(kosk_ctx *ctx, int *index);
+int kosk_registry_history_read(kosk_ctx *ctx, int first, int n, uint8_t *events);
+int kosk_registry_history_prove_events(kosk_ctx *ctx, int size, int n, const int32_t *index, uint8_t *leaves, uint8_t *records, uint8_t *root);
+int kosk_registry_history_prove_consistency(kosk_ctx *ctx, int size, int n, const int32_t *old_size, uint8_t *records, uint8_t *root);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -710,7 +783,12 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 34 launches of k_registry_path (one per launch group of kosk_registry_prove_slots / kosk_registry_prove_peers),
  * 35 launches of the sort kernels k_regsort_keys / k_regsort_tile / k_regsort_step (a rebuild of the sorted tree, or kosk_regsort_order_device),
  * 36 launches of k_regsort_tree (one per tier of a rebuild of the sorted tree; ids 27..34 do not move for any call of that section),
- * 37 launches of k_regsort_prove (one per launch group of kosk_registry_prove_absent). */
+ * 37 launches of k_regsort_prove (one per launch group of kosk_registry_prove_absent),
+ * 38 launches of k_reghist_append (one per tier of an append to the registry history) / 39 leaf groups hashed by those launches (the
+ * tier-0 blocks: ((s + c - 1) >> 10) - (s >> 10) + 1 for c events appended at size s),
+ * 40 launches of k_reghist_frontier (the ragged nodes and the root of one size; a second call at the same size launches nothing),
+ * 41 launches of k_reghist_prove (one per launch group of kosk_registry_history_prove_events / _prove_consistency; ids 27..37 do not move
+ * for kosk_registry_history_head, _read or the proving calls). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -283,6 +283,26 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_sorted_root")):
         sig.update(sorted_tree)
+    # the registry history, kosk-reghist-v1; optional under the same rule (and only then)
+    history = {
+        "kosk_reghist_depth": (C.c_int, [C.c_int]),
+        "kosk_reghist_path_bytes": (sz, [C.c_int]),
+        "kosk_reghist_consistency_bytes": (sz, [C.c_int]),
+        "kosk_reghist_leaf": (C.c_int, [C.c_int, vp, vp]),
+        "kosk_reghist_node": (C.c_int, [vp, vp, vp]),
+        "kosk_reghist_empty_root": (C.c_int, [C.c_int, vp]),
+        "kosk_reghist_root_from_path": (C.c_int, [C.c_int, C.c_int, vp, vp, vp]),
+        "kosk_reghist_check_consistency": (C.c_int, [C.c_int, C.c_int, vp, vp, vp]),
+        "kosk_registry_history_reserve": (C.c_int, [vp, C.c_int]),
+        "kosk_registry_history_level": (C.c_int, [vp, ip, ip]),
+        "kosk_registry_history_head": (C.c_int, [vp, C.c_int, vp, ip]),
+        "kosk_registry_history_checkpoint": (C.c_int, [vp, ip]),
+        "kosk_registry_history_read": (C.c_int, [vp, C.c_int, C.c_int, vp]),
+        "kosk_registry_history_prove_events": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "kosk_registry_history_prove_consistency": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_history_reserve")):
+        sig.update(history)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -330,7 +350,11 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_registry_tree_depth", "kosk_registry_tree_bytes", "kosk_regtree_leaf", "kosk_regtree_node", "kosk_regtree_root_from_path",
            "kosk_registry_root", "kosk_registry_prove_slots", "kosk_registry_prove_peers",
            "kosk_regsort_proof_bytes", "kosk_regsort_leaf", "kosk_regsort_node", "kosk_regsort_root_from_path", "kosk_regsort_check_proof",
-           "kosk_registry_sorted_root", "kosk_registry_prove_absent", "kosk_regsort_order_device"]
+           "kosk_registry_sorted_root", "kosk_registry_prove_absent", "kosk_regsort_order_device",
+           "kosk_reghist_depth", "kosk_reghist_path_bytes", "kosk_reghist_consistency_bytes", "kosk_reghist_leaf", "kosk_reghist_node",
+           "kosk_reghist_empty_root", "kosk_reghist_root_from_path", "kosk_reghist_check_consistency",
+           "kosk_registry_history_reserve", "kosk_registry_history_level", "kosk_registry_history_head", "kosk_registry_history_checkpoint",
+           "kosk_registry_history_read", "kosk_registry_history_prove_events", "kosk_registry_history_prove_consistency"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -480,6 +504,75 @@ def regsort_check_proof(k, depth, x, record, root):
     if rc < 0:
         raise KoskError("regsort_check_proof: bad kyber_k or depth")
     return rc
+
+
+# the registry history, kosk-reghist-v1: the host functions, no handle and no GPU
+REGHIST_ADMIT, REGHIST_EVICT, REGHIST_CHECKPOINT = 1, 2, 3  # KOSK_REGHIST_*
+REGHIST_EVENT_BYTES = 80  # KOSK_REGHIST_EVENT_BYTES
+REGHIST_TIER_LEVELS = 10  # KOSK_REGHIST_TIER_LEVELS
+
+
+def reghist_depth(size): return lib.kosk_reghist_depth(size)
+def reghist_path_bytes(size): return lib.kosk_reghist_path_bytes(size)
+def reghist_consistency_bytes(size): return lib.kosk_reghist_consistency_bytes(size)
+
+
+def reghist_event(op, a, b=0, x=bytes(32), y=bytes(32)):
+    """the 80-byte stored event record: ops 1 / 2 (a = slot, x = the fingerprint), op 3 (a = used, b = capacity, x / y = the two roots)"""
+    import struct
+    return struct.pack("<4I", op, a, b, 0) + _digest("x", x) + _digest("y", y)
+
+
+def reghist_leaf(k, event):
+    """kosk_reghist_leaf: the leaf hash of a stored event record (80 bytes)"""
+    event = bytes(event)
+    if len(event) != REGHIST_EVENT_BYTES:
+        raise KoskError("an event record has %d bytes" % REGHIST_EVENT_BYTES)
+    out = C.create_string_buffer(32)
+    if lib.kosk_reghist_leaf(k, C.c_char_p(event), out):
+        raise KoskError("reghist_leaf: kyber_k outside 2..4, op outside 1..3 or a non-zero reserved field")
+    return out.raw
+
+
+def reghist_node(left, right):
+    """kosk_reghist_node: the inner node over two 32-byte children"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_reghist_node(C.c_char_p(_digest("a node", left)), C.c_char_p(_digest("a node", right)), out):
+        raise KoskError("reghist_node failed")
+    return out.raw
+
+
+def reghist_empty_root(k):
+    """kosk_reghist_empty_root: O, the root of the history without events"""
+    out = C.create_string_buffer(32)
+    if lib.kosk_reghist_empty_root(k, out):
+        raise KoskError("reghist_empty_root: kyber_k outside 2..4")
+    return out.raw
+
+
+def reghist_root_from_path(index, size, leaf, record):
+    """kosk_reghist_root_from_path: the root that leaf `index` of a history of `size` events and its inclusion record imply, or None where
+    the record is malformed; compare it with the published head"""
+    record = bytes(record)
+    if len(record) != reghist_path_bytes(size):
+        raise KoskError("an inclusion record at size %d has %d bytes" % (size, reghist_path_bytes(size)))
+    out = C.create_string_buffer(32)
+    if lib.kosk_reghist_root_from_path(index, size, C.c_char_p(_digest("a leaf", leaf)), C.c_char_p(record), out):
+        return None
+    return out.raw
+
+
+def reghist_check_consistency(old_size, size, root_old, root_new, record):
+    """kosk_reghist_check_consistency: True iff record shows that the history of `size` events under root_new extends the one of old_size
+    events under root_old"""
+    record = bytes(record)
+    if len(record) != reghist_consistency_bytes(size):
+        raise KoskError("a consistency record at size %d has %d bytes" % (size, reghist_consistency_bytes(size)))
+    rc = lib.kosk_reghist_check_consistency(old_size, size, None if root_old is None else C.c_char_p(_digest("a root", root_old)),
+                                            C.c_char_p(_digest("a root", root_new)), C.c_char_p(record))
+    if rc < 0:
+        raise KoskError("reghist_check_consistency: a negative size, old_size > size or size < 1")
+    return bool(rc)
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1422,6 +1515,74 @@ class Kosk:
         self._chk(lib.kosk_regsort_order_device(self._h, n, C.c_void_p(int(d_h)), C.c_void_p(int(d_flag)), C.c_void_p(int(d_order))), "regsort_order")
         return d_order
 
+    # the registry history, kosk-reghist-v1
+    def registry_history_reserve(self, max_events):
+        """kosk_registry_history_reserve: an append-only history of up to max_events events on an EMPTY registry; 0 frees"""
+        self._chk(lib.kosk_registry_history_reserve(self._h, max_events), "registry_history_reserve")
+
+    def registry_history_level(self):
+        """kosk_registry_history_level -> (size, max_events)"""
+        s_, m = C.c_int(), C.c_int()
+        self._chk(lib.kosk_registry_history_level(self._h, C.byref(s_), C.byref(m)), "registry_history_level")
+        return s_.value, m.value
+
+    def registry_history_head(self, size=-1, out=None):
+        """kosk_registry_history_head -> (root, size): the root over the first `size` events (< 0: all); out: an int DEVICE pointer to 32
+        bytes, returned in place of the root"""
+        n = C.c_int()
+        buf = C.create_string_buffer(32) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_registry_history_head(self._h, size, buf, C.byref(n)), "registry_history_head")
+        return (buf.raw if out is None else out), n.value
+
+    def registry_history_checkpoint(self):
+        """kosk_registry_history_checkpoint -> the index of the appended op-3 event, which binds both state roots, used and capacity"""
+        i = C.c_int()
+        self._chk(lib.kosk_registry_history_checkpoint(self._h, C.byref(i)), "registry_history_checkpoint")
+        return i.value
+
+    def registry_history_read(self, first=0, n=None, out=None):
+        """kosk_registry_history_read -> the raw 80-byte records of events first .. first + n - 1 (n None: up to the current size); out: an
+        int DEVICE pointer, returned as it is"""
+        if n is None:
+            n = self.registry_history_level()[0] - first
+        if n == 0 and out is None:
+            return []
+        buf = C.create_string_buffer(max(REGHIST_EVENT_BYTES * n, 1)) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_registry_history_read(self._h, first, n, buf), "registry_history_read")
+        return _cut(buf, REGHIST_EVENT_BYTES, n) if out is None else out
+
+    def _history_size(self, size):
+        return self.registry_history_level()[0] if size < 0 else size
+
+    def registry_history_prove_events(self, indices, size=-1, out=None):
+        """kosk_registry_history_prove_events -> (leaves, records, root): per event index its leaf hash and inclusion record at `size`
+        (< 0: the current size), and the head at that size.  out=(d_leaves, d_records, d_root): int DEVICE pointers (d_leaves and d_root
+        may be None), returned as they are"""
+        n = len(indices)
+        ip_ = (C.c_int32 * max(n, 1))(*indices)
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_registry_history_prove_events(self._h, size, n, ip_, ptr[0], ptr[1], ptr[2]), "registry_history_prove_events")
+            return out
+        rec = reghist_path_bytes(self._history_size(size))
+        leaves = C.create_string_buffer(32 * max(n, 1)); records = C.create_string_buffer(max(rec * n, 1)); root = C.create_string_buffer(32)
+        self._chk(lib.kosk_registry_history_prove_events(self._h, size, n, ip_, leaves, records, root), "registry_history_prove_events")
+        return _cut(leaves, 32, n), [records.raw[rec * b:rec * (b + 1)] for b in range(n)], root.raw
+
+    def registry_history_prove_consistency(self, old_sizes, size=-1, out=None):
+        """kosk_registry_history_prove_consistency -> (records, root): per old size the consistency record to `size` (< 0: the current
+        size), and the head at that size.  out=(d_records, d_root): int DEVICE pointers (d_root may be None), returned as they are"""
+        n = len(old_sizes)
+        op_ = (C.c_int32 * max(n, 1))(*old_sizes)
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_registry_history_prove_consistency(self._h, size, n, op_, ptr[0], ptr[1]), "registry_history_prove_consistency")
+            return out
+        rec = reghist_consistency_bytes(self._history_size(size))
+        records = C.create_string_buffer(max(rec * n, 1)); root = C.create_string_buffer(32)
+        self._chk(lib.kosk_registry_history_prove_consistency(self._h, size, n, op_, records, root), "registry_history_prove_consistency")
+        return [records.raw[rec * b:rec * (b + 1)] for b in range(n)], root.raw
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1576,6 +1737,10 @@ class Kosk:
     PATH_REGSORT_SORT = 35
     PATH_REGSORT_TREE = 36
     PATH_REGSORT_PROVE = 37
+    PATH_REGHIST_APPEND = 38
+    PATH_REGHIST_GROUPS = 39
+    PATH_REGHIST_FRONTIER = 40
+    PATH_REGHIST_PROVE = 41
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -30,6 +30,7 @@
 #include "kosk_ctx.hpp"
 #include "kosk_lanes.hpp"
 #include "kosk_registry_resolve.hpp"
+#include "kosk_reghist.hpp"
 #include "kosk_regsort.hpp"
 #include "kosk_regtree.hpp"
 
@@ -1375,6 +1376,7 @@ size_t kosk_registry_slot_bytes(int k) { return k >= 2 && k <= 4 ? registry_slot
 
 // why a call that names `slots` is refused before anything starts; nullptr: the handle has a registry and every value is one of its slots
 // (distinct: and none is named twice -- the admissions, where the later writer would be undefined)
+static const char *const WHY_HISTORY_FULL = "history is full (kosk_registry_history_reserve): nothing was changed";
 static const char *registry_slots_refusal(const kosk_ctx *ctx, int n, const int32_t *slots, bool distinct)
 {
     const KemRegistry *r = ctx->c->registry;
@@ -1412,17 +1414,41 @@ int kosk_registry_level(const kosk_ctx *ctx, int *used, int *capacity)
 
 // key b of the call (pk records, or pk == nullptr: the resident keys) into slots[b] where accept[b] != 0 (nullptr: everywhere), in launch groups;
 // the mirror follows what the launches wrote.  A launch group that fails (gen_matrix at its block limit) leaves the slots this call wrote empty
-static int registry_admit_run(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *accept, const int32_t *slots)
+// With a history: refused up front where the call's events do not fit; each launch group appends the EVICT events of
+// the occupied slots it is about to overwrite in front of its launch (they read the old fingerprints), and the ADMIT events of every
+// accepted position follow once every group has succeeded.  The clean-up eviction of a failed call appends nothing: its slots were empty
+// before the call, or their EVICT events are in place
+static int registry_admit_run(kosk_ctx *ctx, const char *fn, int n, const uint8_t *pk, const uint8_t *accept, const int32_t *slots)
 {
     std::vector<int32_t> dst((size_t)n);
     for (int b = 0; b < n; b++) dst[(size_t)b] = !accept || accept[b] ? slots[b] : -1;
     const size_t pkb = ctx->c->P.pk_bytes;
+    KemRegistry &r = *ctx->c->registry;
+    const bool hist = r.hist_max != 0;
+    if (hist) {
+        long need = 0;
+        for (int b = 0; b < n; b++)
+            if (dst[(size_t)b] >= 0) need += r.occ[(size_t)dst[(size_t)b]] ? 2 : 1;
+        if (need > (long)r.hist_max - r.hist_size) return refuse(ctx, fn, WHY_HISTORY_FULL);
+    }
+    std::vector<int32_t> ev_op, ev_slot;
     int done = 0; // keys of completed or started launch groups
     const int rc = kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        if (hist) {
+            ev_op.clear(); ev_slot.clear();
+            for (int b = first; b < first + count; b++)
+                if (dst[(size_t)b] >= 0 && r.occ[(size_t)dst[(size_t)b]]) { ev_op.push_back(reghist::OP_EVICT); ev_slot.push_back(dst[(size_t)b]); }
+            if (!ev_op.empty() && reghist_append(c, (int)ev_op.size(), ev_op.data(), ev_slot.data())) return -1;
+        }
         done = first + count;
         return kem_registry_admit(c, count, pk ? pk + (size_t)first * pkb : nullptr, first, dst.data() + first);
     });
-    KemRegistry &r = *ctx->c->registry;
+    if (hist && !rc) {
+        ev_op.clear(); ev_slot.clear();
+        for (int b = 0; b < n; b++)
+            if (dst[(size_t)b] >= 0) { ev_op.push_back(reghist::OP_ADMIT); ev_slot.push_back(dst[(size_t)b]); }
+        if (!ev_op.empty() && reghist_append(*ctx->c, (int)ev_op.size(), ev_op.data(), ev_slot.data())) { ctx->err = ctx->c->err; return -1; }
+    }
     for (int b = 0; b < done; b++) {
         if (dst[(size_t)b] < 0 || r.occ[(size_t)dst[(size_t)b]]) continue; // masked, or a replacement: `used` does not change
         r.occ[(size_t)dst[(size_t)b]] = 1;
@@ -1449,7 +1475,7 @@ int kosk_registry_admit_verified(kosk_ctx *ctx, int n, const int32_t *slots, uin
     if (const char *why = verified_keys_refusal(ctx, n)) return refuse(ctx, "kosk_registry_admit_verified", why);
     std::vector<uint8_t> bits((size_t)n);
     for (int b = 0; b < n; b++) bits[(size_t)b] = ctx->masks[(size_t)b] == 0;
-    if (registry_admit_run(ctx, n, nullptr, bits.data(), slots)) return -1;
+    if (registry_admit_run(ctx, "kosk_registry_admit_verified", n, nullptr, bits.data(), slots)) return -1;
     memcpy(done, bits.data(), (size_t)n);
     return 0;
     GUARD_END
@@ -1461,7 +1487,7 @@ int kosk_registry_admit(kosk_ctx *ctx, int n, const uint8_t *pk, const uint8_t *
     GUARD(ctx)
     ctx->clear_err();
     if (const char *why = registry_slots_refusal(ctx, n, slots, true)) return refuse(ctx, "kosk_registry_admit", why);
-    return registry_admit_run(ctx, n, pk, accept, slots);
+    return registry_admit_run(ctx, "kosk_registry_admit", n, pk, accept, slots);
     GUARD_END
 }
 
@@ -1471,6 +1497,19 @@ int kosk_registry_evict(kosk_ctx *ctx, int n, const int32_t *slots)
     GUARD(ctx)
     ctx->clear_err();
     if (const char *why = registry_slots_refusal(ctx, n, slots, false)) return refuse(ctx, "kosk_registry_evict", why);
+    KemRegistry &r = *ctx->c->registry;
+    if (r.hist_max) { // one EVICT per occupied slot at its first occurrence, in front of the wipe: the events read the fingerprints
+        std::vector<int32_t> ev_op, ev_slot;
+        std::vector<uint8_t> seen((size_t)r.capacity, 0);
+        for (int b = 0; b < n; b++) {
+            const size_t s = (size_t)slots[b];
+            if (!r.occ[s] || seen[s]) continue;
+            seen[s] = 1;
+            ev_op.push_back(reghist::OP_EVICT); ev_slot.push_back(slots[b]);
+        }
+        if ((long)ev_op.size() > (long)r.hist_max - r.hist_size) return refuse(ctx, "kosk_registry_evict", WHY_HISTORY_FULL);
+        if (!ev_op.empty() && reghist_append(*ctx->c, (int)ev_op.size(), ev_op.data(), ev_slot.data())) { ctx->err = ctx->c->err; return -1; }
+    }
     if (registry_evict(*ctx->c, n, slots)) { ctx->err = ctx->c->err; return -1; }
     return 0;
     GUARD_END
@@ -1544,7 +1583,7 @@ static int registry_enrol_run(kosk_ctx *ctx, const char *fn, int n, const uint8_
         std::vector<uint8_t> take((size_t)n);
         std::vector<int32_t> named(dst); // a position that is not admitted names no slot: registry_admit_run masks it
         for (int b = 0; b < n; b++) take[(size_t)b] = st[(size_t)b] == ENROL_ADMITTED;
-        if (registry_admit_run(ctx, n, pk, take.data(), named.data())) return -1;
+        if (registry_admit_run(ctx, fn, n, pk, take.data(), named.data())) return -1;
     }
     memcpy(slots, dst.data(), sizeof(int32_t) * (size_t)n);
     memcpy(status, st.data(), (size_t)n);
@@ -1696,6 +1735,134 @@ int kosk_regsort_order_device(kosk_ctx *ctx, int n, const uint8_t *d_h, const ui
     GUARD(ctx)
     ctx->clear_err();
     if (regsort_order_device(*ctx->c, n, d_h, d_flag, d_order)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+// ---- the registry history, format kosk-reghist-v1 (kosk_reghist.hpp, kosk_reghist.hip) ----
+static_assert((int)KOSK_REGHIST_TIER_LEVELS == (int)reghist::TIER_LEVELS && (int)KOSK_REGHIST_EVENT_BYTES == (int)reghist::EVENT_BYTES &&
+              (int)KOSK_REGHIST_ADMIT == (int)reghist::OP_ADMIT && (int)KOSK_REGHIST_EVICT == (int)reghist::OP_EVICT &&
+              (int)KOSK_REGHIST_CHECKPOINT == (int)reghist::OP_CHECKPOINT, "kosk_mi355x.h and kosk_reghist.hpp");
+static const char *const WHY_NO_HISTORY = "no history is reserved (kosk_registry_history_reserve)";
+int kosk_reghist_depth(int size) { return reghist::depth(size); }
+size_t kosk_reghist_path_bytes(int size) { return reghist::path_bytes(size); }
+size_t kosk_reghist_consistency_bytes(int size) { return reghist::consistency_bytes(size); }
+int kosk_reghist_leaf(int kyber_k, const uint8_t event[80], uint8_t out[32]) { return reghist::leaf(kyber_k, event, out); }
+int kosk_reghist_node(const uint8_t l[32], const uint8_t r[32], uint8_t out[32]) { return reghist::node(l, r, out); }
+int kosk_reghist_empty_root(int kyber_k, uint8_t out[32]) { return reghist::empty_root(kyber_k, out); }
+int kosk_reghist_root_from_path(int index, int size, const uint8_t leaf[32], const uint8_t *record, uint8_t root[32])
+{
+    return reghist::root_from_path(index, size, leaf, record, root);
+}
+int kosk_reghist_check_consistency(int old_size, int size, const uint8_t root_old[32], const uint8_t root_new[32], const uint8_t *record)
+{
+    return reghist::check_consistency(old_size, size, root_old, root_new, record);
+}
+
+int kosk_registry_history_reserve(kosk_ctx *ctx, int max_events)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    const KemRegistry *r = ctx->c->registry;
+    if (!r) return refuse(ctx, "kosk_registry_history_reserve", WHY_NO_REGISTRY);
+    if (max_events < 0 || max_events > reghist::MAX_EVENTS) return refuse(ctx, "kosk_registry_history_reserve", "max_events outside 0 .. 2^24");
+    if (max_events && r->hist_size) return refuse(ctx, "kosk_registry_history_reserve", "the history has events: only 0 (free) is allowed");
+    if (max_events && r->used) return refuse(ctx, "kosk_registry_history_reserve", "the registry is not empty (kosk_registry_evict): replay from event 0 would be incomplete");
+    if (reghist_reserve(*ctx->c, max_events)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_history_level(const kosk_ctx *ctx, int *size, int *max_events)
+{
+    if (!ctx) return -1;
+    const KemRegistry *r = ctx->c->registry;
+    if (size) *size = r ? r->hist_size : 0;
+    if (max_events) *max_events = r ? r->hist_max : 0;
+    return 0;
+}
+
+// why a history call is refused before anything starts; nullptr: there is a history and `size` (resolved: < 0 is the current size) is one of its sizes
+static const char *history_refusal(const kosk_ctx *ctx, int &size)
+{
+    const KemRegistry *r = ctx->c->registry;
+    if (!r) return WHY_NO_REGISTRY;
+    if (!r->hist_max) return WHY_NO_HISTORY;
+    if (size < 0) size = r->hist_size;
+    if (size > r->hist_size) return "size is above the current size of the history";
+    return nullptr;
+}
+
+int kosk_registry_history_head(kosk_ctx *ctx, int size, uint8_t root[32], int *size_out)
+{
+    if (!ctx || !root) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_head", why);
+    if (reghist_head(*ctx->c, size, root)) { ctx->err = ctx->c->err; return -1; }
+    if (size_out) *size_out = size;
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_history_checkpoint(kosk_ctx *ctx, int *index)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    int size = -1;
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_checkpoint", why);
+    if (size >= ctx->c->registry->hist_max) return refuse(ctx, "kosk_registry_history_checkpoint", WHY_HISTORY_FULL);
+    if (reghist_checkpoint(*ctx->c, index)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_history_read(kosk_ctx *ctx, int first, int n, uint8_t *events)
+{
+    if (!ctx || n < 1 || first < 0 || !events) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    int size = -1;
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_read", why);
+    if ((long)first + n > size) return refuse(ctx, "kosk_registry_history_read", "events outside [0, size)");
+    if (reghist_read(*ctx->c, first, n, events)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_history_prove_events(kosk_ctx *ctx, int size, int n, const int32_t *index, uint8_t *leaves, uint8_t *records, uint8_t *root)
+{
+    if (!ctx || n < 1 || !index || !records) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_prove_events", why);
+    for (int b = 0; b < n; b++)
+        if (index[b] < 0 || index[b] >= size) return refuse(ctx, "kosk_registry_history_prove_events", "an index outside [0, size)");
+    const size_t rec = reghist::path_bytes(size);
+    if (kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return reghist_prove(c, 0, size, count, index + first, leaves ? leaves + (size_t)first * 32 : nullptr, records + (size_t)first * rec);
+        })) return -1;
+    if (root && reghist_head(*ctx->c, size, root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_history_prove_consistency(kosk_ctx *ctx, int size, int n, const int32_t *old_size, uint8_t *records, uint8_t *root)
+{
+    if (!ctx || n < 1 || !old_size) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_prove_consistency", why);
+    for (int b = 0; b < n; b++)
+        if (old_size[b] < 0 || old_size[b] > size) return refuse(ctx, "kosk_registry_history_prove_consistency", "an old size outside [0, size]");
+    const size_t rec = reghist::consistency_bytes(size); // 0 for the empty history: no record is written
+    if (rec && !records) return bad_args(ctx, __func__);
+    if (rec && kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+            return reghist_prove(c, 1, size, count, old_size + first, nullptr, records + (size_t)first * rec);
+        })) return -1;
+    if (root && reghist_head(*ctx->c, size, root)) { ctx->err = ctx->c->err; return -1; }
     return 0;
     GUARD_END
 }

@@ -80,7 +80,8 @@ enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEM
               PATH_GRAPH_REPLAY, PATH_DIGEST_COPY, PATH_SMALL_COPY_KERNEL, PATH_FS_DEVICE, PATH_FS_HOST, PATH_TAPE_EXPAND, PATH_KEM_ENC, PATH_KEM_DEC, PATH_DENSE_FILL, PATH_KEM_KEYPAIR, PATH_KEM_CHECK, PATH_KEYSEED, PATH_WIPE,
               PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS,
               PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH,
-              PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_COUNT };
+              PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_REGHIST_APPEND, PATH_REGHIST_GROUPS, PATH_REGHIST_FRONTIER, PATH_REGHIST_PROVE,
+              PATH_COUNT };
 
 struct GemmTable {
     uint8_t *dfrag = nullptr; // limb matrix (kosk_device.hpp) in fragment-linear tile order (pack_frag_table)
@@ -699,6 +700,18 @@ struct KemRegistry {
     bool sorted_valid = false;
     // a mutation changed the set of occupied slots or a fingerprint
     void lookups_stale() { index_valid = false; sorted_valid = false; }
+    // the history (kosk-reghist-v1): allocated by kosk_registry_history_reserve, appended to by every mutating call from then
+    // on; a registry without one (hist_max == 0) allocates and launches what it did before
+    int hist_max = 0, hist_size = 0;
+    uint8_t *d_hev = nullptr;    // [hist_max][80] the stored event records
+    uint8_t *d_hnode = nullptr;  // [reghist::nodes_bytes(hist_max)] the complete nodes, level-major; a node is written once
+    uint8_t *d_hrag = nullptr;   // [33][32] R_l of hist_frontier: the ragged nodes, the root at bit_length(size)
+    int32_t *d_hjob = nullptr;   // [KEM_CHUNK][2] (op, slot) of one append launch
+    int32_t *d_hq = nullptr;     // [hstage_cap] the staged indices / old sizes of one launch group
+    uint8_t *d_hleaf = nullptr;  // [hstage_cap][32] the staged leaves
+    uint8_t *d_hproof = nullptr; // [hstage_cap][reghist::consistency_bytes(hist_max)] the staged proof records
+    int hstage_cap = 0;
+    int hist_frontier = -1;      // the size d_hrag belongs to; -1: none yet
 };
 inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
 // One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
@@ -851,6 +864,43 @@ int registry_prove_absent(Ctx &c, int n, const uint8_t *h, uint8_t *kind, uint8_
 // the sort alone on caller-made fingerprints and flags in device memory (h 8-byte aligned): d_order[i] = the index of the i-th entry, -1 from
 // the number of flagged records on.  Synchronised; the records live in a buffer that comes and goes with the call
 int regsort_order_device(Ctx &c, int n, const uint8_t *d_h, const uint8_t *d_flag, int32_t *d_order);
+
+// The history (kosk_reghist.hip, kosk_reghist.hpp).
+// k_reghist_append, one tier: block i owns group (s >> 10 tier >> 10) + i of 1 024 inputs of level 10 tier.  Tier 0 writes the records of
+// events [s, s + c) (from job[e - s] = (op, slot) and h[slot], or, where job is nullptr, the one checkpoint from root_a / root_b / used /
+// capacity), hashes their leaves and loads the older ones; an upper tier loads its inputs.  Then up to 10 levels through LDS: a node is
+// hashed and written iff it became complete, (i + 1) 2^l in (s, s + c], and loaded otherwise
+struct RegHistAppendJob {
+    int tier, D, K, s, c; // D: reghist::depth(hist_max), the layout of `nodes`
+    const int32_t *job;
+    const uint8_t *h, *root_a, *root_b;
+    uint32_t used, capacity;
+    uint8_t *ev, *nodes;
+};
+// k_reghist_frontier: one wave; rag[l + 1] = R_(l + 1) of size n for every l, the fold of the complete subtrees of the set bits of n up to l
+struct RegHistFrontierJob {
+    int D, n;
+    const uint8_t *nodes;
+    uint8_t *rag;
+};
+// k_reghist_prove: a lane pair per query.  kind 0: the inclusion record of leaf q[b] at `size` (and that leaf to leaves, may be nullptr);
+// kind 1: the consistency record from q[b] to `size`.  rec_bytes per record, header, nodes, zero padding
+struct RegHistProveJob {
+    int n, kind, D, size, rec_bytes;
+    const int32_t *q;
+    const uint8_t *nodes, *rag;
+    uint8_t *leaves, *proof;
+};
+// max_events 0 frees; -1 (c.err set) leaves the earlier state
+int reghist_reserve(Ctx &c, int max_events);
+// `count` events (op[i], slot[i]) read against the CURRENT d_h; the caller has checked that they fit.  Queued and synchronised
+int reghist_append(Ctx &c, int count, const int32_t *ops, const int32_t *slots);
+int reghist_checkpoint(Ctx &c, int *index);
+// the root at size (<= hist_size) to `root` (host or device memory)
+int reghist_head(Ctx &c, int size, uint8_t *root);
+int reghist_read(Ctx &c, int first, int n, uint8_t *events);
+// n <= KEM_CHUNK queries (host, validated) at `size`; leaves (kind 0) and records: host or device memory, leaves may be nullptr
+int reghist_prove(Ctx &c, int kind, int size, int n, const int32_t *q, uint8_t *leaves, uint8_t *records);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches
