@@ -650,6 +650,47 @@ int kosk_registry_history_read(kosk_ctx *ctx, int first, int n, uint8_t *events)
 int kosk_registry_history_prove_events(kosk_ctx *ctx, int size, int n, const int32_t *index, uint8_t *leaves, uint8_t *records, uint8_t *root);
 int kosk_registry_history_prove_consistency(kosk_ctx *ctx, int size, int n, const int32_t *old_size, uint8_t *records, uint8_t *root);
 
+/* ---- The registry monitor (INTEGRATION.md 8.8 is the normative text): the third role of the transparency log.  A monitor takes the stored
+ * event log of a registrar (kosk_registry_history_read) and checks that the events replay cleanly onto an empty table and that, at every
+ * checkpoint, the slot root, the sorted root, used and capacity that the registrar bound into the log are those of the replayed table.
+ * A monitor is optional state on a handle, independent of the handle's registry (one handle may hold both): capacity x (a 32-byte
+ * fingerprint and a flag byte) -- no pk bytes, no A^T --, a slot tree (8.5) and a sorted tree (8.6) over that table, and the complete nodes
+ * and 33 ragged slots of a history tree (8.7) over the events fed so far.  It keeps no event records: 32 bytes of HBM per event.
+ * kosk_monitor_reserve: capacity as for kosk_registry_reserve (>= 1), max_events 1 .. 2^24; allowed at any time, a second call starts a
+ * fresh, empty replay; (0, 0) frees; -1 with a text for anything else or an allocation that fails (no monitor is left then).
+ * kosk_monitor_level: events replayed, max_events, occupied slots, capacity, failed (all 0 without a monitor); any pointer may be NULL.
+ * kosk_monitor_feed: the next n >= 1 stored event records of KOSK_REGHIST_EVENT_BYTES each, in log order, host or device memory of any
+ * alignment.  1: all n were accepted and size has grown by n.  0: the log is invalid; *bad_index = the absolute index of the LOWEST invalid
+ * event, *reason = its lowest-numbered reason (both may be NULL).  -1 with a text that begins with the call's name and nothing started:
+ * NULL, n < 1, no monitor, size + n > max_events ("monitor is full"), a monitor that has failed.
+ * The replay rule.  BAD_RECORD: op outside 1..3 or a reserved field that is not zero (the fields kosk_reghist_leaf rejects); BAD_SLOT: an
+ * ADMIT or EVICT with a >= capacity.  An event on slot s sees the state implied by the latest earlier event on s among all events fed so
+ * far -- an ADMIT leaves s occupied with that event's x, an EVICT leaves it empty, no earlier event means empty -- whether or not that
+ * earlier event was itself valid.  ADMIT_OCCUPIED: an ADMIT on an occupied slot; EVICT_EMPTY: an EVICT on an empty slot; EVICT_MISMATCH:
+ * an EVICT whose x differs from the stored 32 bytes.  A CHECKPOINT is checked in this order, the first failure is the reason: a against the
+ * number of occupied slots (CP_USED), b against capacity (CP_CAPACITY), x against the slot tree's root of the replayed table
+ * (CP_SLOT_ROOT), y against the sorted tree's root (CP_SORTED_ROOT); the comparison runs on the device, no root crosses to the host.
+ * After a rejection the monitor is FAILED: kosk_monitor_level reports failed = 1 and a size <= bad_index; the table, both roots and
+ * kosk_monitor_head(size) are exactly those of events [0, size); every later kosk_monitor_feed returns -1 until kosk_monitor_reserve.  How
+ * far below bad_index the size lands is the implementation's segmentation and is not specified.
+ * kosk_monitor_head: the history root at any size <= the current one (< 0: current; size 0 gives O), as kosk_registry_history_head.
+ * kosk_monitor_roots: brings both state trees up to date and returns their roots; either pointer may be NULL.  kosk_monitor_read:
+ * kosk_registry_read without the pk; state = host memory, h = NULL or n x 32 bytes, zeros for an empty slot.  root, slot_root,
+ * sorted_root and h may be host or device memory.
+ * All calls run unmerged on the handle's own stream, also on a cohort member; reserve and feed follow the thread rule of
+ * kosk_registry_reserve, kosk_registry_admit* and kosk_registry_evict.  No monitor call touches the handle's registry, and no registry call
+ * the monitor: kosk_registry_reserve leaves it alone.  A handle that never reserves a monitor allocates and launches what it did before.
+ * Erasure: the monitor's buffers are public entries of the inventory (a log is public): kosk_secret_scan covers them,
+ * kosk_wipe_secrets and KOSK_WIPE_CALL leave them alone.  kosk_destroy and kosk_monitor_reserve(0, 0) free them. */
+enum { KOSK_MONITOR_OK = 0, KOSK_MONITOR_BAD_RECORD = 1, KOSK_MONITOR_BAD_SLOT = 2, KOSK_MONITOR_ADMIT_OCCUPIED = 3, KOSK_MONITOR_EVICT_EMPTY = 4,
+       KOSK_MONITOR_EVICT_MISMATCH = 5, KOSK_MONITOR_CP_USED = 6, KOSK_MONITOR_CP_CAPACITY = 7, KOSK_MONITOR_CP_SLOT_ROOT = 8, KOSK_MONITOR_CP_SORTED_ROOT = 9 };
+int kosk_monitor_reserve(kosk_ctx *ctx, int capacity, int max_events);
+int kosk_monitor_level(const kosk_ctx *ctx, int *size, int *max_events, int *used, int *capacity, int *failed);
+int kosk_monitor_feed(kosk_ctx *ctx, int n, const uint8_t *events, int *bad_index, int *reason);
+int kosk_monitor_head(kosk_ctx *ctx, int size, uint8_t root[32], int *size_out);
+int kosk_monitor_roots(kosk_ctx *ctx, uint8_t slot_root[32], uint8_t sorted_root[32]);
+int kosk_monitor_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -788,7 +829,14 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * tier-0 blocks: ((s + c - 1) >> 10) - (s >> 10) + 1 for c events appended at size s),
  * 40 launches of k_reghist_frontier (the ragged nodes and the root of one size; a second call at the same size launches nothing),
  * 41 launches of k_reghist_prove (one per launch group of kosk_registry_history_prove_events / _prove_consistency; ids 27..37 do not move
- * for kosk_registry_history_head, _read or the proving calls). */
+ * for kosk_registry_history_head, _read or the proving calls),
+ * 42 launches of k_monitor_keys (one per segment of kosk_monitor_feed),
+ * 43 launches of k_monitor_apply (two per segment: check, then commit),
+ * 44 launches of k_monitor_leaves (one per tier-0 append of the monitor's history),
+ * 45 launches of k_monitor_check (one per checkpoint event fed); the kernels the monitor reuses count in their own ids (32, 33, 35, 36,
+ * 38..40) on the monitor's handle: the slot tree's tiers and subtrees, the sort network of every segment and of every rebuild of the
+ * sorted tree, the history's upper tiers and leaf groups, the frontier; ids 42..45 do not move for kosk_monitor_head, _roots, _read or
+ * _level. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

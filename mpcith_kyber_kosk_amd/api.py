@@ -303,6 +303,17 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_registry_history_reserve")):
         sig.update(history)
+    # the registry monitor; optional under the same rule (and only then)
+    monitor = {
+        "kosk_monitor_reserve": (C.c_int, [vp, C.c_int, C.c_int]),
+        "kosk_monitor_level": (C.c_int, [vp, ip, ip, ip, ip, ip]),
+        "kosk_monitor_feed": (C.c_int, [vp, C.c_int, vp, ip, ip]),
+        "kosk_monitor_head": (C.c_int, [vp, C.c_int, vp, ip]),
+        "kosk_monitor_roots": (C.c_int, [vp, vp, vp]),
+        "kosk_monitor_read": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_monitor_reserve")):
+        sig.update(monitor)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -354,7 +365,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_reghist_depth", "kosk_reghist_path_bytes", "kosk_reghist_consistency_bytes", "kosk_reghist_leaf", "kosk_reghist_node",
            "kosk_reghist_empty_root", "kosk_reghist_root_from_path", "kosk_reghist_check_consistency",
            "kosk_registry_history_reserve", "kosk_registry_history_level", "kosk_registry_history_head", "kosk_registry_history_checkpoint",
-           "kosk_registry_history_read", "kosk_registry_history_prove_events", "kosk_registry_history_prove_consistency"]
+           "kosk_registry_history_read", "kosk_registry_history_prove_events", "kosk_registry_history_prove_consistency",
+           "kosk_monitor_reserve", "kosk_monitor_level", "kosk_monitor_feed", "kosk_monitor_head", "kosk_monitor_roots", "kosk_monitor_read"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -510,6 +522,9 @@ def regsort_check_proof(k, depth, x, record, root):
 REGHIST_ADMIT, REGHIST_EVICT, REGHIST_CHECKPOINT = 1, 2, 3  # KOSK_REGHIST_*
 REGHIST_EVENT_BYTES = 80  # KOSK_REGHIST_EVENT_BYTES
 REGHIST_TIER_LEVELS = 10  # KOSK_REGHIST_TIER_LEVELS
+# KOSK_MONITOR_*: why kosk_monitor_feed rejected a log
+MONITOR_OK, MONITOR_BAD_RECORD, MONITOR_BAD_SLOT, MONITOR_ADMIT_OCCUPIED, MONITOR_EVICT_EMPTY = 0, 1, 2, 3, 4
+MONITOR_EVICT_MISMATCH, MONITOR_CP_USED, MONITOR_CP_CAPACITY, MONITOR_CP_SLOT_ROOT, MONITOR_CP_SORTED_ROOT = 5, 6, 7, 8, 9
 
 
 def reghist_depth(size): return lib.kosk_reghist_depth(size)
@@ -1583,6 +1598,61 @@ class Kosk:
         self._chk(lib.kosk_registry_history_prove_consistency(self._h, size, n, op_, records, root), "registry_history_prove_consistency")
         return [records.raw[rec * b:rec * (b + 1)] for b in range(n)], root.raw
 
+    # the registry monitor
+    def monitor_reserve(self, capacity, max_events):
+        """kosk_monitor_reserve: a fresh, empty replay of up to max_events events onto a table of `capacity` slots; (0, 0) frees"""
+        self._chk(lib.kosk_monitor_reserve(self._h, capacity, max_events), "monitor_reserve")
+
+    def monitor_level(self):
+        """kosk_monitor_level -> (size, max_events, used, capacity, failed)"""
+        v = [C.c_int() for _ in range(5)]
+        self._chk(lib.kosk_monitor_level(self._h, *[C.byref(x) for x in v]), "monitor_level")
+        return v[0].value, v[1].value, v[2].value, v[3].value, bool(v[4].value)
+
+    def monitor_feed(self, events, n=None):
+        """kosk_monitor_feed -> (ok, bad_index, reason): the next events of the log, a list of 80-byte records, one bytes object, or an int
+        DEVICE pointer (with n).  ok False: the log is invalid at bad_index for MONITOR_<reason>; (True, -1, MONITOR_OK) otherwise"""
+        if isinstance(events, (bytes, bytearray)):
+            if len(events) % REGHIST_EVENT_BYTES:
+                raise KoskError("an event record has %d bytes" % REGHIST_EVENT_BYTES)
+            blob = bytes(events)
+            ep, n = C.c_char_p(blob), len(blob) // REGHIST_EVENT_BYTES
+        else:
+            ep, n, _k = self._records("event", events, n, REGHIST_EVENT_BYTES)
+        i, why = C.c_int(), C.c_int()
+        r = lib.kosk_monitor_feed(self._h, n, ep, C.byref(i), C.byref(why))
+        if r < 0:
+            self._chk(r, "monitor_feed")
+        return r == 1, i.value, why.value
+
+    def monitor_head(self, size=-1, out=None):
+        """kosk_monitor_head -> (root, size): the history root over the first `size` events fed (< 0: all); out: an int DEVICE pointer to 32
+        bytes, returned in place of the root"""
+        n = C.c_int()
+        buf = C.create_string_buffer(32) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_monitor_head(self._h, size, buf, C.byref(n)), "monitor_head")
+        return (buf.raw if out is None else out), n.value
+
+    def monitor_roots(self, out=None):
+        """kosk_monitor_roots -> (slot_root, sorted_root) of the replayed table; out=(d_slot_root, d_sorted_root): int DEVICE pointers
+        (either may be None), returned as they are"""
+        if out is not None:
+            ptr = [None if p is None else C.c_void_p(int(p)) for p in out]
+            self._chk(lib.kosk_monitor_roots(self._h, ptr[0], ptr[1]), "monitor_roots")
+            return out
+        a, b = C.create_string_buffer(32), C.create_string_buffer(32)
+        self._chk(lib.kosk_monitor_roots(self._h, a, b), "monitor_roots")
+        return a.raw, b.raw
+
+    def monitor_read(self, slots, out=None):
+        """kosk_monitor_read -> (states, hs): occupancy and the fingerprint per named slot of the replayed table (zeros for an empty one);
+        out: an int DEVICE pointer to n x 32 bytes, returned in place of hs"""
+        sp, n = self._slots(slots)
+        state = C.create_string_buffer(max(n, 1))
+        h = C.create_string_buffer(32 * max(n, 1)) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_monitor_read(self._h, n, sp, state, h), "monitor_read")
+        return list(state.raw[:n]), (_cut(h, 32, n) if out is None else out)
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1741,6 +1811,10 @@ class Kosk:
     PATH_REGHIST_GROUPS = 39
     PATH_REGHIST_FRONTIER = 40
     PATH_REGHIST_PROVE = 41
+    PATH_MONITOR_KEYS = 42
+    PATH_MONITOR_APPLY = 43
+    PATH_MONITOR_LEAVES = 44
+    PATH_MONITOR_CHECK = 45
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -1867,6 +1867,96 @@ int kosk_registry_history_prove_consistency(kosk_ctx *ctx, int size, int n, cons
     GUARD_END
 }
 
+// ---- the registry monitor (kosk_monitor.hip) ----
+static_assert((int)KOSK_MONITOR_OK == (int)MONITOR_OK && (int)KOSK_MONITOR_BAD_RECORD == (int)MONITOR_BAD_RECORD && (int)KOSK_MONITOR_BAD_SLOT == (int)MONITOR_BAD_SLOT &&
+              (int)KOSK_MONITOR_ADMIT_OCCUPIED == (int)MONITOR_ADMIT_OCCUPIED && (int)KOSK_MONITOR_EVICT_EMPTY == (int)MONITOR_EVICT_EMPTY &&
+              (int)KOSK_MONITOR_EVICT_MISMATCH == (int)MONITOR_EVICT_MISMATCH && (int)KOSK_MONITOR_CP_USED == (int)MONITOR_CP_USED &&
+              (int)KOSK_MONITOR_CP_CAPACITY == (int)MONITOR_CP_CAPACITY && (int)KOSK_MONITOR_CP_SLOT_ROOT == (int)MONITOR_CP_SLOT_ROOT &&
+              (int)KOSK_MONITOR_CP_SORTED_ROOT == (int)MONITOR_CP_SORTED_ROOT, "kosk_mi355x.h and kosk_ctx.hpp");
+static const char *const WHY_NO_MONITOR = "no monitor is reserved (kosk_monitor_reserve)";
+
+int kosk_monitor_reserve(kosk_ctx *ctx, int capacity, int max_events)
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (capacity < 0) return refuse(ctx, "kosk_monitor_reserve", "capacity < 0");
+    if (max_events < 0 || max_events > reghist::MAX_EVENTS) return refuse(ctx, "kosk_monitor_reserve", "max_events outside 0 .. 2^24");
+    if (!capacity != !max_events) return refuse(ctx, "kosk_monitor_reserve", "capacity and max_events are both at least 1, or both 0 (free)");
+    if (monitor_reserve(*ctx->c, capacity, max_events)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_monitor_level(const kosk_ctx *ctx, int *size, int *max_events, int *used, int *capacity, int *failed)
+{
+    if (!ctx) return -1;
+    const KemRegistry *r = ctx->c->monitor;
+    if (size) *size = r ? r->hist_size : 0;
+    if (max_events) *max_events = r ? r->hist_max : 0;
+    if (used) *used = r ? r->used : 0;
+    if (capacity) *capacity = r ? r->capacity : 0;
+    if (failed) *failed = r && r->mon_failed;
+    return 0;
+}
+
+int kosk_monitor_feed(kosk_ctx *ctx, int n, const uint8_t *events, int *bad_index, int *reason)
+{
+    if (!ctx || n < 1 || !events) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    const KemRegistry *r = ctx->c->monitor;
+    if (!r) return refuse(ctx, "kosk_monitor_feed", WHY_NO_MONITOR);
+    if (r->mon_failed) return refuse(ctx, "kosk_monitor_feed", "the monitor has failed: a fed log was rejected (kosk_monitor_reserve starts a fresh replay)");
+    if ((long)r->hist_size + n > (long)r->hist_max) return refuse(ctx, "kosk_monitor_feed", "monitor is full (kosk_monitor_reserve): nothing was changed");
+    if (bad_index) *bad_index = -1;
+    if (reason) *reason = KOSK_MONITOR_OK;
+    const int rc = monitor_feed(*ctx->c, n, events, bad_index, reason);
+    if (rc < 0) ctx->err = ctx->c->err;
+    return rc;
+    GUARD_END
+}
+
+int kosk_monitor_head(kosk_ctx *ctx, int size, uint8_t root[32], int *size_out)
+{
+    if (!ctx || !root) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    KemRegistry *r = ctx->c->monitor;
+    if (!r) return refuse(ctx, "kosk_monitor_head", WHY_NO_MONITOR);
+    if (size < 0) size = r->hist_size;
+    if (size > r->hist_size) return refuse(ctx, "kosk_monitor_head", "size is above the current size of the monitor's history");
+    if (reghist_head(*ctx->c, *r, size, root)) { ctx->err = ctx->c->err; return -1; }
+    if (size_out) *size_out = size;
+    return 0;
+    GUARD_END
+}
+
+int kosk_monitor_roots(kosk_ctx *ctx, uint8_t slot_root[32], uint8_t sorted_root[32])
+{
+    if (!ctx) return -1;
+    GUARD(ctx)
+    ctx->clear_err();
+    if (!ctx->c->monitor) return refuse(ctx, "kosk_monitor_roots", WHY_NO_MONITOR);
+    if (monitor_roots(*ctx->c, slot_root, sorted_root)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_monitor_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h)
+{
+    if (!ctx || n < 1 || !slots || !state) return bad_args(ctx, __func__);
+    GUARD(ctx)
+    ctx->clear_err();
+    const KemRegistry *r = ctx->c->monitor;
+    if (!r) return refuse(ctx, "kosk_monitor_read", WHY_NO_MONITOR);
+    for (int b = 0; b < n; b++)
+        if (slots[b] < 0 || slots[b] >= r->capacity) return refuse(ctx, "kosk_monitor_read", "a slot id outside [0, capacity)");
+    if (monitor_read(*ctx->c, n, slots, state, h)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
 // ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----
 int kosk_witness_from_sk(kosk_ctx *ctx, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
 {

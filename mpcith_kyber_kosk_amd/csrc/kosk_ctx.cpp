@@ -64,6 +64,7 @@ Ctx::~Ctx()
     transcode_release(*this);
     kem_key_release(*this);
     registry_release(*this);
+    monitor_release(*this);
     inv.release_all();
     if (pool) pool_destroy(pool);
     if (stream && !is_view) (void)hipStreamDestroy(stream); // a view's stream is its arena's

@@ -81,6 +81,7 @@ enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEM
               PATH_KEM_KEY_SETUP, PATH_KEM_ENC_KEY, PATH_KEM_DEC_KEY, PATH_DENSE_CHECK, PATH_DENSE2_FILL, PATH_DENSE2_CHECK, PATH_BANK_PUT, PATH_BANK_TAKE, PATH_REGISTRY_ADMIT, PATH_KEM_ENC_SLOTS,
               PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH,
               PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_REGHIST_APPEND, PATH_REGHIST_GROUPS, PATH_REGHIST_FRONTIER, PATH_REGHIST_PROVE,
+              PATH_MONITOR_KEYS, PATH_MONITOR_APPLY, PATH_MONITOR_LEAVES, PATH_MONITOR_CHECK,
               PATH_COUNT };
 
 struct GemmTable {
@@ -384,6 +385,7 @@ struct CtxPrivate {
     KemWs *kem = nullptr; // allocated at this context's first KEM call, owned by it (a view's is its own, never the arena's)
     KemKey *kem_key = nullptr; // the key slot: allocated at the first kem_key_set, its own allocation (kem_ensure never moves it), owned like `kem`
     KemRegistry *registry = nullptr; // the verified-key registry: allocated by registry_reserve, its own allocations, owned like `kem`
+    KemRegistry *monitor = nullptr;  // the registry monitor (kosk_monitor.hip): allocated by monitor_reserve, owned like `registry`
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -712,6 +714,15 @@ struct KemRegistry {
     uint8_t *d_hproof = nullptr; // [hstage_cap][reghist::consistency_bytes(hist_max)] the staged proof records
     int hstage_cap = 0;
     int hist_frontier = -1;      // the size d_hrag belongs to; -1: none yet
+    // the monitor (kosk_monitor.hip) is a registry of fingerprints and flags alone (d_pk == d_A == nullptr, no mirror, no
+    // event records) whose buffers come and go with INVG_MONITOR; the tree, sorted-tree and history functions below take either
+    int inv_group = Inventory::INVG_REGISTRY;
+    bool mon_failed = false;     // a feed was rejected: the state is that of events [0, hist_size) until the monitor is reserved again
+    uint8_t *d_mstage = nullptr; // [KEM_CHUNK][80] the stored records of one launch group, 16-byte aligned
+    uint8_t *d_mrec = nullptr;   // [KEM_CHUNK][16] the sort records of one segment
+    uint32_t *d_mword = nullptr; // [0] the verdict: (index << 8) | reason of the lowest invalid event, MONITOR_WORD_OK while there is none; [1] used
+    // the inventory name of a buffer: "registry.<field>" or "monitor.<field>"
+    const char *buf_name(const char *registry_name, const char *monitor_name) const { return inv_group == Inventory::INVG_REGISTRY ? registry_name : monitor_name; }
 };
 inline size_t registry_slot_bytes(int K) { return (size_t)384 * K + 32 + 32 + (size_t)K * K * 512 + 1; }
 // One launch of k_registry_admit: key b of n (16-byte aligned records in HBM, `src_stride` apart, a multiple of 16) into slot[b] (device
@@ -813,11 +824,13 @@ struct RegPathJob {
 hipError_t launch_registry_tree(const RegTreeJob &j, unsigned blocks, hipStream_t st);
 hipError_t launch_registry_path(const RegPathJob &j, hipStream_t st);
 // the tree allocated and current: a no-op while tree_valid; else the tiers, synchronised
-int registry_tree_ensure(Ctx &c);
+int registry_tree_ensure(Ctx &c, KemRegistry &r);
+inline int registry_tree_ensure(Ctx &c) { return registry_tree_ensure(c, *c.registry); }
 // r.d_paths holds n items' paths
 int registry_paths_ensure(Ctx &c, int n);
 // the root of the current tree to `root` (host or device memory); synchronised
-int registry_root(Ctx &c, uint8_t *root);
+int registry_root(Ctx &c, KemRegistry &r, uint8_t *root);
+inline int registry_root(Ctx &c, uint8_t *root) { return registry_root(c, *c.registry, root); }
 // n <= KEM_CHUNK paths.  slots != nullptr (host; valid ids): of those slots, with their stored fingerprints to hout (or nullptr); else of the
 // lowest occupied slots that hold the fingerprints h (k_registry_find in front), with those slots to slots_out and found to done.  paths (may
 // be nullptr when D = 0), hout, slots_out, done: host or device memory.  Synchronised; what was staged in the KEM workspace is zeroed
@@ -840,6 +853,8 @@ struct RegSortJob {
     int32_t *order;      // k_regsort_order: record i < n to its slot, or -1 for class 1
 };
 int regsort_sort(Ctx &c, const RegSortJob &j);
+// the network alone, over records that are in place (k_monitor_keys wrote them): what regsort_sort runs behind k_regsort_keys
+int regsort_network(Ctx &c, const RegSortJob &j);
 // k_regsort_tree, one tier, the shape of k_registry_tree: tier 0 forms S(h[slot], slot) from record i < used and Z from there on
 struct RegSortTreeJob {
     int tier, D, K, used;
@@ -855,9 +870,11 @@ struct RegSortProveJob {
     uint8_t *kind, *proof;
 };
 // the sorted tree allocated and current: a no-op while sorted_valid; else keys, sort, tiers, synchronised
-int registry_sorted_ensure(Ctx &c);
+int registry_sorted_ensure(Ctx &c, KemRegistry &r);
+inline int registry_sorted_ensure(Ctx &c) { return registry_sorted_ensure(c, *c.registry); }
 // the root of the current sorted tree to `root` (host or device memory); synchronised
-int registry_sorted_root(Ctx &c, uint8_t *root);
+int registry_sorted_root(Ctx &c, KemRegistry &r, uint8_t *root);
+inline int registry_sorted_root(Ctx &c, uint8_t *root) { return registry_sorted_root(c, *c.registry, root); }
 // n <= KEM_CHUNK queries (host or device memory of any alignment) -> kind[b] and one proof record each.  Synchronised; the staged queries
 // are zeroed
 int registry_prove_absent(Ctx &c, int n, const uint8_t *h, uint8_t *kind, uint8_t *records);
@@ -876,6 +893,7 @@ struct RegHistAppendJob {
     const uint8_t *h, *root_a, *root_b;
     uint32_t used, capacity;
     uint8_t *ev, *nodes;
+    const uint8_t *rec; // k_monitor_leaves: the stored records of events [s, s + c), 16-byte aligned
 };
 // k_reghist_frontier: one wave; rag[l + 1] = R_(l + 1) of size n for every l, the fold of the complete subtrees of the set bits of n up to l
 struct RegHistFrontierJob {
@@ -897,10 +915,50 @@ int reghist_reserve(Ctx &c, int max_events);
 int reghist_append(Ctx &c, int count, const int32_t *ops, const int32_t *slots);
 int reghist_checkpoint(Ctx &c, int *index);
 // the root at size (<= hist_size) to `root` (host or device memory)
-int reghist_head(Ctx &c, int size, uint8_t *root);
+int reghist_head(Ctx &c, KemRegistry &r, int size, uint8_t *root);
+inline int reghist_head(Ctx &c, int size, uint8_t *root) { return reghist_head(c, *c.registry, size, root); }
+// the tiers of one append of cnt events to r's history of s events.  j.rec != nullptr: tier 0 is k_monitor_leaves over those stored records;
+// else j.job names the events, or (j.job == nullptr) j carries the operands of one checkpoint.  Queued, not synchronised
+int reghist_append_launch(Ctx &c, KemRegistry &r, RegHistAppendJob j, int s, int cnt);
 int reghist_read(Ctx &c, int first, int n, uint8_t *events);
 // n <= KEM_CHUNK queries (host, validated) at `size`; leaves (kind 0) and records: host or device memory, leaves may be nullptr
 int reghist_prove(Ctx &c, int kind, int size, int n, const int32_t *q, uint8_t *leaves, uint8_t *records);
+
+// The registry monitor (kosk_monitor.hip): the replay of a stored event log onto a table of fingerprints and
+// flags, with every checkpoint's roots, used and capacity compared in HBM.
+enum { MONITOR_OK = 0, MONITOR_BAD_RECORD = 1, MONITOR_BAD_SLOT = 2, MONITOR_ADMIT_OCCUPIED = 3, MONITOR_EVICT_EMPTY = 4, MONITOR_EVICT_MISMATCH = 5,
+       MONITOR_CP_USED = 6, MONITOR_CP_CAPACITY = 7, MONITOR_CP_SLOT_ROOT = 8, MONITOR_CP_SORTED_ROOT = 9 };
+enum : uint32_t { MONITOR_WORD_OK = 0xFFFFFFFFu };
+// One segment: n staged records (ev, 80 bytes each, 16-byte aligned) of absolute indices base .. base + n - 1.
+// k_monitor_keys: the record check and the 16-byte sort records (prefix = (slot << 32) | position, class 0; an invalid record and the
+// positions from n to 2^lg are class 1).  k_monitor_apply over the sorted records: commit == 0 checks the ADMIT / EVICT rule against the
+// previous event of the same slot or the table and writes nothing to the table; commit == 1 returns at once where word[0] is set, else
+// writes every touched slot's final flag and fingerprint and adds the net change of `used` to word[1]
+struct MonitorJob {
+    int n, lg, base, capacity, commit;
+    const uint8_t *ev;
+    uint8_t *rec, *h, *flag;
+    uint32_t *word;
+};
+// k_monitor_check, one wave: the staged checkpoint record against word[1], capacity and the two root nodes; the verdict to word[0]
+struct MonitorCheckJob {
+    int index, capacity;
+    const uint8_t *ev, *root_a, *root_b;
+    uint32_t *word;
+};
+hipError_t launch_monitor_keys(const MonitorJob &j, hipStream_t st);
+hipError_t launch_monitor_apply(const MonitorJob &j, hipStream_t st);
+hipError_t launch_monitor_check(const MonitorCheckJob &j, hipStream_t st);
+hipError_t launch_monitor_leaves(const RegHistAppendJob &j, unsigned blocks, hipStream_t st);
+// (0, 0) frees; any other pair starts a fresh, empty replay; -1 (c.err set) leaves no monitor
+int monitor_reserve(Ctx &c, int capacity, int max_events);
+void monitor_release(Ctx &c);
+// the next n events (host or device memory of any alignment; the caller has checked that they fit): 1 accepted, 0 rejected with the lowest
+// invalid index and its lowest reason, -1 an error
+int monitor_feed(Ctx &c, int n, const uint8_t *events, int *bad_index, int *reason);
+int monitor_roots(Ctx &c, uint8_t *slot_root, uint8_t *sorted_root);
+// registry_read without the pk: the flags are read from HBM (a monitor keeps no mirror)
+int monitor_read(Ctx &c, int n, const int32_t *slots, uint8_t *state, uint8_t *h);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches

@@ -14,6 +14,7 @@
 #include "kosk_keccak_wave_dev.hpp"
 #include "kosk_kem_dev.hpp"
 #include "kosk_reghist.hpp"
+#include "kosk_reghist_dev.hpp"
 
 namespace kosk {
 
@@ -21,32 +22,15 @@ using namespace kem;
 
 #define HIPCHK(x) KOSK_HIPCHK(x)
 
-__device__ __forceinline__ U128 words_u128(uint64_t a, uint64_t b) { return U128{(uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32)}; }
-__device__ __forceinline__ void reghist_store(uint8_t *dst, const uint64_t (&d)[4])
-{
-    U128 *o = reinterpret_cast<U128 *>(dst);
-    o[0] = words_u128(d[0], d[1]);
-    o[1] = words_u128(d[2], d[3]);
-}
-__device__ __forceinline__ void reghist_load(const uint8_t *src, uint64_t (&d)[4])
-{
-    const U128 a = reinterpret_cast<const U128 *>(src)[0], b = reinterpret_cast<const U128 *>(src)[1];
-    d[0] = (uint64_t)a.x | (uint64_t)a.y << 32; d[1] = (uint64_t)a.z | (uint64_t)a.w << 32;
-    d[2] = (uint64_t)b.x | (uint64_t)b.y << 32; d[3] = (uint64_t)b.z | (uint64_t)b.w << 32;
-}
-
-// One block, one group of a tier.  so / ne: the complete nodes of the tier's input level before and after the append; the group holds `cnt`
-// of them.  Node i of level lv above (numbered from the group's first) is fresh iff it became complete with this append; a node that was
-// complete before is loaded, for the level above may need it.  All loop bounds are block-uniform.
+// One block, one group of a tier (reghist_group): the new events' records and leaves, the older inputs loaded, then the levels above
+// (reghist_levels, kosk_reghist_dev.hpp).  All loop bounds are block-uniform.
 __global__ __launch_bounds__(256) void k_reghist_append(RegHistAppendJob j)
 {
     __shared__ __align__(16) uint64_t lds[(reghist::TIER_INPUTS + reghist::TIER_INPUTS / 2) * 4];
-    const int tid = threadIdx.x, L0 = j.tier * reghist::TIER_LEVELS;
-    const int so = j.s >> L0, ne = (j.s + j.c) >> L0;
-    const int lo = ((so >> reghist::TIER_LEVELS) + (int)blockIdx.x) << reghist::TIER_LEVELS;
-    const int cnt = ne - lo < (int)reghist::TIER_INPUTS ? ne - lo : (int)reghist::TIER_INPUTS;
-    const int up = j.D - L0 < (int)reghist::TIER_LEVELS ? j.D - L0 : (int)reghist::TIER_LEVELS;
-    uint8_t *in_lvl = j.nodes + regtree::level_offset(j.D, L0) + (size_t)lo * 32;
+    const int tid = threadIdx.x;
+    const RegHistGroup g = reghist_group(j);
+    const int lo = g.lo, cnt = g.cnt;
+    uint8_t *in_lvl = g.in_lvl;
     for (int i = tid; i < cnt; i += 256) {
         const int e = lo + i;
         uint64_t d[4];
@@ -79,31 +63,7 @@ __global__ __launch_bounds__(256) void k_reghist_append(RegHistAppendJob j)
         for (int l = 0; l < 4; l++) lds[4 * i + l] = d[l];
     }
     __syncthreads();
-    int in = 0, out = reghist::TIER_INPUTS * 4; // word offsets of the two buffers
-    for (int lv = 1; lv <= up && (cnt >> lv); lv++) {
-        const int m = cnt >> lv;
-        const size_t first = (size_t)lo >> lv;
-        uint8_t *dst = j.nodes + regtree::level_offset(j.D, L0 + lv) + first * 32;
-        for (int i = tid; i < m; i += 256) {
-            uint64_t l[4];
-            if (((uint64_t)(first + i + 1) << (L0 + lv)) > (uint64_t)j.s) {
-                uint64_t r[4], st[25];
-#pragma unroll
-                for (int w = 0; w < 4; w++) { l[w] = lds[in + 8 * i + w]; r[w] = lds[in + 8 * i + 4 + w]; }
-                reghist::node_state(st, l, r);
-                perm(st);
-#pragma unroll
-                for (int w = 0; w < 4; w++) l[w] = st[w];
-                reghist_store(dst + (size_t)i * 32, l);
-            } else {
-                reghist_load(dst + (size_t)i * 32, l);
-            }
-#pragma unroll
-            for (int w = 0; w < 4; w++) lds[out + 4 * i + w] = l[w];
-        }
-        __syncthreads();
-        const int t = in; in = out; out = t;
-    }
+    reghist_levels(j, g, lds);
 }
 
 // One wave.  acc = the fold of the complete subtrees of the set bits of n from the lowest up to l: R_(l + 1), the hash of the trailing leaves
@@ -222,18 +182,22 @@ int reghist_reserve(Ctx &c, int max_events)
 }
 
 // the tiers of one append of cnt events to a history of s; job == nullptr: the checkpoint whose operands j carries
-static int append_launch(Ctx &c, RegHistAppendJob j, int s, int cnt)
+int reghist_append_launch(Ctx &c, KemRegistry &r, RegHistAppendJob j, int s, int cnt)
 {
-    KemRegistry &r = *c.registry;
     j.D = reghist::depth(r.hist_max); j.K = c.P.K; j.s = s; j.c = cnt; j.ev = r.d_hev; j.nodes = r.d_hnode;
     for (int t = 0; t * reghist::TIER_LEVELS <= j.D; t++) {
         const int L0 = t * reghist::TIER_LEVELS, so = s >> L0, ne = (s + cnt) >> L0;
         if (ne == so || (t && L0 >= j.D)) break; // no node of this level became complete: none above it did
         const unsigned blocks = (unsigned)(((ne - 1) >> reghist::TIER_LEVELS) - (so >> reghist::TIER_LEVELS) + 1);
         j.tier = t;
-        k_reghist_append<<<dim3(blocks), dim3(256), 0, c.stream>>>(j);
-        HIPCHK(hipGetLastError());
-        c.path_n[PATH_REGHIST_APPEND]++;
+        if (j.rec && !t) {
+            HIPCHK(launch_monitor_leaves(j, blocks, c.stream));
+            c.path_n[PATH_MONITOR_LEAVES]++;
+        } else {
+            k_reghist_append<<<dim3(blocks), dim3(256), 0, c.stream>>>(j);
+            HIPCHK(hipGetLastError());
+            c.path_n[PATH_REGHIST_APPEND]++;
+        }
         if (!t) c.path_n[PATH_REGHIST_GROUPS] += (long)blocks;
     }
     return 0;
@@ -252,7 +216,7 @@ int reghist_append(Ctx &c, int count, const int32_t *ops, const int32_t *slots)
         HIPCHK(hipMemcpyAsync(r.d_hjob, jobs.data(), jobs.size() * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
         RegHistAppendJob j{};
         j.job = r.d_hjob; j.h = r.d_h;
-        if (append_launch(c, j, r.hist_size, cnt)) return -1;
+        if (reghist_append_launch(c, r, j, r.hist_size, cnt)) return -1;
         HIPCHK(stream_sync(c)); // the job list is free again, and the events are in place before the caller mutates d_h
         r.hist_size += cnt;
     }
@@ -270,7 +234,7 @@ int reghist_checkpoint(Ctx &c, int *index)
     j.root_a = r.d_tree + regtree::level_offset(D, D); // both roots are read where they lie
     j.root_b = r.d_stree + regtree::level_offset(D, D);
     j.used = (uint32_t)r.used; j.capacity = (uint32_t)r.capacity;
-    if (append_launch(c, j, r.hist_size, 1)) return -1;
+    if (reghist_append_launch(c, r, j, r.hist_size, 1)) return -1;
     HIPCHK(stream_sync(c));
     if (index) *index = r.hist_size;
     r.hist_size++;
@@ -278,9 +242,8 @@ int reghist_checkpoint(Ctx &c, int *index)
 }
 
 // d_hrag holds the ragged nodes and the root of `size` >= 1: queued, not synchronised; a second call at the same size launches nothing
-static int frontier_ensure(Ctx &c, int size)
+static int frontier_ensure(Ctx &c, KemRegistry &r, int size)
 {
-    KemRegistry &r = *c.registry;
     if (r.hist_frontier == size) return 0;
     RegHistFrontierJob j{};
     j.D = reghist::depth(r.hist_max); j.n = size; j.nodes = r.d_hnode; j.rag = r.d_hrag;
@@ -292,9 +255,8 @@ static int frontier_ensure(Ctx &c, int size)
     return 0;
 }
 
-int reghist_head(Ctx &c, int size, uint8_t *root)
+int reghist_head(Ctx &c, KemRegistry &r, int size, uint8_t *root)
 {
-    KemRegistry &r = *c.registry;
     HIPCHK(hipSetDevice(c.device));
     const bool dev = is_device_pointer(root);
     if (!size) {
@@ -304,7 +266,7 @@ int reghist_head(Ctx &c, int size, uint8_t *root)
         else memcpy(root, o, 32);
         return 0;
     }
-    if (frontier_ensure(c, size)) return -1;
+    if (frontier_ensure(c, r, size)) return -1;
     int top = 0;
     while ((size >> top) > 1) top++;
     HIPCHK(hipMemcpyAsync(root, r.d_hrag + (size_t)(top + 1) * 32, 32, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
@@ -349,7 +311,7 @@ int reghist_prove(Ctx &c, int kind, int size, int n, const int32_t *q, uint8_t *
     if (staging_ensure(c, n)) return -1;
     const KemRegistry &r = *c.registry;
     HIPCHK(hipMemcpyAsync(r.d_hq, q, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
-    if (frontier_ensure(c, size)) return -1;
+    if (frontier_ensure(c, *c.registry, size)) return -1;
     RegHistProveJob j{};
     j.n = n; j.kind = kind; j.D = reghist::depth(r.hist_max); j.size = size;
     j.rec_bytes = (int)(kind ? reghist::consistency_bytes(size) : reghist::path_bytes(size));

@@ -305,16 +305,15 @@ static int regtree_wave_tail()
     return v < 0 ? 0 : v > 64 ? 64 : v;
 }
 
-int registry_tree_ensure(Ctx &c)
+int registry_tree_ensure(Ctx &c, KemRegistry &r)
 {
-    KemRegistry &r = *c.registry;
     if (r.tree_valid) return 0;
     HIPCHK(hipSetDevice(c.device));
     const int D = regtree::depth(r.capacity), S = regtree::subtrees(D), T = regtree::tiers(D);
     if (!r.d_tree) { // public, both: hashes of public fingerprints, subtree numbers
-        const int G = Inventory::INVG_REGISTRY;
-        HIPCHK(c.own("registry.d_dirty", &r.d_dirty, (size_t)S * sizeof(int32_t), 0, G));
-        if (c.own("registry.d_tree", &r.d_tree, regtree::tree_bytes(r.capacity), 0, G) != hipSuccess) { // both or neither
+        const int G = r.inv_group;
+        HIPCHK(c.own(r.buf_name("registry.d_dirty", "monitor.d_dirty"), &r.d_dirty, (size_t)S * sizeof(int32_t), 0, G));
+        if (c.own(r.buf_name("registry.d_tree", "monitor.d_tree"), &r.d_tree, regtree::tree_bytes(r.capacity), 0, G) != hipSuccess) { // both or neither
             void **at = reinterpret_cast<void **>(&r.d_dirty);
             c.inv.release_if([at](const InvBuf &b) { return b.at == at; });
             (void)hipGetLastError();
@@ -369,10 +368,9 @@ int registry_paths_ensure(Ctx &c, int n)
     return 0;
 }
 
-int registry_root(Ctx &c, uint8_t *root)
+int registry_root(Ctx &c, KemRegistry &r, uint8_t *root)
 {
-    if (registry_tree_ensure(c)) return -1;
-    const KemRegistry &r = *c.registry;
+    if (registry_tree_ensure(c, r)) return -1;
     const int D = regtree::depth(r.capacity);
     HIPCHK(hipMemcpyAsync(root, r.d_tree + regtree::level_offset(D, D), 32, is_device_pointer(root) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
     HIPCHK(stream_sync(c));

@@ -292,16 +292,21 @@ static hipError_t launch_tile(const RegSortJob &j, int T, unsigned tiles, hipStr
     return hipGetLastError();
 }
 
-int regsort_sort(Ctx &c, const RegSortJob &job)
+int regsort_sort(Ctx &c, const RegSortJob &j)
+{
+    k_regsort_keys<<<dim3(blocks_of((size_t)1 << j.lg, 256)), dim3(256), 0, c.stream>>>(j);
+    HIPCHK(hipGetLastError());
+    c.path_n[PATH_REGSORT_SORT]++;
+    return regsort_network(c, j);
+}
+
+int regsort_network(Ctx &c, const RegSortJob &job)
 {
     RegSortJob j = job;
     const int T = regsort_tile_lg();
     const size_t N = (size_t)1 << j.lg;
     const unsigned tiles = j.lg > T ? 1u << (j.lg - T) : 1u;
     const bool two = regsort_step2();
-    k_regsort_keys<<<dim3(blocks_of(N, 256)), dim3(256), 0, c.stream>>>(j);
-    HIPCHK(hipGetLastError());
-    c.path_n[PATH_REGSORT_SORT]++;
     j.phase = 0;
     HIPCHK(launch_tile(j, T, tiles, c.stream));
     c.path_n[PATH_REGSORT_SORT]++;
@@ -332,16 +337,15 @@ static void release_fields(Ctx &c, void *lo, void *hi)
     (void)hipGetLastError();
 }
 
-int registry_sorted_ensure(Ctx &c)
+int registry_sorted_ensure(Ctx &c, KemRegistry &r)
 {
-    KemRegistry &r = *c.registry;
     if (r.sorted_valid) return 0;
     HIPCHK(hipSetDevice(c.device));
     const int D = regtree::depth(r.capacity), T = regtree::tiers(D);
     if (!r.d_stree) { // public, both: slot numbers, prefixes and hashes of public fingerprints
-        const int G = Inventory::INVG_REGISTRY;
-        if (c.own("registry.d_srec", &r.d_srec, (size_t)16 << D, 0, G) != hipSuccess ||
-            c.own("registry.d_stree", &r.d_stree, regtree::tree_bytes(r.capacity), 0, G) != hipSuccess) { // both or neither
+        const int G = r.inv_group;
+        if (c.own(r.buf_name("registry.d_srec", "monitor.d_srec"), &r.d_srec, (size_t)16 << D, 0, G) != hipSuccess ||
+            c.own(r.buf_name("registry.d_stree", "monitor.d_stree"), &r.d_stree, regtree::tree_bytes(r.capacity), 0, G) != hipSuccess) { // both or neither
             release_fields(c, &r.d_srec, &r.d_stree + 1);
             c.err = "registry_sorted_ensure: out of memory for the sorted tree";
             return -1;
@@ -369,10 +373,9 @@ int registry_sorted_ensure(Ctx &c)
     return 0;
 }
 
-int registry_sorted_root(Ctx &c, uint8_t *root)
+int registry_sorted_root(Ctx &c, KemRegistry &r, uint8_t *root)
 {
-    if (registry_sorted_ensure(c)) return -1;
-    const KemRegistry &r = *c.registry;
+    if (registry_sorted_ensure(c, r)) return -1;
     const int D = regtree::depth(r.capacity);
     HIPCHK(hipMemcpyAsync(root, r.d_stree + regtree::level_offset(D, D), 32, is_device_pointer(root) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
     HIPCHK(stream_sync(c));
