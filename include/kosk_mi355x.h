@@ -691,6 +691,34 @@ int kosk_monitor_head(kosk_ctx *ctx, int size, uint8_t root[32], int *size_out);
 int kosk_monitor_roots(kosk_ctx *ctx, uint8_t slot_root[32], uint8_t sorted_root[32]);
 int kosk_monitor_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state, uint8_t *h);
 
+/* ---- The relying party (INTEGRATION.md 8.9 is the normative text): the role the log exists for.  A relying party holds a signed history
+ * head, has checked a checkpoint event's inclusion under it on the host (kosk_reghist_root_from_path) and taken slot_root and sorted_root
+ * from that event; peers then send their public keys with proofs under those roots.  It has no registry: these calls need no registry,
+ * monitor or history on the handle and touch none.  All items of a call are checked against ONE root; kyber_k is the handle's.
+ * kosk_regtree_check_paths: ok[b] = 1 iff kosk_regtree_root_from_path(kyber_k, depth, slots[b], state[b] ? h + 32 b : NULL, paths_b, r)
+ * returns 0 and r equals root, else 0 -- a slot outside [0, 2^depth) gives 0.  paths: n x depth x 32 bytes (may be NULL when depth = 0);
+ * state: NULL (every item claims "occupied, fingerprint h[b]") or n bytes, a zero byte claims "slot b is empty" and h[b] is ignored; h may
+ * be NULL only if state is given and all zero (an "occupied" claim without fingerprints gives 0).
+ * kosk_regsort_check_proofs: verdict[b] = exactly what kosk_regsort_check_proof(kyber_k, depth, x_b, record_b, root) returns: 0, 1 (ABSENT)
+ * or 2 (PRESENT).  x: n x 32 bytes; records: n x kosk_regsort_proof_bytes(depth).
+ * kosk_kem_enc_proven: pk = n records of kosk_pk_bytes; the call computes h_b = SHA3-256(pk_b) on the device, over the bytes as given;
+ * done[b] = the verdict of kosk_regtree_check_paths for (slots[b], occupied, h_b, paths_b); where done[b] = 1, ct and ss are byte for byte
+ * those of kosk_kem_enc_batch on pk_b with the same coins (fields >= q fold as there); where done[b] = 0 they are zero-filled, as for a miss
+ * of kosk_kem_enc_peers.  The verdict reaches the encapsulation as its mask in HBM: no key whose path fails gets a ciphertext, and no
+ * verdict crosses to the host in between.  Coins are consumed for every position: with coins == NULL one 32-byte draw per item, in item
+ * order, on the caller's thread; a refused call draws none.  "block limit" behaves as for kosk_kem_enc_batch.
+ * Any n >= 1, in launch groups of 16384; unmerged on the handle's own stream, also on a cohort member.  Every array may be host or device
+ * memory of any alignment; slots too (untrusted peer data, not inspected on the host).  -1 with a text that begins with the call's name and
+ * nothing started: a NULL required argument, n < 1, depth outside 0..31.  Whatever a peer could have sent wrong is a verdict, never a
+ * refusal.
+ * Erasure: the staging buffers (paths and proof records, fingerprints, slots, claims, verdicts) are public entries of
+ * the inventory, made at the first of these calls: kosk_secret_scan covers them, kosk_wipe_secrets and KOSK_WIPE_CALL leave them alone.  The
+ * per-call scratch of kosk_kem_enc_proven (coins, K-bar || coins, noise, ss) is secret exactly as for kosk_kem_enc_batch.  A handle that
+ * never makes one of these calls allocates and launches what it did before. */
+int kosk_regtree_check_paths(kosk_ctx *ctx, int n, int depth, const int32_t *slots, const uint8_t *state, const uint8_t *h, const uint8_t *paths, const uint8_t root[32], uint8_t *ok);
+int kosk_regsort_check_proofs(kosk_ctx *ctx, int n, int depth, const uint8_t *x, const uint8_t *records, const uint8_t root[32], uint8_t *verdict);
+int kosk_kem_enc_proven(kosk_ctx *ctx, int n, int depth, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t root[32], const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -836,7 +864,11 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 45 launches of k_monitor_check (one per checkpoint event fed); the kernels the monitor reuses count in their own ids (32, 33, 35, 36,
  * 38..40) on the monitor's handle: the slot tree's tiers and subtrees, the sort network of every segment and of every rebuild of the
  * sorted tree, the history's upper tiers and leaf groups, the frontier; ids 42..45 do not move for kosk_monitor_head, _roots, _read or
- * _level. */
+ * _level,
+ * 46 launches of k_regtree_check (one per launch group of kosk_regtree_check_paths, and one per launch group of kosk_kem_enc_proven),
+ * 47 launches of k_regsort_check (one per launch group of kosk_regsort_check_proofs),
+ * 48 kem_enc_proven: encapsulation launches of kosk_kem_enc_proven, one per launch group (ids 0..45 do not move for any call of that
+ * section: its encapsulation is counted here, not on id 12). */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

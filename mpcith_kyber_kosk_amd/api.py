@@ -314,6 +314,14 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_monitor_reserve")):
         sig.update(monitor)
+    # the relying party; optional under the same rule (and only then)
+    relying = {
+        "kosk_regtree_check_paths": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+        "kosk_regsort_check_proofs": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "kosk_kem_enc_proven": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_regtree_check_paths")):
+        sig.update(relying)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -366,7 +374,8 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_reghist_empty_root", "kosk_reghist_root_from_path", "kosk_reghist_check_consistency",
            "kosk_registry_history_reserve", "kosk_registry_history_level", "kosk_registry_history_head", "kosk_registry_history_checkpoint",
            "kosk_registry_history_read", "kosk_registry_history_prove_events", "kosk_registry_history_prove_consistency",
-           "kosk_monitor_reserve", "kosk_monitor_level", "kosk_monitor_feed", "kosk_monitor_head", "kosk_monitor_roots", "kosk_monitor_read"]
+           "kosk_monitor_reserve", "kosk_monitor_level", "kosk_monitor_feed", "kosk_monitor_head", "kosk_monitor_roots", "kosk_monitor_read",
+           "kosk_regtree_check_paths", "kosk_regsort_check_proofs", "kosk_kem_enc_proven"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -1653,6 +1662,94 @@ class Kosk:
         self._chk(lib.kosk_monitor_read(self._h, n, sp, state, h), "monitor_read")
         return list(state.raw[:n]), (_cut(h, 32, n) if out is None else out)
 
+    # the relying party: no registry on the handle
+    @staticmethod
+    def _peer_slots(slots, n):
+        """a list of slot ids (any int32, they are peer data) or an int pointer (with n) -> (pointer, n, keepalive)"""
+        if isinstance(slots, int):
+            if n is None:
+                raise KoskError("a pointer for slots needs n")
+            return C.c_void_p(slots), n, None
+        arr = (C.c_int32 * max(len(slots), 1))(*[int(s_) for s_ in slots])
+        return arr, len(slots), arr
+
+    @staticmethod
+    def _peer_root(root):
+        """32 bytes, or an int pointer -> (pointer, keepalive)"""
+        if isinstance(root, int):
+            return C.c_void_p(root), None
+        root = _digest("a root", root)
+        return C.c_char_p(root), root
+
+    def regtree_check_paths(self, depth, slots, hs, paths, root, states=None, out=None, n=None):
+        """kosk_regtree_check_paths -> [ok]: item b is 1 iff (slots[b], hs[b] or "empty" where states[b] == 0, paths[b]) walks to root.
+        slots: a list of ints; hs: a list of 32-byte strings, or None where every state is 0; paths: a list of depth x 32-byte strings
+        (None where depth == 0); states: None (all occupied) or one truth value per item.  Each of them may instead be an int pointer
+        to host or DEVICE memory (with n).  out: an int pointer to n bytes, returned as it is"""
+        sp, n, _k0 = self._peer_slots(slots, n)
+        hp, _k1 = None, None
+        if hs is not None:
+            hp, nh, _k1 = self._records("fingerprint", hs, n, 32)
+            if nh != n:
+                raise KoskError("regtree_check_paths: %d slots, %d fingerprints" % (n, nh))
+        pp, _k2 = None, None
+        if paths is not None:
+            pp, np_, _k2 = self._records("path", paths, n, 32 * depth)
+            if np_ != n:
+                raise KoskError("regtree_check_paths: %d slots, %d paths" % (n, np_))
+        stp, _k3 = None, None
+        if states is not None:
+            if isinstance(states, int):
+                stp = C.c_void_p(states)
+            else:
+                if len(states) != n:
+                    raise KoskError("regtree_check_paths: %d slots, %d states" % (n, len(states)))
+                _k3 = bytes(1 if s_ else 0 for s_ in states)
+                stp = C.c_char_p(_k3)
+        rp, _k4 = self._peer_root(root)
+        ok = C.create_string_buffer(max(n, 1)) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_regtree_check_paths(self._h, n, depth, sp, stp, hp, pp, rp, ok), "regtree_check_paths")
+        return list(ok.raw[:n]) if out is None else out
+
+    def regsort_check_proofs(self, depth, xs, records, root, out=None, n=None):
+        """kosk_regsort_check_proofs -> [verdict]: per item what records[b] proves about xs[b] under root: REGSORT_NEITHER, REGSORT_ABSENT
+        or REGSORT_PRESENT.  xs: a list of 32-byte strings; records: a list of regsort_proof_bytes(depth)-byte strings; either may be an
+        int pointer to host or DEVICE memory (with n).  out: an int pointer to n bytes, returned as it is"""
+        xp, n, _k0 = self._records("fingerprint", xs, n, 32)
+        cp, nr, _k1 = self._records("proof record", records, n, regsort_proof_bytes(depth))
+        if nr != n:
+            raise KoskError("regsort_check_proofs: %d fingerprints, %d records" % (n, nr))
+        rp, _k2 = self._peer_root(root)
+        v = C.create_string_buffer(max(n, 1)) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_regsort_check_proofs(self._h, n, depth, xp, cp, rp, v), "regsort_check_proofs")
+        return list(v.raw[:n]) if out is None else out
+
+    def kem_enc_proven(self, depth, pks, slots, paths, root, coins=None, out=None, n=None):
+        """kosk_kem_enc_proven: encapsulate to pks[b] iff (slots[b], SHA3-256(pks[b]), paths[b]) walks to root; the check and the mask stay
+        on the device.  Inputs as in regtree_check_paths / kem_enc.  Returns (cts, sss, done); ct and ss of an item whose path fails are
+        zero-filled.  out=(d_ct, d_ss, d_done): int DEVICE pointers, returned as they are"""
+        pp, n, _k0 = self._records("pk", pks, n, self.pk_bytes)
+        sp, ns, _k1 = self._peer_slots(slots, n)
+        if ns != n:
+            raise KoskError("kem_enc_proven: %d public keys, %d slots" % (n, ns))
+        tp, _k2 = None, None
+        if paths is not None:
+            tp, np_, _k2 = self._records("path", paths, n, 32 * depth)
+            if np_ != n:
+                raise KoskError("kem_enc_proven: %d public keys, %d paths" % (n, np_))
+        cp, _k3 = None, None
+        if coins is not None:
+            cp, nc, _k3 = self._records("coins", coins, n, 32)
+            if nc != n:
+                raise KoskError("coins for %d items, public keys for %d" % (nc, n))
+        rp, _k4 = self._peer_root(root)
+        ctb = ct_bytes(self.k)
+        bufs, host = self._kem_out(out, n, (ctb, SS_BYTES, 1))
+        self._chk(lib.kosk_kem_enc_proven(self._h, n, depth, pp, sp, tp, rp, cp, bufs[0], bufs[1], bufs[2]), "kem_enc_proven")
+        if host is None:
+            return out
+        return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1815,6 +1912,9 @@ class Kosk:
     PATH_MONITOR_APPLY = 43
     PATH_MONITOR_LEAVES = 44
     PATH_MONITOR_CHECK = 45
+    PATH_REGTREE_CHECK = 46  # launches of k_regtree_check (kosk_regtree_check_paths, kosk_kem_enc_proven)
+    PATH_REGSORT_CHECK = 47  # launches of k_regsort_check
+    PATH_KEM_ENC_PROVEN = 48  # encapsulation launches of kosk_kem_enc_proven
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

@@ -1957,6 +1957,74 @@ int kosk_monitor_read(kosk_ctx *ctx, int n, const int32_t *slots, uint8_t *state
     GUARD_END
 }
 
+// ---- the relying party (kosk_relying.hip) ----
+// the one root of a call on the host, wherever the caller keeps it
+static int relying_root(kosk_ctx *ctx, const char *fn, const uint8_t *root, uint8_t (&out)[32])
+{
+    if (!is_device_pointer(root)) { memcpy(out, root, 32); return 0; }
+    if (hipMemcpy(out, root, 32, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return refuse(ctx, fn, "copying the root to the host failed"); }
+    return 0;
+}
+
+int kosk_regtree_check_paths(kosk_ctx *ctx, int n, int depth, const int32_t *slots, const uint8_t *state, const uint8_t *h, const uint8_t *paths, const uint8_t root[32], uint8_t *ok)
+{
+    if (!ctx) return -1;
+    if (!slots || (!state && !h) || (depth > 0 && !paths) || !root || !ok) return refuse(ctx, __func__, "null pointer");
+    if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
+    if (depth < 0 || depth > 31) return refuse(ctx, __func__, "depth outside 0..31");
+    GUARD(ctx)
+    ctx->clear_err();
+    uint8_t r[32];
+    if (relying_root(ctx, "kosk_regtree_check_paths", root, r)) return -1;
+    const size_t rec = (size_t)depth * 32;
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return regtree_check_paths(c, count, depth, slots + first, state ? state + first : nullptr, h ? h + (size_t)first * 32 : nullptr,
+                                   paths ? paths + (size_t)first * rec : nullptr, r, ok + first);
+    });
+    GUARD_END
+}
+
+int kosk_regsort_check_proofs(kosk_ctx *ctx, int n, int depth, const uint8_t *x, const uint8_t *records, const uint8_t root[32], uint8_t *verdict)
+{
+    if (!ctx) return -1;
+    if (!x || !records || !root || !verdict) return refuse(ctx, __func__, "null pointer");
+    if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
+    if (depth < 0 || depth > 31) return refuse(ctx, __func__, "depth outside 0..31");
+    GUARD(ctx)
+    ctx->clear_err();
+    uint8_t r[32];
+    if (relying_root(ctx, "kosk_regsort_check_proofs", root, r)) return -1;
+    const size_t rec = regsort::proof_bytes(depth);
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return regsort_check_proofs(c, count, depth, x + (size_t)first * 32, records + (size_t)first * rec, r, verdict + first);
+    });
+    GUARD_END
+}
+
+int kosk_kem_enc_proven(kosk_ctx *ctx, int n, int depth, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t root[32], const uint8_t *coins,
+                        uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (!ctx) return -1;
+    if (!pk || !slots || (depth > 0 && !paths) || !root || !ct || !ss || !done) return refuse(ctx, __func__, "null pointer"); // before any coin is drawn
+    if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
+    if (depth < 0 || depth > 31) return refuse(ctx, __func__, "depth outside 0..31");
+    WGUARD(ctx)
+    ctx->clear_err();
+    uint8_t r[32];
+    if (relying_root(ctx, "kosk_kem_enc_proven", root, r)) return -1;
+    // coins are drawn for every position, whatever its path proves: the draw order does not depend on peer data
+    std::vector<uint8_t> drawn;
+    VecWiper<uint8_t> drawn_gone(drawn);
+    const uint8_t *m = kem_coins(ctx, n, coins, drawn);
+    const Params &P = ctx->c->P;
+    const size_t ctb = kosk_ct_bytes(P.K), rec = (size_t)depth * 32;
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return kem_enc_proven(c, count, depth, pk + (size_t)first * P.pk_bytes, slots + first, paths ? paths + (size_t)first * rec : nullptr, r,
+                              m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32, done + first);
+    });
+    WGUARD_END
+}
+
 // ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----
 int kosk_witness_from_sk(kosk_ctx *ctx, int n, const uint8_t *sk, int16_t *se_out, uint8_t *ok)
 {

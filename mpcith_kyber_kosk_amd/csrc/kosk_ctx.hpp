@@ -82,6 +82,7 @@ enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEM
               PATH_REGISTRY_INDEX, PATH_REGISTRY_FIND, PATH_KEM_ENC_PEERS, PATH_REGISTRY_TREE, PATH_REGISTRY_SUBTREES, PATH_REGISTRY_PATH,
               PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_REGHIST_APPEND, PATH_REGHIST_GROUPS, PATH_REGHIST_FRONTIER, PATH_REGHIST_PROVE,
               PATH_MONITOR_KEYS, PATH_MONITOR_APPLY, PATH_MONITOR_LEAVES, PATH_MONITOR_CHECK,
+              PATH_REGTREE_CHECK, PATH_REGSORT_CHECK, PATH_KEM_ENC_PROVEN,
               PATH_COUNT };
 
 struct GemmTable {
@@ -386,6 +387,15 @@ struct CtxPrivate {
     KemKey *kem_key = nullptr; // the key slot: allocated at the first kem_key_set, its own allocation (kem_ensure never moves it), owned like `kem`
     KemRegistry *registry = nullptr; // the verified-key registry: allocated by registry_reserve, its own allocations, owned like `kem`
     KemRegistry *monitor = nullptr;  // the registry monitor (kosk_monitor.hip): allocated by monitor_reserve, owned like `registry`
+    // the relying party's staging (kosk_relying.hip): one launch group of peer data, allocated at the first checking call and
+    // grown like the KEM workspace; public entries of the inventory under INVG_RELYING
+    uint8_t *d_rl_rec = nullptr;   // [rl_cap][rl_rec] the paths (depth x 32) or the proof records of the items
+    uint8_t *d_rl_q = nullptr;     // [rl_cap][32] the claimed fingerprints h / the query fingerprints x
+    uint8_t *d_rl_state = nullptr; // [rl_cap] the claims "occupied" / "empty"
+    uint8_t *d_rl_ok = nullptr;    // [rl_cap] the verdicts
+    int32_t *d_rl_slot = nullptr;  // [rl_cap] the claimed slots
+    int rl_cap = 0;
+    size_t rl_rec = 0;
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -959,6 +969,41 @@ int monitor_feed(Ctx &c, int n, const uint8_t *events, int *bad_index, int *reas
 int monitor_roots(Ctx &c, uint8_t *slot_root, uint8_t *sorted_root);
 // registry_read without the pk: the flags are read from HBM (a monitor keeps no mirror)
 int monitor_read(Ctx &c, int n, const int32_t *slots, uint8_t *state, uint8_t *h);
+
+// The relying party (kosk_relying.hip): proofs of the two state trees checked in batches against one root.
+// k_regtree_check: one lane per item; ok[b] = 1 iff slot[b] lies in [0, 2^D) and the walk of kosk_regtree.hpp from L(h_b) (state == nullptr
+// or state[b] != 0; a claim "occupied" without fingerprints, h == nullptr, gives 0) or E up paths[b][D][32] ends in root.  h_b lies at
+// h + b * h_stride (8-byte aligned), paths 16-byte aligned
+struct RegTreeCheckJob {
+    int n, D, K;
+    const int32_t *slot;
+    const uint8_t *state, *h;
+    size_t h_stride;
+    const uint8_t *paths;
+    uint64_t root[4];
+    uint8_t *ok;
+};
+// k_regsort_check: a lane pair per item, one walk each; verdict[b] = regsort::check_proof(K, D, x_b, rec_b, root).  x and the records
+// (regsort::proof_bytes(D) apart) 16-byte aligned
+struct RegSortCheckJob {
+    int n, D, K;
+    const uint8_t *x, *rec;
+    uint64_t root[4];
+    uint8_t *verdict;
+};
+hipError_t launch_regtree_check(const RegTreeCheckJob &j, hipStream_t st);
+hipError_t launch_regsort_check(const RegSortCheckJob &j, hipStream_t st);
+// the staging holds n items with records of rec_bytes each (n rounded up to 1 024, at most KEM_CHUNK): all five buffers or none
+int relying_ensure(Ctx &c, int n, size_t rec_bytes);
+// n <= KEM_CHUNK items, every array host or device memory of any alignment (state, h: may be nullptr; paths: where D == 0), root: host.
+// Synchronised; touches nothing but the staging
+int regtree_check_paths(Ctx &c, int n, int D, const int32_t *slots, const uint8_t *state, const uint8_t *h, const uint8_t *paths, const uint8_t *root, uint8_t *ok);
+int regsort_check_proofs(Ctx &c, int n, int D, const uint8_t *x, const uint8_t *records, const uint8_t *root, uint8_t *verdict);
+// crypto_kem_enc_derand for n <= KEM_CHUNK items, item b to pk_b iff (slots[b], occupied, SHA3-256(pk_b), paths_b) walks to root: H(pk) into
+// the KEM workspace, k_regtree_check writes the mask in HBM, the per-item kernels follow (kosk_kem_kernels.hip); done = the verdicts, ct and
+// ss of a failed item zero-filled
+int kem_enc_proven(Ctx &c, int n, int D, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t *root, const uint8_t *coins,
+                   uint8_t *ct, uint8_t *ss, uint8_t *done);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches

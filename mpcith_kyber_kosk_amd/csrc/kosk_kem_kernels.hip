@@ -38,6 +38,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
+#include <cstring>
 
 #include "kosk_ctx.hpp"
 #include "kosk_keccak_wave_dev.hpp"
@@ -457,6 +458,7 @@ struct KemKeySide {
     size_t pk_stride, h_enc_stride, shat_stride, h_dec_stride, z_stride, A_stride; // A_stride in int16_t elements
     const int32_t *key;                           // nullptr: item b uses key b
     bool derive;                                  // A^T (matrix role, into A) and H(pk) (kem_wave_max() rule, into h_enc) belong to the call
+    bool h_ready;                                 // with derive: a kernel queued on the stream has written H(pk) to h_enc already (kem_enc_proven)
 };
 
 // n records at `rec`, `stride` bytes apart: public keys, or (is_sk) secret keys s-hat || pk || H(pk) || z
@@ -514,9 +516,11 @@ static int kem_enc_body(Ctx &c, int n, const KemKeySide &k, const uint8_t *coins
     KemHashJob h = kem_hash_job(c, n, k);
     h.m = w.d_m; h.h = k.h_enc; h.h_stride = k.h_enc_stride; h.key = k.key;
     if (k.derive) {
-        bool wave = false; // H(pk): one wave per key on the wave sponge, or the seed role hashes pk itself
-        if (kem_hpk_wave(c, n, k.pk, k.pk_stride, D.pk, wave)) return -1;
-        if (!wave) h.h = nullptr;
+        if (!k.h_ready) {
+            bool wave = false; // H(pk): one wave per key on the wave sponge, or the seed role hashes pk itself
+            if (kem_hpk_wave(c, n, k.pk, k.pk_stride, D.pk, wave)) return -1;
+            if (!wave) h.h = nullptr;
+        }
         h.n_mat = D.K * D.K;
     }
     h.n_seed = 1;
@@ -884,6 +888,36 @@ int kem_enc_peers(Ctx &c, int n, const uint8_t *h, const uint8_t *coins, uint8_t
     k.key = w.d_key;
     if (kem_enc_body(c, n, k, coins, ct, ss, w.d_mask, PATH_KEM_ENC_PEERS)) return -1;
     return device_error_check(c); // index overflow
+}
+
+// ---- the relying party (kosk_relying.hip) -------------------------------------------------------------------
+int kem_enc_proven(Ctx &c, int n, int D, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t *root, const uint8_t *coins,
+                   uint8_t *ct, uint8_t *ss, uint8_t *done)
+{
+    if (n < 1 || n > KEM_CHUNK || D < 0 || D > 31 || !pk || !slots || (D > 0 && !paths) || !root || !coins || !ct || !ss || !done) { c.err = "kem_enc_proven: bad arguments"; return -1; }
+    if (kem_ensure(c, n)) return -1;
+    if (relying_ensure(c, n, (size_t)D * 32)) return -1;
+    KemWs &w = *c.kem;
+    const Dims Dm = dims(c.P.K);
+    HIPCHK(hipSetDevice(c.device));
+    HIPCHK(kem_copy_in(c, w.d_pk, pk, (size_t)n * Dm.pk));
+    HIPCHK(kem_copy_in(c, c.d_rl_slot, slots, (size_t)n * sizeof(int32_t)));
+    if (D > 0) HIPCHK(kem_copy_in(c, c.d_rl_rec, paths, (size_t)n * D * 32));
+    bool wave = false; // H(pk) under the two-layout rule, into w.d_h either way: the check reads it there, and so does the seed role
+    if (kem_hpk_wave(c, n, w.d_pk, (size_t)Dm.pk, Dm.pk, wave)) return -1;
+    if (!wave) {
+        k_kem_hpk<<<dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c.stream>>>(n, w.d_pk, (size_t)Dm.pk, Dm.pk, nullptr, w.d_h, 32);
+        HIPCHK(hipGetLastError());
+    }
+    RegTreeCheckJob j{};
+    j.n = n; j.D = D; j.K = Dm.K; j.slot = c.d_rl_slot; j.h = w.d_h; j.h_stride = 32; j.paths = c.d_rl_rec; j.ok = w.d_mask;
+    memcpy(j.root, root, 32);
+    HIPCHK(launch_regtree_check(j, c.stream)); // the verdicts are the mask, in HBM
+    c.path_n[PATH_REGTREE_CHECK]++;
+    HIPCHK(kem_copy_out(c, done, w.d_mask, (size_t)n)); // queued here: the body's last synchronisation covers it
+    KemKeySide k = kem_side_items(w, Dm, w.d_pk, (size_t)Dm.pk, false);
+    k.h_ready = true;
+    return kem_enc_body(c, n, k, coins, ct, ss, w.d_mask, PATH_KEM_ENC_PROVEN);
 }
 
 // ---- the registry tree (kosk_registry.hip) ------------------------------------------------------------------

@@ -99,11 +99,35 @@ inline int32_t le32_in(const uint8_t *p)
 {
     return (int32_t)((uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24);
 }
+// The decision of check_proof over a record's header and what its operands give: cmp_l = memcmp(h_l, x), cmp_r = memcmp(x, h_r);
+// walk_l(): the left walk (pos_l, h_l, slot_l, path_l) gives root; walk_r(): the right walk at pos_l + 1 (S(h_r, slot_r) where bit2 of flags
+// is set, else Z) gives root.  Shared by the host function below and k_regsort_check (kosk_relying.hip), which hands in walks it has done
+template <class WL, class WR>
+KOSK_HD inline int check_decide(int D, int64_t pos_l, uint32_t flags, int cmp_l, int cmp_r, WL &&walk_l, WR &&walk_r)
+{
+    const int64_t P = (int64_t)1 << D;
+    if (flags == (FLAG_LEFT | FLAG_PRESENT))
+        return cmp_l == 0 && pos_l >= 0 && pos_l < P && walk_l() ? KIND_PRESENT : KIND_NEITHER;
+    const bool left = flags & FLAG_LEFT, right = flags & FLAG_RIGHT, key = flags & FLAG_RIGHT_KEY;
+    if ((flags & ~7u) || (!left && !right) || (key && !right)) return KIND_NEITHER;
+    if (left) {
+        if (pos_l < 0 || pos_l >= P || cmp_l >= 0 || !walk_l()) return KIND_NEITHER;
+    } else if (pos_l != -1) {
+        return KIND_NEITHER;
+    }
+    if (right) {
+        if (pos_l + 1 >= P) return KIND_NEITHER;
+        if (key ? cmp_r >= 0 || !walk_r() : !walk_r()) return KIND_NEITHER;
+    } else if (pos_l != P - 1) {
+        return KIND_NEITHER;
+    }
+    return KIND_ABSENT;
+}
 // what `rec` (proof_bytes(D) bytes) proves about x under `root`: KIND_PRESENT, KIND_ABSENT, KIND_NEITHER; -1 for bad arguments
 inline int check_proof(int K, int D, const uint8_t *x, const uint8_t *rec, const uint8_t *root)
 {
     if (K < 2 || K > 4 || D < 0 || D > 31 || !x || !rec || !root) return -1;
-    const int64_t P = (int64_t)1 << D, pos_l = le32_in(rec + REC_POS_L);
+    const int64_t pos_l = le32_in(rec + REC_POS_L);
     const int32_t slot_l = le32_in(rec + REC_SLOT_L), slot_r = le32_in(rec + REC_SLOT_R);
     const uint32_t flags = (uint32_t)le32_in(rec + REC_FLAGS);
     const uint8_t *h_l = rec + REC_H_L, *h_r = rec + REC_H_R, *path_l = rec + REC_PATHS, *path_r = path_l + (size_t)D * 32;
@@ -111,22 +135,9 @@ inline int check_proof(int K, int D, const uint8_t *x, const uint8_t *rec, const
     auto walks = [&](int64_t pos, const uint8_t *h, int32_t slot, const uint8_t *path) {
         return root_from_path(K, D, (int32_t)pos, h, slot, path, got) == 0 && !memcmp(got, root, 32);
     };
-    if (flags == (FLAG_LEFT | FLAG_PRESENT))
-        return !memcmp(h_l, x, 32) && pos_l >= 0 && pos_l < P && walks(pos_l, h_l, slot_l, path_l) ? KIND_PRESENT : KIND_NEITHER;
-    const bool left = flags & FLAG_LEFT, right = flags & FLAG_RIGHT, key = flags & FLAG_RIGHT_KEY;
-    if ((flags & ~7u) || (!left && !right) || (key && !right)) return KIND_NEITHER;
-    if (left) {
-        if (pos_l < 0 || pos_l >= P || memcmp(h_l, x, 32) >= 0 || !walks(pos_l, h_l, slot_l, path_l)) return KIND_NEITHER;
-    } else if (pos_l != -1) {
-        return KIND_NEITHER;
-    }
-    if (right) {
-        if (pos_l + 1 >= P) return KIND_NEITHER;
-        if (key ? memcmp(x, h_r, 32) >= 0 || !walks(pos_l + 1, h_r, slot_r, path_r) : !walks(pos_l + 1, nullptr, 0, path_r)) return KIND_NEITHER;
-    } else if (pos_l != P - 1) {
-        return KIND_NEITHER;
-    }
-    return KIND_ABSENT;
+    return check_decide(D, pos_l, flags, memcmp(h_l, x, 32), memcmp(x, h_r, 32),
+                        [&] { return walks(pos_l, h_l, slot_l, path_l); },
+                        [&] { return flags & FLAG_RIGHT_KEY ? walks(pos_l + 1, h_r, slot_r, path_r) : walks(pos_l + 1, nullptr, 0, path_r); });
 }
 
 } // namespace regsort
