@@ -719,6 +719,45 @@ int kosk_regtree_check_paths(kosk_ctx *ctx, int n, int depth, const int32_t *slo
 int kosk_regsort_check_proofs(kosk_ctx *ctx, int n, int depth, const uint8_t *x, const uint8_t *records, const uint8_t root[32], uint8_t *verdict);
 int kosk_kem_enc_proven(kosk_ctx *ctx, int n, int depth, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t root[32], const uint8_t *coins, uint8_t *ct, uint8_t *ss, uint8_t *done);
 
+/* ---- Signed heads, format kosk-headsig-v1 (INTEGRATION.md 8.10 is the normative text): the registrar's signature over a history head, so
+ * that the trust chain of 8.9 starts from a public key and needs nothing from outside this library.  Winternitz one-time signatures
+ * (w = 8, 34 chains of 255 steps) under a Merkle tree of 2^height one-time keys, the construction of LMS (RFC 8554) over SHAKE256 with
+ * 32-byte outputs; the records are this project's own and claim no RFC type code.  The head of size n is signed with leaf n and only with
+ * it: the history is append-only, so that head never changes and two signatures of one size are byte-identical.  ONE SEED SERVES ONE
+ * HISTORY: a registrar who starts another log under the same seed reuses one-time keys and makes its signatures forgeable.
+ * Public key (KOSK_HEADSIG_PUB_BYTES): LE32(height) || I[16] || T[1][32].  Signature (kosk_headsig_sig_bytes(height) = 1136 + 32 height):
+ * LE32(height), LE32(q), LE32(0), LE32(0), C[32], z[34][32], path[height][32].
+ * Host functions (no handle, no GPU): kosk_headsig_sig_bytes is 0 for a height outside 1..24.  kosk_headsig_statement writes the 56 signed
+ * bytes "kosk-sighead-v1" || 00 || root || LE32(size) || LE32(kyber_k); -1: NULL, kyber_k outside 2..4, size < 0.  kosk_headsig_verify: 1
+ * valid, 0 invalid (the header's height differs from the key's, q != size, q >= 2^height, a non-zero reserved word, or the walk does not end
+ * in T[1]), -1: NULL, bad kyber_k, size < 0, a height outside 1..24 in pub.  kosk_headsig_public_from_seed builds the public key on one
+ * thread (2^height x 8714 permutations): the CPU baseline and the tests' oracle; -1: NULL or a bad height.
+ * The signer lives on the registrar's handle.  kosk_registry_signer_reserve(height 1..24, seed, id, pub) needs a reserved history (of any
+ * size), builds all 2^height leaves and the tree in HBM (64 x 2^height bytes) in launches of at most 65536 leaves, and returns the public
+ * key; height 0 frees.  The same (height, id) over a standing tree restores the seed and builds nothing if the root matches: the call
+ * recomputes leaf 0 from the seed and compares it with the tree's, which decides the same thing (the root is a function of the leaves);
+ * the resident seed is replaced only after that match.  Freeing or re-reserving the history or the registry frees the signer.  kosk_registry_signer_level: the height (0: none) and
+ * whether the seed is there.  kosk_registry_history_sign_head(size < 0: current) signs the head of `size`; the root is read where the
+ * history keeps it in HBM and is returned with the signature (root and size_out may be NULL).  -1 with a text that begins with the call's
+ * name and nothing started: no registry / history / signer, "seed was wiped", size above the current size, "signer is exhausted"
+ * (size >= 2^height).  seed, id, pub, sig and root may be host or device memory of any alignment.
+ * kosk_headsig_verify_heads: ok[b] = 1 iff kosk_headsig_verify(pub, kyber_k of the handle, roots + 32 b, sizes[b], sigs_b) returns 1, for
+ * any n >= 1 in launch groups of 16384 under the rules of the relying party's calls above: no registry needed, host or device arrays of any
+ * alignment, peer data gives a verdict and never a refusal; a bad height in pub is a refusal.
+ * Erasure: the seed is a secret entry of the inventory and long-lived like the slot of kosk_kem_key_set:
+ * kosk_wipe_secrets and kosk_destroy zero it, KOSK_WIPE_CALL leaves it.  After a wipe signing is refused and the tree and public key
+ * stay.  The tree, the staged signature and the verifier's staging are public entries. */
+#define KOSK_HEADSIG_PUB_BYTES 52
+#define KOSK_HEADSIG_ITEMS_PER_BLOCK 7 /* one-time keys per block of k_headsig_leaves / k_headsig_verify: launch edges for tests */
+size_t kosk_headsig_sig_bytes(int height);
+int kosk_headsig_statement(int kyber_k, const uint8_t root[32], int size, uint8_t out[56]);
+int kosk_headsig_verify(const uint8_t pub[52], int kyber_k, const uint8_t root[32], int size, const uint8_t *sig);
+int kosk_headsig_public_from_seed(int height, const uint8_t seed[32], const uint8_t id[16], uint8_t pub[52]);
+int kosk_registry_signer_reserve(kosk_ctx *ctx, int height, const uint8_t seed[32], const uint8_t id[16], uint8_t pub[52]);
+int kosk_registry_signer_level(kosk_ctx *ctx, int *height, int *has_seed);
+int kosk_registry_history_sign_head(kosk_ctx *ctx, int size, uint8_t *sig, uint8_t root[32], int *size_out);
+int kosk_headsig_verify_heads(kosk_ctx *ctx, int n, const uint8_t pub[52], const uint8_t *roots, const int32_t *sizes, const uint8_t *sigs, uint8_t *ok);
+
 /* crypto_kem_keypair_derand / crypto_kem_keypair (kyber/kem.c:25-57) for n >= 1 items, byte for byte: ordinary Kyber key pairs with an
  * independent z, on the KEM workspace alone (no prover workspace, no max_batch limit).  coins: n x 64 bytes, d || z per item; NULL: one
  * 64-byte draw per item, in item order, on the caller's thread, through the randombytes callback / OS entropy (kem.c:53-54).  pk / sk:
@@ -868,7 +907,13 @@ int kosk_bank_timing(kosk_ctx *ctx, int n, int reps, double *put_ms, double *tak
  * 46 launches of k_regtree_check (one per launch group of kosk_regtree_check_paths, and one per launch group of kosk_kem_enc_proven),
  * 47 launches of k_regsort_check (one per launch group of kosk_regsort_check_proofs),
  * 48 kem_enc_proven: encapsulation launches of kosk_kem_enc_proven, one per launch group (ids 0..45 do not move for any call of that
- * section: its encapsulation is counted here, not on id 12). */
+ * section: its encapsulation is counted here, not on id 12),
+ * 49 launches of k_headsig_leaves (ceil(2^height / 65536) per build of kosk_registry_signer_reserve; one for a reserve that only restores
+ * the seed over a standing tree),
+ * 50 launches of k_headsig_tree (one per tier of a build: ceil(height / 10)),
+ * 51 launches of k_headsig_sign (one per kosk_registry_history_sign_head; the frontier it needs counts on id 40),
+ * 52 launches of k_headsig_verify (one per launch group of kosk_headsig_verify_heads); ids 0..48 do not move for any call of that section
+ * except id 40. */
 int kosk_path_count(const kosk_ctx *ctx, int id, long *count);
 /* host worker threads per sub-context (kosk_options::host_threads; else <= 8, <= CPUs of the process / streams; all created by kosk_create) */
 int kosk_host_threads(const kosk_ctx *ctx);

@@ -322,6 +322,19 @@ def _load():
     }
     if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_regtree_check_paths")):
         sig.update(relying)
+    # signed heads, kosk-headsig-v1; optional under the same rule (and only then)
+    headsig = {
+        "kosk_headsig_sig_bytes": (sz, [C.c_int]),
+        "kosk_headsig_statement": (C.c_int, [C.c_int, vp, C.c_int, vp]),
+        "kosk_headsig_verify": (C.c_int, [vp, C.c_int, vp, C.c_int, vp]),
+        "kosk_headsig_public_from_seed": (C.c_int, [C.c_int, vp, vp, vp]),
+        "kosk_registry_signer_reserve": (C.c_int, [vp, C.c_int, vp, vp, vp]),
+        "kosk_registry_signer_level": (C.c_int, [vp, ip, ip]),
+        "kosk_registry_history_sign_head": (C.c_int, [vp, C.c_int, vp, vp, ip]),
+        "kosk_headsig_verify_heads": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, vp]),
+    }
+    if not (os.environ.get("KOSK_LIB_PATH") and not hasattr(lib, "kosk_headsig_verify")):
+        sig.update(headsig)
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)  # AttributeError if the header and the library ever disagree
         fn.restype = res
@@ -375,7 +388,9 @@ EXPORTS = ["kosk_pk_bytes", "kosk_sk_bytes", "kosk_proof_bytes", "kosk_tape_byte
            "kosk_registry_history_reserve", "kosk_registry_history_level", "kosk_registry_history_head", "kosk_registry_history_checkpoint",
            "kosk_registry_history_read", "kosk_registry_history_prove_events", "kosk_registry_history_prove_consistency",
            "kosk_monitor_reserve", "kosk_monitor_level", "kosk_monitor_feed", "kosk_monitor_head", "kosk_monitor_roots", "kosk_monitor_read",
-           "kosk_regtree_check_paths", "kosk_regsort_check_proofs", "kosk_kem_enc_proven"]
+           "kosk_regtree_check_paths", "kosk_regsort_check_proofs", "kosk_kem_enc_proven",
+           "kosk_headsig_sig_bytes", "kosk_headsig_statement", "kosk_headsig_verify", "kosk_headsig_public_from_seed",
+           "kosk_registry_signer_reserve", "kosk_registry_signer_level", "kosk_registry_history_sign_head", "kosk_headsig_verify_heads"]
 HAS_KEM = hasattr(lib, "kosk_kem_enc_batch")  # False only for an older library named by KOSK_LIB_PATH
 
 
@@ -597,6 +612,53 @@ def reghist_check_consistency(old_size, size, root_old, root_new, record):
     if rc < 0:
         raise KoskError("reghist_check_consistency: a negative size, old_size > size or size < 1")
     return bool(rc)
+
+
+HEADSIG_PUB_BYTES = 52  # KOSK_HEADSIG_PUB_BYTES
+HEADSIG_ITEMS_PER_BLOCK = 7  # KOSK_HEADSIG_ITEMS_PER_BLOCK
+
+
+def headsig_sig_bytes(height):
+    """kosk_headsig_sig_bytes: 1136 + 32 height, 0 for a height outside 1..24"""
+    return lib.kosk_headsig_sig_bytes(height)
+
+
+def headsig_statement(k, root, size):
+    """kosk_headsig_statement: the 56 bytes a head signature signs"""
+    out = C.create_string_buffer(56)
+    if lib.kosk_headsig_statement(k, C.c_char_p(_digest("a root", root)), size, out):
+        raise KoskError("headsig_statement: kyber_k outside 2..4 or size < 0")
+    return out.raw
+
+
+def _headsig_height(pub):
+    pub = bytes(pub)
+    if len(pub) != HEADSIG_PUB_BYTES:
+        raise KoskError("a head-signature public key has %d bytes" % HEADSIG_PUB_BYTES)
+    return pub, int.from_bytes(pub[:4], "little")
+
+
+def headsig_verify(pub, k, root, size, sig):
+    """kosk_headsig_verify: True iff sig is the signature of the head (root, size) of a Kyber-k registry under pub"""
+    pub, h = _headsig_height(pub)
+    sig = bytes(sig)
+    if not headsig_sig_bytes(h) or len(sig) != headsig_sig_bytes(h):
+        raise KoskError("a signature under this public key has %d bytes" % headsig_sig_bytes(h))
+    rc = lib.kosk_headsig_verify(C.c_char_p(pub), k, C.c_char_p(_digest("a root", root)), size, C.c_char_p(sig))
+    if rc < 0:
+        raise KoskError("headsig_verify: kyber_k outside 2..4, size < 0 or a height outside 1..24")
+    return bool(rc)
+
+
+def headsig_public_from_seed(height, seed, key_id):
+    """kosk_headsig_public_from_seed: the public key of (height, seed, id) on one host thread: 2^height x 8714 permutations"""
+    seed, key_id = bytes(seed), bytes(key_id)
+    if len(seed) != 32 or len(key_id) != 16:
+        raise KoskError("a seed has 32 bytes and a key identifier 16")
+    out = C.create_string_buffer(HEADSIG_PUB_BYTES)
+    if lib.kosk_headsig_public_from_seed(height, C.c_char_p(seed), C.c_char_p(key_id), out):
+        raise KoskError("headsig_public_from_seed: height outside 1..24")
+    return out.raw
 
 
 TAPE_SEC_KEYSEED, TAPE_SEC_OFFLINE, TAPE_SEC_ONLINE = 0, 1, 2  # kosk_tape_section
@@ -1750,6 +1812,55 @@ class Kosk:
             return out
         return _cut(bufs[0], ctb, n), _cut(bufs[1], SS_BYTES, n), [bool(x) for x in bufs[2].raw[:n]]
 
+    # signed heads, kosk-headsig-v1
+    def registry_signer_reserve(self, height, seed=None, key_id=None, out=None):
+        """kosk_registry_signer_reserve -> the 52-byte public key: builds the 2^height one-time keys and their tree in HBM on a handle with a
+        history; height 0 frees (and returns None).  seed (32 bytes) and key_id (16 bytes) may be int pointers to host or DEVICE memory;
+        out: an int DEVICE pointer to 52 bytes, returned in place of the key"""
+        if height == 0:
+            self._chk(lib.kosk_registry_signer_reserve(self._h, 0, None, None, None), "registry_signer_reserve")
+            return None
+        sp = C.c_void_p(seed) if isinstance(seed, int) else C.c_char_p(bytes(seed))
+        ip_ = C.c_void_p(key_id) if isinstance(key_id, int) else C.c_char_p(bytes(key_id))
+        if not isinstance(seed, int) and len(bytes(seed)) != 32 or not isinstance(key_id, int) and len(bytes(key_id)) != 16:
+            raise KoskError("a seed has 32 bytes and a key identifier 16")
+        buf = C.create_string_buffer(HEADSIG_PUB_BYTES) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_registry_signer_reserve(self._h, height, sp, ip_, buf), "registry_signer_reserve")
+        return buf.raw if out is None else out
+
+    def registry_signer_level(self):
+        """kosk_registry_signer_level -> (height, has_seed); height 0: no signer"""
+        h, s_ = C.c_int(), C.c_int()
+        self._chk(lib.kosk_registry_signer_level(self._h, C.byref(h), C.byref(s_)), "registry_signer_level")
+        return h.value, bool(s_.value)
+
+    def registry_history_sign_head(self, size=-1, out=None):
+        """kosk_registry_history_sign_head -> (sig, root, size): the head over the first `size` events (< 0: all) signed with leaf `size`.
+        out=(d_sig, d_root): int DEVICE pointers, returned in place of the bytes"""
+        h = self.registry_signer_level()[0]
+        n = C.c_int()
+        if out is None:
+            sig, root = C.create_string_buffer(max(headsig_sig_bytes(h), 1)), C.create_string_buffer(32)
+        else:
+            sig, root = C.c_void_p(int(out[0])), C.c_void_p(int(out[1]))
+        self._chk(lib.kosk_registry_history_sign_head(self._h, size, sig, root, C.byref(n)), "registry_history_sign_head")
+        if out is None:
+            return sig.raw[:headsig_sig_bytes(h)], root.raw, n.value
+        return out[0], out[1], n.value
+
+    def headsig_verify_heads(self, pub, roots, sizes, sigs, out=None, n=None):
+        """kosk_headsig_verify_heads -> [ok]: item b is 1 iff headsig_verify(pub, k, roots[b], sizes[b], sigs[b]).  roots, sizes and sigs
+        are lists or int pointers to host or DEVICE memory (with n); out: an int pointer to n bytes, returned as it is"""
+        pub, h = _headsig_height(pub)
+        rp, n, _k0 = self._records("root", roots, n, 32)
+        zp, ns, _k1 = self._peer_slots(sizes, n)
+        gp, ng, _k2 = self._records("signature", sigs, n, headsig_sig_bytes(h))
+        if ns != n or ng != n:
+            raise KoskError("headsig_verify_heads: %d roots, %d sizes, %d signatures" % (n, ns, ng))
+        ok = C.create_string_buffer(max(n, 1)) if out is None else C.c_void_p(int(out))
+        self._chk(lib.kosk_headsig_verify_heads(self._h, n, C.c_char_p(pub), rp, zp, gp, ok), "headsig_verify_heads")
+        return list(ok.raw[:n]) if out is None else out
+
     # proofs for keys that already exist (INTEGRATION.md 9)
     def witness_from_sk(self, sks, n=None):
         """kosk_witness_from_sk: the prover's witness of n secret keys (list of bytes, or an int DEVICE pointer with n), left resident.
@@ -1915,6 +2026,10 @@ class Kosk:
     PATH_REGTREE_CHECK = 46  # launches of k_regtree_check (kosk_regtree_check_paths, kosk_kem_enc_proven)
     PATH_REGSORT_CHECK = 47  # launches of k_regsort_check
     PATH_KEM_ENC_PROVEN = 48  # encapsulation launches of kosk_kem_enc_proven
+    PATH_HEADSIG_LEAVES = 49  # launches of k_headsig_leaves (kosk_registry_signer_reserve)
+    PATH_HEADSIG_TREE = 50  # launches of k_headsig_tree, one per tier
+    PATH_HEADSIG_SIGN = 51  # launches of k_headsig_sign
+    PATH_HEADSIG_VERIFY = 52  # launches of k_headsig_verify, one per launch group
 
     def path_count(self, path_id):
         """one counter of kosk_path_count by number, e.g. PATH_DENSE_FILL: refills of the dense wire format"""

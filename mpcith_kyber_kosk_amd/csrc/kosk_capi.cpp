@@ -30,6 +30,7 @@
 #include "kosk_ctx.hpp"
 #include "kosk_lanes.hpp"
 #include "kosk_registry_resolve.hpp"
+#include "kosk_headsig.hpp"
 #include "kosk_reghist.hpp"
 #include "kosk_regsort.hpp"
 #include "kosk_regtree.hpp"
@@ -2023,6 +2024,78 @@ int kosk_kem_enc_proven(kosk_ctx *ctx, int n, int depth, const uint8_t *pk, cons
                               m + (size_t)first * 32, ct + (size_t)first * ctb, ss + (size_t)first * 32, done + first);
     });
     WGUARD_END
+}
+
+// ---- signed heads, format kosk-headsig-v1 (kosk_headsig.hpp, kosk_headsig.hip) ----
+static_assert((int)KOSK_HEADSIG_PUB_BYTES == (int)headsig::PUB_BYTES && (int)KOSK_HEADSIG_ITEMS_PER_BLOCK == (int)headsig::ITEMS_PER_BLOCK,
+              "kosk_mi355x.h and kosk_headsig.hpp");
+size_t kosk_headsig_sig_bytes(int height) { return headsig::sig_bytes(height); }
+int kosk_headsig_statement(int kyber_k, const uint8_t root[32], int size, uint8_t out[56]) { return headsig::statement(kyber_k, root, size, out); }
+int kosk_headsig_verify(const uint8_t pub[52], int kyber_k, const uint8_t root[32], int size, const uint8_t *sig)
+{
+    return headsig::verify(pub, kyber_k, root, size, sig);
+}
+int kosk_headsig_public_from_seed(int height, const uint8_t seed[32], const uint8_t id[16], uint8_t pub[52])
+{
+    return headsig::public_from_seed(height, seed, id, pub);
+}
+
+int kosk_registry_signer_reserve(kosk_ctx *ctx, int height, const uint8_t seed[32], const uint8_t id[16], uint8_t pub[52])
+{
+    if (!ctx) return -1;
+    if (height && (!seed || !id || !pub)) return refuse(ctx, __func__, "null pointer");
+    if (height < 0 || height > headsig::MAX_HEIGHT) return refuse(ctx, __func__, "height outside 0..24");
+    GUARD(ctx)
+    ctx->clear_err();
+    const KemRegistry *r = ctx->c->registry;
+    if (height && !r) return refuse(ctx, "kosk_registry_signer_reserve", WHY_NO_REGISTRY);
+    if (height && !r->hist_max) return refuse(ctx, "kosk_registry_signer_reserve", WHY_NO_HISTORY);
+    if (headsig_signer_reserve(*ctx->c, height, seed, id, pub)) { ctx->err = ctx->c->err; return -1; }
+    return 0;
+    GUARD_END
+}
+
+int kosk_registry_signer_level(kosk_ctx *ctx, int *height, int *has_seed)
+{
+    if (!ctx) return -1;
+    if (height) *height = ctx->c->sg_height;
+    if (has_seed) *has_seed = ctx->c->sg_height && ctx->c->sg_has_seed ? 1 : 0;
+    return 0;
+}
+
+int kosk_registry_history_sign_head(kosk_ctx *ctx, int size, uint8_t *sig, uint8_t root[32], int *size_out)
+{
+    if (!ctx) return -1;
+    if (!sig) return refuse(ctx, __func__, "null pointer");
+    GUARD(ctx)
+    ctx->clear_err();
+    if (const char *why = history_refusal(ctx, size)) return refuse(ctx, "kosk_registry_history_sign_head", why);
+    const Ctx &c = *ctx->c;
+    if (!c.sg_height) return refuse(ctx, "kosk_registry_history_sign_head", "no signer is reserved (kosk_registry_signer_reserve)");
+    if (!c.sg_has_seed) return refuse(ctx, "kosk_registry_history_sign_head", "seed was wiped (kosk_registry_signer_reserve with the same seed and id restores it)");
+    if (((unsigned)size >> c.sg_height) != 0) return refuse(ctx, "kosk_registry_history_sign_head", "signer is exhausted: size is not below 2^height");
+    if (headsig_sign_head(*ctx->c, size, sig, root)) { ctx->err = ctx->c->err; return -1; }
+    if (size_out) *size_out = size;
+    return 0;
+    GUARD_END
+}
+
+int kosk_headsig_verify_heads(kosk_ctx *ctx, int n, const uint8_t pub[52], const uint8_t *roots, const int32_t *sizes, const uint8_t *sigs, uint8_t *ok)
+{
+    if (!ctx) return -1;
+    if (!pub || !roots || !sizes || !sigs || !ok) return refuse(ctx, __func__, "null pointer");
+    if (n < 1) return refuse(ctx, __func__, "n must be at least 1");
+    GUARD(ctx)
+    ctx->clear_err();
+    uint8_t p[headsig::PUB_BYTES];
+    if (!is_device_pointer(pub)) memcpy(p, pub, sizeof p);
+    else if (hipMemcpy(p, pub, sizeof p, hipMemcpyDeviceToHost) != hipSuccess) { (void)hipGetLastError(); return refuse(ctx, "kosk_headsig_verify_heads", "copying the public key to the host failed"); }
+    const size_t sb = headsig::sig_bytes((int)headsig::le32_in(p));
+    if (!sb) return refuse(ctx, "kosk_headsig_verify_heads", "the public key's height is outside 1..24");
+    return kem_chunks(ctx, n, [&](Ctx &c, int first, int count) {
+        return headsig_verify_heads(c, count, p, roots + (size_t)first * 32, sizes + first, sigs + (size_t)first * sb, ok + first);
+    });
+    GUARD_END
 }
 
 // ---- existing keys: the witness from the secret key, and proofs for keys made elsewhere (kosk_witness_kernels.hip) ----

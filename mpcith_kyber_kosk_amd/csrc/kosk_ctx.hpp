@@ -83,6 +83,7 @@ enum PathId { PATH_HASH_DMA = 0, PATH_HASH_PLAIN, PATH_TABLE_GEMM, PATH_LIMB_GEM
               PATH_REGSORT_SORT, PATH_REGSORT_TREE, PATH_REGSORT_PROVE, PATH_REGHIST_APPEND, PATH_REGHIST_GROUPS, PATH_REGHIST_FRONTIER, PATH_REGHIST_PROVE,
               PATH_MONITOR_KEYS, PATH_MONITOR_APPLY, PATH_MONITOR_LEAVES, PATH_MONITOR_CHECK,
               PATH_REGTREE_CHECK, PATH_REGSORT_CHECK, PATH_KEM_ENC_PROVEN,
+              PATH_HEADSIG_LEAVES, PATH_HEADSIG_TREE, PATH_HEADSIG_SIGN, PATH_HEADSIG_VERIFY,
               PATH_COUNT };
 
 struct GemmTable {
@@ -396,6 +397,14 @@ struct CtxPrivate {
     int32_t *d_rl_slot = nullptr;  // [rl_cap] the claimed slots
     int rl_cap = 0;
     size_t rl_rec = 0;
+    // the head signer (kosk_headsig.hip): allocated by headsig_signer_reserve on a handle with a history, freed with the
+    // history or the registry; entries of the inventory under INVG_SIGNER, the seed a secret one and long-lived like the resident KEM key
+    int sg_height = 0;             // 0: no signer
+    bool sg_has_seed = false;      // false after wipe_secrets(): the tree and the public key stay, signing is refused
+    uint8_t *d_sg_tree = nullptr;  // [headsig::tree_bytes(sg_height)] T[r] at 32 r
+    uint8_t *d_sg_seed = nullptr;  // [64] the seed; behind it a candidate seed while a reserve checks it against the standing tree, else zeros
+    uint8_t *d_sg_sig = nullptr;   // [headsig::sig_bytes(sg_height) + 32] one staged signature, the signed root behind it
+    uint8_t sg_pub[52] = {0};
 
     double phase_sec[PH_COUNT] = {0};
     int prof_on = 0; // 1: the graded kernel only (graphs stay on); 2: every profiled id (plain launches)
@@ -1004,6 +1013,53 @@ int regsort_check_proofs(Ctx &c, int n, int D, const uint8_t *x, const uint8_t *
 // ss of a failed item zero-filled
 int kem_enc_proven(Ctx &c, int n, int D, const uint8_t *pk, const int32_t *slots, const uint8_t *paths, const uint8_t *root, const uint8_t *coins,
                    uint8_t *ct, uint8_t *ss, uint8_t *done);
+
+// Signed heads (kosk_headsig.hip, kosk_headsig.hpp).
+// k_headsig_leaves: a lane per (leaf, chain), 7 leaves a block; leaf first + i of `count` to tree (T[2^h + q] at 32 (2^h + q)), or, where out
+// is not nullptr, to out + 32 i
+struct HeadSigLeavesJob {
+    int h;
+    uint32_t first, count;
+    uint64_t id[2];
+    const uint8_t *seed;
+    uint8_t *tree, *out;
+};
+// k_headsig_tree, one tier: block i reduces up to 1 024 nodes of level 10 tier (counted from the leaves) through up to 10 levels in LDS
+struct HeadSigTreeJob {
+    int h, tier;
+    uint64_t id[2];
+    uint8_t *tree;
+};
+// k_headsig_sign: one block; the root of `size` is read at root (HBM) or, where root is nullptr, is root_imm; the record to sig, the root
+// behind it
+struct HeadSigSignJob {
+    int h, K;
+    uint32_t size;
+    uint64_t id[2], root_imm[4];
+    const uint8_t *seed, *root, *tree;
+    uint8_t *sig;
+};
+// k_headsig_verify: a lane per (item, chain), 7 items a block; ok[b] = headsig::verify(pub, K, roots_b, sizes[b], sigs_b) == 1.  roots and
+// the records (sig_bytes apart) 16-byte aligned
+struct HeadSigVerifyJob {
+    int n, h, K;
+    uint64_t id[2], top[4];
+    const uint8_t *roots, *sigs;
+    const int32_t *sizes;
+    size_t sig_bytes;
+    uint8_t *ok;
+};
+// height 0 frees (the seed is wiped first).  Needs c.registry with a history; seed, id, pub: host or device memory.  The same (height, id)
+// over a standing tree whose leaf 0 the seed reproduces restores the seed and builds nothing.  Synchronised
+int headsig_signer_reserve(Ctx &c, int height, const uint8_t *seed, const uint8_t *id, uint8_t *pub);
+void headsig_signer_release(Ctx &c);
+void headsig_note_wiped(Ctx &c); // wipe_secrets() zeroed the seed
+// the head of `size` (validated: a size of the history, below 2^height) signed with leaf `size`; sig, root: host or device memory
+int headsig_sign_head(Ctx &c, int size, uint8_t *sig, uint8_t *root);
+// n <= KEM_CHUNK items against one public key (host, its height validated); every array host or device memory of any alignment
+int headsig_verify_heads(Ctx &c, int n, const uint8_t *pub, const uint8_t *roots, const int32_t *sizes, const uint8_t *sigs, uint8_t *ok);
+// d_hrag holds the ragged nodes and the root of `size` >= 1: queued, not synchronised (kosk_reghist.hip)
+int reghist_frontier_ensure(Ctx &c, KemRegistry &r, int size);
 
 // ---- erasure (kosk_wipe.hip) ----
 enum { WIPE_MAX_REGIONS = 48 }; // regions per launch of k_wipe (they travel in the kernel arguments); longer lists take more launches

@@ -33,7 +33,7 @@ struct InvBuf {
 
 struct Inventory {
     enum { INV_HOST = 1, INV_SECRET = 2, INV_PER_PROOF = 4 };
-    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK, INVG_REGISTRY, INVG_MONITOR, INVG_RELYING };
+    enum { INVG_CORE = 0, INVG_VERIFY, INVG_COMPACT, INVG_DENSE, INVG_KEM, INVG_WITNESS, INVG_BIND, INVG_KEMKEY, INVG_FORCE, INVG_TRANSCODE, INVG_BANK, INVG_REGISTRY, INVG_MONITOR, INVG_RELYING, INVG_SIGNER };
     InvAlloc mem{};
     size_t records = 0; // proofs behind every per-proof entry: max_batch of the context that allocates them, own_batch of a view
     std::vector<InvBuf> bufs;

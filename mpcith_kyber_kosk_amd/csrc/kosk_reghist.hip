@@ -163,6 +163,7 @@ int reghist_reserve(Ctx &c, int max_events)
     HIPCHK(hipSetDevice(c.device));
     if (r.hist_max) {
         HIPCHK(stream_sync(c));
+        headsig_signer_release(c); // one seed serves one history: the signer goes with it
         release_fields(c, &r.d_hev, &r.d_hproof + 1);
         r.hist_max = r.hist_size = r.hstage_cap = 0;
         r.hist_frontier = -1;
@@ -242,7 +243,7 @@ int reghist_checkpoint(Ctx &c, int *index)
 }
 
 // d_hrag holds the ragged nodes and the root of `size` >= 1: queued, not synchronised; a second call at the same size launches nothing
-static int frontier_ensure(Ctx &c, KemRegistry &r, int size)
+int reghist_frontier_ensure(Ctx &c, KemRegistry &r, int size)
 {
     if (r.hist_frontier == size) return 0;
     RegHistFrontierJob j{};
@@ -266,7 +267,7 @@ int reghist_head(Ctx &c, KemRegistry &r, int size, uint8_t *root)
         else memcpy(root, o, 32);
         return 0;
     }
-    if (frontier_ensure(c, r, size)) return -1;
+    if (reghist_frontier_ensure(c, r, size)) return -1;
     int top = 0;
     while ((size >> top) > 1) top++;
     HIPCHK(hipMemcpyAsync(root, r.d_hrag + (size_t)(top + 1) * 32, 32, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c.stream));
@@ -311,7 +312,7 @@ int reghist_prove(Ctx &c, int kind, int size, int n, const int32_t *q, uint8_t *
     if (staging_ensure(c, n)) return -1;
     const KemRegistry &r = *c.registry;
     HIPCHK(hipMemcpyAsync(r.d_hq, q, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, c.stream));
-    if (frontier_ensure(c, *c.registry, size)) return -1;
+    if (reghist_frontier_ensure(c, *c.registry, size)) return -1;
     RegHistProveJob j{};
     j.n = n; j.kind = kind; j.D = reghist::depth(r.hist_max); j.size = size;
     j.rec_bytes = (int)(kind ? reghist::consistency_bytes(size) : reghist::path_bytes(size));

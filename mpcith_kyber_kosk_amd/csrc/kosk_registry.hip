@@ -399,6 +399,7 @@ void registry_release(Ctx &c)
 {
     KemRegistry *r = c.registry;
     if (!r) return;
+    headsig_signer_release(c); // the signer signs this registry's history
     c.inv.release(Inventory::INVG_REGISTRY);
     delete r;
     c.registry = nullptr;

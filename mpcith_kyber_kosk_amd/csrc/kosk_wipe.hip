@@ -212,7 +212,7 @@ int wipe_secrets(Ctx &c, bool keep_key)
 {
     HIPCHK(hipSetDevice(c.device));
     std::vector<WipeRegion> dev;
-    wipe_regions_list(c, dev, -1, keep_key ? 1u << Inventory::INVG_KEMKEY | 1u << Inventory::INVG_BANK : 0u); // long-lived secrets stay
+    wipe_regions_list(c, dev, -1, keep_key ? 1u << Inventory::INVG_KEMKEY | 1u << Inventory::INVG_BANK | 1u << Inventory::INVG_SIGNER : 0u); // long-lived secrets stay
     // the stream may still carry this context's earlier work on these buffers: the wipe is queued behind it
     if (launch_wipe(c, dev.data(), (int)dev.size())) return -1;
     HIPCHK(stream_sync(c));
@@ -232,6 +232,7 @@ int wipe_secrets(Ctx &c, bool keep_key)
     c.staged_online = false;
     if (!keep_key) bank_note_wiped(c); // every slot is zero: the bank is empty
     if (!keep_key) kem_key_note_wiped(c); // the slot's s-hat and z are zero now: it serves as a public key from here on
+    if (!keep_key) headsig_note_wiped(c); // the signer's seed is zero: signing is refused until it is reserved again
     return 0;
 }
 
